@@ -14,9 +14,18 @@ scaling, every rank owns --reads reads of one (N x reads)-read data set, k-mer s
 minimiser bucket, one all-to-all of supermer records per step.
 
 Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel, algorithmic bytes
-per launch / HIP-event launch time, SURVEY.md 8(d): 32.65 B per k-mer instance at K=48) and, at N=1,
-`cpu_baseline` (the reference's own C++ path -- oracle/_ref/snref_driver -- timed on this box's host
-cores on a bounded sample; falls back to the single-thread C port in oracle/ when the binary is absent).
+per launch / HIP-event launch time, SURVEY.md 8(d): 32.65 B per k-mer instance at K=48).  A plain run does
+only that: set up, warm up, time --steps steps, print the line.
+
+--full adds everything else the bench measures or checks, untimed, after the timed steps: the sharded path's
+self-check against the one-GPU path (N>1 or --sharded), and at N=1 the robust / next / f3 ingest / df_seam /
+large_job rows and `cpu_baseline` (the reference's own C++ path -- oracle/_ref/snref_driver -- timed on this
+box's host cores on a bounded sample; falls back to the single-thread C port in oracle/ when the binary is absent).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float64 / float32,
+under 64 MB in all: the retained k-mer table as a key-hash-selected sample in key order, the spectrum, the
+unitig lengths, and for the one-GPU step a seeded sample of the .bv image, the HBV graph and a seeded sample
+of the good lengths.  The inputs are seeded: the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -49,6 +58,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the untimed rows and checks after the timed steps (sharded self-check, robust / next / f3 / df_seam / large_job rows, "
+                         "CPU baseline); the --no-* options below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
     ap.add_argument("--reads", type=float, default=1e8, help="reads per GPU")
     ap.add_argument("--k", type=int, default=48)
     ap.add_argument("--error-free", action="store_true")
@@ -83,7 +96,7 @@ def parse():
                          "does at start-up; -1 = 1.3 GB per million reads up to 45 %% of the device, 0 = none (every call that outgrows the arena pays "
                          "the driver ~25-30 ms per new GB inside the call)")
     ap.add_argument("--no-df-seam", action="store_true", help="N=1: skip the untimed b1/b2 row (reads.fastb / .qualp / .bci -> device decode -> unitigs)")
-    ap.add_argument("--no-large-job", action="store_true", help="skip config.large_job (800 M reads on this GPU in its own process, ~40 s; only the default run has it)")
+    ap.add_argument("--no-large-job", action="store_true", help="skip config.large_job (800 M reads on this GPU in its own process, ~40 s; only a --full run with no other row skipped has it)")
     ap.add_argument("--large-job-reads", type=float, default=8e8)
     ap.add_argument("--df-reads", type=float, default=1e8, help="reads of the df_seam row's stage-input files")
     ap.add_argument("--df-dir", default="", help="where the df_seam row writes its files (default: $TMPDIR or /tmp)")
@@ -407,6 +420,82 @@ def robust_rows(eng, per_gpu, K, headline_ms, arena_bytes=0):
     return out
 
 
+DUMP_SEED = 0x5EED0D0D
+
+
+def dump_outputs(res, outdir: Path, dev) -> int:
+    """--dump-outputs: what the last timed step hands its caller, as DIR/<name>.npy (float64; float32 where every value is a byte or
+    16-bit), under 64 MB in all.  Large outputs are sampled the same way on every run, so that two builds compare file for file:
+      kmer_keys [m, 4] (u32 words MSB-first, as Result.keys()), kmer_counts [m], kmer_ctx [m]: the retained table entries whose key
+          hashes into a fixed slice (about 2^17 of them, whatever order the table is in), sorted by key;
+      spectrum: the k-mer count histogram;  unitig_lengths: descending (BVComp order);
+      bv_image_sample: bytes of the .bv hand-off image at seeded positions;  hbv_<array>: the HBV graph (one-GPU step);
+      good_len_sample: trimmed read lengths at seeded positions;
+      scalars: n_kmers, n_unitigs, n_instances, unitig_total_bases, n_circles, bv bytes, hbv vertices, hbv edges (-1 = not in this path).
+    Returns the bytes written."""
+    import numpy as np
+    import torch
+    from supernova_amd.sharded import _DevBytes
+    outdir.mkdir(parents=True, exist_ok=True)
+    raw = res.raw
+    view = lambda ptr, nbytes: torch.as_tensor(_DevBytes(ptr, nbytes), device=dev)
+    written = 0
+
+    def save(name, a, dt=np.float64):
+        nonlocal written
+        a = np.ascontiguousarray(a, dtype=dt)
+        np.save(outdir / f"{name}.npy", a)
+        written += a.nbytes
+
+    def positions(total, cap, salt):
+        # every element when it fits, else `cap` seeded positions (sorted) -- the same ones for the same total
+        if total <= cap:
+            return np.arange(total, dtype=np.int64)
+        rng = np.random.default_rng(DUMP_SEED + salt)
+        return np.sort((rng.random(cap) * total).astype(np.int64))
+
+    n = int(res.n_kmers)
+    words = np.zeros((0, 4), np.uint64)
+    cnt, ctx = np.zeros(0, np.uint32), np.zeros(0, np.uint8)
+    if n:
+        kv = view(raw.keys, n * 16).view(torch.int64).view(n, 2)          # (lo, hi) per entry
+        mix = kv[:, 0] * 0x2545F4914F6CDD1D ^ kv[:, 1] * 0x5851F42D4C957F2D
+        shift = max(0, (n - 1).bit_length() - 17)                         # keep 1 in 2^shift: at most ~2^17 entries
+        idx = torch.nonzero(((mix >> 40) & ((1 << shift) - 1)) == 0).squeeze(1)
+        lohi = kv[idx].cpu().numpy().view(np.uint64)
+        cnt = view(raw.counts, n * 4).view(torch.int32)[idx].cpu().numpy().view(np.uint32)
+        ctx = view(raw.ctx, n)[idx].cpu().numpy()
+        order = np.lexsort((lohi[:, 0], lohi[:, 1]))[:1 << 18]
+        lo, hi = lohi[order, 0], lohi[order, 1]
+        words = np.stack([hi >> np.uint64(32), hi & np.uint64(0xFFFFFFFF), lo >> np.uint64(32), lo & np.uint64(0xFFFFFFFF)], axis=1)
+        cnt, ctx = cnt[order], ctx[order]
+    save("kmer_keys", words)
+    save("kmer_counts", cnt)
+    save("kmer_ctx", ctx, np.float32)
+    save("spectrum", res.spectrum())
+    nu = int(res.n_unitigs)
+    off = res._dl(raw.unitig_off, (nu + 1) * 8, np.uint64, (nu + 1,))
+    lens = np.sort(np.diff(off.astype(np.int64)))[::-1]
+    save("unitig_lengths", lens[positions(nu, 1 << 18, 1)])
+    bv_bytes = hbv_v = hbv_e = -1
+    if getattr(res, "bv", None) is not None:
+        ptr, bv_bytes = res.bv
+        pos = positions(bv_bytes, 1 << 22, 2)
+        save("bv_image_sample", view(ptr, bv_bytes)[torch.from_numpy(pos).to(dev)].cpu().numpy(), np.float32)
+    if getattr(res, "hbv_graph", None) is not None:
+        g = res.hbv_graph
+        hbv_v, hbv_e = int(g["n_vertices"]), int(g["n_edges"])
+        for k in ("v_left", "v_right", "src", "is_rc", "fwd", "rev"):      # ('order' indexes the library's own unitig order: not compared)
+            save(f"hbv_{k}", g[k][positions(len(g[k]), 1 << 18, 3)])
+    nr = int(getattr(res, "n_reads", 0))
+    if getattr(raw, "good_len", None) and nr:
+        pos = positions(nr, 1 << 20, 4)
+        save("good_len_sample", view(raw.good_len, nr * 2).view(torch.int16)[torch.from_numpy(pos).to(dev)].cpu().numpy().view(np.uint16), np.float32)
+    save("scalars", [n, nu, int(res.n_instances), int(off[-1]) if nu else 0, int(getattr(res, "n_circles", 0)), bv_bytes, hbv_v, hbv_e])
+    assert written <= 64 << 20, f"--dump-outputs wrote {written} bytes"
+    return written
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` with no launcher around it: run the N ranks under torch.distributed.run on this node (127.0.0.1, a free
     port), exactly as the driver's own N > 1 command does, and return their exit code.  Rank 0's JSON line is the children's stdout."""
@@ -511,7 +600,7 @@ def main():
     # one-GPU path over all of its reads (retained table as a multiset checksum, unitigs as a set).  A transport that
     # drops or garbles bytes shows up here, not as a fast wrong number.
     verified = None
-    if use_dist and not args.grouped and not args.no_verify:
+    if use_dist and not args.grouped and not args.no_verify and args.full:
         import hashlib
         import numpy as np
         per_v = 2_000_000
@@ -570,6 +659,9 @@ def main():
         inst_total = float(tsum[1])
     else:
         inst_total = float(inst_local)
+    if args.dump_outputs and rank == 0:
+        nb = dump_outputs(res, Path(args.dump_outputs), torch.device("cuda", eng.device))
+        print(f"[bench] last step's outputs: {nb} bytes in {args.dump_outputs}", file=sys.stderr, flush=True)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -675,27 +767,27 @@ def main():
             out["config"]["step_includes"] = {"a13_bv_image_bytes": int(res.bv[1]), "a14_hbv_edges": int(res.hbv_graph["n_edges"]),
                                               "a14_hbv_vertices": int(res.hbv_graph["n_vertices"]),
                                               "a13_a14_ms": round(sum(tail_ms[-args.steps:]) / max(1, args.steps), 3)}
-            if not args.no_robust and not args.error_free and per_gpu >= 10_000_000:
+            if args.full and not args.no_robust and not args.error_free and per_gpu >= 10_000_000:
                 try:
                     out["config"]["robust"] = robust_rows(eng, per_gpu, K, ms_per_step, int(getattr(res, "scratch_bytes", 0)))
                 except Exception as ex:
                     out["config"]["robust"] = {"failed": str(ex)}
-            if not args.no_next_rows:
+            if args.full and not args.no_next_rows:
                 try:
                     out["config"]["next_rows"] = next_rows(eng, step(), rows, quals, bc, sp.read_len, K)
                 except Exception as ex:
                     out["config"]["next_rows"] = {"failed": str(ex)}
-            if not args.no_ingest:
+            if args.full and not args.no_ingest:
                 try:
                     out["config"]["f3_ingest"] = ingest_row(eng, args, K, ms_per_step / per_gpu)
                 except Exception as ex:
                     out["config"]["f3_ingest"] = {"failed": str(ex)}
-            if not args.no_df_seam:
+            if args.full and not args.no_df_seam:
                 try:
                     out["config"]["df_seam"] = df_seam_row(eng, args, K)
                 except Exception as ex:
                     out["config"]["df_seam"] = {"failed": str(ex)}
-            if not args.no_robust and not args.error_free and per_gpu >= 10_000_000 and isinstance(out["config"].get("robust"), dict):
+            if args.full and not args.no_robust and not args.error_free and per_gpu >= 10_000_000 and isinstance(out["config"].get("robust"), dict):
                 try:
                     # the first call on a NEW context, same reads, right after the bench's own engine was closed: what it pays for is
                     # mostly the driver clearing the ~150 GB that engine has just handed back (~30 ms per GB; 0.19 s on a clean device:
@@ -718,7 +810,7 @@ def main():
                     e2.close()
                 except Exception as ex:
                     out["config"]["robust"]["new_context_after_close_calls_ms"] = {"failed": str(ex)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(sp, K, args.cpu_sample, tuple(int(x) for x in args.cpu_threads.split(",")), big=args.cpu_sample_10m)
                 c10 = ROOT / "profiles" / "cpu_baseline_10m.json"
@@ -732,7 +824,7 @@ def main():
             except Exception as ex:  # the baseline is a report, never a reason to lose the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "Gk-mers/s", "cores": os.cpu_count(), "kind": "reference",
                                        "sample": f"failed: {ex}"}
-        if (world == 1 and not use_dist and not args.grouped and K == 48 and not args.no_large_job and per_gpu == 100_000_000
+        if (args.full and world == 1 and not use_dist and not args.grouped and K == 48 and not args.no_large_job and per_gpu == 100_000_000
                 and not (args.no_robust or args.no_next_rows or args.no_ingest or args.no_df_seam or args.no_cpu_baseline)):
             # this run's reads, results and arena go back to the device first (the row's process plans with what is free)
             try:
@@ -750,7 +842,7 @@ def main():
             out["config"]["large_job"] = large_job_row(args)
         line = json.dumps(out)
     if use_dist:
-        if use_dist and not args.grouped and not args.no_verify:         # every rank leaves with the same exit code
+        if use_dist and not args.grouped and not args.no_verify and args.full:         # every rank leaves with the same exit code
             vt = torch.tensor([1 if verified else 0], dtype=torch.int64, device=cdev)
             dist.broadcast(vt, 0)
             verified = bool(int(vt.item()))

@@ -87,6 +87,64 @@ def test_bench_starts_its_own_ranks(monkeypatch):
     assert seen["env"].get("HSA_ENABLE_IPC_MODE_LEGACY") == "0"
 
 
+def test_bench_dump_outputs_do_not_depend_on_table_order(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: the same retained table in two different orders (the bucket order is the library's to choose) gives the
+    same files; the sampled entries are the table's own, in key order, and the files stay under 64 MB.  A plain run has --full off.
+    No GPU: the device views bench.py takes of the library's arrays are replaced by host views of host arrays."""
+    import ctypes
+    import importlib.util
+    import sys
+    import torch
+    import supernova_amd.sharded as sharded
+    spec = importlib.util.spec_from_file_location("bench_under_test", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "4"])
+    a = bench.parse()
+    assert a.steps == 4 and not a.full and not a.dump_outputs
+    monkeypatch.setattr(sharded, "_DevBytes", lambda ptr, n: np.ctypeslib.as_array((ctypes.c_uint8 * n).from_address(ptr)))
+
+    class Res:
+        def _dl(self, ptr, nbytes, dtype, shape):
+            return np.frombuffer(ctypes.string_at(ptr, nbytes), dtype=dtype).reshape(shape).copy()
+
+        def spectrum(self):
+            return np.bincount(self.arrays[1], minlength=64)[:64].astype(np.uint64)
+
+    rng = np.random.default_rng(3)
+    n = 300_000
+    keys = rng.integers(0, 2**62, size=(n, 2), dtype=np.uint64)
+    counts = rng.integers(3, 60, size=n, dtype=np.uint32)
+    ctx = rng.integers(0, 256, size=n, dtype=np.uint8)
+    off = np.cumsum(np.r_[0, rng.integers(48, 500, size=100)]).astype(np.uint64)
+    bv = rng.integers(0, 256, size=5_000_000, dtype=np.uint8)
+    good = rng.integers(0, 151, size=2_000_000, dtype=np.uint16)
+    outs = []
+    for seed in (0, 1):
+        p = np.random.default_rng(seed).permutation(n)
+        r = Res()
+        r.arrays = (np.ascontiguousarray(keys[p]), counts[p].copy(), ctx[p].copy(), off, bv, good)
+        r.raw = type("Raw", (), {})()
+        r.raw.keys, r.raw.counts, r.raw.ctx, r.raw.unitig_off, r.raw.good_len = (x.ctypes.data for x in (*r.arrays[:4], good))
+        r.n_kmers, r.n_unitigs, r.n_instances, r.n_circles, r.n_reads = n, 100, 123456, 1, good.size
+        r.bv = (bv.ctypes.data, bv.size)
+        r.hbv_graph = dict(n_vertices=4, n_edges=2, v_left=np.arange(2), v_right=np.arange(2), src=np.arange(2), is_rc=np.zeros(2, np.uint8),
+                           fwd=np.arange(100), rev=np.arange(100), order=np.arange(100))
+        nb = bench.dump_outputs(r, tmp_path / str(seed), torch.device("cpu"))
+        assert 0 < nb <= 64 << 20
+        outs.append({f.name: np.load(f) for f in sorted((tmp_path / str(seed)).glob("*.npy"))})
+    assert outs[0].keys() == outs[1].keys() and {"kmer_keys.npy", "spectrum.npy", "bv_image_sample.npy", "scalars.npy"} <= outs[0].keys()
+    for name, x in outs[0].items():
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, outs[1][name]), name
+    w = outs[0]["kmer_keys.npy"].astype(np.uint64)
+    lo, hi = (w[:, 2] << np.uint64(32)) | w[:, 3], (w[:, 0] << np.uint64(32)) | w[:, 1]
+    assert 1000 < len(lo) < n and np.all(np.lexsort((lo, hi)) == np.arange(len(lo)))
+    table = {(int(k0), int(k1)): (int(c), int(x)) for (k0, k1), c, x in zip(keys, counts, ctx)}
+    got = zip(lo, hi, outs[0]["kmer_counts.npy"], outs[0]["kmer_ctx.npy"])
+    assert all(table[(int(a), int(b))] == (int(c), int(x)) for a, b, c, x in got)
+    assert np.array_equal(outs[0]["unitig_lengths.npy"], np.sort(np.diff(off.astype(np.int64)))[::-1])
+
+
 def test_options_registry_and_no_environment_switches(snk):
     """include/snk.h "tuning": every option has a name and a description; the product reads the environment for tracing and library paths
     only (VERDICT r5 #10: 67 distinct SNK_* switches were read with getenv inside csrc/) -- every algorithmic choice is a context option."""

@@ -147,7 +147,7 @@ def test_bench_two_processes_over_gloo_one_gpu(tmp_path):
     root = Path(__file__).resolve().parent.parent
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           str(root / "bench.py"), "--gpus", "2", "--transport", "gloo", "--reads", "3e6", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+           str(root / "bench.py"), "--gpus", "2", "--transport", "gloo", "--reads", "3e6", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(root))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
@@ -172,7 +172,7 @@ def test_bench_self_launches_its_ranks(extra):
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--transport", "gloo", "--reads", "2e6", "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", *extra]
+           "--full", "--no-cpu-baseline", *extra]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(root), env=env)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{") and '"metric"' in l]

@@ -8,7 +8,7 @@ W=/tmp/snk_prof_$T; mkdir -p $W $O
 if [ "$2" != "notests" ]; then
   timeout 2400 python -m pytest $R/tests -m gpu -x -q > $O/t_$T.log 2>&1; grep -E "passed|failed|rror" $O/t_$T.log | tail -3
 fi
-timeout 1500 python $R/bench.py > $O/bench_$T.log 2>&1; tail -1 $O/bench_$T.log | cut -c1-300
+timeout 1500 python $R/bench.py --full > $O/bench_$T.log 2>&1; tail -1 $O/bench_$T.log | cut -c1-300
 for m in "k48:" "k60:--k 60" "grouped:--grouped" "sharded:--sharded --no-verify"; do
   tag=${m%%:*}; fl=${m#*:}
   rm -rf $W/prof_${T}_$tag
