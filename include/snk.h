@@ -662,6 +662,103 @@ int snk_synth_fasth_write(const char* path, const snk_synth_params* sp, uint64_t
                           char* err, size_t errcap);
 void snk_synth_bc_seq(uint32_t id, char* out16);
 
+/* ---- the graph verifier (supernova_amd/csrc/snk_check.hip) ------------------------------------------------------------------------
+ * The reference's reassembly invariants (lib/tada/src/sim_tests.rs:297-404; EdgeBuilder, BuildReadQGraph48.cc:327-541), checked on the
+ * device over raw arrays -- any producer's, or a corrupted copy -- at any size (entry ids up to 2^32 - 2; 64-bit positions and counters).
+ * The verifier shares the key layout and the context plumbing with the rest of libsnk, nothing of the count or graph code: its own
+ * canonical form, its own hash index, its own trim.  Its scratch (about 8.25 B per entry, 5 B more for the reads level) comes from
+ * the context's arena after the arrays under test and is handed back on return: the snk_dev_result it checks stays valid.
+ *
+ * Graph level (unless SNK_CHECK_DIGEST_ONLY): every counter below counts violations, first[] holds the first offender (table row,
+ * unitig or read index; UINT64_MAX = none).
+ *   table_duplicate_keys   two rows share a key
+ *   table_not_sorted       SNK_CHECK_SORTED_TABLE: a key below the one before it
+ *   count_below_min_freq   a count < min_freq
+ *   bad_unitig             a unitig shorter than K, a base code > 3, offsets that do not start at 0 or decrease
+ *   unitig_kmer_missing    a k-mer of a unitig, canonicalised (group included), is not in the table
+ *   kmer_repeated          a table entry hit by more than one unitig k-mer (a k-mer belongs to exactly one unitig, :492-504)
+ *   kmer_uncovered         a table entry no unitig k-mer hits
+ *   ctx_dangling           a context bit (pred << 4 | succ, canonical orientation) names a neighbour that is not in the table
+ *   ctx_not_reciprocal     ... that is, but does not carry the reciprocal bit (ReadPather.h:356-381)
+ *   interior_break         a step x -> y inside a unitig breaks the walk rule: x has one successor, y's last base; y has one
+ *                          predecessor; neither is a palindrome (EdgeBuilder::extend, :445-464)
+ *   end_extendable         an end of a non-circular unitig the walk rule would extend (up/downstreamExtensionPossible, :408-428)
+ *   not_canonical          a linear unitig not in FWD form; a circle that does not start at its smallest canonical k-mer, in that
+ *                          k-mer's FWD form, before addEdge orients the whole sequence (:348-397,478-486).  A palindrome k-mer is a
+ *                          unitig of its own.  A circle's last K-1 bases repeat its first
+ *   not_ordered            SNK_CHECK_ORDERED: unitigs not ascending by their first K bases (group-major when grouped)
+ *   group_mismatch         grouped runs: a k-mer of a unitig is not in the table under the unitig's group but is under another one
+ *                          (the index hashes the k-mer without its group, so every group's copy lies on one probe chain)
+ *   key_padding            key bits below the K bases that are not zero where no group belongs there (ungrouped runs, K=60)
+ * Reads level (reads != NULL): the k-mers of every read with good length >= K+1 at positions 0 .. good_len-K (Kmerizer::map,
+ * :155-172), looked up in the verifier's index:
+ *   count_mismatch         min(recount, 2^24-1) != min(stored count, 2^24-1)
+ *   ctx_mismatch           (min_freq > 1) the context the reads give -- neighbours both retained -- != the stored byte
+ *   good_len_mismatch      reads->quals given: the trim recomputed (App. A.4, min_qual) != reads->good_len
+ *   instances_mismatch     sum of max(0, good_len-K+1) over reads with good_len >= K+1 != in->n_instances (when that is not 0)
+ * Not re-derived: which k-mers the min_freq / min_bc rules drop.
+ *
+ * Digests (always; mod 2^64, mix = the splitmix64 finaliser z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27,
+ * z *= 0x94D049BB133111EB, z ^= z >> 31): order-independent across rows and unitigs, additive over disjoint shares, position-sensitive
+ * inside a unitig:
+ *   table_digest  = sum over rows     mix(key_lo ^ mix(key_hi ^ mix((min(count, 2^24-1) << 8) | ctx)))
+ *   unitig_digest = sum over unitigs  mix(h_u ^ mix(len_u ^ (group_u << 40))),  h_u = sum over i mix((i << 2) | base_{u,i})
+ * (group_u = 0 outside grouped runs). */
+#define SNK_CHECK_SORTED_TABLE 1u   /* the table must be ascending */
+#define SNK_CHECK_ORDERED 2u        /* unitigs ordered by their first K bases, group-major when grouped (snk_dev_result) */
+#define SNK_CHECK_GROUPED 4u        /* per-group run: the group in the 32 low key bits (K=48); unitig_group and reads->group given */
+#define SNK_CHECK_DIGEST_ONLY 8u    /* digests only: a rank's share of a sharded step, where unitigs cross table shares */
+#define SNK_CHECK_N_COUNTERS 24
+/* counter indices (count[] / first[]) */
+#define SNK_CHECK_TABLE_DUPLICATE_KEYS 0
+#define SNK_CHECK_TABLE_NOT_SORTED 1
+#define SNK_CHECK_COUNT_BELOW_MIN_FREQ 2
+#define SNK_CHECK_BAD_UNITIG 3
+#define SNK_CHECK_UNITIG_KMER_MISSING 4
+#define SNK_CHECK_KMER_REPEATED 5
+#define SNK_CHECK_KMER_UNCOVERED 6
+#define SNK_CHECK_CTX_DANGLING 7
+#define SNK_CHECK_CTX_NOT_RECIPROCAL 8
+#define SNK_CHECK_INTERIOR_BREAK 9
+#define SNK_CHECK_END_EXTENDABLE 10
+#define SNK_CHECK_NOT_CANONICAL 11
+#define SNK_CHECK_NOT_ORDERED 12
+#define SNK_CHECK_GROUP_MISMATCH 13
+#define SNK_CHECK_COUNT_MISMATCH 14
+#define SNK_CHECK_CTX_MISMATCH 15
+#define SNK_CHECK_GOOD_LEN_MISMATCH 16
+#define SNK_CHECK_INSTANCES_MISMATCH 17
+#define SNK_CHECK_KEY_PADDING 18          /* 19 .. 23 reserved */
+typedef struct snk_check_input {   /* raw device arrays, so any producer (and a corrupted copy in a test) can be checked */
+    uint32_t K, flags;             /* SNK_CHECK_* */
+    uint32_t min_freq;
+    uint32_t min_qual;             /* reads level, the trim recomputed from reads->quals (0 = 7) */
+    uint64_t n_instances;          /* what the producer reported (snk_dev_result.n_instances); 0 = not checked */
+    uint64_t n_kmers;
+    const void* keys;              /* as snk_dev_result */
+    const void* counts;
+    const void* ctx;
+    uint64_t n_unitigs;
+    const void* unitig_off;        /* u64[n_unitigs + 1] */
+    const void* unitig_bases;
+    const void* unitig_group;      /* u32[n_unitigs] with SNK_CHECK_GROUPED, else ignored */
+} snk_check_input;
+typedef struct snk_check_report {
+    uint32_t struct_size;          /* the caller sets sizeof(snk_check_report) = 600; the library refuses a smaller one */
+    uint32_t levels;               /* what ran: 1 graph level, 2 reads level (0: digests only) */
+    uint64_t n_kmers, n_unitigs, n_circles, n_palindromes, n_bases;
+    uint64_t n_instances;          /* reads level: the instances the reads give */
+    uint64_t table_digest, unitig_digest;
+    uint64_t count[SNK_CHECK_N_COUNTERS];
+    uint64_t first[SNK_CHECK_N_COUNTERS];
+    uint64_t peak_bytes;           /* verifier scratch */
+    float graph_ms, reads_ms;      /* HIP events: digests + graph level; reads level + the per-entry comparison */
+    uint64_t reserved[16];
+} snk_check_report;
+/* reads: NULL = graph level only (ignored with SNK_CHECK_DIGEST_ONLY).  Returns SNK_OK whatever it found: the report says. */
+int snk_dev_check_graph(snk_ctx* ctx, const snk_check_input* in, const snk_dev_reads* reads, snk_check_report* out, void* stream,
+                        char* err, size_t errcap);
+
 #ifdef __cplusplus
 }
 #endif

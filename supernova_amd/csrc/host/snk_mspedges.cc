@@ -13,6 +13,8 @@
 //                          derives from <head>.dti -- the start of the first 10X dataset (DF.cc:358-363) -- or 0 without one
 //   DEVICE=0               GPU ordinal
 //   SPECTRUM=<file.json>   optional: k-mer spectrum as DF writes it to stats/histogram_kmer_count.json
+//   CHECK=graph            optional: the graph-level verifier (snk_dev_check_graph) on the device result before the .bv is written;
+//                          the report goes to <OUT>.check.json, and a violation ends the run with exit 1 naming the counters
 //   IO_THREADS=<n> SLAB_READS=<n> READ_LEN=<n>   tuning of the ingest (pread workers, reads per slab, row length; defaults: CPU budget, 262144, longest read)
 // Exit codes follow the reference's conventions: 0 ok, 1 fatal (FatalErr), 99 out of memory (system/RunTime.cc:195-221).
 // Only the C ABI of include/snk.h is used -- this file is plain C++ (g++), no HIP, no torch.
@@ -60,6 +62,53 @@ long long bc_start_from_dti(const std::string& head) {
     return out;
 }
 
+// CHECK=graph: the verifier's graph level over the device result (include/snk.h); the report as JSON next to OUT.  Returns the seconds
+// it took (kept out of the timed files -> .bv line)
+double check_graph(snk_ctx* ctx, const snk_params& p, const snk_dev_result& r, const std::string& path) {
+    struct timespec c0, c1;
+    clock_gettime(CLOCK_MONOTONIC, &c0);
+    static const char* names[] = {"table_duplicate_keys", "table_not_sorted", "count_below_min_freq", "bad_unitig", "unitig_kmer_missing",
+                                  "kmer_repeated", "kmer_uncovered", "ctx_dangling", "ctx_not_reciprocal", "interior_break", "end_extendable",
+                                  "not_canonical", "not_ordered", "group_mismatch", "count_mismatch", "ctx_mismatch", "good_len_mismatch",
+                                  "instances_mismatch", "key_padding"};
+    snk_check_input in;
+    memset(&in, 0, sizeof in);
+    in.K = p.K;
+    in.flags = SNK_CHECK_ORDERED | ((p.flags & SNK_F_UNSORTED_TABLE) ? 0u : SNK_CHECK_SORTED_TABLE);
+    in.min_freq = p.min_freq;
+    in.n_instances = r.n_instances;
+    in.n_kmers = r.n_kmers;
+    in.keys = r.keys; in.counts = r.counts; in.ctx = r.ctx;
+    in.n_unitigs = r.n_unitigs;
+    in.unitig_off = r.unitig_off; in.unitig_bases = r.unitig_bases;
+    snk_check_report rep;
+    memset(&rep, 0, sizeof rep);
+    rep.struct_size = sizeof rep;
+    char err[512] = "";
+    int rc;
+    if ((rc = snk_dev_check_graph(ctx, &in, nullptr, &rep, nullptr, err, sizeof err))) fatal(rc, "CHECK=graph", err);
+    FILE* f = fopen(path.c_str(), "w");
+    if (!f) fatal(SNK_E_IO, "CHECK=graph", "cannot write the report");
+    fprintf(f, "{\"n_kmers\": %llu, \"n_unitigs\": %llu, \"n_circles\": %llu, \"n_palindromes\": %llu, \"n_bases\": %llu, "
+               "\"table_digest\": \"%016llx\", \"unitig_digest\": \"%016llx\", \"graph_ms\": %.2f, \"peak_bytes\": %llu, \"counters\": {",
+            (unsigned long long)rep.n_kmers, (unsigned long long)rep.n_unitigs, (unsigned long long)rep.n_circles, (unsigned long long)rep.n_palindromes,
+            (unsigned long long)rep.n_bases, (unsigned long long)rep.table_digest, (unsigned long long)rep.unitig_digest, rep.graph_ms,
+            (unsigned long long)rep.peak_bytes);
+    std::string bad;
+    for (int i = 0; i <= SNK_CHECK_KEY_PADDING; ++i) {
+        fprintf(f, "%s\"%s\": %llu", i ? ", " : "", names[i], (unsigned long long)rep.count[i]);
+        if (rep.count[i]) bad += std::string(bad.empty() ? "" : ", ") + names[i] + "=" + std::to_string((unsigned long long)rep.count[i]);
+    }
+    fprintf(f, "}}\n");
+    fclose(f);
+    if (!bad.empty()) fatal(SNK_E_INTERNAL, "CHECK=graph found violations", bad.c_str());
+    clock_gettime(CLOCK_MONOTONIC, &c1);
+    const double s = (c1.tv_sec - c0.tv_sec) + 1e-9 * (c1.tv_nsec - c0.tv_nsec);
+    fprintf(stderr, "snk_mspedges: CHECK=graph clean: %llu k-mers, %llu unitigs, %.1f ms on the device, %.3f s with the report\n",
+            (unsigned long long)rep.n_kmers, (unsigned long long)rep.n_unitigs, rep.graph_ms, s);
+    return s;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -71,9 +120,10 @@ int main(int argc, char** argv) {
     }
     if (!kv.count("LR") || !kv.count("OUT")) {
         fprintf(stderr, "usage: snk_mspedges LR=<reads.fastb> OUT=<asm_graph.bv> [K=48] [MIN_QUAL=7] [MIN_FREQ=3] [MIN_BC=2] "
-                        "[BC_START=<from .dti>] [DEVICE=0] [SPECTRUM=<file.json>]\n");
+                        "[BC_START=<from .dti>] [DEVICE=0] [SPECTRUM=<file.json>] [CHECK=graph]\n");
         return 1;
     }
+    if (kv.count("CHECK") && kv["CHECK"] != "graph") fatal(SNK_E_ARG, "CHECK", "the one level is CHECK=graph");
     const std::string head = head_of(kv["LR"], ".fastb");
     char err[512] = "";
     int rc;
@@ -108,6 +158,8 @@ int main(int argc, char** argv) {
         clock_gettime(CLOCK_MONOTONIC, &t0);
         snk_dev_ingest st;
         if ((rc = snk_dev_ingest_df_count_graph(ctx, files, 0, info.n_reads, read_len, threads, slab, &p, ign_bc_below, &r, &st, err, sizeof err))) fatal(rc, "count+graph", err);
+        double check_s = 0;
+        if (kv.count("CHECK") && rep == 0) check_s = check_graph(ctx, p, r, kv["OUT"] + ".check.json");
         const void* d_image = nullptr;
         uint64_t image_bytes = 0;
         if ((rc = snk_dev_bv_image(ctx, p.K, r.n_unitigs, r.unitig_off, r.unitig_bases, 1, &d_image, &image_bytes, nullptr, err, sizeof err))) fatal(rc, "unitig file image", err);
@@ -118,7 +170,7 @@ int main(int argc, char** argv) {
         FILE* f = fopen(kv["OUT"].c_str(), "wb");
         if (!f || fwrite(image.data(), 1, image_bytes, f) != image_bytes || fclose(f) != 0) fatal(SNK_E_IO, "OUT", "cannot write the unitig file");
         clock_gettime(CLOCK_MONOTONIC, &t1);
-        const double s = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
+        const double s = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec) - check_s;
         fprintf(stderr, "snk_mspedges: %llu k-mer instances, %llu retained k-mers, %llu unitigs; %.2f GB of file bytes in %u slabs, %.3f s ingest+partition (%.1f GB/s, "
                         "%.3f s waiting for file bytes, %.3f s setup), count+graph %.1f ms; files -> %s in %.3f s = %.2f Gk-mers/s\n",
                 (unsigned long long)r.n_instances, (unsigned long long)r.n_kmers, (unsigned long long)r.n_unitigs, st.text_bytes / 1e9, st.n_batches, st.seconds,

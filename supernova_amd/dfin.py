@@ -88,7 +88,7 @@ class DfFiles:
         stats = dict(n_reads=int(raw.n_reads), file_bytes=int(raw.text_bytes), seconds=float(raw.seconds), io_wait_seconds=float(raw.decode_wait_seconds),
                      n_slabs=int(raw.n_batches), max_len=int(raw.max_len), setup_seconds=float(raw.setup_seconds),
                      mode="streamed" if int(raw.n_files) == 3 else "compact")
-        return Result(engine, res, params.K), stats
+        return Result(engine, res, params.K, params), stats
 
 
 def write_df(head, rows: np.ndarray, quals: np.ndarray, bc: np.ndarray | None = None, lens: np.ndarray | None = None, read_len: int | None = None,

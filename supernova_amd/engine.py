@@ -44,10 +44,11 @@ class Params:
 class Result:
     """Device-resident result of one count_graph call (valid until the next call on the same engine)."""
 
-    def __init__(self, engine: "Engine", raw: _lib.SnkDevResult, K: int):
+    def __init__(self, engine: "Engine", raw: _lib.SnkDevResult, K: int, params: "Params | None" = None):
         self._e = engine
         self.raw = raw
         self.K = K
+        self.params = params
         for f in ("n_reads", "n_instances", "n_supermers", "n_buckets", "n_kmers", "n_unitigs", "unitig_total_bases",
                   "n_circles", "rank_rounds", "buckets_split", "max_slots_used", "scratch_bytes", "n_boundary", "n_overflow",
                   "n_fragments", "repartitioned", "n_hot_buckets"):
@@ -195,6 +196,18 @@ class Result:
             info["unitig_bcs"] = (self._dl(out.unitig_bc_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,)),
                                   self._dl(out.unitig_bcs, nb * 4, np.uint32, (nb,)))
         return off, ne, edges, info
+
+    def check(self, reads: "_lib.SnkDevReads | None" = None, ordered: bool = True) -> dict:
+        """snk_dev_check_graph over this result's own arrays (include/snk.h, "the graph verifier"): the reassembly invariants of the
+        table and the unitigs, and the digests; with `reads` (the snk_dev_reads the result was made from) the reads level as well.
+        The result stays valid."""
+        p = self.params or Params(K=self.K)
+        flags = ((_lib.CHECK_SORTED_TABLE if p.sorted_table else 0) | (_lib.CHECK_ORDERED if ordered else 0)
+                 | (_lib.CHECK_GROUPED if p.grouped else 0))
+        r = self.raw
+        return self._e.check_graph_ptrs(self.K, flags, p.min_freq, self.n_kmers, r.keys, r.counts, r.ctx, self.n_unitigs, r.unitig_off,
+                                        r.unitig_bases, r.unitig_group if p.grouped else None, n_instances=self.n_instances, reads=reads,
+                                        min_qual=p.min_qual)
 
     def unitigs(self) -> list[str]:
         """Canonical unitigs sorted by (length desc, lexicographic) = BVComp, HBVFromEdges.cc:106-111."""
@@ -412,7 +425,7 @@ class Engine:
         rc = self.lib.snk_dev_stream_finish(self._ctx, C.byref(raw), self._stream(), err, 512)
         if rc != 0:
             raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        return Result(self, raw, self._stream_params.K)
+        return Result(self, raw, self._stream_params.K, self._stream_params)
 
     def count_graph_reads(self, r: "_lib.SnkDevReads", params: Params | None = None) -> Result:
         """The same for reads described by plain device pointers (e.g. the arrays of snk_dev_ingest_fasth)."""
@@ -423,4 +436,38 @@ class Engine:
         rc = self.lib.snk_dev_count_graph(self._ctx, C.byref(r), C.byref(p), C.byref(raw), self._stream(), err, 512)
         if rc != 0:
             raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        return Result(self, raw, params.K)
+        return Result(self, raw, params.K, params)
+
+    # ---- the graph verifier (snk_dev_check_graph)
+    def check_graph_ptrs(self, K: int, flags: int, min_freq: int, n_kmers: int, keys, counts, ctx, n_unitigs: int, unitig_off, unitig_bases,
+                         unitig_group=None, n_instances: int = 0, reads: "_lib.SnkDevReads | None" = None, min_qual: int = 7) -> dict:
+        """snk_dev_check_graph over plain device pointers; the report as a dict (lib.SnkCheckReport.to_dict)."""
+        ci = _lib.SnkCheckInput()
+        ci.K, ci.flags, ci.min_freq, ci.min_qual, ci.n_instances = K, flags, min_freq, min_qual, n_instances
+        ci.n_kmers, ci.keys, ci.counts, ci.ctx = n_kmers, keys, counts, ctx
+        ci.n_unitigs, ci.unitig_off, ci.unitig_bases, ci.unitig_group = n_unitigs, unitig_off, unitig_bases, unitig_group
+        rep = _lib.SnkCheckReport()
+        rep.struct_size = C.sizeof(_lib.SnkCheckReport)
+        err = C.create_string_buffer(512)
+        rc = self.lib.snk_dev_check_graph(self._ctx, C.byref(ci), C.byref(reads) if reads is not None else None, C.byref(rep), self._stream(),
+                                          err, 512)
+        if rc != 0:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        return rep.to_dict()
+
+    def check_graph(self, keys: torch.Tensor, counts: torch.Tensor, ctx: torch.Tensor, unitig_off: torch.Tensor, unitig_bases: torch.Tensor,
+                    K: int = 48, min_freq: int = 3, unitig_group: torch.Tensor | None = None, sorted_table: bool = True, ordered: bool = True,
+                    digest_only: bool = False, n_instances: int = 0, reads: "_lib.SnkDevReads | None" = None, min_qual: int = 7) -> dict:
+        """The verifier over device tensors (any producer's arrays, or a corrupted copy): keys [n, 2] int64/uint64 {lo, hi} (or n*16 bytes),
+        counts u32/int32 [n], ctx u8 [n], unitig_off [U + 1] 64-bit, unitig_bases u8, unitig_group 32-bit [U] for a grouped run."""
+        for t in (keys, counts, ctx, unitig_off, unitig_bases) + ((unitig_group,) if unitig_group is not None else ()):
+            assert t.is_cuda and t.is_contiguous()
+        n_kmers = keys.numel() * keys.element_size() // 16
+        assert counts.numel() == n_kmers and ctx.numel() == n_kmers and counts.element_size() == 4 and ctx.element_size() == 1
+        assert unitig_off.element_size() == 8 and unitig_bases.element_size() == 1
+        U = unitig_off.numel() - 1
+        flags = ((_lib.CHECK_SORTED_TABLE if sorted_table else 0) | (_lib.CHECK_ORDERED if ordered else 0)
+                 | (_lib.CHECK_GROUPED if unitig_group is not None else 0) | (_lib.CHECK_DIGEST_ONLY if digest_only else 0))
+        return self.check_graph_ptrs(K, flags, min_freq, n_kmers, keys.data_ptr(), counts.data_ptr(), ctx.data_ptr(), max(U, 0),
+                                     unitig_off.data_ptr(), unitig_bases.data_ptr(),
+                                     unitig_group.data_ptr() if unitig_group is not None else None, n_instances, reads, min_qual)

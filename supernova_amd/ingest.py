@@ -125,4 +125,4 @@ def ingest_count_graph(engine, paths, read_len: int, whitelist: bytes | None = N
     stats = dict(n_reads=int(raw.n_reads), text_bytes=int(raw.text_bytes), compressed_bytes=int(raw.compressed_bytes), seconds=float(raw.seconds),
                  decode_wait_seconds=float(raw.decode_wait_seconds), n_files=int(raw.n_files), n_batches=int(raw.n_batches), max_len=int(raw.max_len),
                  setup_seconds=float(raw.setup_seconds))
-    return Result(engine, res, params.K), stats
+    return Result(engine, res, params.K, params), stats

@@ -128,6 +128,35 @@ class SnkShardResult(C.Structure):
                 ("reserved_u", C.c_uint32), ("pair_max_bytes", C.c_uint64 * 8)]
 
 
+
+CHECK_COUNTERS = ("table_duplicate_keys", "table_not_sorted", "count_below_min_freq", "bad_unitig", "unitig_kmer_missing", "kmer_repeated",
+                  "kmer_uncovered", "ctx_dangling", "ctx_not_reciprocal", "interior_break", "end_extendable", "not_canonical", "not_ordered",
+                  "group_mismatch", "count_mismatch", "ctx_mismatch", "good_len_mismatch", "instances_mismatch", "key_padding")   # SNK_CHECK_* indices
+CHECK_SORTED_TABLE, CHECK_ORDERED, CHECK_GROUPED, CHECK_DIGEST_ONLY = 1, 2, 4, 8
+
+
+class SnkCheckInput(C.Structure):
+    _fields_ = [("K", C.c_uint32), ("flags", C.c_uint32), ("min_freq", C.c_uint32), ("min_qual", C.c_uint32), ("n_instances", C.c_uint64),
+                ("n_kmers", C.c_uint64), ("keys", C.c_void_p), ("counts", C.c_void_p), ("ctx", C.c_void_p), ("n_unitigs", C.c_uint64),
+                ("unitig_off", C.c_void_p), ("unitig_bases", C.c_void_p), ("unitig_group", C.c_void_p)]
+
+
+class SnkCheckReport(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("levels", C.c_uint32), ("n_kmers", C.c_uint64), ("n_unitigs", C.c_uint64),
+                ("n_circles", C.c_uint64), ("n_palindromes", C.c_uint64), ("n_bases", C.c_uint64), ("n_instances", C.c_uint64),
+                ("table_digest", C.c_uint64), ("unitig_digest", C.c_uint64), ("count", C.c_uint64 * 24), ("first", C.c_uint64 * 24),
+                ("peak_bytes", C.c_uint64), ("graph_ms", C.c_float), ("reads_ms", C.c_float), ("reserved", C.c_uint64 * 16)]
+
+    def to_dict(self) -> dict:
+        none = (1 << 64) - 1
+        d = {f: int(getattr(self, f)) for f in ("levels", "n_kmers", "n_unitigs", "n_circles", "n_palindromes", "n_bases", "n_instances",
+                                                "table_digest", "unitig_digest", "peak_bytes")}
+        d["counters"] = {n: int(self.count[i]) for i, n in enumerate(CHECK_COUNTERS)}
+        d["first"] = {n: int(self.first[i]) for i, n in enumerate(CHECK_COUNTERS) if int(self.first[i]) != none}
+        d["violations"] = sum(d["counters"].values())
+        d["graph_ms"], d["reads_ms"] = float(self.graph_ms), float(self.reads_ms)
+        return d
+
 COMM_A2A = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64),
                        C.POINTER(C.c_uint64), C.c_uint32)
 COMM_GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32)
@@ -267,6 +296,7 @@ def _declare(lib: C.CDLL) -> None:
         "snk_shard_stream_append": (C.c_int, [vp, P(SnkDevReads), vp, cp, sz]),
         "snk_shard_stream_finish": (C.c_int, [vp, vp, u32, P(SnkShardResult), vp, cp, sz]),
         "snk_shard_gather_unitigs": (C.c_int, [vp, vp, P(SnkShardResult), u32, u32, u32, P(SnkResult), vp, cp, sz]),
+        "snk_dev_check_graph": (C.c_int, [vp, P(SnkCheckInput), P(SnkDevReads), P(SnkCheckReport), vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -306,6 +306,13 @@ class ShardedResult:
         n, tb = self.n_unitigs, int(self.raw.unitig_total_bases)
         return (self._dl(self.raw.unitig_off, (n + 1) * 8, np.uint64, (n + 1,)), self._dl(self.raw.unitig_bases, tb, np.uint8, (tb,)))
 
+    def check(self) -> dict:
+        """The verifier's digests of this rank's share (snk_dev_check_graph, SNK_CHECK_DIGEST_ONLY: the unitigs cross the table
+        shares, so the graph rules are the whole job's to check).  Digests add up over the ranks to the one-GPU job's."""
+        r = self.raw
+        return self._e.check_graph_ptrs(self.K, _lib.CHECK_DIGEST_ONLY, 0, self.n_kmers, r.keys, r.counts, r.ctx, self.n_unitigs,
+                                        r.unitig_off, r.unitig_bases)
+
     def unitigs(self) -> list[str]:
         """Canonical unitigs this rank wrote (the ones whose head fragment it owns), sorted by BVComp; the union over the ranks
         is the data set's unitig set."""
