@@ -13,9 +13,12 @@
 
 static thread_local char g_last_error[512] = "";
 
+hipError_t snk_enter(snk_ctx* ctx) { return hipSetDevice(ctx->device); }
+
 void snk_set_mlen(snk_ctx* ctx, const snk_params* p) {
     uint32_t m = (p->flags & SNK_F_LONG_MINIMISER) ? (uint32_t)SNK_M_LONG : (uint32_t)SNK_M_OF(p->K);
-    if (ctx->opts.set[snk_opt_index("minimiser_len")]) { const long long v = ctx->opts.v[snk_opt_index("minimiser_len")]; if (v == SNK_M_LONG || v == SNK_M_OF(p->K)) m = (uint32_t)v; }
+    const unsigned long long v = snk_opt_u64(ctx, SNK_OPT_minimiser_len);      // (0 unset)
+    if (v == SNK_M_LONG || v == SNK_M_OF(p->K)) m = (uint32_t)v;
     ctx->mlen = m;
 }
 
@@ -110,7 +113,7 @@ bool va_init(snk_ctx* ctx) {
     if (ctx->va_state) return ctx->va_state > 0;
     ctx->va_state = -1;
     // option arena_vmm = 0: the cached hipMalloc blocks of rounds 1-3
-    { const int ix = snk_opt_index("arena_vmm"); if (ctx->opts.set[ix] && ctx->opts.v[ix] == 0) return false; }
+    if (snk_opt_u64(ctx, SNK_OPT_arena_vmm) == 0) return false;
     if (!va_reserve(ctx)) return false;
     ctx->va_state = 1;
     return true;
@@ -436,7 +439,7 @@ void snk_ctx_plan_mem(snk_ctx* ctx) {
     size_t fr = 0, tot = 0;
     ctx->plan_mem = ctx->device_mem_total;
     ctx->plan_mapped = (uint64_t)ctx->cached_bytes;
-    { const int ix = snk_opt_index("plan_mem_mb"); if (ix >= 0 && ctx->opts.set[ix] && ctx->opts.v[ix] > 0) { ctx->plan_mem = (uint64_t)ctx->opts.v[ix] << 20; return; } }      // (tests: a small device)
+    { const long long mb = (long long)snk_opt_u64(ctx, SNK_OPT_plan_mem_mb); if (mb > 0) { ctx->plan_mem = (uint64_t)mb << 20; return; } }      // (tests: a small device)
     if (hipMemGetInfo(&fr, &tot) != hipSuccess) { (void)hipGetLastError(); return; }
     uint64_t avail = (uint64_t)fr + (uint64_t)ctx->cached_bytes;      // (cached_bytes: the arena's mapped chunks and the plain blocks)
     avail &= ~((8ull << 30) - 1);

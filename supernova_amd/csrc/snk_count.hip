@@ -810,13 +810,12 @@ int launch(hipStream_t st, const snk_count_args& a, char* err, size_t errcap) {
 
 // Workgroups walk strided bucket lists: 2 M one-bucket workgroups spend ~8 % of the kernel in dispatch (73.7 ms at 1e8
 // reads); exactly one residency wave (grid = 2 x CUs) is no better (73.5: whoever finishes early idles to the end); 32-64
-// waves keep both the dispatch cost and the tail small (67.3 ms).  SNK_COUNT_PERSIST sets the number of residency waves.
+// waves keep both the dispatch cost and the tail small (67.3 ms).  `persist` (option count_persist) is the number of residency waves.
 template <int K, bool G>
-int regions(uint32_t nseg, uint32_t NB, uint32_t bc_mode, uint32_t* out, char* err, size_t errcap) {
+int regions(uint32_t nseg, uint32_t NB, uint32_t bc_mode, uint32_t persist, uint32_t* out, char* err, size_t errcap) {
     auto kern = nseg > 1 ? snk_count_kernel<K, cfg<K>::THREADS, cfg<K>::SLOTS, G, true> : snk_count_kernel<K, cfg<K>::THREADS, cfg<K>::SLOTS, G, false>;
     size_t lds = lds_bytes<K, G>(bc_mode);
     SNK_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    uint32_t persist = snk_opt_u32("count_persist", 32);
     if (persist == 0) persist = 1;
     int per_cu = 0, dev = 0, n_cu = 256;
     SNK_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, cfg<K>::THREADS, lds));
@@ -863,10 +862,10 @@ uint32_t snk_count_limit(uint32_t K, uint32_t grouped, uint32_t tight) {
     const uint32_t S = K == 48 ? cfg<48>::SLOTS : cfg<60>::SLOTS, T = K == 48 ? cfg<48>::THREADS : cfg<60>::THREADS;
     return tight ? (tight & 0xFFFFu) : S - T - 64;
 }
-int snk_count_regions(uint32_t K, uint32_t grouped, uint32_t nseg, uint32_t NB, uint32_t bc_mode, uint32_t* n_regions, char* err, size_t errcap) {
-    if (grouped) return regions<48, true>(nseg, NB, bc_mode, n_regions, err, errcap);
-    if (K == 60) return regions<60, false>(nseg, NB, bc_mode, n_regions, err, errcap);
-    return regions<48, false>(nseg, NB, bc_mode, n_regions, err, errcap);
+int snk_count_regions(uint32_t K, uint32_t grouped, uint32_t nseg, uint32_t NB, uint32_t bc_mode, uint32_t persist, uint32_t* n_regions, char* err, size_t errcap) {
+    if (grouped) return regions<48, true>(nseg, NB, bc_mode, persist, n_regions, err, errcap);
+    if (K == 60) return regions<60, false>(nseg, NB, bc_mode, persist, n_regions, err, errcap);
+    return regions<48, false>(nseg, NB, bc_mode, persist, n_regions, err, errcap);
 }
 
 int snk_launch_count(uint32_t K, hipStream_t st, const snk_count_args& a, char* err, size_t errcap) {

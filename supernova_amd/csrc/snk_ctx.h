@@ -83,10 +83,10 @@ struct snk_ctx {
     void (*shard_host_free)(void*) = nullptr;
 };
 
-// every top-level entry point: the context's device is current and its options are the calling thread's
+// every top-level entry point: the context's device is current
 hipError_t snk_enter(snk_ctx* ctx);
 void snk_set_error(char* err, size_t errcap, const char* fmt, ...);
-void snk_set_mlen(snk_ctx* ctx, const snk_params* p);      // ctx->mlen from the call's K and flags (SNK_MINIMISER_LEN=16|20 overrides: tests)
+void snk_set_mlen(snk_ctx* ctx, const snk_params* p);      // ctx->mlen from the call's K and flags (option minimiser_len = 16|20 overrides: tests)
 // every host wait for a stream goes through here: the calling thread's count is what the sharded step reports as
 // host_syncs (a host thread = a rank)
 hipError_t snk_sync_at(hipStream_t st, const char* file, int line);     // SNK_SYNC_TRACE=1: every wait is logged with its site

@@ -739,7 +739,7 @@ extern "C" int snk_dev_ingest_df_count_graph(snk_ctx* ctx, snk_df_files* f, uint
     // (measured, tools/r6_df_errors.py: on clean data the compact form is as fast as the streamed job -- 0.43 against 0.46 s per 100 M reads:
     // 382 small partition launches on the copies' stream cost 52 ms, one resident launch 30 -- and on error-rich data much faster.  So the
     // compact form is what runs unless the caller asks for the streamed job, whose point is that the reads are never resident in any form.)
-    const bool streamed = snk_opt_u32("df_stream", 0) == 2 && !(p->flags & SNK_F_GROUPED);
+    const bool streamed = snk_opt_u32(ctx, SNK_OPT_df_stream) == 2 && !(p->flags & SNK_F_GROUPED);
     struct obuf { uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr; } O[NSLOT];
     auto drop = [&]() {
         (void)hipStreamSynchronize(io->cs);

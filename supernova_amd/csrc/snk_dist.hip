@@ -41,7 +41,7 @@ int snk_shard_begin(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, 
     S->circ_all = nullptr; S->join_circles = 0;
     const uint16_t* good_len = (const uint16_t*)in->good_len;
     int rc;
-    const bool fused = in->n_reads && snk_fused_trim_ok(in);      // the trim inside the partition kernel (snk_msp.hip)
+    const bool fused = in->n_reads && snk_fused_trim_ok(ctx, in);      // the trim inside the partition kernel (snk_msp.hip)
     snk_fused_trim ft;
     if (!good_len) {
         void* gl;
@@ -115,7 +115,7 @@ int snk_shard_job_add(snk_ctx* ctx, const snk_dev_reads* slab, hipStream_t st, c
     if (slab->good_len) {
         SNK_HIP_TRY(hipMemcpyAsync(gl, slab->good_len, slab->n_reads * 2, hipMemcpyDeviceToDevice, st));
         rc = snk_partition_add(ctx, st, &S->job, &r, gl, nullptr, err, errcap);
-    } else if (snk_fused_trim_ok(&r)) {
+    } else if (snk_fused_trim_ok(ctx, &r)) {
         snk_fused_trim ft;
         ft.quals = r.quals; ft.qstride = r.qstride; ft.lens = r.lens; ft.min_qual = S->params.min_qual; ft.good_out = gl;
         rc = snk_partition_add(ctx, st, &S->job, &r, gl, &ft, err, errcap);

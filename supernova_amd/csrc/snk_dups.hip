@@ -282,7 +282,7 @@ static int mark_dups_impl(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_p
         const uint32_t ebits = bits_of(emax), obits = m ? bits_of((uint64_t)omax - omin) : 0u, total_bits = ebits + obits + 10u;
         const unsigned long long* skey;
         const uint32_t* sid;
-        const bool one_sort = total_bits <= 62 && !snk_opt_u32("dups_two_sorts", 0);
+        const bool one_sort = total_bits <= 62 && !snk_opt_u32(ctx, SNK_OPT_dups_two_sorts);
         if (one_sort) {
             // the reference's record order (edge, offset, mate head, read id) in ONE stable sort over total_bits + 1 bits (the bench graph: 42)
             hipLaunchKernelGGL(dup_composite_kernel, dim3(gn), dim3(256), 0, st, key, head, n, m ? omin : 0u, obits, total_bits);

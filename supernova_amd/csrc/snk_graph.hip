@@ -642,7 +642,7 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
                       const uint2** rk_out, uint32_t* n_circles, uint32_t* rounds,
                       char* err, size_t errcap) {
     const uint64_t ns = 2 * n;
-    if (ns < 4096 || snk_opt_u32("rank_wyllie", 0))
+    if (ns < 4096 || snk_opt_u32(ctx, SNK_OPT_rank_wyllie))
         return rank_lists_wyllie(ctx, st, link, n, weights, circ, rk_out, n_circles, rounds, err, errcap);
     uint32_t cut_total = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -652,7 +652,7 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
     G_ALLOC(flag32, uint32_t, ns + 1);
     G_ALLOC(sid, uint32_t, ns + 1);
     SNK_HIP_TRY(hipMemsetAsync(flag32 + ns, 0, 4, st));
-    const uint32_t split_mask = (1u << snk_opt_u32("split_log2", 5)) - 1u;
+    const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
     hipLaunchKernelGGL(spl_mark_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, ns, split_mask, spl, flag32);
     {
         size_t tb = 0;
@@ -691,7 +691,7 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
     uint2* rk = nullptr;
     bool converged = false, unranked = false;
     G_ALLOC(rk, uint2, ns);
-    const int batch0 = (int)snk_opt_u32("rank_round_batch0", 12);
+    const int batch0 = (int)snk_opt_u32(ctx, SNK_OPT_rank_round_batch0);
     for (int r = 0; r < max_rounds && !converged;) {
         const int upto = r == 0 ? (batch0 < max_rounds ? batch0 : max_rounds) : max_rounds;
         SNK_HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
@@ -1556,12 +1556,12 @@ int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
     if (fgroup) G_ALLOC(ugroup, uint32_t, U + 1);
     G_ALLOC(prov, uint8_t, h_tot + 1);
     G_ALLOC(final_bases, uint8_t, h_tot + 1);
-    const bool jdbg = snk_opt_u32("join_dbg", 0) != 0;
+    const bool jdbg = snk_opt_u32(ctx, SNK_OPT_join_dbg) != 0;
     if (jdbg) { SNK_HIP_TRY(hipMemsetAsync(prov, 0xEE, h_tot + 1, st)); SNK_HIP_TRY(hipMemsetAsync(final_bases, 0xEE, h_tot + 1, st)); fprintf(stderr, "[snk join dbg] F %llu unitigs %llu bases %llu\n", (unsigned long long)F, (unsigned long long)U, (unsigned long long)h_tot); }
     hipLaunchKernelGGL(jhead_place_kernel, dim3(nblk(F)), dim3(TB), 0, st, pl_pid, pl_circ, hflag, hidx, hoff, F, pid_base, poff, uoff, ucirc, fgroup, ugroup);
     SNK_HIP_TRY(hipMemcpyAsync(uoff + U, hoff + F, 8, hipMemcpyDeviceToDevice, st));
     // copy every fragment into place
-    hipLaunchKernelGGL(jemit_kernel, dim3((unsigned)std::min<uint64_t>((F + 31) / 32, 1ull << std::min(22u, snk_opt_u32("emit_grid_log2", 22)))), dim3(256), 0, st, F, boff, fbases, pl_pid, pl_koff, nk, poff, pid_base, K, prov);
+    hipLaunchKernelGGL(jemit_kernel, dim3((unsigned)std::min<uint64_t>((F + 31) / 32, 1ull << std::min(22u, snk_opt_u32(ctx, SNK_OPT_emit_grid_log2)))), dim3(256), 0, st, F, boff, fbases, pl_pid, pl_koff, nk, poff, pid_base, K, prov);
     if (jdbg && (rc = jdbg_count(ctx, st, "provisional bases after the fragments' copies", prov, h_tot, err, errcap))) return rc;
     // circles that were cut at an arbitrary fragment boundary: rotate to the reference's cut (minimum k-mer, forward)
     {
@@ -1724,7 +1724,7 @@ int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk
     G_ALLOC(flag32, uint32_t, ns + 1);
     G_ALLOC(sid, uint32_t, ns + 1);
     SNK_HIP_TRY(hipMemsetAsync(flag32 + ns, 0, 4, st));
-    const uint32_t split_mask = (1u << snk_opt_u32("split_log2", 5)) - 1u;
+    const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
     if (ns) hipLaunchKernelGGL(spl_mark_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, ns, split_mask, spl, flag32);
     {
         size_t tb = 0;
@@ -1779,7 +1779,7 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
     while ((1ull << (max_rounds - 1)) < m + 1) ++max_rounds;
     int cur = 0;
     bool converged = false, first = true;
-    const int BATCH_R = (int)snk_opt_u32("rank_round_batch", 8);
+    const int BATCH_R = (int)snk_opt_u32(ctx, SNK_OPT_rank_round_batch);
     for (int r = 0; r < max_rounds && !converged;) {
         int did = 0;
         for (; did < BATCH_R && r < max_rounds && m; ++did, ++r) {

@@ -48,9 +48,9 @@ struct hbv_tables {
 // The host flood walks a few hundred MB of tables at random: with 4-KB pages every access is a TLB miss on top of the cache miss.  Large
 // host arrays are asked for on 2-MB boundaries with MADV_HUGEPAGE BEFORE they are touched (transparent huge pages are "madvise" on these
 // hosts); free() releases them.  Best effort: without huge pages the arrays are what they were.
-bool hbv_huge_pages = true;          // option hbv_huge_pages (a measurement switch: set by the entry points, read here)
-void* huge_alloc(size_t bytes) {
-    if (!hbv_huge_pages || bytes < ((size_t)4 << 20)) return malloc(bytes ? bytes : 1);
+// `huge`: option hbv_huge_pages (a measurement switch).
+void* huge_alloc(size_t bytes, bool huge) {
+    if (!huge || bytes < ((size_t)4 << 20)) return malloc(bytes ? bytes : 1);
     void* p = nullptr;
     const size_t len = (bytes + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
     if (posix_memalign(&p, (size_t)2 << 20, len) != 0) return malloc(bytes);
@@ -61,25 +61,26 @@ template <typename T>
 struct huge_vec {                      // the little of std::vector the tables need; never value-initialised
     T* p = nullptr;
     size_t n = 0;
-    huge_vec() = default;
+    bool huge;
+    explicit huge_vec(bool huge_pages) : huge(huge_pages) {}
     huge_vec(const huge_vec&) = delete;
     huge_vec& operator=(const huge_vec&) = delete;
     ~huge_vec() { free(p); }
-    bool resize(size_t m) { free(p); p = (T*)huge_alloc((m ? m : 1) * sizeof(T)); n = p ? m : 0; return p != nullptr; }
+    bool resize(size_t m) { free(p); p = (T*)huge_alloc((m ? m : 1) * sizeof(T), huge); n = p ? m : 0; return p != nullptr; }
     T* data() { return p; }
     const T* data() const { return p; }
     T& operator[](size_t i) { return p[i]; }
     const T& operator[](size_t i) const { return p[i]; }
 };
 
-int hbv_alloc_out(uint64_t U, uint64_t nruns, snk_hbv* out, char* err, size_t errcap) {
+int hbv_alloc_out(uint64_t U, uint64_t nruns, bool huge, snk_hbv* out, char* err, size_t errcap) {
     out->n_vertices = (int32_t)nruns;
-    out->fwd_xlat = (int32_t*)huge_alloc(U * 4);
-    out->rev_xlat = (int32_t*)huge_alloc(U * 4);
-    out->v_left = (int32_t*)huge_alloc(2 * U * 4);
-    out->v_right = (int32_t*)huge_alloc(2 * U * 4);
-    out->src_unitig = (int32_t*)huge_alloc(2 * U * 4);
-    out->is_rc = (uint8_t*)huge_alloc(2 * U);
+    out->fwd_xlat = (int32_t*)huge_alloc(U * 4, huge);
+    out->rev_xlat = (int32_t*)huge_alloc(U * 4, huge);
+    out->v_left = (int32_t*)huge_alloc(2 * U * 4, huge);
+    out->v_right = (int32_t*)huge_alloc(2 * U * 4, huge);
+    out->src_unitig = (int32_t*)huge_alloc(2 * U * 4, huge);
+    out->is_rc = (uint8_t*)huge_alloc(2 * U, huge);
     if (!out->fwd_xlat || !out->rev_xlat || !out->v_left || !out->v_right || !out->src_unitig || !out->is_rc) {
         snk_hbv_free(out);
         return snk_fail(SNK_E_NOMEM, err, errcap, "snk_hbv: host allocation failed");
@@ -155,19 +156,20 @@ void hbv_flood_component(const hbv_tables& t, uint64_t e0, int rc0, int32_t* vid
     if (want_depth && visited >= 100000)
         fprintf(stderr, "[snk hbv] component of %llu edge copies: %u breadth-first levels (%.1f copies per level)\n", (unsigned long long)visited, depth + 1, (double)visited / (depth + 1));
 }
-// Fills every array of `out`: every component in seed order.
-int hbv_flood(uint64_t U, const uint8_t* pal, const uint32_t* ee, uint64_t n_ee, const int32_t* vtx_of, const uint64_t* run_beg,
+// Fills every array of `out`: every component in seed order.  ctx NULL (snk_hbv_from_unitigs has none): the options' defaults.
+int hbv_flood(const snk_ctx* ctx, uint64_t U, const uint8_t* pal, const uint32_t* ee, uint64_t n_ee, const int32_t* vtx_of, const uint64_t* run_beg,
               uint64_t nruns, snk_hbv* out, char* err, size_t errcap) {
-    int rc = hbv_alloc_out(U, nruns, out, err, errcap);
+    const bool huge = snk_opt_u32(ctx, SNK_OPT_hbv_huge_pages) != 0;
+    int rc = hbv_alloc_out(U, nruns, huge, out, err, errcap);
     if (rc) return rc;
     for (uint64_t i = 0; i < U; ++i) out->fwd_xlat[i] = out->rev_xlat[i] = -1;
-    huge_vec<int32_t> vidv;
+    huge_vec<int32_t> vidv(huge);
     if (!vidv.resize(nruns + 1)) { snk_hbv_free(out); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_hbv: host allocation failed"); }
     int32_t* vid = vidv.data();
     for (uint64_t i = 0; i < nruns; ++i) vid[i] = -1;
     int32_t next_v = 0, next_e = 0;
     std::vector<uint64_t> q;
-    const hbv_tables t{U, pal, ee, vtx_of, run_beg, snk_opt_u32("hbv_short_queue", 1) != 0};
+    const hbv_tables t{U, pal, ee, vtx_of, run_beg, snk_opt_u32(ctx, SNK_OPT_hbv_short_queue) != 0};
     (void)n_ee;
     for (int pass = 0; pass < 2; ++pass)
         for (uint64_t e0 = 0; e0 < U; ++e0)
@@ -225,7 +227,7 @@ extern "C" int snk_hbv_from_unitigs(uint32_t K, uint64_t U, const uint64_t* off,
     }
     const uint64_t nruns = run_beg.size();
     run_beg.push_back(ee.size());
-    return hbv_flood(U, pal.data(), ee.data(), ee.size(), vtx_of.data(), run_beg.data(), nruns, out, err, errcap);
+    return hbv_flood(nullptr, U, pal.data(), ee.data(), ee.size(), vtx_of.data(), run_beg.data(), nruns, out, err, errcap);
 }
 
 // ---- f2: the involution and the files DF keeps the graph in.
@@ -609,12 +611,12 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     uint32_t nruns = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&nruns, cls + (n_ee - 1), 4, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
-    hbv_huge_pages = snk_opt_u32("hbv_huge_pages", 1) != 0;
+    const bool huge = snk_opt_u32(ctx, SNK_OPT_hbv_huge_pages) != 0;
     std::vector<uint32_t> h_order(U);
-    huge_vec<uint32_t> h_ee;
-    huge_vec<int32_t> h_vtx;
-    huge_vec<uint8_t> h_pal;
-    huge_vec<uint64_t> h_run;
+    huge_vec<uint32_t> h_ee(huge);
+    huge_vec<int32_t> h_vtx(huge);
+    huge_vec<uint8_t> h_pal(huge);
+    huge_vec<uint64_t> h_run(huge);
     auto fetch_tables = [&]() -> hipError_t {       // what a flood on the host reads
         if (!h_ee.resize(n_ee) || !h_vtx.resize(n4) || !h_pal.resize(U) || !h_run.resize((size_t)nruns + 1)) return hipErrorOutOfMemory;
         hipError_t e;
@@ -629,7 +631,7 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     // Measured (tools/hbv_scale_probe.py, profiles/r04_hbv_scale.log): 9.5 M unitigs of per-barcode graphs (every component small) 4.8 s
     // -> 0.19 s per call, the flood itself ~5 ms behind the 30 ms of sorts; 6.1 M unitigs of ONE genome (the connected bulk goes to
     // the host either way) 3.15 -> 2.82 s.
-    const uint64_t dev_min = snk_opt_u64("hbv_dev_min", 1ull << 16);
+    const uint64_t dev_min = snk_opt_u64(ctx, SNK_OPT_hbv_dev_min);
     if (U < dev_min) {
         SNK_HIP_TRY(hipEventRecord(e1, st));
         SNK_HIP_TRY(fetch_tables());
@@ -638,7 +640,7 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
         if (device_ms) (void)hipEventElapsedTime(device_ms, e0, e1);
         (void)hipEventDestroy(e0);
         (void)hipEventDestroy(e1);
-        rc = hbv_flood(U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap);
+        rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap);
         if (rc) return rc;
     } else {
         // the sort buffers are dead: node arrays live in `keys` (64 U bytes), the outputs in `keys2`, the vertex ids in `flag`
@@ -649,7 +651,7 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
         int32_t *d_rev = d_fwd + U, *d_vl = d_rev + U, *d_vr = d_vl + n2, *d_src = d_vr + n2;
         uint8_t* d_isrc = (uint8_t*)(d_src + n2);
         int32_t* d_vid = (int32_t*)flag;
-        const uint32_t big_limit = (uint32_t)snk_opt_u64("hbv_big", 1024);
+        const uint32_t big_limit = snk_opt_u32(ctx, SNK_OPT_hbv_big);
         const uint32_t big_cap = (uint32_t)(n2 / ((uint64_t)big_limit + 1) + 1);
         hbv_big* d_big;
         uint32_t* d_nbig;                      // [0] components for the host, [1] error flag
@@ -675,7 +677,7 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
         SNK_HIP_TRY(hipEventRecord(e1, st));
         uint32_t h_nb[2] = {0, 0};
         SNK_HIP_TRY(hipMemcpyAsync(h_nb, d_nbig, 8, hipMemcpyDeviceToHost, st));
-        if ((rc = hbv_alloc_out(U, nruns, out, err, errcap))) return rc;
+        if ((rc = hbv_alloc_out(U, nruns, huge, out, err, errcap))) return rc;
         SNK_HIP_TRY(hipMemcpyAsync(out->fwd_xlat, d_fwd, U * 4, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(hipMemcpyAsync(out->rev_xlat, d_rev, U * 4, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(hipMemcpyAsync(out->v_left, d_vl, n2 * 4, hipMemcpyDeviceToHost, st));
@@ -690,10 +692,10 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
         const uint32_t n_big = h_nb[0];
         if (h_nb[1]) {              // a bounded loop of the device flood ran out (never seen; the flood on the host does not depend on it)
             snk_hbv_free(out);
-            if (snk_opt_u32("hbv_strict", 0)) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: the device flood gave up (flag %u)", h_nb[1]);
+            if (snk_opt_u32(ctx, SNK_OPT_hbv_strict)) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: the device flood gave up (flag %u)", h_nb[1]);
             SNK_HIP_TRY(fetch_tables());
             SNK_HIP_TRY(snk_sync(st));
-            if ((rc = hbv_flood(U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap))) return rc;
+            if ((rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap))) return rc;
             goto flooded;
         }
         out->n_edges = (int32_t)(n2 - h_flags[1]);
@@ -703,11 +705,11 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
             SNK_HIP_TRY(hipMemcpyAsync(h_big.data(), d_big, (size_t)n_big * sizeof(hbv_big), hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(fetch_tables());
             SNK_HIP_TRY(snk_sync(st));
-            huge_vec<int32_t> vidv;
+            huge_vec<int32_t> vidv(huge);
             if (!vidv.resize((size_t)nruns + 1)) { snk_hbv_free(out); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_hbv: host allocation failed"); }
             int32_t* vid = vidv.data();
             for (uint64_t i = 0; i < nruns; ++i) vid[i] = -1;
-            const hbv_tables t{U, h_pal.data(), h_ee.data(), h_vtx.data(), h_run.data(), snk_opt_u32("hbv_short_queue", 1) != 0};
+            const hbv_tables t{U, h_pal.data(), h_ee.data(), h_vtx.data(), h_run.data(), snk_opt_u32(ctx, SNK_OPT_hbv_short_queue) != 0};
             // Components are independent once their id blocks are known (the device's scans): a host thread each, largest first.  The bulk
             // of a genome graph is TWO components -- the forward copies' and its mirror image, the reverse copies' -- whose floods are NOT
             // each other's mirror (a flood pushes the left vertex's edges before the right vertex's), so both are run, side by side.

@@ -395,7 +395,6 @@ int snk_unitigs_to_host(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t U, co
     catch (...) { return snk_fail(SNK_E_INTERNAL, err, errcap, "unexpected exception"); }
 
 extern "C" int snk_count_graph(snk_ctx* ctx, const snk_reads* in, const snk_params* p, snk_result* out, char* err, size_t errcap) {
-    if (ctx) snk_opts_enter(&ctx->opts);
     // every error exit of the implementation leaves through here: uploads / kernels it queued are waited for (the caller may free
     // its input right after, and the next call reuses the context's staging buffers) and what it malloc'ed into *out is released
     int rc;

@@ -112,8 +112,8 @@ struct snk_count_args {
 };
 int snk_launch_count(uint32_t K, hipStream_t st, const snk_count_args& a, char* err, size_t errcap);
 uint32_t snk_count_slots(uint32_t K);   // LDS table slots per workgroup
-// output regions (= workgroups of every launch) for a table over NB buckets
-int snk_count_regions(uint32_t K, uint32_t grouped, uint32_t nseg, uint32_t NB, uint32_t bc_mode, uint32_t* n_regions, char* err, size_t errcap);
+// output regions (= workgroups of every launch) for a table over NB buckets; persist: residency waves (option count_persist, 0 = 1)
+int snk_count_regions(uint32_t K, uint32_t grouped, uint32_t nseg, uint32_t NB, uint32_t bc_mode, uint32_t persist, uint32_t* n_regions, char* err, size_t errcap);
 // gather the used prefix of every region into one dense table; region_off = exclusive scan of region_cursor
 int snk_launch_compact_regions(hipStream_t st, const snk_u128* keys_in, const uint64_t* vals_in, uint64_t region_cap,
                                uint32_t n_regions, const unsigned long long* region_cursor,

@@ -131,7 +131,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         if (p->K != 48) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "SNK_F_GROUPED: the group id rides in the 32 key bits that are free at K=48 only");
         if (!in->group) return snk_fail(SNK_E_ARG, err, errcap, "SNK_F_GROUPED: snk_dev_reads.group is NULL");
         if (p->min_bc > 0 && in->bc) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "SNK_F_GROUPED: per-group graphs use the frequency rule only (min_bc = 0)");
-        if ((p->flags & SNK_F_GLOBAL_GRAPH) || snk_opt_u32("global_graph", 0)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "SNK_F_GROUPED needs the bucket-local graph stage");
+        if ((p->flags & SNK_F_GLOBAL_GRAPH) || snk_opt_u32(ctx, SNK_OPT_global_graph)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "SNK_F_GROUPED needs the bucket-local graph stage");
     }
     SNK_HIP_TRY(snk_enter(ctx));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
@@ -148,7 +148,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     // ---- K1 trim: inside the partition kernel when the quality rows allow it (its loads ride under the slot reservations),
     // else its own streaming kernel
     const uint16_t* good_len = (const uint16_t*)in->good_len;
-    const bool fused = n_reads && snk_fused_trim_ok(in);
+    const bool fused = n_reads && snk_fused_trim_ok(ctx, in);
     snk_fused_trim ft;
     if (!good_len && n_reads) {
         void* gl = nullptr;
@@ -192,7 +192,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     // looks at its first 1/64 of the buckets and asks for a second partition when they overflow as a rule.
     // ---- is this the data set the context's sizing history was made on?  (one 8-byte read-back: ~40 us)
     bool same_data = true;
-    if (n_reads && p->n_buckets == 0 && snk_opt_u32("input_fp", 1)) {
+    if (n_reads && p->n_buckets == 0 && snk_opt_u32(ctx, SNK_OPT_input_fp)) {
         void* q;
         if ((rc = snk_ctx_alloc(ctx, 64, &q, err, errcap))) return rc;
         unsigned long long* d_fp = (unsigned long long*)q;
@@ -217,9 +217,9 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     ctx->count_tight = 0;
     const uint32_t plain_target = K == 48 ? 5000u : 3500u;
     auto tight_for = [&](double ratio) -> uint32_t {
-        const uint32_t tries = snk_opt_u32("tight_tries", 48) << 16;
-        if (snk_opt_is_set("count_tight")) {
-            const uint32_t v = snk_opt_u32("count_tight", 0);
+        const uint32_t tries = snk_opt_u32(ctx, SNK_OPT_tight_tries) << 16;
+        if (snk_opt_is_set(ctx, SNK_OPT_count_tight)) {
+            const uint32_t v = snk_opt_u32(ctx, SNK_OPT_count_tight);
             return v ? (std::min(std::max(v, 256u), snk_count_slots(K) - 64u) | tries) : 0u;
         }
         const bool full = grouped || (ratio > 0.0 && 0.65 * (double)snk_count_limit(K, 0u, 0u) / ratio < (double)plain_target);
@@ -229,25 +229,25 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     // (... unless the bit filter in front of the table is on -- min_freq >= 2: then the table only sees the (group, k-mer) pairs that can be retained,
     // one in ten, and a bucket is as large as one batch of 512 records and ten instances per lane allow: beyond 6000 buckets start to fall out
     // of the filter -- 92.9 ms at 4800, 92.2 at 5600, 94.6 at 6400, `profiles/r05_count_screen_groups.log`)
-    const bool group_screen = grouped && snk_opt_u32("count_screen", 1) != 0 && p->min_freq >= (snk_opt_u32("count_screen", 1) >= 2 ? 2u : 3u);
+    const bool group_screen = grouped && snk_opt_u32(ctx, SNK_OPT_count_screen) != 0 && p->min_freq >= (snk_opt_u32(ctx, SNK_OPT_count_screen) >= 2 ? 2u : 3u);
     auto default_target_now = [&]() -> uint32_t { return grouped ? ((group_screen && ctx->count_tight) ? 5200u : (uint32_t)(0.74 * snk_count_limit(K, 1u, ctx->count_tight))) : plain_target; };
-    const bool target_forced = snk_opt_is_set("target_inst");
+    const bool target_forced = snk_opt_is_set(ctx, SNK_OPT_target_inst);
     // ... and the RETAINED k-mers of a bucket are one chunk of the bucket-local graph stage, whose one-wave kernels hold 256 of them
     // (larger chunks take the slower big-chunk variants): at half the coverage twice as many k-mers survive per instance, every other
     // chunk was over the line and the graph stage took 81 instead of ~58 ms.  From the previous call's retained share: chunks of ~180 (28x coverage, with merged chunks behind it: 153.2 ms at 120, 149.5 at 150, 147.7 at 180, 147.5 at 210).
     const double retain = (same_data && ctx->retain_ratio > 0.0 && ctx->claim_ratio_reads == n_reads && ctx->claim_ratio_k == K * 2 + (grouped ? 1u : 0u) + 256u * ctx->mlen) ? ctx->retain_ratio : 0.0;
     auto target_for = [&](double ratio) -> uint32_t {
         const uint32_t default_target = default_target_now();
-        if (target_forced) return snk_opt_u32("target_inst", default_target);
-        if (ctx->count_screen && !grouped) return snk_opt_u32("screen_target", 4000);
+        if (target_forced) return snk_opt_u32(ctx, SNK_OPT_target_inst);
+        if (ctx->count_screen && !grouped) return snk_opt_u32(ctx, SNK_OPT_screen_target);
         if (retain > 0.0 && (!grouped || group_screen)) {       // (groups behind the bit filter: buckets of 5200 instances, unless that many would retain more than a graph chunk holds)
-            const double t = (double)snk_opt_u32("chunk_kmers", 180) / retain;
+            const double t = (double)snk_opt_u32(ctx, SNK_OPT_chunk_kmers) / retain;
             if (t < (double)default_target) {
                 uint32_t tt = t < 600.0 ? 600u : (uint32_t)t;
                 if (ratio > 0.0) {           // the tighter of the two limits
                     const double lim = (double)snk_count_limit(K, 0u, ctx->count_tight);
                     if (0.65 * lim / ratio < (double)default_target) {
-                        const double t2 = 0.01 * snk_opt_u32("bucket_fill_pct", 50) * lim / ratio;
+                        const double t2 = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ratio;
                         if (t2 < (double)tt) tt = t2 < 600.0 ? 600u : (uint32_t)t2;
                     }
                 }
@@ -259,17 +259,17 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         // that would fill them further do best at ~50 % (0.6 % errors: 239 ms with the default size, 186 at 80 %, 154 at 50 %)
         const double lim = (double)snk_count_limit(K, grouped ? 1u : 0u, ctx->count_tight);
         if (0.65 * lim / ratio >= (double)default_target) return default_target;
-        const double t = 0.01 * snk_opt_u32("bucket_fill_pct", 50) * lim / ratio;
+        const double t = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ratio;
         return t >= (double)default_target ? default_target : (t < 600.0 ? 600u : (uint32_t)t);
     };
     const bool have_hint = same_data && ctx->claim_ratio > 0.0 && ctx->claim_ratio_reads == n_reads && ctx->claim_ratio_k == K * 2 + (grouped ? 1u : 0u) + 256u * ctx->mlen;
     double ratio = have_hint ? ctx->claim_ratio : 0.0;
-    const bool adaptive = p->n_buckets == 0 && !target_forced && !grouped && snk_opt_u32("adaptive_buckets", 1) != 0;      // (the per-barcode default is tuned at ratio ~1)
+    const bool adaptive = p->n_buckets == 0 && !target_forced && !grouped && snk_opt_u32(ctx, SNK_OPT_adaptive_buckets) != 0;      // (the per-barcode default is tuned at ratio ~1)
     uint32_t NB = 0;
     snk_partition part;
     snk_table tab;
     void* records = nullptr;
-    const bool local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32("global_graph", 0);
+    const bool local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32(ctx, SNK_OPT_global_graph);
     const uint64_t mark = ctx->alloc_serial;
     const unsigned long long ub_inst = h_plan[0], ub_live = h_plan[1];
     for (int pass = 0; pass < 2; ++pass) {
@@ -281,10 +281,10 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         // (0.6 % errors, ratio 0.21, lose with it: a fifth of their instances are singletons, the first pass costs more than it saves)
         {
             const double r_now = adaptive ? ratio : (have_hint ? ctx->claim_ratio : 0.0);
-            const uint32_t ng = snk_opt_u32("count_screen_ng", 1);
-            ctx->count_screen = (!grouped && K == 48 && p->min_freq >= 3 && (!in->bc || p->min_bc <= 2) && ng && (ng >= 2 || r_now > 0.01 * snk_opt_u32("screen_ratio_pct", 30))) ? 3u : 0u;
-            if (snk_opt_is_set("count_tight") && snk_opt_u32("count_tight", 1) == 0u) ctx->count_screen = 0;      // (the filter comes with booked slots)
-            if (ctx->count_screen && !ctx->count_tight) ctx->count_tight = (snk_count_slots(K) - snk_count_slots(K) / 16u) | (snk_opt_u32("tight_tries", 48) << 16);
+            const uint32_t ng = snk_opt_u32(ctx, SNK_OPT_count_screen_ng);
+            ctx->count_screen = (!grouped && K == 48 && p->min_freq >= 3 && (!in->bc || p->min_bc <= 2) && ng && (ng >= 2 || r_now > 0.01 * snk_opt_u32(ctx, SNK_OPT_screen_ratio_pct))) ? 3u : 0u;
+            if (snk_opt_is_set(ctx, SNK_OPT_count_tight) && snk_opt_u32(ctx, SNK_OPT_count_tight) == 0u) ctx->count_screen = 0;      // (the filter comes with booked slots)
+            if (ctx->count_screen && !ctx->count_tight) ctx->count_tight = (snk_count_slots(K) - snk_count_slots(K) / 16u) | (snk_opt_u32(ctx, SNK_OPT_tight_tries) << 16);
             if (ctx->count_screen && r_now > 0.0) ctx->screen_ratio = r_now;      // (what the screened call reports is the table's view: the decision keeps the ratio it was made on)
             ctx->last_count_limit = snk_count_limit(K, grouped ? 1u : 0u, ctx->count_tight);
             if ((ctx->count_screen || (group_screen && ctx->count_tight)) && K == 48) ctx->last_count_limit = std::min(ctx->last_count_limit, snk_count_screen_limit());
@@ -309,7 +309,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         h_plan[0] = ub_inst; h_plan[1] = ub_live;
         // ---- a job whose slots would not fit: bucket-range passes over one slot array (snk_stages.h); the count stage's range hook
         //      partitions range r right before range r is counted
-        const uint32_t n_passes = (NB >= 2 && !snk_opt_u32("msp_dense", 0)) ? std::min<uint32_t>(snk_partition_passes_needed(ctx, K, NB, ub_inst, ub_live, grouped), NB) : 1u;
+        const uint32_t n_passes = (NB >= 2 && !snk_opt_u32(ctx, SNK_OPT_msp_dense)) ? std::min<uint32_t>(snk_partition_passes_needed(ctx, K, NB, ub_inst, ub_live, grouped), NB) : 1u;
         ctx->last_partition_passes = n_passes;
         if (n_passes > 1) {
             snk_partition_passes PS;
@@ -369,7 +369,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         // measurement aid: SNK_OVERLAP_PROBE = 1: the partition kernel once more (into scratch) on a second stream NEXT TO the count
         // kernel; 2: the same launch alone (waited for before the count starts); +4: the second stream has high priority;
         // SNK_OVERLAP_PROBE_DBG = the relaunched kernel's dbg mode (1 no record stores, 2 no slot atomics, 3 scan only)
-        const uint32_t oprobe = snk_opt_u32("overlap_probe", 0);
+        const uint32_t oprobe = snk_opt_u32(ctx, SNK_OPT_overlap_probe);
         hipStream_t s2 = nullptr, s2hi = nullptr;      // (a measurement aid of tuning builds: created per probed call, destroyed below)
         hipStream_t sp2 = nullptr;
         hipEvent_t pe[3] = {nullptr, nullptr, nullptr};
@@ -380,7 +380,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
             SNK_HIP_TRY(hipEventRecord(pe[0], st));
             SNK_HIP_TRY(hipStreamWaitEvent(sp2, pe[0], 0));
             SNK_HIP_TRY(hipEventRecord(pe[1], sp2));
-            if ((rc = snk_probe_relaunch_msp(ctx, sp2, snk_opt_u32("overlap_probe_dbg", 0), err, errcap))) return rc;
+            if ((rc = snk_probe_relaunch_msp(ctx, sp2, snk_opt_u32(ctx, SNK_OPT_overlap_probe_dbg), err, errcap))) return rc;
             SNK_HIP_TRY(hipEventRecord(pe[2], sp2));
             if ((oprobe & 3u) == 2u) SNK_HIP_TRY(hipStreamSynchronize(sp2));
         }
@@ -469,11 +469,11 @@ extern "C" int snk_dev_stream_begin(snk_ctx* ctx, const snk_params* p, uint32_t 
     uint32_t NB = p->n_buckets;
     if (NB == 0) {
         uint32_t target = K == 48 ? 5000u : 3500u;
-        if (snk_opt_is_set("target_inst")) target = snk_opt_u32("target_inst", target);
+        if (snk_opt_is_set(ctx, SNK_OPT_target_inst)) target = snk_opt_u32(ctx, SNK_OPT_target_inst);
         else if (ctx->claim_ratio > 0.0 && ctx->claim_ratio_reads == total_reads_ub && ctx->claim_ratio_k == K * 2 + 256u * ctx->mlen) {
             const double lim = (double)snk_count_limit(K, 0u, ctx->count_tight);
             if (0.65 * lim / ctx->claim_ratio < (double)target) {
-                const double t = 0.01 * snk_opt_u32("bucket_fill_pct", 50) * lim / ctx->claim_ratio;
+                const double t = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ctx->claim_ratio;
                 target = t < 600.0 ? 600u : (uint32_t)t;
             }
         }
@@ -521,7 +521,7 @@ extern "C" int snk_dev_stream_append(snk_ctx* ctx, const snk_dev_reads* slab, vo
     if (slab->good_len) {
         SNK_HIP_TRY(hipMemcpyAsync(gl, slab->good_len, slab->n_reads * 2, hipMemcpyDeviceToDevice, st));
         rc = snk_partition_add(ctx, st, &j->J, &r, gl, nullptr, err, errcap);
-    } else if (snk_fused_trim_ok(&r)) {
+    } else if (snk_fused_trim_ok(ctx, &r)) {
         snk_fused_trim ft;
         ft.quals = r.quals; ft.qstride = r.qstride; ft.lens = r.lens; ft.min_qual = j->p.min_qual; ft.good_out = gl;
         rc = snk_partition_add(ctx, st, &j->J, &r, gl, &ft, err, errcap);
@@ -566,7 +566,7 @@ extern "C" int snk_dev_stream_finish(snk_ctx* ctx, snk_dev_result* out, void* st
     out->n_buckets = j->NB;
     out->n_supermers = part.n_supermers;
     out->n_overflow = part.n_overflow;
-    const bool local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32("global_graph", 0);
+    const bool local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32(ctx, SNK_OPT_global_graph);
     snk_hot hot;
     if ((rc = snk_stage_hot(ctx, st, K, false, &part, &hot, err, errcap))) return rc;
     out->n_hot_buckets = hot.n_hot;

@@ -105,7 +105,7 @@ struct snk_fused_trim {
     const void* quals; uint32_t qstride; const void* lens; uint32_t min_qual;
     uint16_t* good_out;            // [n_reads] the good lengths, as snk_dev_trim writes them
 };
-bool snk_fused_trim_ok(const snk_dev_reads* in);
+bool snk_fused_trim_ok(const snk_ctx* ctx, const snk_dev_reads* in);
 int snk_stage_partition(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_reads* in, const uint16_t* good_len, uint32_t NB,
                         unsigned long long n_inst, unsigned long long n_live, bool grouped, uint32_t* status, snk_partition* out,
                         char* err, size_t errcap, const unsigned long long* d_plan = nullptr, unsigned long long* h_plan = nullptr,

@@ -23,14 +23,14 @@ int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, uint32_t K, const void* 
                           uint32_t* status, bool want_sort, snk_table* out, char* err, size_t errcap, const snk_count_ranges* ranges, snk_count_pilot* pilot,
                           const uint32_t* gidx, bool defer_compact, const snk_hot* hot) {
     if (hot && hot->NBv == 0) hot = nullptr;
-    defer_compact = defer_compact && !want_sort && snk_opt_u32("defer_compact", 1) != 0;
+    defer_compact = defer_compact && !want_sort && snk_opt_u32(ctx, SNK_OPT_defer_compact) != 0;
     int rc;
     snk_phase_timer tm(st), kt(st);
     tm.mark();
     // ---- K5-K8 count + filter into a region-partitioned table, then gather the regions densely.
     // Every retained k-mer has >= min_freq instances; deep coverage retains far fewer (56x: ~1/38 of them).
     uint32_t n_regions = 1;
-    if ((rc = snk_count_regions(K, grouped, nseg, NB, bc_mode, &n_regions, err, errcap))) return rc;
+    if ((rc = snk_count_regions(K, grouped, nseg, NB, bc_mode, snk_opt_u32(ctx, SNK_OPT_count_persist), &n_regions, err, errcap))) return rc;
     uint64_t est = n_inst_hint / (min_freq > 1 ? 12 : 1) + 4096;     // first call only; a wrong guess costs one re-run
     // A job in bucket-range passes is short of memory, and instances / 12 are 2 bytes per instance it may not have (deep coverage retains 1 in 38):
     // it starts from 1 in 32 and lets its first range say what the data retain (`range0_probe` below: one repeated range when that is more)
@@ -94,7 +94,7 @@ int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, uint32_t K, const void* 
         // (per-barcode groups, min_freq >= 3: three reads of one barcode over one k-mer are rare, two -- the mates of a pair -- are not; with
         // min_freq 2 a quarter of the instances pass the filter and the larger buckets cost more than they save: 428 against 270 ms.
         // SNK_COUNT_SCREEN: 0 never, 1 at min_freq >= 3, 2 at min_freq >= 2 as well)
-        { const uint32_t sc = grouped ? snk_opt_u32("count_screen", 1) : 0u; ca.screen = (sc && min_freq >= (sc >= 2 ? 2u : 3u)) ? std::min(min_freq, 3u) : 0u; }
+        { const uint32_t sc = grouped ? snk_opt_u32(ctx, SNK_OPT_count_screen) : 0u; ca.screen = (sc && min_freq >= (sc >= 2 ? 2u : 3u)) ? std::min(min_freq, 3u) : 0u; }
         if (!grouped && K == 48 && ctx->count_screen && ctx->count_tight && bc_mode <= 2u) ca.screen = std::min(std::min(min_freq, 3u), ctx->count_screen);
         ca.bucket0 = 0;
         ca.out_keys = keys_r;
@@ -107,7 +107,7 @@ int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, uint32_t K, const void* 
         ca.chunk_base = chunk_base;
         ca.extra = extra;
         ca.extra_cap = extra_cap;
-        ca.dbg = snk_opt_u32("count_dbg", 0);
+        ca.dbg = snk_opt_u32(ctx, SNK_OPT_count_dbg);
         ca.prof = nullptr;
 #ifdef SNK_COUNT_PROF
         {
@@ -143,7 +143,7 @@ int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, uint32_t K, const void* 
                 // ... and should the caller partition again (retarget), its next run sizes its regions from what survived here, not from the
                 // blanket instances / 12: at 1.5 % errors that is 20 GB of regions mapped for 7 GB of survivors -- on a first call the arena
                 // grows by what is asked for, at the driver's ~30 ms per GB
-                if (b0 == 0 && sum && snk_opt_u32("pilot_est", 1)) { ctx->last_n_kmers = (uint64_t)((double)sum * ((double)NB / NBp)); ctx->last_n_instances = n_inst_hint; }
+                if (b0 == 0 && sum && snk_opt_u32(ctx, SNK_OPT_pilot_est)) { ctx->last_n_kmers = (uint64_t)((double)sum * ((double)NB / NBp)); ctx->last_n_instances = n_inst_hint; }
             }
             if (pilot->agree && (r2 = pilot->agree(pilot->user, &pilot->per_bucket))) return snk_fail(SNK_E_INTERNAL, err, errcap, "count: the pilot's exchange failed (%d)", r2);
             *retarget = pilot->per_bucket > 0.85 * snk_count_limit(K, grouped, ctx->count_tight) && !h_p[1];
@@ -346,10 +346,10 @@ __global__ void __launch_bounds__(256) cursor_exact_kernel(const uint64_t* __res
     if (b < NB) cursor[b] = (uint32_t)((seg[(uint64_t)NB + b] - seg[b]) + (seg[3ull * NB + b] - seg[2ull * NB + b]));
 }
 // slot reservations stop for a bucket that was handed slot hot_thr (SNK_MSP_HOT_FACTOR x capacity, 0 = never)
-static uint32_t msp_hot_thr(uint32_t cap) {
-    const uint64_t f = snk_opt_u32("msp_hot_factor", 32);
+static uint32_t msp_hot_thr(const snk_ctx* ctx, uint32_t cap) {
+    const uint64_t f = snk_opt_u32(ctx, SNK_OPT_msp_hot_factor);
     const uint64_t t = f * cap;
-    const uint64_t lo = snk_opt_u32("msp_hot_min", 4096);
+    const uint64_t lo = snk_opt_u32(ctx, SNK_OPT_msp_hot_min);
     return f == 0 ? 0xFFFFFFFFu : (uint32_t)(t < lo ? lo : (t > 0x7FFFFFFFull ? 0x7FFFFFFFull : t));
 }
 // (instances, contributing reads) of one slab added to the streamed job's counters
@@ -451,9 +451,9 @@ int snk_stage_partition_plan(snk_ctx* ctx, hipStream_t st, uint32_t K, const uin
     return SNK_OK;
 }
 
-bool snk_fused_trim_ok(const snk_dev_reads* in) {
+bool snk_fused_trim_ok(const snk_ctx* ctx, const snk_dev_reads* in) {
     return in->quals && !in->good_len && (in->qstride & 3u) == 0 && (((uintptr_t)in->quals) & 3u) == 0 && in->read_len <= 160 && in->qstride >= in->read_len &&
-           (!in->lens || (((uintptr_t)in->lens) & 1u) == 0) && snk_opt_u32("trim_fused", 1) != 0;
+           (!in->lens || (((uintptr_t)in->lens) & 1u) == 0) && snk_opt_u32(ctx, SNK_OPT_trim_fused) != 0;
 }
 
 // expected supermers of a pass and the record slots a bucket gets
@@ -470,7 +470,7 @@ static void partition_capacity(snk_ctx* ctx, uint32_t K, uint32_t NB, unsigned l
     // ONE site), where 2.5 x mean lost a tenth of the supermers to the overflow list, overran it, and ran the pass twice
     // (78 instead of 34 ms).  c is a property of the data set: 48 covers 70x; per-barcode groups see a site once or twice.
     // Overflowing supermers are correct (segment 1), only slower; the slots that stay empty are never touched.
-    const double site_records = (double)snk_opt_u32("msp_site_records", grouped ? 3u : 48u);
+    const double site_records = (double)(snk_opt_is_set(ctx, SNK_OPT_msp_site_records) ? snk_opt_u32(ctx, SNK_OPT_msp_site_records) : grouped ? 3u : 48u);
     // ... and how many sigma is a matter of memory: at 5 the slots are 2.9 x the records (100 M reads: 66 GB of slots for 22 GB of records, nothing
     // overflows); at 3 sigma 0.03 % of the supermers take the overflow list, at 1.2 sigma 2.2 % do, for +1 / +1.5 ms of the 104 ms step
     // (tools/r6_cap_sigma.sh, profiles/r06_cap_sigma.log).  So: 5 sigma while the slots stay below 30 % of the device, 3 above, 1.5 if those are
@@ -480,7 +480,7 @@ static void partition_capacity(snk_ctx* ctx, uint32_t K, uint32_t NB, unsigned l
     // bucket-range passes is short of memory by definition: 1.5 sigma (what saves a pass saves a scan of every read).
     double sig = 5.0;
     const double sigma = std::sqrt(mean * site_records);
-    if (snk_opt_is_set("msp_sigmas_x10")) sig = 0.1 * snk_opt_u32("msp_sigmas_x10", 50);
+    if (snk_opt_is_set(ctx, SNK_OPT_msp_sigmas_x10)) sig = 0.1 * snk_opt_u32(ctx, SNK_OPT_msp_sigmas_x10);
     // (1.5 where that saves a pass -- a pass fewer at 600 and 800 M reads: 73.4 -> 83.3 and 64.5 -> 72.3 Gk-mers/s, 1.5-2 % of the supermers take the overflow lists --
     // and as much slack as the same number of passes holds otherwise: snk_partition_passes_needed leaves its choice in ctx->pass_sigma)
     else if (passes > 1) sig = mean >= 4.0 * site_records ? (ctx->pass_sigma > 0.0 ? ctx->pass_sigma : 1.5) : 5.0;
@@ -492,13 +492,13 @@ static void partition_capacity(snk_ctx* ctx, uint32_t K, uint32_t NB, unsigned l
         // process used before it hands it out, ~33 ms per GB (a second snk_mspedges run on 100 M reads spent 2.06 s mapping its 62.5 GB of
         // 5-sigma slots and 0.5 s computing: profiles/r06_oneshot.log) -- 35 GB of slack cost a second, the overflow list it saves 1.5 ms.
         // So the slack is taken only when the arena has it (a host that wants the last 1.5 ms maps ahead: snk_ctx_reserve, as bench.py does).
-        if (sig > 1.5 && snk_opt_u32("lean_cold", 1)) {
+        if (sig > 1.5 && snk_opt_u32(ctx, SNK_OPT_lean_cold)) {
             const double other = 2.6 * (double)n_inst;          // regions, table, graph stage: ~27 GB per 10 G instances at 56x
             if ((double)ctx->plan_mapped < (mean + sig * sigma + 16.0) * NB * 32.0 + other) sig = 1.5;
         }
     }
     uint64_t cap64 = (uint64_t)(mean + sig * sigma + 16.0);
-    cap64 = cap64 * snk_opt_u32("msp_cap_pct", 100) / 100;
+    cap64 = cap64 * snk_opt_u32(ctx, SNK_OPT_msp_cap_pct) / 100;
     if (cap64 < 2) cap64 = 2;
     cap64 = (cap64 + 1) & ~1ull;
     if (ideal_out) *ideal_out = cap64;
@@ -571,7 +571,7 @@ int partition_dense(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_read
         ma.group = grouped ? (const uint32_t*)in->group : nullptr;
         ma.records = (uint4*)records;
         ma.dense_bkt = bkt; ma.dense_cursor = d_cur; ma.dense_cap = dcap;
-        ma.dbg = snk_opt_u32("msp_dbg", 0);
+        ma.dbg = snk_opt_u32(ctx, SNK_OPT_msp_dbg);
         if (ft) {
             ma.good_len = ft->good_out; ma.quals = (const uint8_t*)ft->quals; ma.qstride = ft->qstride; ma.min_qual = ft->min_qual;
             ma.lens = (const uint16_t*)ft->lens; ma.good_out = ft->good_out; ma.plan = d_fplan;
@@ -737,7 +737,7 @@ int snk_stage_partition(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_
     double est_super = 0;
     uint64_t cap64 = 0;
     partition_capacity(ctx, K, NB, n_inst, n_live, grouped, &est_super, &cap64);
-    if (allow_dense && est_super * 1.25 + 2e6 < 4.0e9 && snk_opt_u32("msp_dense", 0))
+    if (allow_dense && est_super * 1.25 + 2e6 < 4.0e9 && snk_opt_u32(ctx, SNK_OPT_msp_dense))
         return partition_dense(ctx, st, K, in, good_len, NB, est_super, grouped, status, out, err, errcap, d_plan, h_plan, ft);
     if (cap64 * NB >= (1ull << 40) || cap64 >= (1ull << 31)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "bucket capacity out of range");
     const uint32_t cap = (uint32_t)cap64;
@@ -788,8 +788,8 @@ int snk_stage_partition(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_
         ma.group = grouped ? (const uint32_t*)in->group : nullptr;
         ma.cursor = cursor; ma.records = (uint4*)records; ma.cap = cap; ma.ovf_cap = (uint32_t)sub_cap;
         ma.ovf_base = (uint64_t)NB * cap; ma.ovf_bucket = ovf_bucket; ma.ovf_cursor = ovf_cur;
-        ma.hot_tab = cursor + NB + 1; ma.hot_thr = msp_hot_thr(cap);
-        ma.dbg = snk_opt_u32("msp_dbg", 0);
+        ma.hot_tab = cursor + NB + 1; ma.hot_thr = msp_hot_thr(ctx, cap);
+        ma.dbg = snk_opt_u32(ctx, SNK_OPT_msp_dbg);
         if (ft) {
             ma.good_len = ft->good_out; ma.quals = (const uint8_t*)ft->quals; ma.qstride = ft->qstride; ma.min_qual = ft->min_qual;
             ma.lens = (const uint16_t*)ft->lens; ma.good_out = ft->good_out; ma.plan = d_fplan;
@@ -871,7 +871,7 @@ __global__ void __launch_bounds__(256) seg0_range_kernel(const uint32_t* __restr
 }  // namespace
 
 uint32_t snk_partition_passes_needed(snk_ctx* ctx, uint32_t K, uint32_t NB, unsigned long long n_inst, unsigned long long n_live, bool grouped) {
-    const uint32_t forced = snk_opt_u32("partition_passes", 0);
+    const uint32_t forced = snk_opt_u32(ctx, SNK_OPT_partition_passes);
     ctx->pass_sigma = 0.0;
     if (forced) return forced > 64 ? 64u : forced;
     double est = 0;
@@ -950,7 +950,7 @@ int snk_partition_passes_run(void* user, uint32_t r) {
     ma.group = S->grouped ? (const uint32_t*)in->group : nullptr;
     ma.cursor = S->cursor; ma.records = (uint4*)S->records; ma.cap = S->cap; ma.ovf_cap = (uint32_t)(S->ovf_cap / SNK_OVF_SUBLISTS);
     ma.ovf_base = S->slots_per_pass; ma.ovf_bucket = S->ovf_bucket; ma.ovf_cursor = S->ovf_cur;
-    ma.hot_tab = S->cursor + NB + 1; ma.hot_thr = msp_hot_thr(S->cap);
+    ma.hot_tab = S->cursor + NB + 1; ma.hot_thr = msp_hot_thr(ctx, S->cap);
     ma.b_lo = b_lo; ma.b_hi = b_hi;
     if (trim_now) {
         ma.quals = (const uint8_t*)S->ft.quals; ma.qstride = S->ft.qstride; ma.min_qual = S->ft.min_qual;
@@ -1068,7 +1068,7 @@ int snk_partition_add(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, const 
     ma.group = J->grouped ? (const uint32_t*)in->group : nullptr;
     ma.cursor = J->cursor; ma.records = (uint4*)J->records; ma.cap = J->cap; ma.ovf_cap = (uint32_t)(J->ovf_cap / SNK_OVF_SUBLISTS);
     ma.ovf_base = (uint64_t)J->NB * J->cap; ma.ovf_bucket = J->ovf_bucket; ma.ovf_cursor = J->ovf_cur;
-    ma.hot_tab = J->cursor + J->NB + 1; ma.hot_thr = msp_hot_thr(J->cap);
+    ma.hot_tab = J->cursor + J->NB + 1; ma.hot_thr = msp_hot_thr(ctx, J->cap);
     if (ft) {
         ma.good_len = ft->good_out; ma.quals = (const uint8_t*)ft->quals; ma.qstride = ft->qstride; ma.min_qual = ft->min_qual;
         ma.lens = (const uint16_t*)ft->lens; ma.good_out = ft->good_out; ma.plan = J->d_plan;

@@ -163,12 +163,18 @@ def test_options_registry_and_no_environment_switches(snk):
     allowed = {"SNK_TUNING", "SNK_SYNC_TRACE", "SNK_ARENA_TRACE", "SNK_ARENA_POISON", "SNK_INGEST_TRACE", "SNK_HBV_DEPTH", "SNK_RCCL_LIB",
                "SNK_FASTH_LIBDEFLATE", "SNK_FASTH_WHOLE_MAX_MB"}
     assert env <= allowed, env - allowed
-    # every option a stage looks up is registered (a look-up of an unknown name aborts at run time: caught here instead)
-    looked = set()
-    for f in (ROOT / "supernova_amd" / "csrc").glob("*.hip"):
-        looked |= set(re.findall(r'snk_opt_(?:u32|u64|is_set)\("([a-z0-9_]+)"', f.read_text()))
-        looked |= set(re.findall(r'snk_opt_index\("([a-z0-9_]+)"\)', f.read_text()))
-    assert looked <= set(names), looked - set(names)
+    # stages read options by id (SNK_OPT_<name>: an unknown one does not compile); names are looked up by the registry's by-name ABI only,
+    # every registered option is read somewhere, and no option state lives outside the context
+    csrc = ROOT / "supernova_amd" / "csrc"
+    read = set()
+    for f in csrc.rglob("*"):
+        if f.suffix in (".hip", ".h", ".cc") and f.is_file() and f.name not in ("snk_opts.hip", "snk_opts.h"):
+            text = f.read_text(errors="ignore")
+            assert not re.search(r'snk_opt_\w*\(\s*"|snk_opt_index\(|snk_opts_enter|\bopts\.(?:v|set)\[', text), f.name
+            read |= set(re.findall(r'\bSNK_OPT_([a-z0-9_]+)\b', text))
+    assert read == set(names), (set(names) - read, read - set(names))
+    opts_src = (csrc / "snk_opts.hip").read_text()
+    assert "thread_local" not in opts_src and "abort(" not in opts_src
     t = __import__("supernova_amd.lib", fromlist=["SnkTuning"]).SnkTuning()
     snk.snk_tuning_default(C.byref(t))
     assert t.count_kernel == 0 and t.target_inst == 0

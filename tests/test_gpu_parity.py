@@ -1143,6 +1143,23 @@ def test_device_hbv_many_unitigs(engine, flood, monkeypatch, tune):
         assert np.array_equal(h[k], h2[k]), k
 
 
+def test_context_free_hbv_writer_after_a_closed_engine(snk, tmp_path):
+    """snk_hbv_from_unitigs / snk_write_hbv take no context: they read the options' defaults, never those of a context this thread
+    used before (nor that context's memory once it is destroyed)."""
+    from supernova_amd import graphio
+    from supernova_amd.engine import Engine
+    c = goldens.load("adversarial")
+    off, bases = graphio.unitigs_to_arrays(c.exp_unitigs)
+    graphio.write_hbv(tmp_path / "before.hbv", tmp_path / "before.inv", 48, off, bases)
+    e = Engine(0)
+    e.set_option("hbv_short_queue", 0)
+    e.set_option("hbv_huge_pages", 0)
+    e.close()
+    graphio.write_hbv(tmp_path / "after.hbv", tmp_path / "after.inv", 48, off, bases)
+    assert (tmp_path / "after.hbv").read_bytes() == (tmp_path / "before.hbv").read_bytes() == c.exp_ahbv
+    assert (tmp_path / "after.inv").read_bytes() == (tmp_path / "before.inv").read_bytes() == c.exp_ainv
+
+
 @pytest.mark.parametrize("lookup", ["index", "kmer_dictionary"])
 @pytest.mark.parametrize("name", goldens.CASES)
 def test_read_paths_match_reference(engine, graph_stage, name, lookup, monkeypatch, tune):
