@@ -127,7 +127,8 @@ typedef struct snk_tuning {
 void snk_tuning_default(snk_tuning* t);
 int snk_ctx_set_tuning(snk_ctx* ctx, const snk_tuning* t, char* err, size_t errcap);
 void snk_ctx_get_tuning(const snk_ctx* ctx, snk_tuning* t);
-int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long value, char* err, size_t errcap);
+int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long value, char* err, size_t errcap);   /* SNK_E_ARG: no such option, or a value out of its range */
+int snk_option_check(const char* name, long long value, char* err, size_t errcap);                    /* no context: would snk_ctx_set_option take it? */
 int snk_ctx_clear_option(snk_ctx* ctx, const char* name);                    /* NULL: every option back to the library's choice */
 int snk_ctx_get_option(const snk_ctx* ctx, const char* name, long long* value);   /* 1 set, 0 not set, < 0 no such option */
 const char* snk_option_name(uint32_t i);                                      /* NULL past the last one */
@@ -475,6 +476,8 @@ typedef struct snk_dev_paths {
     float bcs_ms;              /* HIP events: key sort + run heads + per-unitig lists (SNK_PATH_UNITIG_BCS) */
     uint32_t lookup_index;     /* 1: the look-ups went through the minimiser index (the k-mer dictionary did not fit, or SNK_PATH_INDEX=1); dict_slots then counts its places */
     uint64_t n_slow;           /* reads the fast pass left to the full algorithm (a miss, or an exact-match run that ended inside the read) */
+    uint32_t retries;          /* lists that overflowed and made the call run the pass again with a longer one: bit 0 the reads for the
+                                  full-capacity pass, bit 1 the second and later path edges, bit 2 the (unitig, barcode) keys */
 } snk_dev_paths;
 #define SNK_PATH_UNITIG_BCS 1u
 #define SNK_PATH_UNITIG_BCS_EXHAUSTIVE 2u   /* (with SNK_PATH_UNITIG_BCS) derive the lists the slow, literal way -- every k-mer of every barcoded

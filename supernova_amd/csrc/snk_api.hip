@@ -83,7 +83,7 @@ extern "C" int snk_ctx_create(int device, snk_ctx** out, char* err, size_t errca
     snk_opts_init(&c->opts);
     if (const char* tv = getenv("SNK_TUNING")) {        // shell tools: "name=value,name=value", applied once, here
         char bad[96] = "";
-        if (snk_opts_parse(&c->opts, tv, bad, sizeof bad)) { delete c; return snk_fail(SNK_E_ARG, err, errcap, "SNK_TUNING: cannot apply '%s' (unknown option or not an integer)", bad); }
+        if (snk_opts_parse(&c->opts, tv, bad, sizeof bad)) { delete c; return snk_fail(SNK_E_ARG, err, errcap, "SNK_TUNING: cannot apply '%s' (unknown option, not an integer or out of the option's range)", bad); }
     }
     c->device = device;
     c->n_cu = prop.multiProcessorCount;

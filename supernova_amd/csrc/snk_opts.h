@@ -6,7 +6,8 @@
 // SNK_OPTIONS is the one registry: name, default, doc, in the order snk_option_name / snk_option_doc list them.  A stage reads an option of
 // the context it was handed by id (snk_opt_u32(ctx, SNK_OPT_hot)); a NULL context reads the defaults.  Names are looked up only by the
 // by-name C ABI and SNK_TUNING.  Where the default depends on the data (count_tight, target_inst, msp_sigmas_x10, msp_site_records,
-// chunk_merge, path_index) the entry's 0 is never read: the call site asks snk_opt_is_set and chooses itself.
+// chunk_merge, path_index, path_edge_cap, path_redo_cap, path_ubc_cap) the entry's 0 is never read: the call site asks snk_opt_is_set and
+// chooses itself.
 #pragma once
 #include <stdint.h>
 
@@ -66,12 +67,15 @@
     /* ---- read pathing, duplicates, HBV */ \
     X(path_index, 0, "look-ups through the minimiser index: 1 always, 0 never; unset: when the k-mer dictionary does not fit") \
     X(path_dict_max_kb, 0, "a k-mer dictionary above this size 'does not fit' (tests)") \
-    X(path_slots_x10, 30, "dictionary slots per unitig k-mer x 10 (30)") \
+    X(path_slots_x10, 30, "dictionary slots per unitig k-mer x 10 (30; at least 11: the table must keep free slots)") \
     X(path_two_pass, 1, "second pass with 16 lanes per read (1)") \
     X(path_fast_gs, 8, "lanes per read of the first pass (8)") \
     X(path_fused, 0, "1: one kernel for both passes") \
     X(path_redo_all, 0, "1: every read takes the second pass (tests)") \
     X(path_fp_mask, 0, "mask of the dictionary's fingerprints (tests: collisions)") \
+    X(path_edge_cap, 0, "first capacity of the pather's list of second and later path edges (tests: the re-run with a longer list; unset: n/4 + 65536)") \
+    X(path_redo_cap, 0, "first capacity of the pather's list of reads for the full-capacity pass (tests: the re-run; unset: n/64 + 65536)") \
+    X(path_ubc_cap, 0, "first capacity of the (unitig, barcode) keys beyond a read's first (tests: the re-run; unset: n/4 + 65536)") \
     X(path_idx_dbg, 0, "index look-up debug mode") \
     X(unitig_bc_cut, 20000, "entries a unitig's barcode list is cut at (20000)") \
     X(dups_two_sorts, 0, "1: the two-pass sort of MarkDups") \
@@ -102,6 +106,7 @@ extern const snk_opt_def snk_opt_defs[SNK_OPT_COUNT];
 int snk_opt_index(const char* name);                 // -1: no such option
 void snk_opts_init(snk_opts* o);                     // nothing set
 int snk_opts_parse(snk_opts* o, const char* text, char* bad, unsigned badcap);      // "name=value,name=value"; 0 ok, else the offending item in `bad`
+bool snk_opt_valid(int id, long long value);         // the option's range (path_slots_x10: at least 11); every setter refuses what lies outside
 // the context's value if it set one, else the registry's default (ctx NULL: the defaults)
 struct snk_ctx;
 bool snk_opt_is_set(const snk_ctx* ctx, snk_opt_id id);

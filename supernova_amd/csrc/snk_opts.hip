@@ -35,7 +35,7 @@ int snk_opts_parse(snk_opts* o, const char* text, char* bad, unsigned badcap) {
         char* endp = nullptr;
         long long v = 0;
         if (eq) { *eq = 0; ix = snk_opt_index(item); v = strtoll(eq + 1, &endp, 0); }
-        if (ix < 0 || !eq || endp == eq + 1 || *endp) {
+        if (ix < 0 || !eq || endp == eq + 1 || *endp || !snk_opt_valid(ix, v)) {
             if (eq) *eq = '=';
             if (bad && badcap) { strncpy(bad, item, badcap - 1); bad[badcap - 1] = 0; }
             return -1;
@@ -45,6 +45,10 @@ int snk_opts_parse(snk_opts* o, const char* text, char* bad, unsigned badcap) {
     }
     return 0;
 }
+
+// path_slots_x10: the dictionary gets nk * x / 10 + 1024 slots for nk unitig k-mers, and its insertion probes until it finds a free one --
+// below 11 there may be none
+bool snk_opt_valid(int id, long long value) { return id != SNK_OPT_path_slots_x10 || value >= 11; }
 
 bool snk_opt_is_set(const snk_ctx* ctx, snk_opt_id id) { return ctx && ctx->opts.set[id]; }
 uint32_t snk_opt_u32(const snk_ctx* ctx, snk_opt_id id) { return (uint32_t)snk_opt_u64(ctx, id); }
@@ -57,7 +61,14 @@ extern "C" int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long valu
     if (!ctx || !name) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: NULL argument");
     const int ix = snk_opt_index(name);
     if (ix < 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: no option '%s' (snk_option_name lists them)", name);
+    if (!snk_opt_valid(ix, value)) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: %lld is out of range for '%s' (%s)", value, name, snk_opt_defs[ix].doc);
     ctx->opts.v[ix] = value; ctx->opts.set[ix] = true;
+    return SNK_OK;
+}
+extern "C" int snk_option_check(const char* name, long long value, char* err, size_t errcap) {
+    const int ix = snk_opt_index(name);
+    if (ix < 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_option_check: no option '%s'", name ? name : "(NULL)");
+    if (!snk_opt_valid(ix, value)) return snk_fail(SNK_E_ARG, err, errcap, "snk_option_check: %lld is out of range for '%s' (%s)", value, name, snk_opt_defs[ix].doc);
     return SNK_OK;
 }
 extern "C" int snk_ctx_clear_option(snk_ctx* ctx, const char* name) {

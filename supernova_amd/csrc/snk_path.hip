@@ -31,11 +31,17 @@
 
 namespace {
 
-constexpr int PCAP = 112;      // path parts per read (a 150-base read has at most 103 k-mers)
-constexpr int PMAX = 64;       // edges per read path
-// The parts of sixteen reads sit in LDS.  At full capacity that is 29 KB per workgroup and four workgroups per CU; a read of a
-// deep data set has one to three parts, so the kernel runs with room for PCAP1 parts / PMAX1 edges (8 KB, occupancy limited
-// by registers) and the few reads that need more are listed and redone by the full-capacity variant.
+// Full capacity: room for every read the entry point takes (at most 256 bases, K >= 48: at most 209 k-mers), so that no read is ever
+// refused.  Parts: gaps and seeds alike cover one k-mer at least and together cover the read's k-mers once.  Edges: a path edge comes
+// from a seed, a left extension from the leading gap (it runs while 10 or more k-mers are left in front of the path and every edge takes
+// one at least), a right extension from what lies behind the path's end (likewise): one k-mer at least each, so never more edges than
+// k-mers either.  Reads inside a homopolymer (a one-k-mer unitig with a self-loop: a part per k-mer) or a period-2 / period-3 repeat
+// (the path alternates between edges of a k-mer or two) come close to both bounds.
+constexpr int PCAP = 256 - 48 + 1;     // path parts per read
+constexpr int PMAX = PCAP;             // edges per read path
+// The parts of sixteen reads sit in LDS.  At full capacity that is 67 KB per workgroup (86 KB with the minimiser keys), one workgroup
+// per CU; a read of a deep data set has one to three parts, so the kernel runs with room for PCAP1 parts / PMAX1 edges (8 KB, occupancy
+// limited by registers) and the few reads that need more are listed and redone by the full-capacity variant.
 constexpr int PCAP1 = 20;
 constexpr int PMAX1 = 16;
 constexpr int GPARTS = 4;      // parts per read that travel to the finishing kernel
@@ -582,7 +588,7 @@ __device__ __forceinline__ bool dict_find(const path_graph& G, const uint32_t* r
 #endif
 // GS lanes per read (16 or 8): the kernel is latency bound -- a clean read is a chain of ~6 dependent HBM round trips whatever the
 // number of lanes that wait for them -- so eight lanes per read put twice as many reads in flight per wave (round 3: 134 -> see DESIGN);
-// the full-capacity second pass keeps sixteen (its parts take 29 KB of LDS per sixteen reads).
+// the full-capacity second pass keeps sixteen (its parts take 67 KB of LDS per sixteen reads).
 // MODE 0 "fast": every read, but only as far as a clean read goes -- first k-mer found, exact-match run to the end of the read;
 //        anything else (a miss, a run that ends early) marks the read (gm = 0xFE) and moves on.  Four reads share a wave and the
 //        wave takes the time of its slowest: with one read in four carrying an error, 70 % of the waves paid an error read's
@@ -593,7 +599,7 @@ __device__ __forceinline__ bool dict_find(const path_graph& G, const uint32_t* r
 // IDX: the look-ups go through the minimiser index (its own instantiation: the key array in LDS and the second look-up path cost the
 // dictionary variant 9 % when they were a run-time switch)
 template <int K, int PC, int PM, int MODE, int GS, bool IDX>
-__global__ void __launch_bounds__(256, MODE == 2 ? 4 : SNK_PATH_OCC) path_kernel(path_args a) {
+__global__ void __launch_bounds__(256, MODE == 2 ? 1 : SNK_PATH_OCC) path_kernel(path_args a) {
     constexpr bool SECOND = MODE == 2;
     constexpr int NG = 256 / GS;                      // reads per workgroup
     constexpr uint32_t GM = (1u << GS) - 1u;
@@ -1148,9 +1154,12 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     if ((rc = dev(ctx, n + 1, &out_n, err, errcap)) || (rc = dev(ctx, n + 1, &out_start, err, errcap)) || (rc = dev(ctx, n + 1, &out_off, err, errcap)) || (rc = dev(ctx, n + 1, &out_e0, err, errcap)) ||
         (rc = dev(ctx, 4, &cursor, err, errcap)) || (rc = dev(ctx, n + 2, &n64, err, errcap)) || (rc = dev(ctx, n + 2, &pos, err, errcap)))
         return rc;
-    uint64_t scap = n / 4 + 65536;                    // second and later edges only; a wrong guess costs one re-run
+    // first capacities of the three lists the passes fill through a cursor: a wrong guess costs one re-run (path_edge_cap, path_redo_cap and
+    // path_ubc_cap set them for the tests of that re-run)
+    auto cap0 = [&](snk_opt_id o, uint64_t dflt) { return snk_opt_is_set(ctx, o) ? snk_opt_u64(ctx, o) : dflt; };
+    uint64_t scap = cap0(SNK_OPT_path_edge_cap, n / 4 + 65536);         // second and later edges only
     const bool want_bcs = (flags & SNK_PATH_UNITIG_BCS) && in->bc;
-    uint64_t ubcap = want_bcs ? n / 4 + 65536 : 0;    // (unitig, barcode) keys beyond a read's first
+    uint64_t ubcap = want_bcs ? cap0(SNK_OPT_path_ubc_cap, n / 4 + 65536) : 0;      // (unitig, barcode) keys beyond a read's first
     unsigned long long* ubk = nullptr;                // [n + ubcap]: the reads' first keys, then the further ones
     unsigned long long h_cur[4] = {0, 0, 0, 0};
     ppart* gparts = nullptr;
@@ -1160,7 +1169,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     }
     uint32_t* redo = nullptr;
     uint64_t *slow_flag = nullptr, *slow_pos = nullptr;
-    uint64_t rcap = n / 64 + 65536;
+    uint64_t rcap = cap0(SNK_OPT_path_redo_cap, n / 64 + 65536);
     for (int attempt = 0; attempt < 3; ++attempt) {
         if (!scratch && (rc = dev(ctx, scap, &scratch, err, errcap))) return rc;
         if (want_bcs && !ubk && (rc = dev(ctx, n + ubcap, &ubk, err, errcap))) return rc;
@@ -1223,7 +1232,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         SNK_HIP_TRY(snk_sync(st));
         if (h_cur[3] > rcap) {                       // more reads to redo than the list holds: once more with a longer list
             if (attempt == 2) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_path_reads: redo list overflow");
-            snk_ctx_release_block(ctx, redo); redo = nullptr; rcap = h_cur[3] + 1024;
+            snk_ctx_release_block(ctx, redo); redo = nullptr; rcap = h_cur[3] + 1024; out->retries |= 1u;
             continue;
         }
         if (h_cur[3]) {                              // the reads with many parts / edges, at full capacity
@@ -1237,12 +1246,12 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
             SNK_HIP_TRY(hipMemcpyAsync(h_cur, cursor, 32, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
         }
-        if (h_cur[1] & 1ull) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_path_reads: a read has more than %d path parts or %d edges", PCAP, PMAX);
+        if (h_cur[1] & 1ull) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_path_reads: a read has more than %d path parts or %d edges (internal: a read of at most 256 bases never has)", PCAP, PMAX);
         const bool e_over = (h_cur[1] & 2ull) != 0, b_over = want_bcs && h_cur[2] > ubcap;
         if (!e_over && !b_over) break;
         if (attempt == 2) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_path_reads: path scratch overflow");
-        if (e_over) { snk_ctx_release_block(ctx, scratch); scratch = nullptr; scap = h_cur[0] + 1024; }
-        if (b_over) { snk_ctx_release_block(ctx, ubk); ubk = nullptr; ubcap = h_cur[2] + 1024; }
+        if (e_over) { snk_ctx_release_block(ctx, scratch); scratch = nullptr; scap = h_cur[0] + 1024; out->retries |= 2u; }
+        if (b_over) { snk_ctx_release_block(ctx, ubk); ubk = nullptr; ubcap = h_cur[2] + 1024; out->retries |= 4u; }
     }
     hipLaunchKernelGGL(widen_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, st, out_n, n, n64);
     if ((rc = scan64(ctx, st, n64, pos, n + 1, err, errcap))) return rc;

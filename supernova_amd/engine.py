@@ -140,7 +140,8 @@ class Result:
         info['dups'] = dict(dup u8[n/2], interdup_rate, n_dup_pairs, n_dup_reads, n_art_pairs, n_placed, ms).
         unitig_bcs: the rest of f4 -- per unitig (numbering of unitig_arrays()) the sorted distinct barcodes > 0 of the reads with a
         k-mer on it (tada's edge -> barcode sets) -> info['unitig_bcs'] = (off u64[U+1], bcs u32[...]); unitig_bcs="exhaustive" derives them
-        the slow, literal way (every k-mer of every barcoded read looked up); bcs_nocut: without the 20 000-entry cut."""
+        the slow, literal way (every k-mer of every barcoded read looked up); bcs_nocut: without the 20 000-entry cut.
+        info['retries']: the lists that overflowed and were regrown (snk_dev_paths.retries: 1 redo list, 2 path edges, 4 barcode keys)."""
         e = self._e
         h = _lib.SnkHbv()
         ms = C.c_float(0)
@@ -180,7 +181,7 @@ class Result:
         if not download:          # timings only (bench.py: the results stay on the device)
             info = dict(dict_ms=float(out.dict_ms), path_ms=float(out.path_ms), bcs_ms=float(out.bcs_ms), hbv_device_ms=float(ms.value),
                         dict_slots=int(out.dict_slots), n_edges_total=tot, n_unitig_bcs=int(out.n_unitig_bcs), n_slow=int(out.n_slow),
-                        lookup=("index" if out.lookup_index else "kmer_dictionary"))
+                        lookup=("index" if out.lookup_index else "kmer_dictionary"), retries=int(out.retries))
             if dups is not None:
                 info["dups"] = {k: v for k, v in dups.items() if k != "dup"}
             return None, None, None, info
@@ -188,7 +189,7 @@ class Result:
         ne = self._dl(out.n_edges, n * 4, np.uint32, (n,))
         edges = self._dl(out.edges, tot * 4, np.int32, (tot,))
         info = dict(dict_ms=float(out.dict_ms), path_ms=float(out.path_ms), bcs_ms=float(out.bcs_ms), hbv_device_ms=float(ms.value), dict_slots=int(out.dict_slots), lookup=("index" if out.lookup_index else "kmer_dictionary"),
-                    n_slow=int(out.n_slow))
+                    n_slow=int(out.n_slow), retries=int(out.retries))
         if dups is not None:
             info["dups"] = dups
         if unitig_bcs and out.unitig_bc_off:

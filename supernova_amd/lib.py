@@ -78,7 +78,7 @@ class SnkDevPaths(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_edges_total", C.c_uint64), ("offset", C.c_void_p), ("n_edges", C.c_void_p),
                 ("start", C.c_void_p), ("edges", C.c_void_p), ("dict_slots", C.c_uint64), ("dict_ms", C.c_float),
                 ("path_ms", C.c_float), ("unitig_bc_off", C.c_void_p), ("unitig_bcs", C.c_void_p), ("n_unitig_bcs", C.c_uint64),
-                ("bcs_ms", C.c_float), ("lookup_index", C.c_uint32), ("n_slow", C.c_uint64)]
+                ("bcs_ms", C.c_float), ("lookup_index", C.c_uint32), ("n_slow", C.c_uint64), ("retries", C.c_uint32)]
 
 
 class SnkDevDups(C.Structure):
@@ -216,6 +216,7 @@ def _declare(lib: C.CDLL) -> None:
         "snk_ctx_set_tuning": (C.c_int, [vp, P(SnkTuning), cp, sz]),
         "snk_ctx_get_tuning": (None, [vp, P(SnkTuning)]),
         "snk_ctx_set_option": (C.c_int, [vp, cp, C.c_longlong, cp, sz]),
+        "snk_option_check": (C.c_int, [cp, C.c_longlong, cp, sz]),
         "snk_ctx_clear_option": (C.c_int, [vp, cp]),
         "snk_ctx_get_option": (C.c_int, [vp, cp, P(C.c_longlong)]),
         "snk_option_name": (cp, [u32]),

@@ -189,3 +189,19 @@ def test_tools_and_bench_compile():
     assert (root / "tools" / "r6_full_job.py") in files
     for f in files:
         py_compile.compile(str(f), doraise=True)
+
+
+def test_dictionary_load_below_eleven_is_refused_without_a_context(snk):
+    """path_slots_x10 sizes the pather's k-mer dictionary (nk * x / 10 + 1024 slots for nk unitig k-mers); below 11 it could hold fewer
+    slots than k-mers and its insertion would never find a free one.  The registry's range check (snk_ctx_set_option, SNK_TUNING) refuses
+    such a value: snk_option_check asks it without a context."""
+    err = C.create_string_buffer(256)
+    for v in (10, 1, 0, -1):
+        assert snk.snk_option_check(b"path_slots_x10", v, err, 256) == -1, v
+        assert b"path_slots_x10" in err.value
+    for v in (11, 30, 100):
+        assert snk.snk_option_check(b"path_slots_x10", v, err, 256) == 0, v
+    assert snk.snk_option_check(b"path_fast_gs", 0, err, 256) == 0
+    assert snk.snk_option_check(b"no_such_option", 1, err, 256) == -1
+    for name in (b"path_edge_cap", b"path_redo_cap", b"path_ubc_cap"):
+        assert snk.snk_option_check(name, 1, err, 256) == 0
