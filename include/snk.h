@@ -520,6 +520,49 @@ typedef struct snk_dev_dups {
 } snk_dev_dups;
 int snk_dev_mark_dups(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_paths* paths, snk_dev_dups* out, void* stream, char* err, size_t errcap);
 
+/* ---- the paths index and the rest of a.48/ ------------------------------------------------------------------------
+ * writePathsIndex, lib/assembly/src/10X/PathsIndex.cc:23-145 (10X/DF.cc:588 runs it on the paths just made): per HBV edge the ids of
+ * the reads whose path holds it -- what every later stage of the reference opens first (a.paths.inv; StageFindPatch, DF.cc:636-638) --
+ * and the read support per edge (a.countsb).  The reference writes one (edge, read id) pair per path entry into 15 temporary chunk files,
+ * reads them back and comparison-sorts each (:38-114); here the entries of snk_dev_paths, already ordered by read id, go through one
+ * stable radix sort over the ceil(log2 n_hbv_edges) bits an edge id has.
+ *   paths        of snk_dev_path_reads (edge ids = HBV edge ids); it must stay valid across the call, and does: the call takes its
+ *                memory from the context's arena behind it and hands its scratch back on return
+ *   inv          HOST array, int32[n_hbv_edges], of snk_hbv_involution
+ *   index_off    u64[n_hbv_edges + 1], index_ids u64[n_entries]: the reads of edge e are index_ids[index_off[e] .. index_off[e + 1]),
+ *                ascending, a read repeated as often as its path holds e (the reference keeps the duplicates of its sorted pairs,
+ *                :51-57,90,104-107: a path through a tandem repeat visits an edge many times)
+ *   counts       i32[n_hbv_edges]: entries of e, and for every pair e != inv[e] both replaced by their sum; a self-inverse edge keeps
+ *                its own (:122-133).  A sum above 2^31 - 1 is refused (SNK_E_UNSUPPORTED): the file holds int
+ * Device memory of the context, valid until its next top-level call.  SNK_E_ARG: an edge id outside [0, n_hbv_edges), an inv that is not
+ * an involution, start / n_edges that do not add up to n_edges_total.  The result is bit-identical from call to call and depends on no
+ * tuning option. */
+typedef struct snk_dev_pidx {
+    uint64_t n_hbv_edges, n_entries;     /* n_entries = paths->n_edges_total */
+    const void* index_off;
+    const void* index_ids;
+    const void* counts;
+    uint64_t n_empty_edges;              /* edges no read's path holds (the reference writes an empty entry for them, :101-102) */
+    float ms;                            /* HIP events around the whole call (the upload of inv included) */
+    uint32_t key_bits;                   /* bits of an edge id the sort looked at */
+    uint64_t reserved[6];
+} snk_dev_pidx;
+int snk_dev_paths_index(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t n_hbv_edges, const int32_t* inv, snk_dev_pidx* out, void* stream,
+                        char* err, size_t errcap);
+/* The files (host arrays; no GPU needed), byte for byte what the reference leaves in a.48/:
+ *   snk_write_paths        a.paths = the tmp.paths of pathReads (BuildReadQGraph48.cc:1441-1469, renamed at DF.cc:584): feudal
+ *                          MasterVec<ReadPath> -- control block, per read i32 offset, u32 last skip (always 0: :1408-1418 is commented
+ *                          out) and its edge ids (paths/long/ReadPath.h:61-63), then the table of n_reads + 1 file offsets.
+ *                          start may be NULL: the paths follow each other in `edges`
+ *   snk_write_paths_index  a.paths.inv = IncrementalWriter<ULongVec> (PathsIndex.cc:76,100-108): feudal, per edge its read ids as u64;
+ *                          a.countsb = BinaryWriter::writeFile(vec<vec<int>>) with one inner vector (:75,135).  Either path may be NULL
+ *   snk_write_dup          a.dup = BinaryWriter::writeFile(vec<Bool>) (DF.cc:599-600): "BINWRITE", u64 count, one byte per pair */
+int snk_write_paths(const char* path, uint64_t n_reads, const int32_t* offset, const uint32_t* n_edges, const uint64_t* start, const int32_t* edges,
+                    char* err, size_t errcap);
+int snk_write_paths_index(const char* path_inv, const char* path_countsb, uint64_t n_hbv_edges, const uint64_t* index_off, const uint64_t* index_ids,
+                          const int32_t* counts, char* err, size_t errcap);
+int snk_write_dup(const char* path, uint64_t n_pairs, const uint8_t* dup, char* err, size_t errcap);
+
 /* ---- f3: barcode ids on the device --------------------------------------------------------------
  * BcIndexer, lib/tada/src/utils.rs:101-164: whitelist line -> index (identical lines: the last one wins); a read's
  * barcode field "SEQ[-gg][,raw]" (FASTH line 6, lib/tada/src/multifastq.rs:72-126) gets

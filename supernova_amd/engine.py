@@ -132,7 +132,8 @@ class Result:
         self._e.lib.snk_hbv_free(C.byref(h))
         return out
 
-    def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False):
+    def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
+                   paths_index=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -141,7 +142,10 @@ class Result:
         unitig_bcs: the rest of f4 -- per unitig (numbering of unitig_arrays()) the sorted distinct barcodes > 0 of the reads with a
         k-mer on it (tada's edge -> barcode sets) -> info['unitig_bcs'] = (off u64[U+1], bcs u32[...]); unitig_bcs="exhaustive" derives them
         the slow, literal way (every k-mer of every barcoded read looked up); bcs_nocut: without the 20 000-entry cut.
-        info['retries']: the lists that overflowed and were regrown (snk_dev_paths.retries: 1 redo list, 2 path edges, 4 barcode keys)."""
+        info['retries']: the lists that overflowed and were regrown (snk_dev_paths.retries: 1 redo list, 2 path edges, 4 barcode keys).
+        paths_index: writePathsIndex over these paths (10X/PathsIndex.cc:23-145; snk_dev_paths_index) -> info['paths_index'] = (off u64[E+1],
+        ids u64[...]): the reads of HBV edge e are ids[off[e]:off[e+1]], ascending, a read as often as its path holds e; info['countsb'] =
+        i32[E] read support, an edge and its reverse complement summed; info['inv'] = the involution; info['pidx'] = counters and time."""
         e = self._e
         h = _lib.SnkHbv()
         ms = C.c_float(0)
@@ -175,6 +179,21 @@ class Result:
                 dups = dict(dup=self._dl(dd.dup, npairs, np.uint8, (npairs,)) if download else None, interdup_rate=float(dd.interdup_rate),
                             n_dup_pairs=int(dd.n_dup_pairs), n_dup_reads=int(dd.n_dup_reads), n_interdup_reads=int(dd.n_interdup_reads),
                             n_art_pairs=int(dd.n_art_pairs), n_placed=int(dd.n_placed), ms=float(dd.ms))
+            pidx = None
+            if paths_index:
+                ne_hbv = int(h.n_edges)
+                inv = np.zeros(max(ne_hbv, 1), dtype=np.int32)
+                rc = e.lib.snk_hbv_involution(C.byref(h), self.n_unitigs, inv.ctypes.data, err, 512)
+                px = _lib.SnkDevPidx()
+                if not rc:
+                    rc = e.lib.snk_dev_paths_index(e._ctx, C.byref(out), ne_hbv, inv.ctypes.data, C.byref(px), e._stream(), err, 512)
+                if rc:
+                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+                nent = int(px.n_entries)
+                pidx = dict(n_hbv_edges=ne_hbv, n_entries=nent, n_empty_edges=int(px.n_empty_edges), key_bits=int(px.key_bits), ms=float(px.ms))
+                if download:
+                    pidx_arrays = (self._dl(px.index_off, (ne_hbv + 1) * 8, np.uint64, (ne_hbv + 1,)), self._dl(px.index_ids, nent * 8, np.uint64, (nent,)),
+                                   self._dl(px.counts, ne_hbv * 4, np.int32, (ne_hbv,)), inv[:ne_hbv].copy())
         finally:
             e.lib.snk_hbv_free(C.byref(h))
         n, tot = int(out.n_reads), int(out.n_edges_total)
@@ -184,6 +203,8 @@ class Result:
                         lookup=("index" if out.lookup_index else "kmer_dictionary"), retries=int(out.retries))
             if dups is not None:
                 info["dups"] = {k: v for k, v in dups.items() if k != "dup"}
+            if pidx is not None:
+                info["pidx"] = pidx
             return None, None, None, info
         off = self._dl(out.offset, n * 4, np.int32, (n,))
         ne = self._dl(out.n_edges, n * 4, np.uint32, (n,))
@@ -192,6 +213,8 @@ class Result:
                     n_slow=int(out.n_slow), retries=int(out.retries))
         if dups is not None:
             info["dups"] = dups
+        if pidx is not None:
+            info["pidx"], info["paths_index"], info["countsb"], info["inv"] = pidx, pidx_arrays[:2], pidx_arrays[2], pidx_arrays[3]
         if unitig_bcs and out.unitig_bc_off:
             nb = int(out.n_unitig_bcs)
             info["unitig_bcs"] = (self._dl(out.unitig_bc_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,)),

@@ -3,6 +3,9 @@
   write_bv / read_bv   the `.bv` file tada writes and DF reads through MSPEDGES=
                        (lib/tada/src/debruijn.rs:895-929; BuildReadQGraph48.cc:1640-1642)
   hbv_from_unitigs     buildHBVFromEdges (lib/assembly/src/paths/long/HBVFromEdges.cc:244-296)
+  write_hbv            a.hbv / a.inv as DF keeps the graph (paths/HyperBasevector.cc:121-125)
+  write_paths, write_paths_index, write_dup, write_a48
+                       the rest of a.48/: a.paths, a.paths.inv, a.countsb, a.dup (10X/DF.cc:584-600, 10X/PathsIndex.cc:23-145)
 """
 from __future__ import annotations
 
@@ -101,6 +104,65 @@ def write_hbv(path_hbv, path_inv, K: int, off: np.ndarray, bases: np.ndarray) ->
         return inv[:h.n_edges].copy()
     finally:
         lib.snk_hbv_free(C.byref(h))
+
+
+def _call(fn, *args):
+    err = C.create_string_buffer(512)
+    rc = fn(*args, err, 512)
+    if rc:
+        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+
+
+def write_paths(path, offset: np.ndarray, n_edges: np.ndarray, edges: np.ndarray, start: np.ndarray | None = None) -> None:
+    """a.paths (the tmp.paths of pathReads, BuildReadQGraph48.cc:1441-1469): per read its offset and HBV edge ids.  start = position of
+    every read's first edge in `edges`, None = the paths follow each other."""
+    offset = np.ascontiguousarray(offset, dtype=np.int32)
+    n_edges = np.ascontiguousarray(n_edges, dtype=np.uint32)
+    edges = np.ascontiguousarray(edges, dtype=np.int32)
+    assert len(offset) == len(n_edges)
+    if start is not None:
+        start = np.ascontiguousarray(start, dtype=np.uint64)
+        assert len(start) >= len(n_edges)
+    _call(_lib.load().snk_write_paths, str(path).encode(), len(n_edges), offset.ctypes.data, n_edges.ctypes.data,
+          start.ctypes.data if start is not None else None, edges.ctypes.data)
+
+
+def write_paths_index(path_inv, path_countsb, off: np.ndarray, ids: np.ndarray, counts: np.ndarray) -> None:
+    """a.paths.inv and a.countsb (writePathsIndex, 10X/PathsIndex.cc:23-145) from the index of snk_dev_paths_index: the reads of edge e
+    are ids[off[e]:off[e+1]].  Either path may be None."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.int32)
+    E = len(off) - 1
+    assert E >= 0 and len(counts) == E and len(ids) == int(off[-1])
+    _call(_lib.load().snk_write_paths_index, str(path_inv).encode() if path_inv else None, str(path_countsb).encode() if path_countsb else None, E,
+          off.ctypes.data, ids.ctypes.data, counts.ctypes.data)
+
+
+def write_dup(path, dup: np.ndarray) -> None:
+    """a.dup (vec<Bool> of MarkDups, 10X/DF.cc:599-600): one flag per read pair."""
+    dup = np.ascontiguousarray(dup, dtype=np.uint8)
+    _call(_lib.load().snk_write_dup, str(path).encode(), len(dup), dup.ctypes.data)
+
+
+def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.ndarray, path_n_edges: np.ndarray, path_edges: np.ndarray, info: dict) -> np.ndarray:
+    """The six files DF leaves in a.<K>/ after StageBuildGraph (10X/DF.cc:564-601) from one result: a.hbv, a.inv (the unitigs in BVComp
+    order: graphio.unitigs_to_arrays(res.unitigs())), a.paths (what res.path_reads returned), a.paths.inv, a.countsb (info['paths_index'],
+    info['countsb']: path_reads(..., paths_index=True)) and a.dup (info['dups']['dup']: mark_dups=True).  Returns the involution."""
+    from pathlib import Path
+    d = Path(dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for k in ("paths_index", "countsb", "dups"):
+        if k not in info:
+            raise KeyError(f"write_a48 needs info[{k!r}]: path_reads(..., mark_dups=True, paths_index=True)")
+    inv = write_hbv(d / "a.hbv", d / "a.inv", K, off, bases)
+    iv = info.get("inv")
+    if iv is not None and not np.array_equal(iv, inv):
+        raise ValueError("write_a48: the unitigs are not the ones the paths index was made on (involutions differ)")
+    write_paths(d / "a.paths", path_offset, path_n_edges, path_edges)
+    write_paths_index(d / "a.paths.inv", d / "a.countsb", info["paths_index"][0], info["paths_index"][1], info["countsb"])
+    write_dup(d / "a.dup", info["dups"]["dup"])
+    return inv
 
 
 def hbv_text(unitigs: list[str], h: dict) -> str:

@@ -87,6 +87,12 @@ class SnkDevDups(C.Structure):
                 ("interdup_rate", C.c_double), ("ms", C.c_float)]
 
 
+class SnkDevPidx(C.Structure):
+    _fields_ = [("n_hbv_edges", C.c_uint64), ("n_entries", C.c_uint64), ("index_off", C.c_void_p), ("index_ids", C.c_void_p),
+                ("counts", C.c_void_p), ("n_empty_edges", C.c_uint64), ("ms", C.c_float), ("key_bits", C.c_uint32),
+                ("reserved", C.c_uint64 * 6)]
+
+
 class SnkFasthBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("first_pair", C.c_uint64), ("file", C.c_uint32), ("max_len", C.c_uint32),
                 ("ascii", C.c_void_p), ("quals", C.c_void_p), ("lens", C.c_void_p), ("bc_fields", C.c_void_p),
@@ -245,6 +251,10 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_path_reads": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_path_reads2": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), u32, P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_mark_dups": (C.c_int, [vp, P(SnkDevReads), P(SnkDevPaths), P(SnkDevDups), vp, cp, sz]),
+        "snk_dev_paths_index": (C.c_int, [vp, P(SnkDevPaths), u64, vp, P(SnkDevPidx), vp, cp, sz]),
+        "snk_write_paths": (C.c_int, [cp, u64, vp, vp, vp, vp, cp, sz]),
+        "snk_write_paths_index": (C.c_int, [cp, cp, u64, vp, vp, vp, cp, sz]),
+        "snk_write_dup": (C.c_int, [cp, u64, vp, cp, sz]),
         "snk_hbv_involution": (C.c_int, [P(SnkHbv), u64, vp, cp, sz]),
         "snk_write_hbv": (C.c_int, [cp, cp, u32, u64, vp, vp, P(SnkHbv), cp, sz]),
         "snk_read_fastb": (C.c_int, [cp, P(u64), P(u32), P(P(C.c_uint16)), P(P(u32)), cp, sz]),
