@@ -537,10 +537,7 @@ extern "C" int snk_synth_dev(snk_ctx* ctx, const snk_synth_params* sp, uint64_t 
     if (n == 0) return SNK_OK;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
-    uint64_t nb = (n + 255) / 256;
-    if (nb > 65536) nb = 65536;
-    hipLaunchKernelGGL(snk_synth_kernel, dim3((unsigned)nb), dim3(256), 0, st, *sp, first, n, (uint32_t*)d_rows, row_words,
-                       (uint8_t*)d_quals, qstride, (int32_t*)d_bc);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(snk_synth_kernel, snk_blocks_capped(n, 256, 65536), 256, 0, st, *sp, first, n, (uint32_t*)d_rows, row_words,
+                           (uint8_t*)d_quals, qstride, (int32_t*)d_bc));
     return SNK_OK;
 }

@@ -504,10 +504,7 @@ __global__ void __launch_bounds__(CB) ck_final_kernel(ck_args a, int reads, int 
     ck_note(a.acc, C_CTX_MM, nctx, fctx);
 }
 
-unsigned ck_grid(uint64_t items, uint64_t per_block = CB) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, 65536));
-}
+constexpr uint64_t CK_GRID_CAP = 65536;     // every kernel of this file strides over what its grid does not cover
 
 }  // namespace
 
@@ -593,13 +590,12 @@ extern "C" int snk_dev_check_graph(snk_ctx* ctx, const snk_check_input* in, cons
         SNK_HIP_TRY(hipMemsetAsync(a.vis, 0, (a.t.n + 15) / 16 * 4, st));
         a.t.slots = slots;
     }
-    if (a.t.n) hipLaunchKernelGGL(ck_table_kernel, dim3(ck_grid(a.t.n)), dim3(CB), 0, st, a, digest_only ? 0 : 1);
-    if (a.n_unitigs) hipLaunchKernelGGL(ck_unitig_kernel, dim3(ck_grid(a.n_unitigs, CB / 64)), dim3(CB), 0, st, a, digest_only ? 1 : 0);
+    if (a.t.n) SNK_HIP_TRY(snk_launch(ck_table_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a, digest_only ? 0 : 1));
+    if (a.n_unitigs) SNK_HIP_TRY(snk_launch(ck_unitig_kernel, snk_blocks_capped(a.n_unitigs, CB / 64, CK_GRID_CAP), CB, 0, st, a, digest_only ? 1 : 0));
     if (!digest_only) {
-        if (a.t.n) hipLaunchKernelGGL(ck_ctx_kernel, dim3(ck_grid(a.t.n)), dim3(CB), 0, st, a);
-        if (a.n_unitigs && total) hipLaunchKernelGGL(ck_pos_kernel, dim3(ck_grid((total + CK_SEG - 1) / CK_SEG)), dim3(CB), 0, st, a);
+        if (a.t.n) SNK_HIP_TRY(snk_launch(ck_ctx_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a));
+        if (a.n_unitigs && total) SNK_HIP_TRY(snk_launch(ck_pos_kernel, snk_blocks_capped(snk_blocks(total, CK_SEG), CB, CK_GRID_CAP), CB, 0, st, a));
     }
-    SNK_HIP_TRY(hipGetLastError());
     SNK_HIP_TRY(hipEventRecord(ev[1], st));
     if (do_reads) {
         if ((rc = alloc(a.t.n * 4, (void**)&a.recount)) || (rc = alloc((a.t.n + 3) / 4 * 4, (void**)&a.shadow))) return rc;
@@ -616,10 +612,9 @@ extern "C" int snk_dev_check_graph(snk_ctx* ctx, const snk_check_input* in, cons
         r.read_len = reads->read_len;
         r.qstride = reads->qstride;
         r.min_qual = in->min_qual ? in->min_qual : 7;
-        hipLaunchKernelGGL(ck_reads_kernel, dim3(ck_grid(r.n)), dim3(CB), 0, st, a, r);
+        SNK_HIP_TRY(snk_launch(ck_reads_kernel, snk_blocks_capped(r.n, CB, CK_GRID_CAP), CB, 0, st, a, r));
     }
-    if (!digest_only && a.t.n) hipLaunchKernelGGL(ck_final_kernel, dim3(ck_grid(a.t.n)), dim3(CB), 0, st, a, do_reads ? 1 : 0, in->min_freq > 1 ? 1 : 0);
-    SNK_HIP_TRY(hipGetLastError());
+    if (!digest_only && a.t.n) SNK_HIP_TRY(snk_launch(ck_final_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a, do_reads ? 1 : 0, in->min_freq > 1 ? 1 : 0));
     SNK_HIP_TRY(hipEventRecord(ev[2], st));
     ck_acc h;
     SNK_HIP_TRY(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, st));

@@ -803,8 +803,7 @@ int launch(hipStream_t st, const snk_count_args& a, char* err, size_t errcap) {
     // workgroup w counts the buckets == w (mod n_regions) and appends to region w
     snk_count_args b = a;
     b.bucket_stride = a.n_regions;
-    hipLaunchKernelGGL(kern, dim3(a.n_regions), dim3(cfg<K>::THREADS), lds, st, b);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(kern, a.n_regions, cfg<K>::THREADS, lds, st, b));
     return SNK_OK;
 }
 
@@ -848,9 +847,8 @@ int snk_launch_compact_regions(hipStream_t st, const snk_u128* keys_in, const ui
                                uint32_t n_regions, const unsigned long long* region_cursor,
                                const unsigned long long* region_off, snk_u128* keys_out, uint64_t* vals_out, char* err,
                                size_t errcap) {
-    hipLaunchKernelGGL(compact_regions_kernel, dim3(n_regions), dim3(256), 0, st, keys_in, vals_in, region_cap, region_cursor,
-                       region_off, keys_out, vals_out);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(compact_regions_kernel, n_regions, 256, 0, st, keys_in, vals_in, region_cap, region_cursor,
+                           region_off, keys_out, vals_out));
     return SNK_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/snk.h"
+#include "snk_launch.h"
 #include "snk_opts.h"
 
 struct snk_ctx {

@@ -418,7 +418,7 @@ int scan_max_len(snk_ctx* ctx, df_io* io, const snk_df_files* f, uint64_t first,
     hipError_t e = hipMalloc((void**)&d, std::min(piece, n) * 4);
     if (e != hipSuccess) { (void)hipHostFree(pin); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dfin: hipMalloc failed"); }
     int rc = SNK_OK;
-    (void)hipMemsetAsync(io->d_errs + 8, 0, 4, io->cs);
+    if (hipMemsetAsync(io->d_errs + 8, 0, 4, io->cs) != hipSuccess) rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dfin: length scan failed");
     io_pool local(8);
     for (uint64_t a = 0; a < n && !rc; a += piece) {
         const uint64_t k = std::min(piece, n - a);
@@ -427,8 +427,7 @@ int scan_max_len(snk_ctx* ctx, df_io* io, const snk_df_files* f, uint64_t first,
         local.wait(&left);
         if (failed.load()) { rc = snk_fail(SNK_E_IO, err, errcap, "%s: read error in the length table", f->fb.path.c_str()); break; }
         if (hipMemcpyAsync(d, pin, k * 4, hipMemcpyHostToDevice, io->cs) != hipSuccess) { rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dfin: upload failed"); break; }
-        hipLaunchKernelGGL(df_maxlen_kernel, dim3(1024), dim3(256), 0, io->cs, d, k, io->d_errs + 8);
-        if (hipStreamSynchronize(io->cs) != hipSuccess) { rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dfin: length scan failed"); break; }
+        if (snk_launch(df_maxlen_kernel, 1024, 256, 0, io->cs, d, k, io->d_errs + 8) != hipSuccess || hipStreamSynchronize(io->cs) != hipSuccess) { rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dfin: length scan failed"); break; }
     }
     if (!rc && hipMemcpy(out, io->d_errs + 8, 4, hipMemcpyDeviceToHost) != hipSuccess) rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dfin: download failed");
     (void)hipFree(d);
@@ -551,13 +550,12 @@ int run_slabs(snk_ctx* ctx, df_io* io, const snk_df_files* f, uint64_t first, ui
             if ((rc = target(s, a - first + done, take, &sd))) return rc;
             sd.first = a + done; sd.n = take;
             const uint64_t words = take * row_words;
-            hipLaunchKernelGGL(df_bases_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, cs, reinterpret_cast<const uint64_t*>(D + L.foffs) + done,
-                               reinterpret_cast<const uint32_t*>(D + L.flens) + done, reinterpret_cast<const uint32_t*>(D + L.fdata), f0, f1 - f0, take, row_words,
-                               max_len, sd.first, sd.rows, sd.lens, io->d_errs);
-            hipLaunchKernelGGL((df_quals_kernel<16>), dim3((unsigned)((take + 15) / 16)), dim3(256), 16 * qstride, cs, reinterpret_cast<const uint64_t*>(D + L.qoffs) + done,
-                               D + qat, q0, q1 - q0, take, qstride, sd.first, sd.quals, io->d_errs);
-            if (sd.bc) hipLaunchKernelGGL(df_bc_kernel, dim3((unsigned)((take + 255) / 256)), dim3(256), 0, cs, io->d_bci, m_bci, sd.first, take, sd.bc);
-            SNK_HIP_TRY(hipGetLastError());
+            SNK_HIP_TRY(snk_launch(df_bases_kernel, snk_blocks(words, 256), 256, 0, cs, reinterpret_cast<const uint64_t*>(D + L.foffs) + done,
+                                   reinterpret_cast<const uint32_t*>(D + L.flens) + done, reinterpret_cast<const uint32_t*>(D + L.fdata), f0, f1 - f0, take, row_words,
+                                   max_len, sd.first, sd.rows, sd.lens, io->d_errs));
+            SNK_HIP_TRY(snk_launch(df_quals_kernel<16>, snk_blocks(take, 16), 256, 16 * qstride, cs, reinterpret_cast<const uint64_t*>(D + L.qoffs) + done,
+                                   D + qat, q0, q1 - q0, take, qstride, sd.first, sd.quals, io->d_errs));
+            if (sd.bc) SNK_HIP_TRY(snk_launch(df_bc_kernel, snk_blocks(take, 256), 256, 0, cs, io->d_bci, m_bci, sd.first, take, sd.bc));
             if ((rc = consume(s, sd))) return rc;
             if (st) { st->file_bytes += (f1 - f0) + (q1 - q0) + (done == 0 ? (c + 1) * 16 + c * 4 : 0); ++st->n_slabs; }
             done += take;
@@ -754,7 +752,7 @@ extern "C" int snk_dev_ingest_df_count_graph(snk_ctx* ctx, snk_df_files* f, uint
         if (streamed && f->have_bci) DF_TRY(hipMalloc((void**)&o.bc, (slab_reads + 2) * 4ull));
     }
     if (!streamed && (io->c_reads < n || io->c_row_words != row_words || (f->have_bci && !io->c_bc))) {
-        SNK_HIP_TRY(hipStreamSynchronize(io->cs));
+        DF_TRY(hipStreamSynchronize(io->cs));
         io->release_compact();
         DF_TRY(hipMalloc((void**)&io->c_rows, (n + 1) * row_words * 4ull));
         DF_TRY(hipMalloc((void**)&io->c_gl, (n + 8) * 2ull));

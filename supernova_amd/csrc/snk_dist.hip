@@ -475,9 +475,8 @@ static int place_and_count(snk_ctx* ctx, snk_shard_state* S, hipStream_t st, uin
     if ((rc = snk_ctx_alloc(ctx, 2ull * (S->world + 1) * 8, &q, err, errcap))) return rc; S->rt_count = (unsigned long long*)q;
     if ((rc = snk_ctx_alloc(ctx, 2ull * (S->world + 1) * 8, &q, err, errcap))) return rc; S->rt_cursor = (unsigned long long*)q;
     SNK_HIP_TRY(hipMemsetAsync(S->rt_count, 0, 2ull * (S->world + 1) * 8, st));
-    if (Fl) hipLaunchKernelGGL((route_kernel<false>), dim3((unsigned)((Fl + 256 * ROUTE_TILES - 1) / (256 * ROUTE_TILES))), dim3(256), 4ull * S->world * 8, st, Fl, (unsigned long long)S->my_frag_off, S->frags.nk, S->pl.pid, S->pl.koff,
-                               S->pl.N, S->pl.circ, (const unsigned long long*)d_frag_off, S->world, K, S->frags.boff, S->frags.bases, S->rt_count, nullptr, nullptr, nullptr);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(route_kernel<false>, snk_blocks(Fl, 256 * ROUTE_TILES), 256, 4ull * S->world * 8, st, Fl, (unsigned long long)S->my_frag_off, S->frags.nk, S->pl.pid, S->pl.koff,
+                           S->pl.N, S->pl.circ, (const unsigned long long*)d_frag_off, S->world, K, S->frags.boff, S->frags.bases, S->rt_count, nullptr, nullptr, nullptr));
     std::vector<unsigned long long> h(2 * S->world);
     SNK_HIP_TRY(hipMemcpyAsync(h.data(), S->rt_count, 2ull * S->world * 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
@@ -588,10 +587,9 @@ extern "C" int snk_shard_route_fill(snk_ctx* ctx, uint32_t K, const void* d_frag
     const uint64_t Fl = S->frags.n_frags;
     SNK_HIP_TRY(hipMemcpyAsync(S->rt_cursor, d_hdr_off, S->world * 8ull, hipMemcpyDeviceToDevice, st));
     SNK_HIP_TRY(hipMemcpyAsync(S->rt_cursor + S->world, d_base_off, S->world * 8ull, hipMemcpyDeviceToDevice, st));
-    if (Fl) hipLaunchKernelGGL((route_kernel<true>), dim3((unsigned)((Fl + 256 * ROUTE_TILES - 1) / (256 * ROUTE_TILES))), dim3(256), 4ull * S->world * 8, st, Fl, (unsigned long long)S->my_frag_off, S->frags.nk, S->pl.pid, S->pl.koff,
-                               S->pl.N, S->pl.circ, (const unsigned long long*)d_frag_off, S->world, K, S->frags.boff, S->frags.bases, S->rt_cursor,
-                               (unsigned long long*)d_hdr, (uint8_t*)d_bases, (const unsigned long long*)d_base_off);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(route_kernel<true>, snk_blocks(Fl, 256 * ROUTE_TILES), 256, 4ull * S->world * 8, st, Fl, (unsigned long long)S->my_frag_off, S->frags.nk, S->pl.pid, S->pl.koff,
+                           S->pl.N, S->pl.circ, (const unsigned long long*)d_frag_off, S->world, K, S->frags.boff, S->frags.bases, S->rt_cursor,
+                           (unsigned long long*)d_hdr, (uint8_t*)d_bases, (const unsigned long long*)d_base_off));
     return SNK_OK;
 }
 
@@ -615,9 +613,8 @@ extern "C" int snk_shard_emit(snk_ctx* ctx, uint32_t K, uint64_t n_recv, const v
     if ((rc = snk_ctx_alloc(ctx, (n_recv + 1) * 8, &q, err, errcap))) return rc; N = (unsigned long long*)q;
     if ((rc = snk_ctx_alloc(ctx, (n_recv + 1), &q, err, errcap))) return rc; circ = (uint8_t*)q;
     if ((rc = snk_ctx_alloc(ctx, (n_recv + 2) * 8, &q, err, errcap))) return rc; boff = (uint64_t*)q;
-    if (n_recv) hipLaunchKernelGGL(unroute_kernel, dim3((unsigned)((n_recv + 255) / 256)), dim3(256), 0, st, (const unsigned long long*)d_hdr, n_recv,
-                                   (const unsigned long long*)d_hdr_seg, (const unsigned long long*)d_base_seg, S->world, nk, gfid, pid, koff, N, circ, boff);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(unroute_kernel, snk_blocks(n_recv, 256), 256, 0, st, (const unsigned long long*)d_hdr, n_recv,
+                           (const unsigned long long*)d_hdr_seg, (const unsigned long long*)d_base_seg, S->world, nk, gfid, pid, koff, N, circ, boff));
     snk_join_out jo;
     // every pid received here is a terminal state of one of this rank's own fragments
     rc = snk_join_emit(ctx, st, K, n_recv, nk, gfid, pid, koff, N, circ, (uint32_t)(2 * S->my_frag_off), 2 * S->frags.n_frags, boff, (const uint8_t*)d_bases,
@@ -684,8 +681,7 @@ extern "C" int snk_dev_pack2(snk_ctx* ctx, const void* d_bases, uint64_t n_bases
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
     const uint64_t nt = (n_bases + 15) / 16;
-    hipLaunchKernelGGL(pack2_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, (const uint8_t*)d_bases, n_bases, (uint8_t*)d_packed);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(pack2_kernel, snk_blocks(nt, 256), 256, 0, st, (const uint8_t*)d_bases, n_bases, (uint8_t*)d_packed));
     return SNK_OK;
 }
 
@@ -698,7 +694,6 @@ extern "C" int snk_dev_unpack2(snk_ctx* ctx, const void* d_packed, uint64_t n_ba
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
     const uint64_t nt = (n_bases + 15) / 16;
-    hipLaunchKernelGGL(unpack2_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, (const uint8_t*)d_packed, n_bases, (uint8_t*)d_bases);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(unpack2_kernel, snk_blocks(nt, 256), 256, 0, st, (const uint8_t*)d_packed, n_bases, (uint8_t*)d_bases));
     return SNK_OK;
 }

@@ -263,12 +263,12 @@ static int mark_dups_impl(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_p
     unsigned long long h_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t n_placed_total = 0;
     if (n) {
-        const unsigned gn = (unsigned)((n + 255) / 256);
+        const uint64_t gn = snk_blocks(n, 256);
         uint32_t* range;
         if ((rc = dev(ctx, 768, &range, err, errcap))) return rc;
         SNK_HIP_TRY(hipMemsetAsync(range, 0, 512 * 4, st));
         SNK_HIP_TRY(hipMemsetAsync(range + 512, 0xFF, 256 * 4, st));
-        hipLaunchKernelGGL(dup_key_kernel, dim3(gn), dim3(256), 0, st, a, key, head, id, stat + 8, range);
+        SNK_HIP_TRY(snk_launch(dup_key_kernel, gn, 256, 0, st, a, key, head, id, stat + 8, range));
         unsigned long long h_placed[256];
         uint32_t h_range[768];
         SNK_HIP_TRY(hipMemcpyAsync(h_placed, stat + 8, sizeof h_placed, hipMemcpyDeviceToHost, st));
@@ -285,7 +285,7 @@ static int mark_dups_impl(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_p
         const bool one_sort = total_bits <= 62 && !snk_opt_u32(ctx, SNK_OPT_dups_two_sorts);
         if (one_sort) {
             // the reference's record order (edge, offset, mate head, read id) in ONE stable sort over total_bits + 1 bits (the bench graph: 42)
-            hipLaunchKernelGGL(dup_composite_kernel, dim3(gn), dim3(256), 0, st, key, head, n, m ? omin : 0u, obits, total_bits);
+            SNK_HIP_TRY(snk_launch(dup_composite_kernel, gn, 256, 0, st, key, head, n, m ? omin : 0u, obits, total_bits));
             size_t tb = 0;
             SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, key, key2, id, id2, (size_t)n, 0u, total_bits + 1u, st));
             uint8_t* tmp;
@@ -301,20 +301,19 @@ static int mark_dups_impl(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_p
             if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
             size_t t = tb;
             SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, t, head, head2, id, id2, (size_t)n, 0u, 10u, st));          // id2 = ids by (head, id)
-            hipLaunchKernelGGL(dup_gather_key_kernel, dim3(gn), dim3(256), 0, st, id2, key, n, key2);
+            SNK_HIP_TRY(snk_launch(dup_gather_key_kernel, gn, 256, 0, st, id2, key, n, key2));
             t = tb;
             SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, t, key2, key, id2, id, (size_t)n, 0u, 64u, st));            // key / id = (edge, offset, head, id) order
             skey = key; sid = id;
         }
         if (m) {
-            const unsigned gm = (unsigned)((m + 255) / 256);
-            if (one_sort) hipLaunchKernelGGL(dup_flag1_kernel, dim3(gm), dim3(256), 0, st, skey, m, gstart, multi);
-            else hipLaunchKernelGGL(dup_flag_kernel, dim3(gm), dim3(256), 0, st, skey, sid, head, m, gstart, multi);
-            hipLaunchKernelGGL(dup_qsum_kernel, dim3(gm), dim3(256), 0, st, a, sid, multi, m, qsum);
-            hipLaunchKernelGGL(dup_group_kernel, dim3(gm), dim3(256), 0, st, a, skey, sid, head, gstart, qsum, m, dup, art, stat);
+            const uint64_t gm = snk_blocks(m, 256);
+            if (one_sort) SNK_HIP_TRY(snk_launch(dup_flag1_kernel, gm, 256, 0, st, skey, m, gstart, multi));
+            else SNK_HIP_TRY(snk_launch(dup_flag_kernel, gm, 256, 0, st, skey, sid, head, m, gstart, multi));
+            SNK_HIP_TRY(snk_launch(dup_qsum_kernel, gm, 256, 0, st, a, sid, multi, m, qsum));
+            SNK_HIP_TRY(snk_launch(dup_group_kernel, gm, 256, 0, st, a, skey, sid, head, gstart, qsum, m, dup, art, stat));
         }
-        if (np) hipLaunchKernelGGL(dup_count_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, dup, art, np, stat);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(dup_count_kernel, snk_blocks(np, 256), 256, 0, st, dup, art, np, stat));
         SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, 64, hipMemcpyDeviceToHost, st));
     }
     SNK_HIP_TRY(hipEventRecord(e1, st));

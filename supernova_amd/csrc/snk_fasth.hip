@@ -608,7 +608,7 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
         ING_RC(snk_dev_pack_ascii(ctx, st_ascii[slot], stride, read_len, nr, A.rows + n_reads * row_words, row_words, cs));
         if (ix) {
             ING_RC(snk_dev_bc_ids(ctx, ix, st_bcf[slot], 64, b.n_pairs, st_ids[slot], cs, err, errcap));
-            hipLaunchKernelGGL(pair_ids_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, cs, st_ids[slot], b.n_pairs, A.bc + n_reads);
+            ING_TRY(snk_launch(pair_ids_kernel, snk_blocks(nr, 256), 256, 0, cs, st_ids[slot], b.n_pairs, A.bc + n_reads));
         }
         ING_TRY(hipEventRecord(st_ev[slot], cs));
         st_busy[slot] = true;
@@ -749,7 +749,7 @@ extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths
         ING_RC(snk_dev_pack_ascii(ctx, q.ascii, stride, read_len, nr, q.rows, row_words, cs));
         if (ix) {
             ING_RC(snk_dev_bc_ids(ctx, ix, q.bcf, 64, b.n_pairs, q.ids, cs, err, errcap));
-            hipLaunchKernelGGL(pair_ids_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, cs, q.ids, b.n_pairs, q.bc);
+            ING_TRY(snk_launch(pair_ids_kernel, snk_blocks(nr, 256), 256, 0, cs, q.ids, b.n_pairs, q.bc));
         }
         snk_dev_reads slab;
         memset(&slab, 0, sizeof slab);

@@ -316,8 +316,6 @@ __global__ void __launch_bounds__(TB) spectrum_kernel(const uint32_t* __restrict
         if (h[j]) atomicAdd(&bins[j], (unsigned long long)h[j]);
 }
 
-inline unsigned nblk(uint64_t n) { return (unsigned)((n + TB - 1) / TB); }
-
 }  // namespace
 
 #define G_ALLOC(ptr, type, count)                                                       \
@@ -358,7 +356,7 @@ int snk_graph_sort(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t n, snk_u12
         SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, begin_bit,
                                               128u, st));
         SNK_HIP_TRY(hipMemsetAsync(bad, 0, 4, st));
-        hipLaunchKernelGGL(sorted_check_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys_out, n, bad);
+        SNK_HIP_TRY(snk_launch(sorted_check_kernel, snk_blocks(n, 256), 256, 0, st, keys_out, n, bad));
         uint32_t h_bad = 0;
         SNK_HIP_TRY(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
@@ -403,13 +401,13 @@ static int rank_lists_wyllie(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint6
     uint32_t rounds_total = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         cur = 0;
-        if (weights) hipLaunchKernelGGL(rank_init_w_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, weights, ns, nxt[0], dst[0], tl[0]);
-        else hipLaunchKernelGGL(rank_init_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, ns, nxt[0], dst[0], tl[0]);
+        if (weights) SNK_HIP_TRY(snk_launch(rank_init_w_kernel, snk_blocks(ns, TB), TB, 0, st, link, weights, ns, nxt[0], dst[0], tl[0]));
+        else SNK_HIP_TRY(snk_launch(rank_init_kernel, snk_blocks(ns, TB), TB, 0, st, link, ns, nxt[0], dst[0], tl[0]));
         bool converged = false;
         for (int r = 0; r < max_rounds; ++r) {
             SNK_HIP_TRY(hipMemsetAsync(flags, 0, 4, st));
-            hipLaunchKernelGGL(rank_round_kernel, dim3(nblk(ns)), dim3(TB), 0, st, nxt[cur], dst[cur], tl[cur], ns,
-                               nxt[cur ^ 1], dst[cur ^ 1], tl[cur ^ 1], flags);
+            SNK_HIP_TRY(snk_launch(rank_round_kernel, snk_blocks(ns, TB), TB, 0, st, nxt[cur], dst[cur], tl[cur], ns,
+                                   nxt[cur ^ 1], dst[cur ^ 1], tl[cur ^ 1], flags));
             cur ^= 1;
             ++rounds_total;
             SNK_HIP_TRY(hipMemcpyAsync(h_flags, flags, 4, hipMemcpyDeviceToHost, st));
@@ -423,15 +421,14 @@ static int rank_lists_wyllie(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint6
         uint32_t* mn[2];
         G_ALLOC(mn[0], uint32_t, ns);
         G_ALLOC(mn[1], uint32_t, ns);
-        hipLaunchKernelGGL(cyc_init_kernel, dim3(nblk(ns)), dim3(TB), 0, st, nxt[cur], link, ns, jump[0], mn[0]);
+        SNK_HIP_TRY(snk_launch(cyc_init_kernel, snk_blocks(ns, TB), TB, 0, st, nxt[cur], link, ns, jump[0], mn[0]));
         int c2 = 0;
         for (int r = 0; r < max_rounds; ++r) {
-            hipLaunchKernelGGL(cyc_round_kernel, dim3(nblk(ns)), dim3(TB), 0, st, jump[c2], mn[c2], ns, jump[c2 ^ 1], mn[c2 ^ 1]);
+            SNK_HIP_TRY(snk_launch(cyc_round_kernel, snk_blocks(ns, TB), TB, 0, st, jump[c2], mn[c2], ns, jump[c2 ^ 1], mn[c2 ^ 1]));
             c2 ^= 1;
         }
         SNK_HIP_TRY(hipMemsetAsync(flags + 1, 0, 4, st));
-        hipLaunchKernelGGL(cyc_cut_kernel, dim3(nblk(n)), dim3(TB), 0, st, mn[c2], n, link, flags + 1, circ);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(cyc_cut_kernel, snk_blocks(n, TB), TB, 0, st, mn[c2], n, link, flags + 1, circ));
     }
     SNK_HIP_TRY(hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
@@ -440,8 +437,7 @@ static int rank_lists_wyllie(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint6
     (void)hipHostFree(h_flags);
     uint2* rkz;
     G_ALLOC(rkz, uint2, ns);
-    hipLaunchKernelGGL(rank_zip_kernel, dim3(nblk(ns)), dim3(TB), 0, st, dst[cur], tl[cur], ns, rkz);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(rank_zip_kernel, snk_blocks(ns, TB), TB, 0, st, dst[cur], tl[cur], ns, rkz));
     *rk_out = rkz;
     return SNK_OK;
 }
@@ -608,28 +604,27 @@ static int cut_circles_sparse(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint
     uint8_t* reach;
     G_ALLOC(reach, uint8_t, ns + 1);
     SNK_HIP_TRY(hipMemsetAsync(reach, 0, ns + 1, st));
-    if (m) hipLaunchKernelGGL(spl_reach_kernel, dim3(nblk(m)), dim3(TB), 0, st, wrec, spl_state, m, reach);
+    SNK_HIP_TRY(snk_launch(spl_reach_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, m, reach));
     if (!jump_converged && m) {
         uint32_t *jump[2], *mn[2];
         for (int b = 0; b < 2; ++b) { G_ALLOC(jump[b], uint32_t, m + 1); G_ALLOC(mn[b], uint32_t, m + 1); }
-        hipLaunchKernelGGL(scyc_init_kernel, dim3(nblk(m)), dim3(TB), 0, st, rn_final, rn_orig, spl_state, m, jump[0], mn[0]);
+        SNK_HIP_TRY(snk_launch(scyc_init_kernel, snk_blocks(m, TB), TB, 0, st, rn_final, rn_orig, spl_state, m, jump[0], mn[0]));
         int max_rounds = 2;
         while ((1ull << (max_rounds - 1)) < m + 1) ++max_rounds;
         int c2 = 0;
         for (int r = 0; r < max_rounds; ++r) {
-            hipLaunchKernelGGL(cyc_round_kernel, dim3(nblk(m)), dim3(TB), 0, st, jump[c2], mn[c2], m, jump[c2 ^ 1], mn[c2 ^ 1]);
+            SNK_HIP_TRY(snk_launch(cyc_round_kernel, snk_blocks(m, TB), TB, 0, st, jump[c2], mn[c2], m, jump[c2 ^ 1], mn[c2 ^ 1]));
             c2 ^= 1;
         }
-        hipLaunchKernelGGL(scyc_cut_kernel, dim3(nblk(m)), dim3(TB), 0, st, mn[c2], spl_state, m, link, d_flags, circ);
+        SNK_HIP_TRY(snk_launch(scyc_cut_kernel, snk_blocks(m, TB), TB, 0, st, mn[c2], spl_state, m, link, d_flags, circ));
     }
     {
         const uint32_t cap = 1u << 18;
         uint32_t* list;
         G_ALLOC(list, uint32_t, cap);
-        hipLaunchKernelGGL(free_circle_find_kernel, dim3(nblk(ns)), dim3(TB), 0, st, reach, ns, (const uint32_t*)link, list, cap, d_flags + 2, d_flags + 1);
-        hipLaunchKernelGGL(cut_list_kernel, dim3(cap / TB), dim3(TB), 0, st, (const uint32_t*)list, (const uint32_t*)(d_flags + 2), cap, link, d_flags, circ);
+        SNK_HIP_TRY(snk_launch(free_circle_find_kernel, snk_blocks(ns, TB), TB, 0, st, reach, ns, (const uint32_t*)link, list, cap, d_flags + 2, d_flags + 1));
+        SNK_HIP_TRY(snk_launch(cut_list_kernel, cap / TB, TB, 0, st, (const uint32_t*)list, (const uint32_t*)(d_flags + 2), cap, link, d_flags, circ));
     }
-    SNK_HIP_TRY(hipGetLastError());
     uint32_t h[2] = {0, 0};
     SNK_HIP_TRY(hipMemcpyAsync(h, d_flags, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
@@ -653,7 +648,7 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
     G_ALLOC(sid, uint32_t, ns + 1);
     SNK_HIP_TRY(hipMemsetAsync(flag32 + ns, 0, 4, st));
     const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
-    hipLaunchKernelGGL(spl_mark_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, ns, split_mask, spl, flag32);
+    SNK_HIP_TRY(snk_launch(spl_mark_kernel, snk_blocks(ns, TB), TB, 0, st, link, ns, split_mask, spl, flag32));
     {
         size_t tb = 0;
         SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, flag32, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
@@ -667,14 +662,13 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
     SNK_HIP_TRY(snk_sync(st));
     const uint64_t m = m32;
     uint32_t* spl_state = flag32;      // flag32 is dead after the scan: reuse it for the compacted splitter list
-    if (m) hipLaunchKernelGGL(spl_collect_kernel, dim3(nblk(ns)), dim3(TB), 0, st, spl, sid, ns, spl_state);
+    if (m) SNK_HIP_TRY(snk_launch(spl_collect_kernel, snk_blocks(ns, TB), TB, 0, st, spl, sid, ns, spl_state));
     uint32_t *rn[2], *rd[2], *rt[2];
     for (int b = 0; b < 2; ++b) { G_ALLOC(rn[b], uint32_t, m + 1); G_ALLOC(rd[b], uint32_t, m + 1); G_ALLOC(rt[b], uint32_t, m + 1); }
     unsigned long long* wrec;
     G_ALLOC(wrec, unsigned long long, ns);
-    hipLaunchKernelGGL(spl_pack_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, spl, sid, ns, wrec);
-    if (m) hipLaunchKernelGGL(spl_walk1_kernel, dim3(nblk(m)), dim3(TB), 0, st, wrec, spl_state, weights, m, rn[0], rd[0], rt[0]);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(spl_pack_kernel, snk_blocks(ns, TB), TB, 0, st, link, spl, sid, ns, wrec));
+    SNK_HIP_TRY(snk_launch(spl_walk1_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, m, rn[0], rd[0], rt[0]));
     uint32_t* rn_orig;
     G_ALLOC(rn_orig, uint32_t, m + 1);
     if (m) SNK_HIP_TRY(hipMemcpyAsync(rn_orig, rn[0], m * 4, hipMemcpyDeviceToDevice, st));
@@ -696,15 +690,15 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
         const int upto = r == 0 ? (batch0 < max_rounds ? batch0 : max_rounds) : max_rounds;
         SNK_HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
         for (; r < upto; ++r) {
-            if (m) hipLaunchKernelGGL(rank_round_kernel, dim3(nblk(m)), dim3(TB), 0, st, rn[cur], rd[cur], rt[cur], m, rn[cur ^ 1], rd[cur ^ 1], rt[cur ^ 1],
-                                      r + 1 == upto ? flags : flags + 2);      // only the batch's last round reports
+            SNK_HIP_TRY(snk_launch(rank_round_kernel, snk_blocks(m, TB), TB, 0, st, rn[cur], rd[cur], rt[cur], m, rn[cur ^ 1], rd[cur ^ 1], rt[cur ^ 1],
+                                   r + 1 == upto ? flags : flags + 2));      // only the batch's last round reports
             cur ^= 1;
             ++r_done;
         }
         // optimistic: rank the states from what the rounds left (harmless if they had not converged: it is redone)
         SNK_HIP_TRY(hipMemsetAsync(rk, 0xFF, ns * 8, st));
-        if (m) hipLaunchKernelGGL(spl_walk2_kernel, dim3(nblk(m)), dim3(TB), 0, st, wrec, spl_state, weights, rd[cur], rt[cur], m, rk);
-        hipLaunchKernelGGL(unranked_check_kernel, dim3(nblk(ns)), dim3(TB), 0, st, rk, ns, flags + 1);
+        SNK_HIP_TRY(snk_launch(spl_walk2_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, rd[cur], rt[cur], m, rk));
+        SNK_HIP_TRY(snk_launch(unranked_check_kernel, snk_blocks(ns, TB), TB, 0, st, rk, ns, flags + 1));
         uint32_t h2[2] = {0, 0};
         SNK_HIP_TRY(hipMemcpyAsync(h2, flags, 8, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
@@ -857,15 +851,14 @@ static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const 
     unsigned long long* tab;
     G_ALLOC(tab, unsigned long long, tg);
     SNK_HIP_TRY(hipMemsetAsync(tab, 0, tg * 8, st));
-    hipLaunchKernelGGL(index_build_kernel, dim3(nblk(n)), dim3(TB), 0, st, keys, n, tab, tg - 1);
+    SNK_HIP_TRY(snk_launch(index_build_kernel, snk_blocks(n, TB), TB, 0, st, keys, n, tab, tg - 1));
     // prune
     uint8_t* ctx_out; uint32_t* count_out; uint32_t* nbr;
     G_ALLOC(ctx_out, uint8_t, n);
     G_ALLOC(count_out, uint32_t, n);
     G_ALLOC(nbr, uint32_t, 2 * n);
-    hipLaunchKernelGGL((prune_kernel<K>), dim3(nblk(n)), dim3(TB), 0, st, keys, vals, n, tab, tg - 1, do_prune, ctx_out,
-                       count_out, nbr);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(prune_kernel<K>, snk_blocks(n, TB), TB, 0, st, keys, vals, n, tab, tg - 1, do_prune, ctx_out,
+                           count_out, nbr));
     out->ctx = ctx_out;
     out->counts = count_out;
     // spectrum
@@ -878,8 +871,7 @@ static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const 
     const uint64_t ns = 2 * n;
     uint32_t* link;
     G_ALLOC(link, uint32_t, ns);
-    hipLaunchKernelGGL((link_kernel<K>), dim3(nblk(ns)), dim3(TB), 0, st, keys, ctx_out, nbr, n, link);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(link_kernel<K>, snk_blocks(ns, TB), TB, 0, st, keys, ctx_out, nbr, n, link));
 
     const uint2* rk = nullptr;
     {
@@ -890,7 +882,7 @@ static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const 
     uint8_t* prev;
     G_ALLOC(prev, uint8_t, ns);
     SNK_HIP_TRY(hipMemsetAsync(prev, 0, ns, st));
-    hipLaunchKernelGGL((orient_kernel<K>), dim3(nblk(n)), dim3(TB), 0, st, keys, rk, n, prev);
+    SNK_HIP_TRY(snk_launch(orient_kernel<K>, snk_blocks(n, TB), TB, 0, st, keys, rk, n, prev));
     uint32_t *hflag, *hidx;
     uint64_t *hlen, *hoff;
     G_ALLOC(hflag, uint32_t, n + 1);
@@ -899,8 +891,7 @@ static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const 
     G_ALLOC(hoff, uint64_t, n + 1);
     SNK_HIP_TRY(hipMemsetAsync(hflag + n, 0, 4, st));
     SNK_HIP_TRY(hipMemsetAsync(hlen + n, 0, 8, st));
-    hipLaunchKernelGGL(head_kernel, dim3(nblk(n)), dim3(TB), 0, st, rk, prev, n, (uint32_t)K, hflag, hlen);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(head_kernel, snk_blocks(n, TB), TB, 0, st, rk, prev, n, (uint32_t)K, hflag, hlen));
     {
         size_t t1 = 0, t2 = 0;
         SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, t1, hflag, hidx, 0u, (size_t)(n + 1), rocprim::plus<uint32_t>(), st));
@@ -922,10 +913,9 @@ static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const 
     G_ALLOC(poff, uint64_t, ns);
     G_ALLOC(uoff, uint64_t, n_unitigs + 1);
     G_ALLOC(bases, uint8_t, total_bases);
-    hipLaunchKernelGGL(head_place_kernel, dim3(nblk(n)), dim3(TB), 0, st, rk, hflag, hidx, hoff, n, poff, uoff);
+    SNK_HIP_TRY(snk_launch(head_place_kernel, snk_blocks(n, TB), TB, 0, st, rk, hflag, hidx, hoff, n, poff, uoff));
     SNK_HIP_TRY(hipMemcpyAsync(uoff + n_unitigs, hoff + n, 8, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL((emit_kernel<K>), dim3(nblk(n)), dim3(TB), 0, st, keys, rk, prev, poff, n, bases);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(emit_kernel<K>, snk_blocks(n, TB), TB, 0, st, keys, rk, prev, poff, n, bases));
     out->n_unitigs = n_unitigs;
     out->total_bases = total_bases;
     out->unitig_off = uoff;
@@ -1401,7 +1391,7 @@ static int chunk_owners(snk_ctx* ctx, hipStream_t st, uint32_t* nch /*[count+1],
     uint32_t* owner;
     G_ALLOC(owner, uint32_t, (uint64_t)total + 1);
     SNK_HIP_TRY(hipMemsetAsync(owner, 0, ((uint64_t)total + 1) * 4, st));
-    hipLaunchKernelGGL(jchunk_owner_kernel, dim3(nblk(count)), dim3(TB), 0, st, choff, count, owner);
+    SNK_HIP_TRY(snk_launch(jchunk_owner_kernel, snk_blocks(count, TB), TB, 0, st, choff, count, owner));
     if (total) {
         size_t tb = 0;
         SNK_HIP_TRY(rocprim::inclusive_scan((void*)nullptr, tb, owner, owner, (size_t)total, rocprim::maximum<uint32_t>(), st));
@@ -1417,14 +1407,12 @@ static int chunk_owners(snk_ctx* ctx, hipStream_t st, uint32_t* nch /*[count+1],
 
 int snk_dist_answer(snk_ctx* ctx, hipStream_t st, snk_dist_graph* g, const void* d_queries, uint64_t nq, void* d_ans, char* err,
                     size_t errcap) {
-    if (nq) hipLaunchKernelGGL(answer_kernel, dim3(nblk(nq)), dim3(TB), 0, st, (const unsigned long long*)d_queries, nq, g->keys, g->index, g->index_mask, (uint32_t*)d_ans);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(answer_kernel, snk_blocks(nq, TB), TB, 0, st, (const unsigned long long*)d_queries, nq, g->keys, g->index, g->index_mask, (uint32_t*)d_ans));
     return SNK_OK;
 }
 int snk_dist_apply(snk_ctx* ctx, hipStream_t st, snk_dist_graph* g, const void* d_qbuf, const void* d_ans, uint64_t nq,
                    const unsigned long long* d_qoff, char* err, size_t errcap) {
-    if (nq) hipLaunchKernelGGL(apply_answers_kernel, dim3(nblk(nq)), dim3(TB), 0, st, (const unsigned long long*)d_qbuf, (const uint32_t*)d_ans, nq, d_qoff, g->world, g->do_prune, reinterpret_cast<uint32_t*>(g->ctx), g->rq_idx, g->rq_meta);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(apply_answers_kernel, snk_blocks(nq, TB), TB, 0, st, (const unsigned long long*)d_qbuf, (const uint32_t*)d_ans, nq, d_qoff, g->world, g->do_prune, reinterpret_cast<uint32_t*>(g->ctx), g->rq_idx, g->rq_meta));
     return SNK_OK;
 }
 
@@ -1441,7 +1429,7 @@ int snk_dist_join(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
     if (!flink) G_ALLOC(flink, uint32_t, ne);
     if (flink_given) {
     } else if (sfrag) {
-        hipLaunchKernelGGL(jmatch_direct_kernel, dim3(nblk(ne)), dim3(TB), 0, st, hl_self, hl_nb, ne, sfrag, n_states, flink);
+        SNK_HIP_TRY(snk_launch(jmatch_direct_kernel, snk_blocks(ne, TB), TB, 0, st, hl_self, hl_nb, ne, sfrag, n_states, flink));
     } else {
         uint64_t tg = 1024;
         while (tg < 2 * ne) tg <<= 1;
@@ -1450,10 +1438,9 @@ int snk_dist_join(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
         G_ALLOC(hk, unsigned long long, tg);
         G_ALLOC(hv, uint32_t, tg);
         SNK_HIP_TRY(hipMemsetAsync(hk, 0, tg * 8, st));
-        hipLaunchKernelGGL(jhash_build_kernel, dim3(nblk(ne)), dim3(TB), 0, st, hl_self, ne, hk, hv, tg - 1);
-        hipLaunchKernelGGL(jmatch_kernel, dim3(nblk(ne)), dim3(TB), 0, st, hl_self, hl_nb, ne, hk, hv, tg - 1, flink);
+        SNK_HIP_TRY(snk_launch(jhash_build_kernel, snk_blocks(ne, TB), TB, 0, st, hl_self, ne, hk, hv, tg - 1));
+        SNK_HIP_TRY(snk_launch(jmatch_kernel, snk_blocks(ne, TB), TB, 0, st, hl_self, hl_nb, ne, hk, hv, tg - 1, flink));
     }
-    SNK_HIP_TRY(hipGetLastError());
     uint8_t* circ;     // per fragment-end state: terminal created by cutting a circle
     G_ALLOC(circ, uint8_t, ne + 1);
     SNK_HIP_TRY(hipMemsetAsync(circ, 0, ne + 1, st));
@@ -1492,8 +1479,7 @@ int snk_join_place(snk_ctx* ctx, hipStream_t st, const uint2* rk, const uint32_t
     G_ALLOC(pl->koff, unsigned long long, Fl + 1);
     G_ALLOC(pl->N, unsigned long long, Fl + 1);
     G_ALLOC(pl->circ, uint8_t, Fl + 1);
-    if (Fl) hipLaunchKernelGGL(jplace_kernel, dim3(nblk(Fl)), dim3(TB), 0, st, rk, rk_f0, nk, circ, f0, Fl, pl->pid, pl->koff, pl->N, pl->circ);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(jplace_kernel, snk_blocks(Fl, TB), TB, 0, st, rk, rk_f0, nk, circ, f0, Fl, pl->pid, pl->koff, pl->N, pl->circ));
     return SNK_OK;
 }
 
@@ -1507,7 +1493,7 @@ static int jdbg_count(snk_ctx* ctx, hipStream_t st, const char* what, const uint
     unsigned long long* d;
     G_ALLOC(d, unsigned long long, 1);
     SNK_HIP_TRY(hipMemsetAsync(d, 0, 8, st));
-    hipLaunchKernelGGL(jdbg_count_kernel, dim3(4096), dim3(256), 0, st, b, n, d);
+    SNK_HIP_TRY(snk_launch(jdbg_count_kernel, 4096, 256, 0, st, b, n, d));
     unsigned long long h = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
@@ -1536,7 +1522,7 @@ int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
     G_ALLOC(hoff, uint64_t, F + 1);
     SNK_HIP_TRY(hipMemsetAsync(hflag + F, 0, 4, st));
     SNK_HIP_TRY(hipMemsetAsync(hlen + F, 0, 8, st));
-    hipLaunchKernelGGL(jhead_kernel, dim3(nblk(F)), dim3(TB), 0, st, pl_pid, pl_koff, pl_N, gfid, F, K, hflag, hlen);
+    SNK_HIP_TRY(snk_launch(jhead_kernel, snk_blocks(F, TB), TB, 0, st, pl_pid, pl_koff, pl_N, gfid, F, K, hflag, hlen));
     if ((rc = excl_scan<uint32_t>(ctx, st, hflag, hidx, F + 1, err, errcap))) return rc;
     if ((rc = excl_scan<uint64_t>(ctx, st, hlen, hoff, F + 1, err, errcap))) return rc;
     uint32_t h_nu = 0;
@@ -1558,10 +1544,10 @@ int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
     G_ALLOC(final_bases, uint8_t, h_tot + 1);
     const bool jdbg = snk_opt_u32(ctx, SNK_OPT_join_dbg) != 0;
     if (jdbg) { SNK_HIP_TRY(hipMemsetAsync(prov, 0xEE, h_tot + 1, st)); SNK_HIP_TRY(hipMemsetAsync(final_bases, 0xEE, h_tot + 1, st)); fprintf(stderr, "[snk join dbg] F %llu unitigs %llu bases %llu\n", (unsigned long long)F, (unsigned long long)U, (unsigned long long)h_tot); }
-    hipLaunchKernelGGL(jhead_place_kernel, dim3(nblk(F)), dim3(TB), 0, st, pl_pid, pl_circ, hflag, hidx, hoff, F, pid_base, poff, uoff, ucirc, fgroup, ugroup);
+    SNK_HIP_TRY(snk_launch(jhead_place_kernel, snk_blocks(F, TB), TB, 0, st, pl_pid, pl_circ, hflag, hidx, hoff, F, pid_base, poff, uoff, ucirc, fgroup, ugroup));
     SNK_HIP_TRY(hipMemcpyAsync(uoff + U, hoff + F, 8, hipMemcpyDeviceToDevice, st));
     // copy every fragment into place
-    hipLaunchKernelGGL(jemit_kernel, dim3((unsigned)std::min<uint64_t>((F + 31) / 32, 1ull << std::min(22u, snk_opt_u32(ctx, SNK_OPT_emit_grid_log2)))), dim3(256), 0, st, F, boff, fbases, pl_pid, pl_koff, nk, poff, pid_base, K, prov);
+    SNK_HIP_TRY(snk_launch(jemit_kernel, snk_blocks_capped(F, 32, 1ull << std::min(22u, snk_opt_u32(ctx, SNK_OPT_emit_grid_log2))), 256, 0, st, F, boff, fbases, pl_pid, pl_koff, nk, poff, pid_base, K, prov));
     if (jdbg && (rc = jdbg_count(ctx, st, "provisional bases after the fragments' copies", prov, h_tot, err, errcap))) return rc;
     // circles that were cut at an arbitrary fragment boundary: rotate to the reference's cut (minimum k-mer, forward)
     {
@@ -1569,21 +1555,18 @@ int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
         G_ALLOC(clist, uint32_t, U + 1);
         G_ALLOC(ccnt, uint32_t, 4);
         SNK_HIP_TRY(hipMemsetAsync(ccnt, 0, 4, st));
-        hipLaunchKernelGGL(jcirc_list_kernel, dim3(nblk(U)), dim3(TB), 0, st, ucirc, U, clist, ccnt);
-        if (U) {
-            const unsigned cg = (unsigned)(U < 1024 ? U : 1024);
-            if (K == 48) hipLaunchKernelGGL((jcircle_kernel<48>), dim3(cg), dim3(256), 0, st, clist, ccnt, uoff, prov, final_bases);
-            else hipLaunchKernelGGL((jcircle_kernel<60>), dim3(cg), dim3(256), 0, st, clist, ccnt, uoff, prov, final_bases);
-        }
+        SNK_HIP_TRY(snk_launch(jcirc_list_kernel, snk_blocks(U, TB), TB, 0, st, ucirc, U, clist, ccnt));
+        const uint64_t cg = U < 1024 ? U : 1024;
+        if (K == 48) SNK_HIP_TRY(snk_launch(jcircle_kernel<48>, cg, 256, 0, st, clist, ccnt, uoff, prov, final_bases));
+        else SNK_HIP_TRY(snk_launch(jcircle_kernel<60>, cg, 256, 0, st, clist, ccnt, uoff, prov, final_bases));
     }
-    hipLaunchKernelGGL(jform_kernel, dim3(nblk(U)), dim3(TB), 0, st, uoff, U, prov, urev);
+    SNK_HIP_TRY(snk_launch(jform_kernel, snk_blocks(U, TB), TB, 0, st, uoff, U, prov, urev));
     uint32_t *unch, *uchoff, *uowner, utotal = 0;
     G_ALLOC(unch, uint32_t, U + 1);
     SNK_HIP_TRY(hipMemsetAsync(unch + U, 0, 4, st));
-    hipLaunchKernelGGL(jchunks_kernel, dim3(nblk(U)), dim3(TB), 0, st, uoff, U, unch);
+    SNK_HIP_TRY(snk_launch(jchunks_kernel, snk_blocks(U, TB), TB, 0, st, uoff, U, unch));
     if ((rc = chunk_owners(ctx, st, unch, U, &uchoff, &uowner, &utotal, err, errcap, chunks_ub))) return rc;
-    if (utotal) hipLaunchKernelGGL(jfinal_kernel, dim3(utotal), dim3(256), 0, st, uoff, uowner, uchoff, urev, prov, final_bases);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(jfinal_kernel, utotal, 256, 0, st, uoff, uowner, uchoff, urev, prov, final_bases));
     if (jdbg && (rc = jdbg_count(ctx, st, "oriented bases", final_bases, h_tot, err, errcap))) return rc;
     // deterministic order (fragment ids depend on the order in which workgroups reserved their output)
     uint64_t* noff = uoff;
@@ -1603,8 +1586,8 @@ int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
         G_ALLOC(ocirc, uint8_t, U + 1);
         if (ugroup) G_ALLOC(ogroup, uint32_t, U + 1);
         obases = prov;         // the provisional buffer is dead: reuse it for the ordered copy
-        if (K == 48) hipLaunchKernelGGL((jorder_key_kernel<48>), dim3(nblk(U)), dim3(TB), 0, st, uoff, final_bases, U, (const uint32_t*)ugroup, ok_in, oi_in);
-        else hipLaunchKernelGGL((jorder_key_kernel<60>), dim3(nblk(U)), dim3(TB), 0, st, uoff, final_bases, U, (const uint32_t*)ugroup, ok_in, oi_in);
+        if (K == 48) SNK_HIP_TRY(snk_launch(jorder_key_kernel<48>, snk_blocks(U, TB), TB, 0, st, uoff, final_bases, U, (const uint32_t*)ugroup, ok_in, oi_in));
+        else SNK_HIP_TRY(snk_launch(jorder_key_kernel<60>, snk_blocks(U, TB), TB, 0, st, uoff, final_bases, U, (const uint32_t*)ugroup, ok_in, oi_in));
         {
             size_t tb = 0;
             SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, ok_in, ok_out, oi_in, oi_out, (size_t)U, 0u, 128u, st));
@@ -1612,16 +1595,15 @@ int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
             if ((rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap))) return rc;
             SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, ok_in, ok_out, oi_in, oi_out, (size_t)U, 0u, 128u, st));
         }
-        hipLaunchKernelGGL(jorder_len_kernel, dim3(nblk(U + 1)), dim3(TB), 0, st, uoff, oi_out, U, olen);
+        SNK_HIP_TRY(snk_launch(jorder_len_kernel, snk_blocks(U + 1, TB), TB, 0, st, uoff, oi_out, U, olen));
         if ((rc = excl_scan<uint64_t>(ctx, st, olen, noff, U + 1, err, errcap))) return rc;
         uint32_t *onch, *ochoff, *oowner, ototal = 0;
         G_ALLOC(onch, uint32_t, U + 1);
         SNK_HIP_TRY(hipMemsetAsync(onch + U, 0, 4, st));
-        hipLaunchKernelGGL(jchunks_kernel, dim3(nblk(U)), dim3(TB), 0, st, noff, U, onch);
+        SNK_HIP_TRY(snk_launch(jchunks_kernel, snk_blocks(U, TB), TB, 0, st, noff, U, onch));
         if ((rc = chunk_owners(ctx, st, onch, U, &ochoff, &oowner, &ototal, err, errcap, chunks_ub))) return rc;
         if (jdbg) SNK_HIP_TRY(hipMemsetAsync(obases, 0xEE, h_tot + 1, st));
-        if (ototal) hipLaunchKernelGGL(jorder_copy_kernel, dim3(ototal), dim3(256), 0, st, oowner, ochoff, noff, uoff, oi_out, final_bases, ucirc, obases, ocirc, (const uint32_t*)ugroup, ogroup);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(jorder_copy_kernel, ototal, 256, 0, st, oowner, ochoff, noff, uoff, oi_out, final_bases, ucirc, obases, ocirc, (const uint32_t*)ugroup, ogroup));
         if (jdbg && (rc = jdbg_count(ctx, st, "ordered bases", obases, h_tot, err, errcap))) return rc;
     }
     // nothing is waited for here: the unitigs are stream-ordered results, the step's closing wait is the caller's
@@ -1656,12 +1638,7 @@ int snk_spectrum(snk_ctx* ctx, hipStream_t st, const uint32_t* counts, uint64_t 
     unsigned long long* bins;
     G_ALLOC(bins, unsigned long long, nbins);
     SNK_HIP_TRY(hipMemsetAsync(bins, 0, (size_t)nbins * 8, st));
-    if (n) {
-        unsigned g = nblk(n);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(spectrum_kernel, dim3(g), dim3(TB), 0, st, counts, n, bins, nbins);
-        SNK_HIP_TRY(hipGetLastError());
-    }
+    if (n) SNK_HIP_TRY(snk_launch(spectrum_kernel, snk_blocks_capped(n, TB, 2048), TB, 0, st, counts, n, bins, nbins));
     *bins_out = bins;
     *nbins_out = nbins;
     return SNK_OK;
@@ -1674,16 +1651,14 @@ int snk_dist_links_query(snk_ctx* ctx, hipStream_t st, bool fill, const snk_frag
     if (ne == 0) return SNK_OK;
     if (ne >= (1ull << 32)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments on one rank");
     const size_t lds = (size_t)world * 12 + 16;
-    if (fill) hipLaunchKernelGGL((jlink_query_kernel<true>), dim3(nblk((ne + RT_TILES - 1) / RT_TILES)), dim3(TB), lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_count_or_cursor, (unsigned long long*)d_qbuf);
-    else hipLaunchKernelGGL((jlink_query_kernel<false>), dim3(nblk((ne + RT_TILES - 1) / RT_TILES)), dim3(TB), lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_count_or_cursor, (unsigned long long*)nullptr);
-    SNK_HIP_TRY(hipGetLastError());
+    if (fill) SNK_HIP_TRY(snk_launch(jlink_query_kernel<true>, snk_blocks(snk_blocks(ne, RT_TILES), TB), TB, lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_count_or_cursor, (unsigned long long*)d_qbuf));
+    else SNK_HIP_TRY(snk_launch(jlink_query_kernel<false>, snk_blocks(snk_blocks(ne, RT_TILES), TB), TB, lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_count_or_cursor, (unsigned long long*)nullptr));
     return SNK_OK;
 }
 int snk_dist_links_answer(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_queries, uint64_t nq, unsigned long long my_state_base,
                           uint64_t n_local_states, unsigned long long my_end_base, void* d_ans, char* err, size_t errcap) {
-    if (nq) hipLaunchKernelGGL(jlink_answer_kernel, dim3(nblk(nq)), dim3(TB), 0, st, (const unsigned long long*)d_queries, nq, fr->hl_self, fr->hl_nb,
-                               2 * fr->n_frags, fr->sfrag, my_state_base, n_local_states, my_end_base, (uint32_t*)d_ans);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(jlink_answer_kernel, snk_blocks(nq, TB), TB, 0, st, (const unsigned long long*)d_queries, nq, fr->hl_self, fr->hl_nb,
+                           2 * fr->n_frags, fr->sfrag, my_state_base, n_local_states, my_end_base, (uint32_t*)d_ans));
     return SNK_OK;
 }
 int snk_dist_links_apply(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_qbuf, const void* d_ans, uint64_t nq, uint32_t** flink_out,
@@ -1692,8 +1667,7 @@ int snk_dist_links_apply(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, c
     uint32_t* flink;
     G_ALLOC(flink, uint32_t, ne + 2);
     SNK_HIP_TRY(hipMemsetAsync(flink, 0xFF, (ne + 2) * 4, st));
-    if (nq) hipLaunchKernelGGL(jlink_apply_kernel, dim3(nblk(nq)), dim3(TB), 0, st, (const unsigned long long*)d_qbuf, (const uint32_t*)d_ans, nq, flink);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(jlink_apply_kernel, snk_blocks(nq, TB), TB, 0, st, (const unsigned long long*)d_qbuf, (const uint32_t*)d_ans, nq, flink));
     *flink_out = flink;
     return SNK_OK;
 }
@@ -1705,9 +1679,8 @@ int snk_dist_links_apply_regions(snk_ctx* ctx, hipStream_t st, const snk_frag_ou
     G_ALLOC(flink, uint32_t, ne + 2);
     SNK_HIP_TRY(hipMemsetAsync(flink, 0xFF, (ne + 2) * 4, st));
     for (uint32_t p = 0; p < world; ++p)
-        if (counts[p]) hipLaunchKernelGGL(jlink_apply_kernel, dim3(nblk(counts[p])), dim3(TB), 0, st, (const unsigned long long*)d_qbuf + 3 * cap * p,
-                                          (const uint32_t*)d_ans + cap * p, (uint64_t)counts[p], flink);
-    SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(jlink_apply_kernel, snk_blocks(counts[p], TB), TB, 0, st, (const unsigned long long*)d_qbuf + 3 * cap * p,
+                               (const uint32_t*)d_ans + cap * p, (uint64_t)counts[p], flink));
     *flink_out = flink;
     return SNK_OK;
 }
@@ -1725,7 +1698,7 @@ int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk
     G_ALLOC(sid, uint32_t, ns + 1);
     SNK_HIP_TRY(hipMemsetAsync(flag32 + ns, 0, 4, st));
     const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
-    if (ns) hipLaunchKernelGGL(spl_mark_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, ns, split_mask, spl, flag32);
+    SNK_HIP_TRY(snk_launch(spl_mark_kernel, snk_blocks(ns, TB), TB, 0, st, link, ns, split_mask, spl, flag32));
     {
         size_t tb = 0;
         SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, flag32, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
@@ -1740,15 +1713,14 @@ int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk
     const uint64_t m = m32;
     P->m = m;
     P->spl_state = flag32;             // flag32 is dead after the scan: reuse it for the compacted splitter list
-    if (m) hipLaunchKernelGGL(spl_collect_kernel, dim3(nblk(ns)), dim3(TB), 0, st, spl, sid, ns, P->spl_state);
+    if (m) SNK_HIP_TRY(snk_launch(spl_collect_kernel, snk_blocks(ns, TB), TB, 0, st, spl, sid, ns, P->spl_state));
     G_ALLOC(P->wrec, unsigned long long, ns + 1);
-    if (ns) hipLaunchKernelGGL(spl_pack_kernel, dim3(nblk(ns)), dim3(TB), 0, st, link, spl, sid, ns, P->wrec);
+    SNK_HIP_TRY(snk_launch(spl_pack_kernel, snk_blocks(ns, TB), TB, 0, st, link, spl, sid, ns, P->wrec));
     P->k0 = m * rank / world;
     P->k1 = m * (rank + 1) / world;
     const uint64_t cnt = P->k1 - P->k0;
     G_ALLOC(P->w1_share, uint4, cnt + 1);
-    if (cnt) hipLaunchKernelGGL(spl_walk1p_kernel, dim3(nblk(cnt)), dim3(TB), 0, st, P->wrec, P->spl_state, nk, P->k0, cnt, P->w1_share);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(spl_walk1p_kernel, snk_blocks(cnt, TB), TB, 0, st, P->wrec, P->spl_state, nk, P->k0, cnt, P->w1_share));
     return SNK_OK;
 }
 
@@ -1767,7 +1739,7 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
     G_ALLOC(tot, unsigned long long, 2);
     G_ALLOC(flags, uint32_t, 4);
     SNK_HIP_TRY(hipMemsetAsync(tot, 0, 8, st));
-    if (m) hipLaunchKernelGGL(prank_unzip_kernel, dim3(nblk(m)), dim3(TB), 0, st, w1_all, m, rn[0], rd[0], rt[0], tot);
+    SNK_HIP_TRY(snk_launch(prank_unzip_kernel, snk_blocks(m, TB), TB, 0, st, w1_all, m, rn[0], rd[0], rt[0], tot));
     uint32_t* rn_orig;
     G_ALLOC(rn_orig, uint32_t, m + 1);
     if (m) SNK_HIP_TRY(hipMemcpyAsync(rn_orig, rn[0], m * 4, hipMemcpyDeviceToDevice, st));
@@ -1784,7 +1756,7 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
         int did = 0;
         for (; did < BATCH_R && r < max_rounds && m; ++did, ++r) {
             SNK_HIP_TRY(hipMemsetAsync(flags, 0, 4, st));
-            hipLaunchKernelGGL(rank_round_kernel, dim3(nblk(m)), dim3(TB), 0, st, rn[cur], rd[cur], rt[cur], m, rn[cur ^ 1], rd[cur ^ 1], rt[cur ^ 1], flags);
+            SNK_HIP_TRY(snk_launch(rank_round_kernel, snk_blocks(m, TB), TB, 0, st, rn[cur], rd[cur], rt[cur], m, rn[cur ^ 1], rd[cur ^ 1], rt[cur ^ 1], flags));
             cur ^= 1;
             ++*rounds;
         }
@@ -1813,15 +1785,14 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
     uint64_t *steps, *pos;
     G_ALLOC(steps, uint64_t, cnt + 1);
     G_ALLOC(pos, uint64_t, cnt + 1);
-    hipLaunchKernelGGL(prank_steps_kernel, dim3(nblk(cnt + 1)), dim3(TB), 0, st, w1_all, P->k0, cnt, steps);
+    SNK_HIP_TRY(snk_launch(prank_steps_kernel, snk_blocks(cnt + 1, TB), TB, 0, st, w1_all, P->k0, cnt, steps));
     int rc = excl_scan<uint64_t>(ctx, st, steps, pos, cnt + 1, err, errcap);
     if (rc) return rc;
     uint64_t n_rec = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&n_rec, pos + cnt, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
     G_ALLOC(P->rec, uint4, n_rec + 1);
-    if (cnt) hipLaunchKernelGGL(spl_walk2p_kernel, dim3(nblk(cnt)), dim3(TB), 0, st, P->wrec, P->spl_state, P->w, rd[cur], rt[cur], P->k0, cnt, pos, P->rec);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(spl_walk2p_kernel, snk_blocks(cnt, TB), TB, 0, st, P->wrec, P->spl_state, P->w, rd[cur], rt[cur], P->k0, cnt, pos, P->rec));
     P->n_rec = n_rec;
     return SNK_OK;
 }
@@ -1829,10 +1800,9 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
 int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, bool fill, const unsigned long long* d_frag_off, uint32_t world,
                     unsigned long long* d_cnt_or_cur, void* d_out, char* err, size_t errcap) {
     if (!P->n_rec) return SNK_OK;
-    const unsigned nb = (unsigned)((P->n_rec + 256 * PR_TILES - 1) / (256 * PR_TILES));
-    if (fill) hipLaunchKernelGGL((prank_route_kernel<true>), dim3(nb), dim3(256), world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cnt_or_cur, (uint4*)d_out);
-    else hipLaunchKernelGGL((prank_route_kernel<false>), dim3(nb), dim3(256), world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cnt_or_cur, (uint4*)nullptr);
-    SNK_HIP_TRY(hipGetLastError());
+    const uint64_t nb = snk_blocks(P->n_rec, 256 * PR_TILES);
+    if (fill) SNK_HIP_TRY(snk_launch(prank_route_kernel<true>, nb, 256, world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cnt_or_cur, (uint4*)d_out));
+    else SNK_HIP_TRY(snk_launch(prank_route_kernel<false>, nb, 256, world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cnt_or_cur, (uint4*)nullptr));
     return SNK_OK;
 }
 
@@ -1845,8 +1815,8 @@ int snk_prank_apply(snk_ctx* ctx, hipStream_t st, const void* d_rec, uint64_t n,
     G_ALLOC(flag, uint32_t, 4);
     SNK_HIP_TRY(hipMemsetAsync(rk, 0xFF, (n_local_states + 1) * 8, st));
     SNK_HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
-    if (n) hipLaunchKernelGGL(prank_apply_kernel, dim3(nblk(n)), dim3(TB), 0, st, (const uint4*)d_rec, n, state_base, n_local_states, rk, flag);
-    if (n_local_states) hipLaunchKernelGGL(unranked_check_kernel, dim3(nblk(n_local_states)), dim3(TB), 0, st, (const uint2*)rk, n_local_states, flag + 1);
+    SNK_HIP_TRY(snk_launch(prank_apply_kernel, snk_blocks(n, TB), TB, 0, st, (const uint4*)d_rec, n, state_base, n_local_states, rk, flag));
+    SNK_HIP_TRY(snk_launch(unranked_check_kernel, snk_blocks(n_local_states, TB), TB, 0, st, (const uint2*)rk, n_local_states, flag + 1));
     uint32_t h[2] = {0, 0};
     SNK_HIP_TRY(hipMemcpyAsync(h, flag, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));

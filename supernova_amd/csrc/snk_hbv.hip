@@ -574,8 +574,8 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     SNK_HIP_TRY(hipEventCreate(&e1));
     SNK_HIP_TRY(hipEventRecord(e0, st));
     SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
-    const unsigned gU = (unsigned)((U + HB - 1) / HB), g4 = (unsigned)((n4 + HB - 1) / HB);
-    hipLaunchKernelGGL(hbv_head_kernel, dim3(gU), dim3(HB), 0, st, off, bases, U, K, keys, idx, pal, flags);
+    const uint64_t gU = snk_blocks(U, HB), g4 = snk_blocks(n4, HB);
+    SNK_HIP_TRY(snk_launch(hbv_head_kernel, gU, HB, 0, st, off, bases, U, K, keys, idx, pal, flags));
     // BVComp rank: sort by first k-mer, then stable sort by descending length
     size_t tmp_bytes = 0, tb2 = 0, tb3 = 0;
     SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tmp_bytes, lkey, lkey2, idx, order, (size_t)U, 0u, 64u, st));
@@ -588,10 +588,10 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     if ((rc = dalloc(sl, tmp_bytes, &tmp, err, errcap))) return rc;
     size_t tbx = tmp_bytes;
     SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, keys, keys2, idx, codes, (size_t)U, 0u, 128u, st));   // codes = first-k-mer order
-    hipLaunchKernelGGL(hbv_lenkey_kernel, dim3(gU), dim3(HB), 0, st, off, codes, U, lkey);
+    SNK_HIP_TRY(snk_launch(hbv_lenkey_kernel, gU, HB, 0, st, off, codes, U, lkey));
     tbx = tmp_bytes;
     SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, lkey, lkey2, codes, order, (size_t)U, 0u, 64u, st));
-    hipLaunchKernelGGL(hbv_ends_kernel, dim3(g4), dim3(HB), 0, st, off, bases, order, pal, U, K, keys, codes, palr);
+    SNK_HIP_TRY(snk_launch(hbv_ends_kernel, g4, HB, 0, st, off, bases, order, pal, U, K, keys, codes, palr));
     // vertex-major order of the ends: stable sort by the (K-1)-mer; inside a vertex the generation order (rank, rc,
     // position) is EEComp
     tbx = tmp_bytes;
@@ -601,13 +601,12 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     SNK_HIP_TRY(snk_sync(st));
     if (h_flags[0]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_hbv: a unitig is shorter than K");
     const uint64_t n_ee = n4 - 2ull * h_flags[1];            // the missing ends of palindromes sorted last
-    const unsigned ge = (unsigned)((n_ee + HB - 1) / HB);
-    hipLaunchKernelGGL(hbv_flag_kernel, dim3(ge), dim3(HB), 0, st, keys2, n_ee, flag);
+    const uint64_t ge = snk_blocks(n_ee, HB);
+    SNK_HIP_TRY(snk_launch(hbv_flag_kernel, ge, HB, 0, st, keys2, n_ee, flag));
     tbx = tmp_bytes;
     SNK_HIP_TRY(rocprim::inclusive_scan(tmp, tbx, flag, cls, (size_t)n_ee, rocprim::plus<uint32_t>(), st));
     SNK_HIP_TRY(hipMemsetAsync(vtx_of, 0xFF, n4 * 4, st));
-    hipLaunchKernelGGL(hbv_class_kernel, dim3(ge), dim3(HB), 0, st, cls, flag, codes2, n_ee, vtx_of, run_beg);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(hbv_class_kernel, ge, HB, 0, st, cls, flag, codes2, n_ee, vtx_of, run_beg));
     uint32_t nruns = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&nruns, cls + (n_ee - 1), 4, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
@@ -662,18 +661,17 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
         SNK_HIP_TRY(hipMemsetAsync(d_fwd, 0xFF, U * 8, st));                  // fwd, rev
         SNK_HIP_TRY(hipMemsetAsync(d_vid, 0xFF, (size_t)nruns * 4, st));
         SNK_HIP_TRY(hipMemsetAsync(d_nbig, 0, 8, st));
-        const unsigned g2 = (unsigned)((n2 + HB - 1) / HB), gr = (unsigned)(((uint64_t)nruns + HB - 1) / HB);
-        hipLaunchKernelGGL(hbv_cc_init_kernel, dim3(g2), dim3(HB), 0, st, par, n2);
-        hipLaunchKernelGGL(hbv_cc_union_kernel, dim3(ge), dim3(HB), 0, st, codes2, cls, run_beg, n_ee, (uint32_t)U, par, d_nbig + 1);
-        hipLaunchKernelGGL(hbv_cc_nodes_kernel, dim3(g2), dim3(HB), 0, st, par, palr, (uint32_t)U, ce, d_nbig + 1);
-        hipLaunchKernelGGL(hbv_cc_classes_kernel, dim3(gr), dim3(HB), 0, st, par, codes2, run_beg, (uint64_t)nruns, (uint32_t)U, cv, d_nbig + 1);
+        const uint64_t g2 = snk_blocks(n2, HB), gr = snk_blocks(nruns, HB);
+        SNK_HIP_TRY(snk_launch(hbv_cc_init_kernel, g2, HB, 0, st, par, n2));
+        SNK_HIP_TRY(snk_launch(hbv_cc_union_kernel, ge, HB, 0, st, codes2, cls, run_beg, n_ee, (uint32_t)U, par, d_nbig + 1));
+        SNK_HIP_TRY(snk_launch(hbv_cc_nodes_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, d_nbig + 1));
+        SNK_HIP_TRY(snk_launch(hbv_cc_classes_kernel, gr, HB, 0, st, par, codes2, run_beg, (uint64_t)nruns, (uint32_t)U, cv, d_nbig + 1));
         tbx = tmp_bytes;
         SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tbx, ce, be, 0u, (size_t)n2, rocprim::plus<uint32_t>(), st));
         tbx = tmp_bytes;
         SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tbx, cv, bv, 0u, (size_t)n2, rocprim::plus<uint32_t>(), st));
-        hipLaunchKernelGGL(hbv_flood_kernel, dim3(g2), dim3(HB), 0, st, par, palr, (uint32_t)U, ce, be, bv, codes2, vtx_of, run_beg, big_limit,
-                           d_fwd, d_rev, d_vid, d_vl, d_vr, d_src, d_isrc, d_big, big_cap, d_nbig, nruns, d_nbig + 1);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(hbv_flood_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, be, bv, codes2, vtx_of, run_beg, big_limit,
+                               d_fwd, d_rev, d_vid, d_vl, d_vr, d_src, d_isrc, d_big, big_cap, d_nbig, nruns, d_nbig + 1));
         SNK_HIP_TRY(hipEventRecord(e1, st));
         uint32_t h_nb[2] = {0, 0};
         SNK_HIP_TRY(hipMemcpyAsync(h_nb, d_nbig, 8, hipMemcpyDeviceToHost, st));

@@ -232,24 +232,23 @@ int unitigs_bv_device(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t U, cons
         }
         uint8_t* tmp;
         if ((rc = arena(ctx, std::max(tb, std::max(tb2, tb3)), &tmp, err, errcap))) return rc;
-        if (by_first_kmer) hipLaunchKernelGGL(bv_lenkey_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, d_off, U, key, idx);
+        if (by_first_kmer) SNK_HIP_TRY(snk_launch(bv_lenkey_kernel, snk_blocks(U, 256), 256, 0, st, d_off, U, key, idx));
         else {
-            hipLaunchKernelGGL(bv_headkey_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, d_off, d_bases, U, K, hk, idx);
+            SNK_HIP_TRY(snk_launch(bv_headkey_kernel, snk_blocks(U, 256), 256, 0, st, d_off, d_bases, U, K, hk, idx));
             SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb3, hk, hk2, idx, idx1, (size_t)U, 0u, 128u, st));
-            hipLaunchKernelGGL(bv_lenkey_of_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, d_off, idx1, U, key);
+            SNK_HIP_TRY(snk_launch(bv_lenkey_of_kernel, snk_blocks(U, 256), 256, 0, st, d_off, idx1, U, key));
             idx = idx1;
         }
         SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, key, key2, idx, order, (size_t)U, 0u, 64u, st));
-        hipLaunchKernelGGL(bv_sizes_kernel, dim3((unsigned)((U + 256) / 256)), dim3(256), 0, st, d_off, order, U, want_image ? 1 : 0, sz);
+        SNK_HIP_TRY(snk_launch(bv_sizes_kernel, snk_blocks(U + 1, 256), 256, 0, st, d_off, order, U, want_image ? 1 : 0, sz));
         SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb2, sz, noff, (uint64_t)0, (size_t)(U + 1), rocprim::plus<uint64_t>(), st));
         SNK_HIP_TRY(hipMemcpyAsync(&total, noff + U, 8, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
     }
     uint8_t* d_out;
     if ((rc = arena(ctx, header_bytes + total + 16, &d_out, err, errcap))) return rc;
-    if (total) hipLaunchKernelGGL(bv_gather_kernel, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, st, d_off, d_bases, order, noff, U, total,
-                                  want_image ? 1 : 0, d_out + header_bytes);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(bv_gather_kernel, snk_blocks(total, 1024), 256, 0, st, d_off, d_bases, order, noff, U, total,
+                           want_image ? 1 : 0, d_out + header_bytes));
     *d_out_p = d_out;
     *d_noff_p = noff;
     *total_p = total;
@@ -365,7 +364,7 @@ int count_graph_impl(snk_ctx* ctx, const snk_reads* in, const snk_params* p, snk
     if (nk) {
         uint4* kw;
         if ((rc = arena(ctx, nk, &kw, err, errcap))) return rc;
-        hipLaunchKernelGGL(key_words_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, st, (const snk_kmer*)r.keys, nk, kw);
+        SNK_HIP_TRY(snk_launch(key_words_kernel, snk_blocks(nk, 256), 256, 0, st, (const snk_kmer*)r.keys, nk, kw));
         SNK_HIP_TRY(hipMemcpyAsync(out->kmers, kw, nk * 16, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(hipMemcpyAsync(out->counts, r.counts, nk * 4, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(hipMemcpyAsync(out->ctx, r.ctx, nk, hipMemcpyDeviceToHost, st));
@@ -424,8 +423,7 @@ extern "C" int snk_dev_bv_image(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, co
         int rc = unitigs_bv_device(ctx, st, K, n_unitigs, (const uint64_t*)d_unitig_off, (const uint8_t*)d_unitig_bases, by_first_kmer != 0, true, 16, &d_out, &noff, &total,
                                    err, errcap);
         if (rc) return rc;
-        hipLaunchKernelGGL(bv_header_kernel, dim3(1), dim3(64), 0, st, d_out, n_unitigs);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(bv_header_kernel, 1, 64, 0, st, d_out, n_unitigs));
         *d_image = d_out;
         *image_bytes = 16 + total;
         return SNK_OK;

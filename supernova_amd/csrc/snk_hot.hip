@@ -230,10 +230,9 @@ int alloc(snk_ctx* ctx, size_t n, T** out, char* err, size_t errcap) {
 template <int K, bool GROUPED>
 int expand(hipStream_t st, const hot_tab& h, uint64_t total_records, const uint4* records, const uint64_t* saved, uint32_t nseg, uint32_t* vcount,
            const uint64_t* voff, uint4* out, bool scatter, char* err, size_t errcap) {
-    const unsigned grid = (unsigned)((total_records + HT - 1) / HT);
-    if (!scatter) hipLaunchKernelGGL((hot_expand_kernel<K, GROUPED, false>), dim3(grid), dim3(HT), 0, st, h, records, saved, nseg, vcount, voff, out);
-    else hipLaunchKernelGGL((hot_expand_kernel<K, GROUPED, true>), dim3(grid), dim3(HT), 0, st, h, records, saved, nseg, vcount, voff, out);
-    SNK_HIP_TRY(hipGetLastError());
+    const uint64_t grid = snk_blocks(total_records, HT);
+    if (!scatter) SNK_HIP_TRY(snk_launch(hot_expand_kernel<K, GROUPED, false>, grid, HT, 0, st, h, records, saved, nseg, vcount, voff, out));
+    else SNK_HIP_TRY(snk_launch(hot_expand_kernel<K, GROUPED, true>, grid, HT, 0, st, h, records, saved, nseg, vcount, voff, out));
     return SNK_OK;
 }
 
@@ -277,8 +276,7 @@ static int hot_expand_run(snk_ctx* ctx, hipStream_t st, const void* records, snk
     if ((rc = alloc(ctx, 2 * (size_t)n_inst + 2, &vrec, err, errcap))) return rc;
     SNK_HIP_TRY(hipMemsetAsync(P->vcount, 0, ((size_t)NBv + 1) * 4, st));
     if ((rc = run(true, vrec))) return rc;
-    hipLaunchKernelGGL(hot_seg_kernel, dim3((NBv + 255) / 256), dim3(256), 0, st, P->voff, NBv, P->vseg);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(hot_seg_kernel, snk_blocks(NBv, 256), 256, 0, st, P->voff, NBv, P->vseg));
     hot->n_instances = n_inst;
     hot->records = vrec;
     hot->seg = P->vseg;
@@ -315,8 +313,8 @@ int snk_stage_hot_plan(snk_ctx* ctx, hipStream_t st, uint32_t K, bool grouped, u
         return rc;
     SNK_HIP_TRY(hipMemsetAsync(ctr, 0, 64, st));
     const seg_tab sg{seg_beg, seg_end, stride, nseg};
-    hipLaunchKernelGGL(hot_scan_kernel, dim3((NB + 255) / 256), dim3(256), 0, st, sg, NB, (uint32_t)thr, hot_cap, hot_b, hot_r, ctr);
-    hipLaunchKernelGGL(hot_plan_kernel, dim3(1), dim3(64), 0, st, hot_r, hot_cap, snk_opt_u32(ctx, SNK_OPT_hot_class_inst), lg, rbase, vbase, ctr);
+    SNK_HIP_TRY(snk_launch(hot_scan_kernel, snk_blocks(NB, 256), 256, 0, st, sg, NB, (uint32_t)thr, hot_cap, hot_b, hot_r, ctr));
+    SNK_HIP_TRY(snk_launch(hot_plan_kernel, 1, 64, 0, st, hot_r, hot_cap, snk_opt_u32(ctx, SNK_OPT_hot_class_inst), lg, rbase, vbase, ctr));
     unsigned long long h_ctr[3] = {0, 0, 0};
     SNK_HIP_TRY(hipMemcpyAsync(h_ctr, ctr, 24, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
@@ -334,9 +332,8 @@ int snk_stage_hot_plan(snk_ctx* ctx, hipStream_t st, uint32_t K, bool grouped, u
         snk_stage_hot_drop(hot);
         return rc;
     }
-    hipLaunchKernelGGL(hot_mask_kernel, dim3((n_hot + 255) / 256), dim3(256), 0, st, P->h, seg_beg, seg_end, stride, nseg, P->saved);
-    hipLaunchKernelGGL(hot_meta_kernel, dim3((NBv + 255) / 256), dim3(256), 0, st, P->h, vmeta);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(hot_mask_kernel, snk_blocks(n_hot, 256), 256, 0, st, P->h, seg_beg, seg_end, stride, nseg, P->saved));
+    SNK_HIP_TRY(snk_launch(hot_meta_kernel, snk_blocks(NBv, 256), 256, 0, st, P->h, vmeta));
     hot->n_hot = n_hot;
     hot->NBv = NBv;
     hot->n_records = P->n_rec;

@@ -163,9 +163,8 @@ extern "C" int snk_dev_bc_ids(snk_ctx* ctx, const snk_bc_index* ix, const void* 
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
     SNK_HIP_TRY(hipMemsetAsync(ix->d_err, 0, 16, st));
-    hipLaunchKernelGGL(bc_ids_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint8_t*)d_fields, stride, n_reads,
-                       ix->d_hash, ix->d_line, ix->d_text, ix->n, ix->num_bcs, (int32_t*)d_ids, ix->d_err);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(bc_ids_kernel, snk_blocks(n_reads, 256), 256, 0, st, (const uint8_t*)d_fields, stride, n_reads,
+                           ix->d_hash, ix->d_line, ix->d_text, ix->n, ix->num_bcs, (int32_t*)d_ids, ix->d_err));
     uint32_t h_err[2] = {0, 0};
     SNK_HIP_TRY(hipMemcpyAsync(h_err, ix->d_err, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));

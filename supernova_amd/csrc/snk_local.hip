@@ -37,7 +37,6 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr unsigned long long NONE64 = ~0ull;
 constexpr uint16_t NONE16 = 0xFFFFu;
 constexpr int TB = 256;
-inline unsigned nblk(uint64_t n) { return (unsigned)((n + TB - 1) / TB); }
 
 struct chunk_src {
     const uint32_t* chunk_n;
@@ -918,7 +917,7 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
         uint32_t* merged;
         G_ALLOC(span, uint8_t, (uint64_t)tab->NB + 1);
         G_ALLOC(merged, uint32_t, (uint64_t)tab->NB + 1);
-        hipLaunchKernelGGL(bl_chunk_merge_kernel, dim3((tab->n_regions + 255) / 256), dim3(256), 0, st, tab->chunk_n, tab->chunk_base, tab->NB, tab->n_regions, merge_cap, span, merged);
+        SNK_HIP_TRY(snk_launch(bl_chunk_merge_kernel, snk_blocks(tab->n_regions, 256), 256, 0, st, tab->chunk_n, tab->chunk_base, tab->NB, tab->n_regions, merge_cap, span, merged));
         cs.span = span;
         cs.chunk_n = merged;
     }
@@ -927,7 +926,7 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
     G_ALLOC(B->desc, uint4, (uint64_t)nchunks + 1);
     uint64_t* desc_src = nullptr;
     if (tab->keys_r) G_ALLOC(desc_src, uint64_t, (uint64_t)nchunks + 1);
-    hipLaunchKernelGGL(bl_chunk_desc_kernel, dim3((nchunks + 255) / 256), dim3(256), 0, st, cs, nchunks, B->desc, tab->region_cap, desc_src);
+    SNK_HIP_TRY(snk_launch(bl_chunk_desc_kernel, snk_blocks(nchunks, 256), 256, 0, st, cs, nchunks, B->desc, tab->region_cap, desc_src));
     uint32_t *nbnd, *ctr;
     G_ALLOC(B->ctx, uint8_t, n + 16);
     G_ALLOC(B->pend, uint8_t, n + 16);
@@ -967,18 +966,16 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
     rg.keys_r = tab->keys_r; rg.vals_r = tab->vals_r; rg.desc_src = desc_src;
     rg.keys_dense = const_cast<snk_u128*>(tab->keys);
     const bool long_m = ctx->mlen == (uint32_t)SNK_M_LONG;
-    hipLaunchKernelGGL((long_m ? bl_prune_kernel<K, SCAP, ST, false, GR, SNK_M_LONG> : bl_prune_kernel<K, SCAP, ST, false, GR, SNK_M_OF(K)>), dim3((nchunks + cpw - 1) / cpw), dim3(ST), 0, st, (const uint4*)B->desc, NBh, sh, rg,
-                       (const uint32_t*)nullptr, nchunks, cpw, tab->keys, tab->vals, B->do_prune | (snk_opt_u32(ctx, SNK_OPT_bl_noclassify) ? 2u : 0u), B->ctx, B->counts, B->pend, B->nbr, nbnd,
-                       B->biglist, ctr, (const uint32_t*)nullptr, index0, tg0 - 1);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(long_m ? bl_prune_kernel<K, SCAP, ST, false, GR, SNK_M_LONG> : bl_prune_kernel<K, SCAP, ST, false, GR, SNK_M_OF(K)>, snk_blocks(nchunks, cpw), ST, 0, st, (const uint4*)B->desc, NBh, sh, rg,
+                           (const uint32_t*)nullptr, nchunks, cpw, tab->keys, tab->vals, B->do_prune | (snk_opt_u32(ctx, SNK_OPT_bl_noclassify) ? 2u : 0u), B->ctx, B->counts, B->pend, B->nbr, nbnd,
+                           B->biglist, ctr, (const uint32_t*)nullptr, index0, tg0 - 1));
     // the chunks that did not fit the one-wave variant (split sub-passes near the table's capacity): their number stays on the
     // device until the read-back below -- the big variant runs a fixed grid that strides over the list
     uint32_t h_nbig = 0;
     SNK_HIP_TRY(hipMemcpyAsync(ctr + 1, ctr, 4, hipMemcpyDeviceToDevice, st));       // (ctr[0] is the small kernel's list cursor)
-    hipLaunchKernelGGL((long_m ? bl_prune_kernel<K, BCAP, BT, true, GR, SNK_M_LONG> : bl_prune_kernel<K, BCAP, BT, true, GR, SNK_M_OF(K)>), dim3(2048), dim3(BT), 0, st, (const uint4*)B->desc, NBh, sh, rg,
-                       (const uint32_t*)B->biglist, 0u, 1u, tab->keys, tab->vals, B->do_prune | (snk_opt_u32(ctx, SNK_OPT_bl_noclassify) ? 2u : 0u), B->ctx, B->counts, B->pend, B->nbr,
-                       nbnd, B->biglist, ctr + 2, (const uint32_t*)(ctr + 1), index0, tg0 - 1);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(long_m ? bl_prune_kernel<K, BCAP, BT, true, GR, SNK_M_LONG> : bl_prune_kernel<K, BCAP, BT, true, GR, SNK_M_OF(K)>, 2048, BT, 0, st, (const uint4*)B->desc, NBh, sh, rg,
+                           (const uint32_t*)B->biglist, 0u, 1u, tab->keys, tab->vals, B->do_prune | (snk_opt_u32(ctx, SNK_OPT_bl_noclassify) ? 2u : 0u), B->ctx, B->counts, B->pend, B->nbr,
+                           nbnd, B->biglist, ctr + 2, (const uint32_t*)(ctr + 1), index0, tg0 - 1));
     if (tab->keys_r) {       // the region-partitioned copy is dead (stream order): later stages may reuse it
         snk_ctx_release_block(ctx, tab->keys_r);
         snk_ctx_release_block(ctx, tab->vals_r);
@@ -1013,11 +1010,10 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
     }
     B->index_mask = tg - 1;
     if (h_bnd) {
-        if (!fused_ok) hipLaunchKernelGGL(bl_index_build_kernel, dim3(nblk(n)), dim3(TB), 0, st, tab->keys, B->pend, n, B->index, tg - 1);
-        hipLaunchKernelGGL((bl_resolve_kernel<K, GR>), dim3((unsigned)((n + 8 * TB - 1) / (8 * TB))), dim3(TB), 0, st, tab->keys, B->pend, n,
-                           B->index, tg - 1, B->do_prune, B->ctx, B->rq, (const uint8_t*)B->premote);
+        if (!fused_ok) SNK_HIP_TRY(snk_launch(bl_index_build_kernel, snk_blocks(n, TB), TB, 0, st, tab->keys, B->pend, n, B->index, tg - 1));
+        SNK_HIP_TRY(snk_launch(bl_resolve_kernel<K, GR>, snk_blocks(n, 8 * TB), TB, 0, st, tab->keys, B->pend, n,
+                               B->index, tg - 1, B->do_prune, B->ctx, B->rq, (const uint8_t*)B->premote));
     }
-    SNK_HIP_TRY(hipGetLastError());
     return SNK_OK;
 }
 
@@ -1037,18 +1033,16 @@ static int bl_fragments_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, cons
     bl_extra_pool xp0;
     memset(&xp0, 0, sizeof xp0);
     // sizing pass: open paths per chunk (links only, no ranking)
-    hipLaunchKernelGGL((bl_frag_kernel<K, SCAP, ST, false, false, DIST, GR>), dim3(nchunks), dim3(ST), 0, st, (const uint4*)B->desc,
-                       (const uint32_t*)nullptr, tab->keys, B->ctx, B->pend, B->nbr, B->rq, da, nfrag, (const uint32_t*)nullptr,
-                       (const uint64_t*)nullptr, (uint32_t*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                       (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, xp0);
-    if (h_nbig)
-        hipLaunchKernelGGL((bl_frag_kernel<K, BCAP, BT, true, false, DIST, GR>), dim3(h_nbig), dim3(BT), 0, st, (const uint4*)B->desc,
+    SNK_HIP_TRY(snk_launch(bl_frag_kernel<K, SCAP, ST, false, false, DIST, GR>, nchunks, ST, 0, st, (const uint4*)B->desc,
+                           (const uint32_t*)nullptr, tab->keys, B->ctx, B->pend, B->nbr, B->rq, da, nfrag, (const uint32_t*)nullptr,
+                           (const uint64_t*)nullptr, (uint32_t*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                           (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, xp0));
+    SNK_HIP_TRY(snk_launch(bl_frag_kernel<K, BCAP, BT, true, false, DIST, GR>, h_nbig, BT, 0, st, (const uint4*)B->desc,
                            (const uint32_t*)B->biglist, tab->keys, B->ctx, B->pend, B->nbr, B->rq, da, nfrag, (const uint32_t*)nullptr,
                            (const uint64_t*)nullptr, (uint32_t*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                           (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, xp0);
-    hipLaunchKernelGGL(bl_chunk_bases_kernel, dim3(nblk((uint64_t)nchunks + 1)), dim3(TB), 0, st, (const uint4*)B->desc, nfrag, nchunks,
-                       (uint32_t)K, nbases);
-    SNK_HIP_TRY(hipGetLastError());
+                           (uint64_t*)nullptr, (uint8_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, xp0));
+    SNK_HIP_TRY(snk_launch(bl_chunk_bases_kernel, snk_blocks((uint64_t)nchunks + 1, TB), TB, 0, st, (const uint4*)B->desc, nfrag, nchunks,
+                           (uint32_t)K, nbases));
     int rc;
     if ((rc = excl_scan<uint32_t>(ctx, st, nfrag, foff, (size_t)nchunks + 1, err, errcap))) return rc;
     if ((rc = excl_scan<uint64_t>(ctx, st, nbases, boff, (size_t)nchunks + 1, err, errcap))) return rc;
@@ -1079,14 +1073,12 @@ static int bl_fragments_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, cons
         xp.b0 = h_B;
         xp.fcap = xf_cap;
         xp.bcap = xb_cap;
-        hipLaunchKernelGGL((bl_frag_kernel<K, SCAP, ST, false, true, DIST, GR>), dim3(nchunks), dim3(ST), 0, st, (const uint4*)B->desc,
-                           (const uint32_t*)nullptr, tab->keys, B->ctx, B->pend, B->nbr, B->rq, da, nfrag, foff, boff, out->nk, out->hl_self,
-                           out->hl_nb, out->boff, out->bases, out->fgroup, out->sfrag, xp);
-        if (h_nbig)
-            hipLaunchKernelGGL((bl_frag_kernel<K, BCAP, BT, true, true, DIST, GR>), dim3(h_nbig), dim3(BT), 0, st, (const uint4*)B->desc,
+        SNK_HIP_TRY(snk_launch(bl_frag_kernel<K, SCAP, ST, false, true, DIST, GR>, nchunks, ST, 0, st, (const uint4*)B->desc,
+                               (const uint32_t*)nullptr, tab->keys, B->ctx, B->pend, B->nbr, B->rq, da, nfrag, foff, boff, out->nk, out->hl_self,
+                               out->hl_nb, out->boff, out->bases, out->fgroup, out->sfrag, xp));
+        SNK_HIP_TRY(snk_launch(bl_frag_kernel<K, BCAP, BT, true, true, DIST, GR>, h_nbig, BT, 0, st, (const uint4*)B->desc,
                                (const uint32_t*)B->biglist, tab->keys, B->ctx, B->pend, B->nbr, B->rq, da, nfrag, foff, boff, out->nk,
-                               out->hl_self, out->hl_nb, out->boff, out->bases, out->fgroup, out->sfrag, xp);
-        SNK_HIP_TRY(hipGetLastError());
+                               out->hl_self, out->hl_nb, out->boff, out->bases, out->fgroup, out->sfrag, xp));
         SNK_HIP_TRY(hipMemcpyAsync(h_x, xcur, 16, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
         if (h_x[0] <= xf_cap && h_x[1] <= xb_cap) break;
@@ -1170,15 +1162,14 @@ static int local_graph_impl(snk_ctx* ctx, hipStream_t st, const snk_table* tab, 
         G_ALLOC(v_in, uint64_t, n + 1);
         G_ALLOC(v_out, uint64_t, n + 1);
         G_ALLOC(k_out, snk_u128, n + 1);
-        hipLaunchKernelGGL(bl_pack_vals_kernel, dim3(nblk(n)), dim3(TB), 0, st, B.counts, B.ctx, n, v_in);
+        SNK_HIP_TRY(snk_launch(bl_pack_vals_kernel, snk_blocks(n, TB), TB, 0, st, B.counts, B.ctx, n, v_in));
         rc = snk_graph_sort(ctx, st, K, n, tab->keys, v_in, k_out, v_out, err, errcap);
         if (rc) return rc;
-        hipLaunchKernelGGL(bl_unpack_vals_kernel, dim3(nblk(n)), dim3(TB), 0, st, v_out, n, B.counts, B.ctx);
+        SNK_HIP_TRY(snk_launch(bl_unpack_vals_kernel, snk_blocks(n, TB), TB, 0, st, v_out, n, B.counts, B.ctx));
         *keys_final = k_out;
     }
     if ((rc = snk_spectrum(ctx, st, B.counts, n, &out->spectrum, &out->spectrum_bins, err, errcap))) return rc;
     tm.mark();  // 5
-    SNK_HIP_TRY(hipGetLastError());
     if (ms) { ms[0] = tm.ms(0, 1); ms[1] = tm.ms(1, 2); ms[2] = tm.ms(2, 3); ms[3] = tm.ms(3, 4); ms[4] = tm.ms(4, 5); }
     return SNK_OK;
 }
@@ -1218,10 +1209,9 @@ int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, unsigned lon
     int rc = B->K == 48 ? bl_prune_impl<48, false>(ctx, st, B, err, errcap) : bl_prune_impl<60, false>(ctx, st, B, err, errcap);
     if (rc) return rc;
     const size_t lds = (size_t)B->world * 12 + 16;
-    const unsigned grid = (unsigned)((n + QSPAN - 1) / QSPAN);
-    if (B->K == 48) hipLaunchKernelGGL((bl_query_kernel<48, false>), dim3(grid), dim3(TB), lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcount, (unsigned long long*)nullptr);
-    else hipLaunchKernelGGL((bl_query_kernel<60, false>), dim3(grid), dim3(TB), lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcount, (unsigned long long*)nullptr);
-    SNK_HIP_TRY(hipGetLastError());
+    const uint64_t grid = snk_blocks(n, QSPAN);
+    if (B->K == 48) SNK_HIP_TRY(snk_launch(bl_query_kernel<48, false>, grid, TB, lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcount, (unsigned long long*)nullptr));
+    else SNK_HIP_TRY(snk_launch(bl_query_kernel<60, false>, grid, TB, lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcount, (unsigned long long*)nullptr));
     if (h_qcount) {
         SNK_HIP_TRY(hipMemcpyAsync(h_qcount, B->qcount, B->world * 8ull, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
@@ -1233,10 +1223,9 @@ int snk_bl_dist_fill(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, const unsign
     if (n == 0) return SNK_OK;
     SNK_HIP_TRY(hipMemcpyAsync(B->qcursor, d_qoff, (B->world + 1) * 8ull, hipMemcpyDeviceToDevice, st));
     const size_t lds = (size_t)B->world * 12 + 16;
-    const unsigned grid = (unsigned)((n + QSPAN - 1) / QSPAN);
-    if (B->K == 48) hipLaunchKernelGGL((bl_query_kernel<48, true>), dim3(grid), dim3(TB), lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcursor, (unsigned long long*)d_qbuf);
-    else hipLaunchKernelGGL((bl_query_kernel<60, true>), dim3(grid), dim3(TB), lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcursor, (unsigned long long*)d_qbuf);
-    SNK_HIP_TRY(hipGetLastError());
+    const uint64_t grid = snk_blocks(n, QSPAN);
+    if (B->K == 48) SNK_HIP_TRY(snk_launch(bl_query_kernel<48, true>, grid, TB, lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcursor, (unsigned long long*)d_qbuf));
+    else SNK_HIP_TRY(snk_launch(bl_query_kernel<60, true>, grid, TB, lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcursor, (unsigned long long*)d_qbuf));
     return SNK_OK;
 }
 int snk_bl_dist_fragments(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, const unsigned long long* d_node_off, unsigned long long my_node_off,

@@ -559,10 +559,9 @@ size_t snk_msp_lds_bytes(uint32_t K, uint32_t M, uint32_t row_words) {
 template <int K, int M, bool TRIM, bool DENSE>
 static int launch_msp_ktd(hipStream_t st, const snk_msp_args& a, char* err, size_t errcap) {
     size_t lds = snk_msp_lds_bytes(K, M, a.row_words);
-    unsigned nb = (unsigned)((a.n_reads + BD - 1) / BD);
+    const uint64_t nb = snk_blocks(a.n_reads, BD);
     SNK_HIP_TRY(hipFuncSetAttribute((const void*)snk_msp_kernel<K, M, TRIM, DENSE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((snk_msp_kernel<K, M, TRIM, DENSE>), dim3(nb), dim3(BD), lds, st, a);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(snk_msp_kernel<K, M, TRIM, DENSE>, nb, BD, lds, st, a));
     return SNK_OK;
 }
 template <int K, int M, bool TRIM>
@@ -570,10 +569,9 @@ static int launch_msp_kt(hipStream_t st, const snk_msp_args& a, char* err, size_
     if (a.b_hi) {
         if (a.dense_bkt) return snk_fail(SNK_E_ARG, err, errcap, "partition: bucket-range passes take the slot layout, not the dense one");
         size_t lds = snk_msp_lds_bytes(K, M, a.row_words);
-        unsigned nb = (unsigned)((a.n_reads + BD - 1) / BD);
+        const uint64_t nb = snk_blocks(a.n_reads, BD);
         SNK_HIP_TRY(hipFuncSetAttribute((const void*)snk_msp_kernel<K, M, TRIM, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((snk_msp_kernel<K, M, TRIM, false, true>), dim3(nb), dim3(BD), lds, st, a);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(snk_msp_kernel<K, M, TRIM, false, true>, nb, BD, lds, st, a));
         return SNK_OK;
     }
     if (a.dense_bkt) {
@@ -604,11 +602,6 @@ int snk_launch_msp(uint32_t K, uint32_t mlen, hipStream_t st, const snk_msp_args
 int snk_launch_msp_plan(hipStream_t st, const uint16_t* good_len, uint64_t n_reads, uint32_t K, unsigned long long* out2,
                         char* err, size_t errcap) {
     SNK_HIP_TRY(hipMemsetAsync(out2, 0, 16, st));
-    if (n_reads) {
-        unsigned g = (unsigned)((n_reads / 8 + 255) / 256 + 1);
-        if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(snk_msp_plan_kernel, dim3(g), dim3(256), 0, st, good_len, n_reads, K, out2);
-    }
-    SNK_HIP_TRY(hipGetLastError());
+    if (n_reads) SNK_HIP_TRY(snk_launch(snk_msp_plan_kernel, std::min<uint64_t>(snk_blocks(n_reads / 8, 256) + 1, 2048), 256, 0, st, good_len, n_reads, K, out2));
     return SNK_OK;
 }

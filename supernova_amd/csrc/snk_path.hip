@@ -1039,7 +1039,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     if ((rc = up(ctx, st, drop, &d_drop, err, errcap))) return rc;
     uint4* uinfo;
     if ((rc = dev(ctx, 2 * U + 2, &uinfo, err, errcap))) return rc;
-    if (U) hipLaunchKernelGGL(uinfo_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, st, d_uoff, U, G.fwd, G.rev, d_drop, uinfo);
+    SNK_HIP_TRY(snk_launch(uinfo_kernel, snk_blocks(U, 256), 256, 0, st, d_uoff, U, G.fwd, G.rev, d_drop, uinfo));
     G.uinfo = uinfo;
     const uint64_t total_bases = h_off_last;
     {
@@ -1049,7 +1049,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         if ((rc = dev(ctx, n_words + 2 * (UPAD / 16) + 2, &upack, err, errcap))) return rc;
         SNK_HIP_TRY(hipMemsetAsync(upack, 0, (UPAD / 16) * 4, st));
         SNK_HIP_TRY(hipMemsetAsync(upack + UPAD / 16 + n_words, 0, (UPAD / 16 + 2) * 4, st));
-        hipLaunchKernelGGL(upack_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_ubases, total_bases, upack + UPAD / 16, n_words);
+        SNK_HIP_TRY(snk_launch(upack_kernel, snk_blocks(n_words, 256), 256, 0, st, d_ubases, total_bases, upack + UPAD / 16, n_words));
         G.upack = upack;
     }
     const uint64_t nk = total_bases >= U * (uint64_t)(K - 1) ? total_bases - U * (uint64_t)(K - 1) : 0;
@@ -1087,20 +1087,20 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     if (snk_opt_is_set(ctx, SNK_OPT_path_fp_mask)) { const unsigned long long m = snk_opt_u64(ctx, SNK_OPT_path_fp_mask) & 0x3FFFFFFFull; if (m) fp_mask = m; }
     if ((rc = dev(ctx, cap, &dslot, err, errcap))) return rc;
     SNK_HIP_TRY(hipMemsetAsync(dslot, 0xFF, cap * 8, st));
-    if (total_bases) hipLaunchKernelGGL((dict_build_kernel<K>), dim3((unsigned)(((total_bases + DB_RUN - 1) / DB_RUN + 255) / 256)), dim3(256), 0, st, d_uoff, d_ubases, U, total_bases, dslot, cap, fp_mask);
+    SNK_HIP_TRY(snk_launch(dict_build_kernel<K>, snk_blocks(snk_blocks(total_bases, DB_RUN), 256), 256, 0, st, d_uoff, d_ubases, U, total_bases, dslot, cap, fp_mask));
     }
     uint64_t n_ment = 0;
     if (use_index) {
         // places per workgroup, their offsets, the places, sorted by key, the directory over the key's top bits
-        const uint64_t n_wg = total_bases ? ((total_bases + MM_RUN - 1) / MM_RUN + 255) / 256 : 0;
+        const uint64_t n_wg = snk_blocks(snk_blocks(total_bases, MM_RUN), 256);
         uint32_t *wgc, *okey, *okey2, *mdir, *mhist;
         uint64_t *wg64, *wgo;
         unsigned long long *oval, *oval2;
         if ((rc = dev(ctx, n_wg + 2, &wgc, err, errcap)) || (rc = dev(ctx, n_wg + 2, &wg64, err, errcap)) || (rc = dev(ctx, n_wg + 2, &wgo, err, errcap))) return rc;
         if (n_wg) {
-            hipLaunchKernelGGL((mm_scan_kernel<K, false>), dim3((unsigned)n_wg), dim3(256), 0, st, d_uoff, G.upack, U, total_bases, wgc, (const uint64_t*)nullptr, (uint32_t*)nullptr,
-                               (unsigned long long*)nullptr);
-            hipLaunchKernelGGL(mm_widen_kernel, dim3((unsigned)((n_wg + 256) / 256)), dim3(256), 0, st, wgc, n_wg, wg64);
+            SNK_HIP_TRY(snk_launch(mm_scan_kernel<K, false>, n_wg, 256, 0, st, d_uoff, G.upack, U, total_bases, wgc, (const uint64_t*)nullptr, (uint32_t*)nullptr,
+                                   (unsigned long long*)nullptr));
+            SNK_HIP_TRY(snk_launch(mm_widen_kernel, snk_blocks(n_wg + 1, 256), 256, 0, st, wgc, n_wg, wg64));
             if ((rc = scan64(ctx, st, wg64, wgo, n_wg + 1, err, errcap))) return rc;
             SNK_HIP_TRY(hipMemcpyAsync(&n_ment, wgo + n_wg, 8, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
@@ -1115,13 +1115,13 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         SNK_HIP_TRY(hipMemsetAsync(mdir, 0, ((1ull << bits) + 2) * 4, st));
         SNK_HIP_TRY(hipMemsetAsync(mhist, 0, ((1ull << bits) + 2) * 4, st));
         if (n_ment) {
-            hipLaunchKernelGGL((mm_scan_kernel<K, true>), dim3((unsigned)n_wg), dim3(256), 0, st, d_uoff, G.upack, U, total_bases, wgc, (const uint64_t*)wgo, okey, oval);
+            SNK_HIP_TRY(snk_launch(mm_scan_kernel<K, true>, n_wg, 256, 0, st, d_uoff, G.upack, U, total_bases, wgc, (const uint64_t*)wgo, okey, oval));
             size_t tb = 0;
             SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, okey, okey2, oval, oval2, (size_t)n_ment, 0u, 32u, st));
             void* tmp;
             if ((rc = snk_ctx_alloc(ctx, tb + 64, &tmp, err, errcap))) return rc;
             SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, okey, okey2, oval, oval2, (size_t)n_ment, 0u, 32u, st));
-            hipLaunchKernelGGL(mm_hist_kernel, dim3((unsigned)((n_ment + 255) / 256)), dim3(256), 0, st, okey2, n_ment, 32u - bits, mhist);
+            SNK_HIP_TRY(snk_launch(mm_hist_kernel, snk_blocks(n_ment, 256), 256, 0, st, okey2, n_ment, 32u - bits, mhist));
             size_t tb2 = 0;
             SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb2, mhist, mdir, 0u, ((size_t)1 << bits) + 1, rocprim::plus<uint32_t>(), st));
             void* tmp2;
@@ -1136,11 +1136,10 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         const uint64_t n_blk = (total_bases >> 8) + 2;
         uint32_t* ublk;
         if ((rc = dev(ctx, n_blk, &ublk, err, errcap))) return rc;
-        if (U) hipLaunchKernelGGL(ublk_kernel, dim3((unsigned)((n_blk + 255) / 256)), dim3(256), 0, st, d_uoff, U, n_blk, ublk);
+        if (U) SNK_HIP_TRY(snk_launch(ublk_kernel, snk_blocks(n_blk, 256), 256, 0, st, d_uoff, U, n_blk, ublk));
         else SNK_HIP_TRY(hipMemsetAsync(ublk, 0, n_blk * 4, st));
         G.ublk = ublk;
     }
-    SNK_HIP_TRY(hipGetLastError());
     SNK_HIP_TRY(snk_sync(st));            // drop[] has been copied
     G.dslot = dslot; G.dcap = cap; G.fp_mask = fp_mask;
     SNK_HIP_TRY(hipEventRecord(e1, st));
@@ -1181,26 +1180,24 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         a.gparts = gparts; a.gm = gm;
         if (n) {
             // sixteen lanes per read (eight put twice the reads in flight but the kernel is issue bound: 145.6 ms against 134.5)
-            uint64_t grid = (n + 15) / 16;
             const uint64_t gmax = (uint64_t)ctx->n_cu * 64;
-            if (grid > gmax) grid = gmax;
+            const uint64_t grid = snk_blocks_capped(n, 16, gmax);
             if (gparts && snk_opt_u32(ctx, SNK_OPT_path_two_pass)) {
 #ifndef SNK_PATH_FAST_GS
 #define SNK_PATH_FAST_GS 4          // lanes per read of the fast pass (the template's 8 of round 3 -> 4: sixteen reads share a wave's instructions; 62.2 -> 57.7 ms with the slow pass at 8)
 #endif
                 if (snk_opt_u32(ctx, SNK_OPT_path_fast_gs) == 8) {
-                    uint64_t g0 = (n + 256 / SNK_PATH_FAST_GS - 1) / (256 / SNK_PATH_FAST_GS);
-                    if (g0 > gmax) g0 = gmax;
-                    if (use_index) hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 0, 8, true>), dim3((unsigned)g0), dim3(256), 0, st, a);
+                    const uint64_t g0 = snk_blocks_capped(n, 256 / SNK_PATH_FAST_GS, gmax);
+                    if (use_index) SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 0, 8, true>, g0, 256, 0, st, a));
 #ifndef SNK_PATH_FAST_PC
 #define SNK_PATH_FAST_PC 4           // parts per read the fast pass has room for (it writes one: 4 KB of LDS per workgroup instead of 20)
 #endif
-                    else hipLaunchKernelGGL((path_kernel<K, SNK_PATH_FAST_PC, PMAX1, 0, SNK_PATH_FAST_GS, false>), dim3((unsigned)g0), dim3(256), 0, st, a);
-                } else if (use_index) hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 0, 16, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 0, 16, false>), dim3((unsigned)grid), dim3(256), 0, st, a);
+                    else SNK_HIP_TRY(snk_launch(path_kernel<K, SNK_PATH_FAST_PC, PMAX1, 0, SNK_PATH_FAST_GS, false>, g0, 256, 0, st, a));
+                } else if (use_index) SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 0, 16, true>, grid, 256, 0, st, a));
+                else SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 0, 16, false>, grid, 256, 0, st, a));
                 // the reads it left, in read order
                 if (!slow_flag && ((rc = dev(ctx, n + 2, &slow_flag, err, errcap)) || (rc = dev(ctx, n + 2, &slow_pos, err, errcap)))) return rc;
-                hipLaunchKernelGGL(slow_flag_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, st, gm, n, slow_flag);
+                SNK_HIP_TRY(snk_launch(slow_flag_kernel, snk_blocks(n + 1, 256), 256, 0, st, gm, n, slow_flag));
                 if ((rc = scan64(ctx, st, slow_flag, slow_pos, n + 1, err, errcap))) return rc;
                 uint64_t n_slow = 0;
                 SNK_HIP_TRY(hipMemcpyAsync(&n_slow, slow_pos + n, 8, hipMemcpyDeviceToHost, st));
@@ -1208,26 +1205,22 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
                 if (n_slow) {
                     uint32_t* slow;
                     if ((rc = dev(ctx, n_slow + 1, &slow, err, errcap))) return rc;
-                    hipLaunchKernelGGL(slow_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gm, slow_pos, n, slow);
+                    SNK_HIP_TRY(snk_launch(slow_fill_kernel, snk_blocks(n, 256), 256, 0, st, gm, slow_pos, n, slow));
                     a.slow = slow; a.n_slow = n_slow;
 #ifndef SNK_PATH_SLOW_GS
 #define SNK_PATH_SLOW_GS 8           // lanes per read of the slow pass: the pass is bound by its instruction stream (profiles/r06_path_wide_rounds.log), eight reads share a wave's
 #endif                               //   instructions instead of four: 63.3 -> 60.3 ms per 100 M reads (four alternating runs each, same box)
-                    uint64_t g1 = (n_slow + 256 / SNK_PATH_SLOW_GS - 1) / (256 / SNK_PATH_SLOW_GS);
-                    if (g1 > gmax) g1 = gmax;
-                    if (use_index) hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 1, 16, true>), dim3((unsigned)g1), dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 1, SNK_PATH_SLOW_GS, false>), dim3((unsigned)g1), dim3(256), 0, st, a);
+                    const uint64_t g1 = snk_blocks_capped(n_slow, 256 / SNK_PATH_SLOW_GS, gmax);
+                    if (use_index) SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 1, 16, true>, g1, 256, 0, st, a));
+                    else SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 1, SNK_PATH_SLOW_GS, false>, g1, 256, 0, st, a));
                 }
                 out->n_slow = n_slow;
-            } else if (use_index) hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 3, 16, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((path_kernel<K, PCAP1, PMAX1, 3, 16, false>), dim3((unsigned)grid), dim3(256), 0, st, a);
+            } else if (use_index) SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 3, 16, true>, grid, 256, 0, st, a));
+            else SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 3, 16, false>, grid, 256, 0, st, a));
             if (gparts) {
-                uint64_t g2 = (n + 255) / 256;
-                if (g2 > gmax) g2 = gmax;
-                hipLaunchKernelGGL((path_finish_kernel<K>), dim3((unsigned)g2), dim3(256), 0, st, a);
+                SNK_HIP_TRY(snk_launch(path_finish_kernel<K>, snk_blocks_capped(n, 256, gmax), 256, 0, st, a));
             }
         }
-        SNK_HIP_TRY(hipGetLastError());
         SNK_HIP_TRY(hipMemcpyAsync(h_cur, cursor, 32, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
         if (h_cur[3] > rcap) {                       // more reads to redo than the list holds: once more with a longer list
@@ -1237,12 +1230,9 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         }
         if (h_cur[3]) {                              // the reads with many parts / edges, at full capacity
             a.n_redo = h_cur[3];
-            uint64_t grid = (a.n_redo + 15) / 16;
-            const uint64_t gmax = (uint64_t)ctx->n_cu * 64;
-            if (grid > gmax) grid = gmax;
-            if (use_index) hipLaunchKernelGGL((path_kernel<K, PCAP, PMAX, 2, 16, true>), dim3((unsigned)grid), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((path_kernel<K, PCAP, PMAX, 2, 16, false>), dim3((unsigned)grid), dim3(256), 0, st, a);
-            SNK_HIP_TRY(hipGetLastError());
+            const uint64_t grid = snk_blocks_capped(a.n_redo, 16, (uint64_t)ctx->n_cu * 64);
+            if (use_index) SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP, PMAX, 2, 16, true>, grid, 256, 0, st, a));
+            else SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP, PMAX, 2, 16, false>, grid, 256, 0, st, a));
             SNK_HIP_TRY(hipMemcpyAsync(h_cur, cursor, 32, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
         }
@@ -1253,14 +1243,13 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         if (e_over) { snk_ctx_release_block(ctx, scratch); scratch = nullptr; scap = h_cur[0] + 1024; out->retries |= 2u; }
         if (b_over) { snk_ctx_release_block(ctx, ubk); ubk = nullptr; ubcap = h_cur[2] + 1024; out->retries |= 4u; }
     }
-    hipLaunchKernelGGL(widen_kernel, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, st, out_n, n, n64);
+    SNK_HIP_TRY(snk_launch(widen_kernel, snk_blocks(n + 1, 256), 256, 0, st, out_n, n, n64));
     if ((rc = scan64(ctx, st, n64, pos, n + 1, err, errcap))) return rc;
     uint64_t total = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&total, pos + n, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
     if ((rc = dev(ctx, total + 1, &edges, err, errcap))) return rc;
-    if (n) hipLaunchKernelGGL(path_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out_n, out_e0, out_start, pos, scratch, n, edges);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(path_gather_kernel, snk_blocks(n, 256), 256, 0, st, out_n, out_e0, out_start, pos, scratch, n, edges));
     SNK_HIP_TRY(hipEventRecord(e2, st));
     SNK_HIP_TRY(snk_sync(st));
     snk_ctx_release_block(ctx, scratch);
@@ -1281,8 +1270,8 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
             unsigned long long* xk;
             if ((rc = dev(ctx, xcap, &xk, err, errcap))) return rc;
             SNK_HIP_TRY(hipMemsetAsync(cursor, 0, 8, st));
-            if (n) hipLaunchKernelGGL((ubc_exhaustive_kernel<K>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, G, a.rows, a.row_words, a.read_len, a.lens,
-                                      (const int32_t*)in->bc, n, xk, xcap, cursor);
+            SNK_HIP_TRY(snk_launch(ubc_exhaustive_kernel<K>, snk_blocks(n, 256), 256, 0, st, G, a.rows, a.row_words, a.read_len, a.lens,
+                                   (const int32_t*)in->bc, n, xk, xcap, cursor));
             unsigned long long hx = 0;
             SNK_HIP_TRY(hipMemcpyAsync(&hx, cursor, 8, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
@@ -1314,13 +1303,13 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         uint64_t n_unique = 0;
         if (nkeys) {
             SNK_HIP_TRY(rocprim::radix_sort_keys(tmp, tb, ubk, ks, (size_t)nkeys, 0u, end_bit, st));
-            hipLaunchKernelGGL(ubc_flag_kernel, dim3((unsigned)((nkeys + 256) / 256)), dim3(256), 0, st, ks, nkeys, flag);
+            SNK_HIP_TRY(snk_launch(ubc_flag_kernel, snk_blocks(nkeys + 1, 256), 256, 0, st, ks, nkeys, flag));
             if ((rc = scan64(ctx, st, flag, upos, nkeys + 1, err, errcap))) return rc;
             SNK_HIP_TRY(hipMemcpyAsync(&n_unique, upos + nkeys, 8, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
         }
         SNK_HIP_TRY(hipMemsetAsync(per_u, 0, (U + 2) * 8, st));
-        if (nkeys) hipLaunchKernelGGL(ubc_scatter_kernel, dim3((unsigned)((nkeys + 255) / 256)), dim3(256), 0, st, ks, flag, upos, nkeys, bcs, per_u);
+        SNK_HIP_TRY(snk_launch(ubc_scatter_kernel, snk_blocks(nkeys, 256), 256, 0, st, ks, flag, upos, nkeys, bcs, per_u));
         if ((rc = scan64(ctx, st, per_u, uoff_out, U + 1, err, errcap))) return rc;
         SNK_HIP_TRY(hipGetLastError());
         SNK_HIP_TRY(snk_sync(st));
@@ -1333,7 +1322,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
             uint32_t* any;
             if ((rc = dev(ctx, U + 2, &clen, err, errcap)) || (rc = dev(ctx, U + 2, &noff2, err, errcap)) || (rc = dev(ctx, 4, &any, err, errcap))) return rc;
             SNK_HIP_TRY(hipMemsetAsync(any, 0, 4, st));
-            hipLaunchKernelGGL(ubc_cut_len_kernel, dim3((unsigned)((U + 256) / 256)), dim3(256), 0, st, uoff_out, U, cut, clen, any);
+            SNK_HIP_TRY(snk_launch(ubc_cut_len_kernel, snk_blocks(U + 1, 256), 256, 0, st, uoff_out, U, cut, clen, any));
             uint32_t h_any = 0;
             SNK_HIP_TRY(hipMemcpyAsync(&h_any, any, 4, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
@@ -1344,8 +1333,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
                 SNK_HIP_TRY(snk_sync(st));
                 uint32_t* bcs2;
                 if ((rc = dev(ctx, n_cut + 1, &bcs2, err, errcap))) return rc;
-                hipLaunchKernelGGL(ubc_cut_copy_kernel, dim3((unsigned)U), dim3(64), 0, st, uoff_out, noff2, U, bcs, bcs2);
-                SNK_HIP_TRY(hipGetLastError());
+                SNK_HIP_TRY(snk_launch(ubc_cut_copy_kernel, U, 64, 0, st, uoff_out, noff2, U, bcs, bcs2));
                 uoff_out = noff2; bcs = bcs2; n_unique = n_cut;
             }
         }

@@ -38,12 +38,9 @@ int dev(snk_ctx* ctx, size_t n, T** out, char* err, size_t errcap) {
     return rc;
 }
 
-// every launch of this file: a grid that covers `items` work items at `per_block` a workgroup, cut at 2^20 workgroups -- the kernels
-// stride over what is left, with 64-bit indices (a grid computed in 32 bits silently drops the items above 2^32)
-unsigned pidx_grid(uint64_t items, uint64_t per_block = PB) {
-    const uint64_t g = (items + per_block - 1) / per_block;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(g, 1u << 20));
-}
+// every launch of this file: a grid that covers its work items at PB a workgroup, cut at 2^20 workgroups -- the kernels stride over
+// what is left, with 64-bit indices
+constexpr uint64_t PIDX_GRID_CAP = 1u << 20;
 
 __global__ void __launch_bounds__(PB) pidx_fill_kernel(const unsigned long long* __restrict__ start, const uint32_t* __restrict__ n_edges, uint64_t n_reads,
                                                        uint64_t n_entries, unsigned long long* __restrict__ rid, uint32_t* __restrict__ bad) {
@@ -183,10 +180,9 @@ static int paths_index_impl(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E
     uint32_t key_bits = 0;
     while (key_bits < 32 && (1ull << key_bits) < E) ++key_bits;
     if (n) {
-        hipLaunchKernelGGL(pidx_fill_kernel, dim3(pidx_grid(n_reads)), dim3(PB), 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges, n_reads, n, rid,
-                           range + 256);
-        hipLaunchKernelGGL(pidx_range_kernel, dim3(pidx_grid(n / 4 + 1)), dim3(PB), 0, st, (const uint32_t*)paths->edges, n, range);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(pidx_fill_kernel, snk_blocks_capped(n_reads, PB, PIDX_GRID_CAP), PB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges, n_reads, n, rid,
+                               range + 256));
+        SNK_HIP_TRY(snk_launch(pidx_range_kernel, snk_blocks_capped(n / 4 + 1, PB, PIDX_GRID_CAP), PB, 0, st, (const uint32_t*)paths->edges, n, range));
         uint32_t h_range[257];
         SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
@@ -202,9 +198,8 @@ static int paths_index_impl(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E
         if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
         SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)paths->edges, skey, rid, ids, (size_t)n, 0u, bits, st));
     }
-    hipLaunchKernelGGL(pidx_offsets_kernel, dim3(pidx_grid(n ? (n + 3) / 4 : E + 1)), dim3(PB), 0, st, skey, n, E, off);
-    if (E) hipLaunchKernelGGL(pidx_counts_kernel, dim3(pidx_grid(E)), dim3(PB), 0, st, off, d_inv, E, counts, stat);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(pidx_offsets_kernel, snk_blocks_capped(n ? (n + 3) / 4 : E + 1, PB, PIDX_GRID_CAP), PB, 0, st, skey, n, E, off));
+    if (E) SNK_HIP_TRY(snk_launch(pidx_counts_kernel, snk_blocks_capped(E, PB, PIDX_GRID_CAP), PB, 0, st, off, d_inv, E, counts, stat));
     unsigned long long h_stat[512];
     SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(hipEventRecord(e1, st));

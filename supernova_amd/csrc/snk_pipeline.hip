@@ -200,7 +200,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         const uint64_t n16 = (((uintptr_t)in->rows & 15u) == 0) ? n_reads * (uint64_t)in->row_words / 4 : 0;
         const void* aux = in->quals ? in->quals : in->good_len;
         const uint64_t m16 = (aux && ((uintptr_t)aux & 15u) == 0) ? (in->quals ? n_reads * (uint64_t)in->qstride : n_reads * 2ull) / 16 : 0;
-        hipLaunchKernelGGL(input_fp_kernel, dim3(1), dim3(256), 0, st, (const uint4*)in->rows, n16, (const uint4*)aux, m16, d_fp);
+        SNK_HIP_TRY(snk_launch(input_fp_kernel, 1, 256, 0, st, (const uint4*)in->rows, n16, (const uint4*)aux, m16, d_fp));
         unsigned long long h_fp = 0;
         SNK_HIP_TRY(hipMemcpyAsync(&h_fp, d_fp, 8, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));

@@ -301,7 +301,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             if (fake > 1 && fake <= 32 && part.n_overflow == 0) {
                 uint64_t* T;
                 ALLOC(T, uint64_t, 2ull * fake * NB_total + 2);
-                hipLaunchKernelGGL(fake_seg_kernel, dim3((NB_total + 255) / 256), dim3(256), 0, st, part.cursor, NB_total, part.cap, fake, T);
+                SNK_HIP_TRY(snk_launch(fake_seg_kernel, snk_blocks(NB_total, 256), 256, 0, st, part.cursor, NB_total, part.cap, fake, T));
                 TRY(snk_stage_count_table(ctx, st, K, part.records, T, T + (uint64_t)fake * NB_total, NB_total, fake, NB_total, p->min_freq,
                                           has_bc ? p->min_bc : 0u, 0u, inst_hint, S->status, false, &S->tab, err, errcap));
             } else {
@@ -333,8 +333,8 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             if (R > 64) R = 64;
             ull* d_rs;      // [2][W][R] records per (destination, range) and per (source, range)
             ALLOC(d_rs, ull, 2ull * W * R + 1);
-            hipLaunchKernelGGL(range_sum_kernel, dim3(W * R), dim3(256), 0, st, hsend_x, NBl, R, d_rs);
-            hipLaunchKernelGGL(range_sum_kernel, dim3(W * R), dim3(256), 0, st, hrecv, NBl, R, d_rs + (size_t)W * R);
+            SNK_HIP_TRY(snk_launch(range_sum_kernel, (uint64_t)W * R, 256, 0, st, hsend_x, NBl, R, d_rs));
+            SNK_HIP_TRY(snk_launch(range_sum_kernel, (uint64_t)W * R, 256, 0, st, hrecv, NBl, R, d_rs + (size_t)W * R));
             uint32_t* soff32;
             ull* roff;
             ALLOC(soff32, uint32_t, (uint64_t)NB_total + 4);
@@ -380,9 +380,8 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             uint64_t* T;
             ALLOC(T, uint64_t, 2ull * nseg * NBl + 2);
             const ull delta = (ull)(((intptr_t)part.records - (intptr_t)recvb) / 32);
-            hipLaunchKernelGGL(seg_table_kernel, dim3((NBl + 255) / 256), dim3(256), 0, st, roff, hrecv, part.cursor, part.seg, W, me, NBl, NB_total, part.cap,
-                               nseg, delta, T);
-            SNK_HIP_TRY(hipGetLastError());
+            SNK_HIP_TRY(snk_launch(seg_table_kernel, snk_blocks(NBl, 256), 256, 0, st, roff, hrecv, part.cursor, part.seg, W, me, NBl, NB_total, part.cap,
+                                   nseg, delta, T));
             tm.mark();   // 3
             std::vector<uint32_t> bounds(R + 1);
             for (uint32_t r = 0; r <= R; ++r) bounds[r] = (uint32_t)((uint64_t)NBl * r / R);
@@ -793,11 +792,10 @@ extern "C" int snk_shard_gather_unitigs(snk_ctx* ctx, snk_comm* comm, const snk_
             const uint64_t uq = all[2 * q], tq = all[2 * q + 1];
             if (tq) TRY(snk_dev_unpack2(ctx, pk_in + pbase[q], tq, bases + bbase[q], st));
             // a source's offsets start at 0: shift them to where its bases landed (the last source also writes the closing offset)
-            hipLaunchKernelGGL(shift_offsets_kernel, dim3((unsigned)((uq + 1 + 255) / 256)), dim3(256), 0, st, off_in + ubase[q], uq + (q + 1 == W ? 1 : 0), bbase[q],
-                               off + uacc);
+            SNK_HIP_TRY(snk_launch(shift_offsets_kernel, snk_blocks(uq + 1, 256), 256, 0, st, off_in + ubase[q], uq + (q + 1 == W ? 1 : 0), bbase[q],
+                                   off + uacc));
             uacc += uq;
         }
-        SNK_HIP_TRY(hipGetLastError());
         return snk_unitigs_to_host(ctx, st, K, Ut, off, bases, false, (flags & SNK_F_BV_IMAGE) != 0, out, err, errcap);
     };
     int rc = body();

@@ -423,16 +423,15 @@ static int snk_msp_segments(snk_ctx* ctx, hipStream_t st, uint32_t NB, uint32_t 
         if ((rc = snk_ctx_alloc(ctx, (size_t)n_ovf * 4 + 16, &q, err, errcap))) return rc; idx_out = (uint32_t*)q;
         if ((rc = snk_ctx_alloc(ctx, (size_t)n_ovf * 4 + 16, &q, err, errcap))) return rc; key_in = (uint32_t*)q;
         if ((rc = snk_ctx_alloc(ctx, (size_t)n_ovf * 4 + 16, &q, err, errcap))) return rc; key_out = (uint32_t*)q;
-        hipLaunchKernelGGL(ovf_index_kernel, dim3((n_ovf + 255) / 256), dim3(256), 0, st, P, (uint32_t)sub_cap, ovf_bucket, n_ovf, idx_in, key_in);
+        SNK_HIP_TRY(snk_launch(ovf_index_kernel, snk_blocks(n_ovf, 256), 256, 0, st, P, (uint32_t)sub_cap, ovf_bucket, n_ovf, idx_in, key_in));
         size_t tb = 0;
         SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, key_in, key_out, idx_in, idx_out, (size_t)n_ovf, 0u, 32u, st));
         if ((rc = snk_ctx_alloc(ctx, tb, &q, err, errcap))) return rc;
         SNK_HIP_TRY(rocprim::radix_sort_pairs(q, tb, key_in, key_out, idx_in, idx_out, (size_t)n_ovf, 0u, 32u, st));
         // the grouped copy goes behind all the sub-lists
-        hipLaunchKernelGGL(ovf_gather_kernel, dim3((n_ovf + 255) / 256), dim3(256), 0, st, records, ovf_base, ovf_base + sub_cap * SNK_OVF_SUBLISTS, idx_out,
-                           key_out, n_ovf, NB, records, seg);
+        SNK_HIP_TRY(snk_launch(ovf_gather_kernel, snk_blocks(n_ovf, 256), 256, 0, st, records, ovf_base, ovf_base + sub_cap * SNK_OVF_SUBLISTS, idx_out,
+                               key_out, n_ovf, NB, records, seg));
     }
-    SNK_HIP_TRY(hipGetLastError());
     return SNK_OK;
 }
 
@@ -614,8 +613,7 @@ int partition_dense(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_read
         void* tmp;
         if ((rc = snk_ctx_alloc(ctx, tb + 64, &tmp, err, errcap))) return rc;
         SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, bkt, bkt2, pos, gidx, n, 0u, bits, st));
-        hipLaunchKernelGGL(seg_from_sorted_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, bkt2, (uint32_t)n, NB, seg);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(seg_from_sorted_kernel, snk_blocks(n, 256), 256, 0, st, bkt2, (uint32_t)n, NB, seg));
         snk_ctx_release_block(ctx, tmp);
     }
     kt.mark();  // 2
@@ -701,15 +699,13 @@ int snk_probe_relaunch_msp(snk_ctx* ctx, hipStream_t s2, uint32_t dbg, char* err
         if (dbg >= 16) {          // 16 + w: persistent grid of w workgroups (waves) per CU, all the records
             n = (uint64_t)(0.98 * (double)NB * ma.cap * 0.55);
             const uint32_t wpc = dbg - 16;
-            hipLaunchKernelGGL(probe_lean_emit_persistent, dim3((unsigned)ctx->n_cu * wpc), dim3(64), 0, s2, cur, recs, NB, ma.cap, n);
-            SNK_HIP_TRY(hipGetLastError());
+            SNK_HIP_TRY(snk_launch(probe_lean_emit_persistent, (uint64_t)ctx->n_cu * wpc, 64, 0, s2, cur, recs, NB, ma.cap, n));
             fprintf(stderr, "[snk overlap probe] persistent lean emitter: %llu records, %u waves per CU\n", (unsigned long long)n, wpc);
             return SNK_OK;
         }
         const uint32_t per = (dbg & 1u) ? 16u : 1u;
-        const uint64_t threads = (n + per - 1) / per;
-        hipLaunchKernelGGL(probe_lean_emit_kernel, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, s2, cur, recs, NB, ma.cap, n, per);
-        SNK_HIP_TRY(hipGetLastError());
+        const uint64_t threads = snk_blocks(n, per);
+        SNK_HIP_TRY(snk_launch(probe_lean_emit_kernel, snk_blocks(threads, 64), 64, 0, s2, cur, recs, NB, ma.cap, n, per));
         fprintf(stderr, "[snk overlap probe] lean emitter: %llu records into %u buckets of %u slots, %u per thread\n", (unsigned long long)n, NB, ma.cap, per);
         return SNK_OK;
     }
@@ -805,7 +801,7 @@ int snk_stage_partition(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_
         // segment 0 (the fixed-capacity slots) and the supermer total need the cursors only: one read-back for everything the
         // host wants to know about this pass (overflow count, supermers, and the caller's trim statistics if asked for)
         SNK_HIP_TRY(hipMemsetAsync(d_total, 0, 64 * 8, st));
-        hipLaunchKernelGGL(seg0_kernel, dim3((NB + 255) / 256), dim3(256), 0, st, cursor, NB, cap, seg, d_total);
+        SNK_HIP_TRY(snk_launch(seg0_kernel, snk_blocks(NB, 256), 256, 0, st, cursor, NB, cap, seg, d_total));
         SNK_HIP_TRY(hipMemcpyAsync(h_cur, ovf_cur, sizeof h_cur, hipMemcpyDeviceToHost, st));
         unsigned long long h_tot64[64];
         SNK_HIP_TRY(hipMemcpyAsync(h_tot64, d_total, sizeof h_tot64, hipMemcpyDeviceToHost, st));
@@ -833,7 +829,7 @@ int snk_stage_partition(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_
     }
     // segment 1: the overflow records grouped by bucket
     if ((rc = snk_msp_segments(ctx, st, NB, cap, cursor, (uint4*)records, (uint64_t)NB * cap, ovf_cap / SNK_OVF_SUBLISTS, ovf_bucket, h_sub, seg, err, errcap))) return rc;
-    if (h_novf) hipLaunchKernelGGL(cursor_exact_kernel, dim3((NB + 255) / 256), dim3(256), 0, st, seg, NB, cursor);
+    if (h_novf) SNK_HIP_TRY(snk_launch(cursor_exact_kernel, snk_blocks(NB, 256), 256, 0, st, seg, NB, cursor));
     out->NB = NB;
     out->cap = cap;
     out->nseg = h_novf ? 2u : 1u;
@@ -963,7 +959,7 @@ int snk_partition_passes_run(void* user, uint32_t r) {
     if ((rc = snk_launch_msp(S->K, ctx->mlen, st, ma, err, errcap))) return rc;
     kt.mark();
     SNK_HIP_TRY(hipMemsetAsync(S->d_total, 0, 64 * 8, st));
-    hipLaunchKernelGGL(seg0_range_kernel, dim3((b_hi - b_lo + 255) / 256), dim3(256), 0, st, S->cursor, b_lo, b_hi, NB, S->cap, S->seg, S->d_total);
+    SNK_HIP_TRY(snk_launch(seg0_range_kernel, snk_blocks(b_hi - b_lo, 256), 256, 0, st, S->cursor, b_lo, b_hi, NB, S->cap, S->seg, S->d_total));
     uint32_t h_cur[SNK_OVF_SUBLISTS * SNK_OVF_CUR_STRIDE], h_sub[SNK_OVF_SUBLISTS];
     unsigned long long h_tot64[64];
     std::vector<unsigned long long> h_fplan(2 * SNK_MSP_PLAN_SLOTS);
@@ -991,7 +987,7 @@ int snk_partition_passes_run(void* user, uint32_t r) {
         snk_hot hot;
         if ((rc = snk_stage_hot_plan(ctx, st, S->K, S->grouped, S->seg + b_lo, S->seg + NB + b_lo, 2 * NB, 2, b_hi - b_lo, S->cap, &hot, err, errcap))) return rc;
         if (hot.NBv) {
-            hipLaunchKernelGGL(vmeta_shift_kernel, dim3((hot.NBv + 255) / 256), dim3(256), 0, st, const_cast<uint2*>(hot.vmeta), hot.NBv, b_lo);      // (the plan numbered the range's buckets from 0)
+            SNK_HIP_TRY(snk_launch(vmeta_shift_kernel, snk_blocks(hot.NBv, 256), 256, 0, st, const_cast<uint2*>(hot.vmeta), hot.NBv, b_lo));      // (the plan numbered the range's buckets from 0)
             if ((rc = snk_stage_hot_expand(ctx, st, S->records, &hot, err, errcap))) return rc;
             S->n_hot += hot.n_hot;
             S->hots->push_back(hot);
@@ -1003,9 +999,8 @@ int snk_partition_passes_run(void* user, uint32_t r) {
 int snk_stage_partition_compact(snk_ctx* ctx, hipStream_t st, const snk_partition* part, const uint32_t* d_offsets, void* d_out, char* err,
                                 size_t errcap) {
     if (part->NB == 0) return SNK_OK;
-    hipLaunchKernelGGL(compact_buckets_kernel, dim3((part->NB + 3) / 4), dim3(256), 0, st, (const uint4*)part->records, part->seg, part->NB,
-                       d_offsets, (uint4*)d_out, 0u, 0u);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(compact_buckets_kernel, snk_blocks(part->NB, 4), 256, 0, st, (const uint4*)part->records, part->seg, part->NB,
+                           d_offsets, (uint4*)d_out, 0u, 0u));
     SNK_HIP_TRY(snk_sync(st));
     snk_ctx_release_block(ctx, part->records);      // the slot layout is dead once the send buffer is filled
     return SNK_OK;
@@ -1016,9 +1011,8 @@ int snk_stage_partition_compact(snk_ctx* ctx, hipStream_t st, const snk_partitio
 int snk_stage_partition_compact_remote(snk_ctx* ctx, hipStream_t st, const snk_partition* part, const uint32_t* d_offsets, void* d_out,
                                        uint32_t skip_lo, uint32_t skip_hi, char* err, size_t errcap) {
     if (part->NB == 0) return SNK_OK;
-    hipLaunchKernelGGL(compact_buckets_kernel, dim3((part->NB + 3) / 4), dim3(256), 0, st, (const uint4*)part->records, part->seg, part->NB,
-                       d_offsets, (uint4*)d_out, skip_lo, skip_hi);
-    SNK_HIP_TRY(hipGetLastError());
+    SNK_HIP_TRY(snk_launch(compact_buckets_kernel, snk_blocks(part->NB, 4), 256, 0, st, (const uint4*)part->records, part->seg, part->NB,
+                           d_offsets, (uint4*)d_out, skip_lo, skip_hi));
     return SNK_OK;
 }
 
@@ -1081,8 +1075,7 @@ int snk_partition_add(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, const 
         void* q;
         if ((rc = snk_ctx_alloc(ctx, 64, &q, err, errcap))) return rc; two = (unsigned long long*)q;
         if ((rc = snk_launch_msp_plan(st, good_len, in->n_reads, J->K, two, err, errcap))) return rc;
-        hipLaunchKernelGGL(plan_add_kernel, dim3(1), dim3(64), 0, st, two, J->d_plan);
-        SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(plan_add_kernel, 1, 64, 0, st, two, J->d_plan));
     }
     J->n_reads += in->n_reads;
     ++J->n_slabs;
@@ -1093,7 +1086,7 @@ int snk_partition_close(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, snk_
     memset(out, 0, sizeof *out);
     const uint32_t NB = J->NB;
     SNK_HIP_TRY(hipMemsetAsync(J->d_total, 0, 64 * 8, st));
-    hipLaunchKernelGGL(seg0_kernel, dim3((NB + 255) / 256), dim3(256), 0, st, J->cursor, NB, J->cap, J->seg, J->d_total);
+    SNK_HIP_TRY(snk_launch(seg0_kernel, snk_blocks(NB, 256), 256, 0, st, J->cursor, NB, J->cap, J->seg, J->d_total));
     uint32_t h_novf = 0;
     uint32_t h_sub[SNK_OVF_SUBLISTS];
     uint32_t h_cur[SNK_OVF_SUBLISTS * SNK_OVF_CUR_STRIDE];      // the cursors as they lie on the device, one per 128 bytes
@@ -1117,7 +1110,7 @@ int snk_partition_close(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, snk_
                         "underestimated, or a few minimisers carry a large share of the data): run it resident or with a larger total", h_novf, (unsigned long long)J->ovf_cap);
     int rc;
     if ((rc = snk_msp_segments(ctx, st, NB, J->cap, J->cursor, (uint4*)J->records, (uint64_t)NB * J->cap, J->ovf_cap / SNK_OVF_SUBLISTS, J->ovf_bucket, h_sub, J->seg, err, errcap))) return rc;
-    if (h_novf) hipLaunchKernelGGL(cursor_exact_kernel, dim3((NB + 255) / 256), dim3(256), 0, st, J->seg, NB, J->cursor);
+    if (h_novf) SNK_HIP_TRY(snk_launch(cursor_exact_kernel, snk_blocks(NB, 256), 256, 0, st, J->seg, NB, J->cursor));
     out->NB = NB;
     out->cap = J->cap;
     out->nseg = h_novf ? 2u : 1u;

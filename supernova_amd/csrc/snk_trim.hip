@@ -103,15 +103,14 @@ extern "C" int snk_dev_trim(snk_ctx* ctx, const void* d_quals, uint32_t qstride,
     if (n_reads == 0) return SNK_OK;
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
-    uint64_t nb = (n_reads + 255) / 256;
+    const uint64_t nb = snk_blocks(n_reads, 256);
     const bool tiled = (qstride & 3u) == 0 && qstride <= 160 && (((uintptr_t)d_quals) & 15u) == 0 && !snk_opt_u32(ctx, SNK_OPT_trim_rowwise);
     if (tiled)
-        hipLaunchKernelGGL(snk_trim_tile_kernel, dim3((unsigned)nb), dim3(256), 256 * qstride, st, (const uint8_t*)d_quals, qstride,
-                           (const uint16_t*)d_lens, read_len, n_reads, K, min_qual, (uint16_t*)d_good_len);
+        SNK_HIP_TRY(snk_launch(snk_trim_tile_kernel, nb, 256, 256 * qstride, st, (const uint8_t*)d_quals, qstride,
+                               (const uint16_t*)d_lens, read_len, n_reads, K, min_qual, (uint16_t*)d_good_len));
     else
-        hipLaunchKernelGGL(snk_trim_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const uint8_t*)d_quals, qstride,
-                           (const uint16_t*)d_lens, read_len, n_reads, K, min_qual, (uint16_t*)d_good_len);
-    SNK_HIP_TRY(hipGetLastError());
+        SNK_HIP_TRY(snk_launch(snk_trim_kernel, nb, 256, 0, st, (const uint8_t*)d_quals, qstride,
+                               (const uint16_t*)d_lens, read_len, n_reads, K, min_qual, (uint16_t*)d_good_len));
     return SNK_OK;
 }
 
@@ -150,9 +149,8 @@ extern "C" int snk_dev_pack_ascii(snk_ctx* ctx, const void* d_ascii, uint32_t as
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
     uint64_t total = n_reads * row_words;
-    uint64_t nb = (total + 255) / 256;
-    hipLaunchKernelGGL(snk_pack_kernel, dim3((unsigned)nb), dim3(256), 0, st, (const uint8_t*)d_ascii, astride, read_len,
-                       n_reads, (uint32_t*)d_rows, row_words);
-    SNK_HIP_TRY(hipGetLastError());
+    const uint64_t nb = snk_blocks(total, 256);
+    SNK_HIP_TRY(snk_launch(snk_pack_kernel, nb, 256, 0, st, (const uint8_t*)d_ascii, astride, read_len,
+                           n_reads, (uint32_t*)d_rows, row_words));
     return SNK_OK;
 }

@@ -180,6 +180,34 @@ def test_options_registry_and_no_environment_switches(snk):
     assert t.count_kernel == 0 and t.target_inst == 0
 
 
+def test_every_launch_goes_through_the_checked_helper():
+    """csrc/snk_launch.h: HIP cuts a launch of 2^32 or more work items short without an error ("round 6" (5)), so the one
+    launch of the library sits behind a host-side check of its shape, and the grids are computed by the two shared 64-bit functions -- no
+    file launches on its own or keeps a private grid helper."""
+    launch = re.compile(r"hipLaunchKernelGGL|<<<|hipLaunchKernel\(|hipModuleLaunchKernel|hipExtLaunch")
+    helper = re.compile(r"\b(?:nblk|pidx_grid|ck_grid)\s*\([^;{]*\)\s*\{")
+    n_files = 0
+    for f in (ROOT / "supernova_amd" / "csrc").rglob("*"):
+        if f.suffix in (".hip", ".h", ".cc") and f.is_file():
+            text = f.read_text(errors="ignore")
+            n_files += 1
+            assert not helper.search(text), f.name
+            assert len(launch.findall(text)) == (1 if f.name == "snk_launch.h" else 0), f.name
+    assert n_files > 20 and (ROOT / "supernova_amd" / "csrc" / "snk_launch.h").is_file()
+
+
+def test_launch_arithmetic_on_the_host(tmp_path):
+    """The arithmetic of csrc/snk_launch.h needs no HIP: tests/launch_shape_host.cc is built with the host compiler and checks the ceiling
+    division (64 bits, no truncation), its capped form and which launch shapes are refused."""
+    import os
+    import subprocess
+    exe = tmp_path / "launch_shape_host"
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-Wall", "-Werror", "-O1", f"-I{ROOT / 'supernova_amd' / 'csrc'}",
+                    str(ROOT / "tests" / "launch_shape_host.cc"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
 def test_tools_and_bench_compile():
     """bench.py runs tools/r6_full_job.py in a process of its own (config.large_job) and the evidence scripts drive the others: a tool that
     does not even compile must not wait for a GPU box to be noticed."""
