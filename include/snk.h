@@ -127,12 +127,12 @@ typedef struct snk_tuning {
 void snk_tuning_default(snk_tuning* t);
 int snk_ctx_set_tuning(snk_ctx* ctx, const snk_tuning* t, char* err, size_t errcap);
 void snk_ctx_get_tuning(const snk_ctx* ctx, snk_tuning* t);
-int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long value, char* err, size_t errcap);   /* SNK_E_ARG: no such option, or a value out of its range */
+int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long value, char* err, size_t errcap);   /* SNK_E_ARG: no such option, or a value out of its range (snk_option_doc ends with it) */
 int snk_option_check(const char* name, long long value, char* err, size_t errcap);                    /* no context: would snk_ctx_set_option take it? */
 int snk_ctx_clear_option(snk_ctx* ctx, const char* name);                    /* NULL: every option back to the library's choice */
 int snk_ctx_get_option(const snk_ctx* ctx, const char* name, long long* value);   /* 1 set, 0 not set, < 0 no such option */
 const char* snk_option_name(uint32_t i);                                      /* NULL past the last one */
-const char* snk_option_doc(uint32_t i);
+const char* snk_option_doc(uint32_t i);                                       /* "... [lo..hi]", "[0 or lo..hi]", "[lo..hi step s]": what the setters accept */
 
 /* ---- synthetic linked reads; counter-based, bit-identical host vs device ---------- */
 typedef struct snk_synth_params {

@@ -270,10 +270,6 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
             uint64_t ktag = 0;
             if (GR) { ktag = kk.lo & 0xFFFFFFFFull; kk.lo &= ~0xFFFFFFFFull; }
             const int first = bit < 4 ? 1 : 0;   // successors share positions 1..K-M, predecessors 0..K-M-1
-            if (do_prune & 2u) {                 // measurement aid (SNK_BL_NOCLASSIFY): every miss is pending, the index resolves them all -- same result
-                if (on && sub == 0) atomicOr(&resL[th], (1u << bit) | (0x100u << bit));
-                continue;
-            }
             uint32_t mk = 0xFFFFFFFFu;
             for (int t = 0; t < PER; ++t) {
                 const int sp = (int)sub * PER + t;
@@ -311,7 +307,10 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
                     snk_kmer_hash_count<(K > 48) || GR>(cn, &h1, &h2);       // the count kernel's split function
                     here = (h2 & split_mask) == ch.id;
                 }
-                if (here) { if (!(do_prune & 1u)) atomicOr(&resL[th], 1u << bit); }
+                // (do_prune & 2, option bl_noclassify, a measurement aid: a miss is never settled here, the index resolves them all -- same result.
+                // The neighbour's bucket is still worked out: on a rank of an N-GPU job it says whether the k-mer is another rank's to answer;
+                // without it such misses were looked up in this rank's index, not found, and their context bits dropped.)
+                if (here && !(do_prune & 2u)) { if (!(do_prune & 1u)) atomicOr(&resL[th], 1u << bit); }
                 else atomicOr(&resL[th], (1u << bit) | (0x100u << bit) | (remote ? (0x10000u << bit) : 0u));
             }
         }
@@ -950,7 +949,7 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
     sh.G = tab->n_regions ? tab->n_regions : 1u;
     sh.premote = B->premote;
     const uint32_t NBh = B->premote ? B->NB_total : tab->NB;      // bucket count of the minimiser hash
-    const uint32_t cpw = std::max(1u, snk_opt_u32(ctx, SNK_OPT_bl_cpw));      // (chunks per workgroup: merged-away chunks are empty; 1 -> 4: graph 29.2 -> 28.8 ms, 1.5 % errors 38.7 -> 37.6)
+    const uint32_t cpw = snk_opt_u32(ctx, SNK_OPT_bl_cpw);                 // (chunks per workgroup: merged-away chunks are empty; 1 -> 4: graph 29.2 -> 28.8 ms, 1.5 % errors 38.7 -> 37.6)
     // boundary index, filled by the prune kernel itself: sized from what the previous call of this context found for a table of
     // this size (first call: n / 5); too small = too full -> the separate build pass below redoes it with the exact size
     uint64_t tg0 = 0;

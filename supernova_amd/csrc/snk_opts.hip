@@ -1,12 +1,15 @@
 // snk_opts.hip -- the option registry behind snk_ctx_set_option / snk_ctx_set_tuning (snk_opts.h).
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+
+#include <string>
 
 #include "snk_ctx.h"
 #include "snk_opts.h"
 
 const snk_opt_def snk_opt_defs[SNK_OPT_COUNT] = {
-#define X(name, dflt, doc) {#name, dflt, doc},
+#define X(name, dflt, range, doc) {#name, dflt, range, doc},
     SNK_OPTIONS(X)
 #undef X
 };
@@ -46,9 +49,30 @@ int snk_opts_parse(snk_opts* o, const char* text, char* bad, unsigned badcap) {
     return 0;
 }
 
-// path_slots_x10: the dictionary gets nk * x / 10 + 1024 slots for nk unitig k-mers, and its insertion probes until it finds a free one --
-// below 11 there may be none
-bool snk_opt_valid(int id, long long value) { return id != SNK_OPT_path_slots_x10 || value >= 11; }
+// the registry's range of the option (snk_opts.h says where each comes from)
+bool snk_opt_valid(int id, long long value) {
+    if (id < 0 || id >= SNK_OPT_COUNT) return false;
+    const snk_opt_def& d = snk_opt_defs[id];
+    return (value == 0 && d.zero) || (value >= d.lo && value <= d.hi && (value - d.lo) % d.step == 0);
+}
+
+// "<text> [lo..hi]", "[0 or lo..hi]", "[lo..hi step s]": what snk_option_doc and the setters' refusals show
+const char* snk_opt_doc(int id) {
+    static const struct docs {
+        std::string text[SNK_OPT_COUNT];
+        docs() {
+            for (int i = 0; i < SNK_OPT_COUNT; ++i) {
+                const snk_opt_def& d = snk_opt_defs[i];
+                char r[96];
+                int n = snprintf(r, sizeof r, " [%s%lld..%lld", d.zero ? "0 or " : "", d.lo, d.hi);
+                if (d.step != 1) n += snprintf(r + n, sizeof r - (size_t)n, " step %lld", d.step);
+                snprintf(r + n, sizeof r - (size_t)n, "]");
+                text[i] = std::string(d.doc) + r;
+            }
+        }
+    } all;
+    return id >= 0 && id < SNK_OPT_COUNT ? all.text[id].c_str() : nullptr;
+}
 
 bool snk_opt_is_set(const snk_ctx* ctx, snk_opt_id id) { return ctx && ctx->opts.set[id]; }
 uint32_t snk_opt_u32(const snk_ctx* ctx, snk_opt_id id) { return (uint32_t)snk_opt_u64(ctx, id); }
@@ -61,14 +85,14 @@ extern "C" int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long valu
     if (!ctx || !name) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: NULL argument");
     const int ix = snk_opt_index(name);
     if (ix < 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: no option '%s' (snk_option_name lists them)", name);
-    if (!snk_opt_valid(ix, value)) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: %lld is out of range for '%s' (%s)", value, name, snk_opt_defs[ix].doc);
+    if (!snk_opt_valid(ix, value)) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_option: %lld is out of range for '%s' (%s)", value, name, snk_opt_doc(ix));
     ctx->opts.v[ix] = value; ctx->opts.set[ix] = true;
     return SNK_OK;
 }
 extern "C" int snk_option_check(const char* name, long long value, char* err, size_t errcap) {
     const int ix = snk_opt_index(name);
     if (ix < 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_option_check: no option '%s'", name ? name : "(NULL)");
-    if (!snk_opt_valid(ix, value)) return snk_fail(SNK_E_ARG, err, errcap, "snk_option_check: %lld is out of range for '%s' (%s)", value, name, snk_opt_defs[ix].doc);
+    if (!snk_opt_valid(ix, value)) return snk_fail(SNK_E_ARG, err, errcap, "snk_option_check: %lld is out of range for '%s' (%s)", value, name, snk_opt_doc(ix));
     return SNK_OK;
 }
 extern "C" int snk_ctx_clear_option(snk_ctx* ctx, const char* name) {
@@ -87,7 +111,7 @@ extern "C" int snk_ctx_get_option(const snk_ctx* ctx, const char* name, long lon
     return ctx->opts.set[ix] ? 1 : 0;
 }
 extern "C" const char* snk_option_name(uint32_t i) { return i < (uint32_t)SNK_OPT_COUNT ? snk_opt_defs[i].name : nullptr; }
-extern "C" const char* snk_option_doc(uint32_t i) { return i < (uint32_t)SNK_OPT_COUNT ? snk_opt_defs[i].doc : nullptr; }
+extern "C" const char* snk_option_doc(uint32_t i) { return i < (uint32_t)SNK_OPT_COUNT ? snk_opt_doc((int)i) : nullptr; }
 
 // the documented knobs as one struct: 0 in a field = the library's own choice (the option is cleared)
 namespace {
@@ -107,13 +131,19 @@ extern "C" void snk_tuning_default(snk_tuning* t) { if (t) memset(t, 0, sizeof *
 extern "C" int snk_ctx_set_tuning(snk_ctx* ctx, const snk_tuning* t, char* err, size_t errcap) {
     if (!ctx || !t) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_tuning: NULL argument");
     if (t->count_kernel > SNK_COUNT_KERNEL_SCREEN) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_tuning: count_kernel %u", t->count_kernel);
-    if (t->minimiser_len && t->minimiser_len != 16 && t->minimiser_len != 20) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_tuning: minimiser_len is 0, 16 or 20");
     if (t->path_lookup > 2 || t->join_ranking > 2 || t->adaptive_buckets > 2 || t->hot_buckets > 2)
         return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_tuning: a 0/1/2 field is out of range");
-    auto put = [&](snk_opt_id o, bool on, long long v) { ctx->opts.set[o] = on; ctx->opts.v[o] = on ? v : 0; };
-    for (const tfield& f : tfields) { const uint32_t v = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(t) + f.off); put(f.opt, v != 0, v); }
-    // count kernel: auto | margin (the default kernel) | booked slots | bit filter + booked slots
+    auto field = [&](const tfield& f) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(t) + f.off); };
+    // a field that is not 0 is a value of its option and has that option's range; nothing is applied unless everything is in range
+    for (const tfield& f : tfields)
+        if (field(f) && !snk_opt_valid(f.opt, field(f)))
+            return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_tuning: %u is out of range for '%s' (%s)", field(f), snk_opt_defs[f.opt].name, snk_opt_doc(f.opt));
     const uint32_t slots = t->count_tight_slots ? t->count_tight_slots : 1920u;
+    if (t->count_kernel == SNK_COUNT_KERNEL_BOOKED && !snk_opt_valid(SNK_OPT_count_tight, slots))
+        return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_set_tuning: count_tight_slots %u is out of range (%s)", slots, snk_opt_doc(SNK_OPT_count_tight));
+    auto put = [&](snk_opt_id o, bool on, long long v) { ctx->opts.set[o] = on; ctx->opts.v[o] = on ? v : 0; };
+    for (const tfield& f : tfields) put(f.opt, field(f) != 0, field(f));
+    // count kernel: auto | margin (the default kernel) | booked slots | bit filter + booked slots
     switch (t->count_kernel) {
         case SNK_COUNT_KERNEL_AUTO: put(SNK_OPT_count_tight, false, 0); put(SNK_OPT_count_screen_ng, false, 0); break;
         case SNK_COUNT_KERNEL_MARGIN: put(SNK_OPT_count_tight, true, 0); put(SNK_OPT_count_screen_ng, true, 0); break;

@@ -327,10 +327,8 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             SNK_HIP_TRY(hipMemcpyAsync(hsend_x, part.cursor, (size_t)NB_total * 4, hipMemcpyDeviceToDevice, st));
             SNK_HIP_TRY(hipMemsetAsync(hsend_x + (uint64_t)me * NBl, 0, (size_t)NBl * 4, st));
             SNK_HIP_TRY(hipMemsetAsync(hrecv + (uint64_t)me * NBl, 0, (size_t)NBl * 4, st));
-            uint32_t R = snk_opt_u32(ctx, SNK_OPT_exchange_ranges);
-            if (R < 1) R = 1;
+            uint32_t R = snk_opt_u32(ctx, SNK_OPT_exchange_ranges);      // (1 .. 64 by the option's range)
             if (R > NBl) R = NBl;
-            if (R > 64) R = 64;
             ull* d_rs;      // [2][W][R] records per (destination, range) and per (source, range)
             ALLOC(d_rs, ull, 2ull * W * R + 1);
             SNK_HIP_TRY(snk_launch(range_sum_kernel, (uint64_t)W * R, 256, 0, st, hsend_x, NBl, R, d_rs));

@@ -233,3 +233,209 @@ def test_dictionary_load_below_eleven_is_refused_without_a_context(snk):
     assert snk.snk_option_check(b"no_such_option", 1, err, 256) == -1
     for name in (b"path_edge_cap", b"path_redo_cap", b"path_ubc_cap"):
         assert snk.snk_option_check(name, 1, err, 256) == 0
+
+
+# ---- the registry's ranges (csrc/snk_opts.h): snk_option_check asks the one range check every setter goes through, without a context
+
+_RANGE = re.compile(r" \[(0 or )?(\d+)\.\.(\d+)( step (\d+))?\]$")
+
+
+def _registry(snk):
+    """-> {name: (doc, zero_also, lo, hi, step)} from snk_option_name / snk_option_doc: every doc string ends with its range."""
+    out, i = {}, 0
+    while snk.snk_option_name(i):
+        name, doc = snk.snk_option_name(i).decode(), snk.snk_option_doc(i).decode()
+        m = _RANGE.search(doc)
+        assert m, f"the description of option '{name}' does not end with its range: {doc!r}"
+        out[name] = (doc, bool(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(5) or 1))
+        i += 1
+    return out
+
+
+def _takes(snk, name, value):
+    err = C.create_string_buffer(512)
+    rc = snk.snk_option_check(name.encode(), value, err, 512)
+    assert rc in (0, -1) and (rc == 0 or name.encode() in err.value)
+    return rc == 0
+
+
+def test_every_option_has_a_range_and_refuses_what_lies_outside(snk):
+    """include/snk.h: snk_ctx_set_option returns SNK_E_ARG for "a value out of its range" -- for EVERY option: both ends of the range are
+    taken, one below, one above, -1 and 2^40 are not (no option is open on either side), a stepped range refuses what lies between its
+    steps, and 0 is taken exactly where the range starts there or names it."""
+    reg = _registry(snk)
+    assert len(reg) >= 70
+    for name, (doc, zero, lo, hi, step) in reg.items():
+        assert 0 <= lo <= hi < 2**40 and step >= 1 and (hi - lo) % step == 0, (name, doc)
+        assert _takes(snk, name, lo) and _takes(snk, name, hi), name
+        assert not _takes(snk, name, hi + 1) and not _takes(snk, name, -1) and not _takes(snk, name, 2**40), name
+        assert not _takes(snk, name, -2**40) and not _takes(snk, name, 2**63 - 1) and not _takes(snk, name, -2**63), name
+        assert _takes(snk, name, 0) == (zero or lo == 0), name
+        if lo - 1 > 0:
+            assert not _takes(snk, name, lo - 1), name
+        if step > 1:
+            assert not _takes(snk, name, lo + 1) and _takes(snk, name, lo + step), name
+
+
+# values that reach a shift, a divisor, a loop bound or a packed field at the call site (file:line as of the commit that added the ranges)
+HARMFUL = {
+    "split_log2": (0, 32, 40, 64),                   # (1u << v) - 1u, snk_graph.hip rank_lists / snk_prank_mark: undefined from 32 on
+    "rank_round_batch0": (0,),                       # no round runs, the flag stays zero, "converged": unconverged ranks go out
+    "rank_round_batch": (0,),                        # the same in snk_prank_walk
+    "tight_tries": (0, 65536, 1 << 20),              # << 16 into the high half of a 32-bit word (snk_pipeline.hip tight_for)
+    "hot_class_inst": (0, 1), "screen_target": (0, 1), "target_inst": (1, 7), "chunk_kmers": (0,),     # divisors and bucket targets
+    "bucket_fill_pct": (0, 101, 1000), "msp_cap_pct": (0, 101),
+    "count_tight": (1, 255, 1985, 2048, 1 << 16),    # the doc string's own 256 .. slots - 64
+    "count_screen": (3,), "count_screen_ng": (3,), "minimiser_len": (1, 15, 17, 18, 24, 32), "path_fast_gs": (4, 12, 32),
+    "bl_cpw": (0,), "exchange_ranges": (0, 65), "emit_grid_log2": (23, 32), "partition_passes": (65,), "dbg_fake_segs": (33,),
+    "path_slots_x10": (0, 10), "path_fp_mask": (1 << 30,), "rank_wyllie": (2,), "arena_vmm": (2,), "trim_rowwise": (2,),
+}
+
+
+def test_harmful_option_values_are_refused(snk):
+    """The values whose call sites cannot take them, read off the code (never run): each is refused by name, so that a range which grows
+    back over one of them fails here."""
+    reg = _registry(snk)
+    for name, values in HARMFUL.items():
+        assert name in reg, name
+        for v in values:
+            assert not _takes(snk, name, v), (name, v)
+    # the fields of snk_tuning keep "0 = the library's choice"; by name, 0 is a value like any other
+    for name in ("hot_class_inst", "target_inst", "chunk_kmers", "bucket_fill_pct", "exchange_ranges", "hot_min", "hot_factor", "unitig_bc_cut"):
+        assert not _takes(snk, name, 0), name
+
+
+def _registry_defaults():
+    src = (ROOT / "supernova_amd" / "csrc" / "snk_opts.h").read_text()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"^\s*X\((\w+),\s*(\d+),", src, re.M)}
+
+
+def test_registry_defaults_lie_in_their_own_range(snk):
+    """The default of every entry is a value its setter would take -- except where the entry's 0 is never read because the call site asks
+    snk_opt_is_set and chooses from the data (snk_opts.h names them): there the test looks for that question in the sources."""
+    reg, dflt = _registry(snk), _registry_defaults()
+    assert set(dflt) == set(reg)
+    csrc = "".join(f.read_text(errors="ignore") for f in (ROOT / "supernova_amd" / "csrc").glob("*.hip") if f.name != "snk_opts.hip")
+    for name, d in dflt.items():
+        if _takes(snk, name, d):
+            continue
+        assert d == 0 and re.search(r"(snk_opt_is_set\(ctx, |cap0\()SNK_OPT_%s\b" % name, csrc), (name, d)
+
+
+def _values_set_today():
+    """(file, option, value) for every literal option value in the tests, the tools, bench.py and the Python package: tune("name", v),
+    set_option("name", v), "name": v / "SNK_NAME": "v" in dicts, name=v in SNK_TUNING strings and keyword arguments, name=int(rng.choice([..]))."""
+    names = set(_registry_defaults())
+    files = [ROOT / "bench.py"] + [f for d in ("tests", "tests/tools", "tools", "supernova_amd") for f in sorted((ROOT / d).glob("*.py"))]
+    num = r"(-?(?:0x[0-9a-fA-F]+|\d[\d_]*))"
+    pats = [re.compile(r"""(?:tune|set_option)\(\s*["'](?:SNK_)?(\w+)["'],\s*["']?%s["']?\s*\)""" % num),
+            re.compile(r"""["'](?:SNK_)?(\w+)["']:\s*["']?%s["']?\s*[,})]""" % num),
+            re.compile(r"""\b([a-z][a-z0-9_]+)=%s\b""" % num)]
+    lists = re.compile(r"""\b([a-z][a-z0-9_]+)=int\(rng\.choice\(\[([^\]]+)\]\)\)""")
+    found = []
+    for f in files:
+        text = f.read_text(errors="ignore")
+        if f.name == "test_abi.py":
+            text = text.split("# ---- the registry's ranges", 1)[0]      # (this section names refused values on purpose)
+        for p in pats:
+            for m in p.finditer(text):
+                if m.group(1).lower() in names:
+                    found.append((f.name, m.group(1).lower(), int(m.group(2).replace("_", ""), 0)))
+        for m in lists.finditer(text):
+            if m.group(1) in names:
+                found += [(f.name, m.group(1), int(v.strip(), 0)) for v in m.group(2).split(",")]
+    return found
+
+
+def test_every_value_a_caller_sets_today_is_accepted(snk):
+    """A range that would refuse what a test, a tool, bench.py or the package sets is wrong, and shows here rather than on the GPU box."""
+    found = _values_set_today()
+    assert len(found) >= 60 and {"bench.py", "fuzz_parity.py", "test_gpu_parity.py", "msp_probe2.py"} <= {f for f, _, _ in found}, len(found)
+    assert ("test_gpu_paths.py", "path_fast_gs", 16) in found and ("test_gpu_sharded.py", "hot_class_inst", 300) in found
+    refused_on_purpose = {("test_gpu_paths.py", "path_slots_x10", 10), ("test_gpu_paths.py", "path_slots_x10", 0)}
+    bad = [x for x in found if not _takes(snk, x[1], x[2]) and x not in refused_on_purpose]
+    assert not bad, bad
+    import test_gpu_option_invariance as inv
+    for name, spec in inv.NEUTRAL.items():
+        for v in spec["values"]:
+            assert _takes(snk, name, v), (name, v)
+        for k, v in spec.get("with", {}).items():
+            assert _takes(snk, k, v), (name, k, v)
+
+
+INVALIDATING = ("count_dbg", "msp_dbg", "overlap_probe", "overlap_probe_dbg", "path_idx_dbg", "join_dbg", "dbg_fake_segs")
+# option -> the existing test that forces it (file::function); the function's source must name the option
+ALREADY_FORCED = {
+    "count_tight": "test_gpu_parity.py::test_booked_table_slots_count_the_same_table",
+    "count_screen": "test_gpu_parity.py::test_grouped_per_barcode_graphs",
+    "count_screen_ng": "test_gpu_parity.py::COUNT_VARIANTS",
+    "screen_ratio_pct": "test_gpu_parity.py::test_error_rich_reads_are_repartitioned_into_smaller_buckets",
+    "target_inst": "test_gpu_dfin.py::test_tuning_struct_and_options",
+    "adaptive_buckets": "test_gpu_parity.py::test_error_rich_reads_are_repartitioned_into_smaller_buckets",
+    "count_persist": "test_gpu_parity.py::test_count_launch_shapes",
+    "minimiser_len": "test_gpu_dfin.py::test_tuning_struct_and_options",
+    "global_graph": "test_gpu_parity.py::graph_stage",
+    "partition_passes": "test_gpu_parity.py::test_hot_buckets_are_repartitioned_by_kmer_hash",
+    "msp_cap_pct": "test_gpu_parity.py::test_partition_overflow_segment",
+    "msp_dense": "test_gpu_parity.py::test_dense_partition_mode",
+    "msp_hot_factor": "test_gpu_sharded.py::test_sharded_overflowing_buckets_and_the_hot_table",
+    "msp_hot_min": "test_gpu_sharded.py::test_sharded_overflowing_buckets_and_the_hot_table",
+    "trim_fused": "test_gpu_parity.py::test_trim_inside_the_partition_kernel",
+    "hot_min": "test_gpu_sharded.py::test_sharded_hot_buckets_are_repartitioned_on_their_owner",
+    "hot_factor": "test_gpu_sharded.py::test_sharded_hot_buckets_are_repartitioned_on_their_owner",
+    "hot_class_inst": "test_gpu_sharded.py::test_sharded_hot_buckets_are_repartitioned_on_their_owner",
+    "bl_pool": "test_gpu_parity.py::test_circle_pool_retry",
+    "emit_grid_log2": "test_gpu_parity.py::test_golden_case_strided_fragment_copy",
+    "plan_mem_mb": "test_gpu_parity.py::test_a_small_device_plans_passes_and_probes_its_regions",
+    "hbv_huge_pages": "test_gpu_parity.py::test_context_free_hbv_writer_after_a_closed_engine",
+    "hbv_short_queue": "test_gpu_parity.py::test_context_free_hbv_writer_after_a_closed_engine",
+    "join_replicated": "test_gpu_sharded.py::test_sharded_replicated_ranking_with_circles",
+    "path_index": "test_gpu_paths.py::test_long_tandem_reads",
+    "path_dict_max_kb": "test_gpu_parity.py::test_read_paths_match_reference",
+    "path_slots_x10": "test_gpu_paths.py::VARIANTS",
+    "path_two_pass": "test_gpu_paths.py::VARIANTS",
+    "path_fast_gs": "test_gpu_paths.py::VARIANTS",
+    "path_fused": "test_gpu_parity.py::test_read_paths_full_capacity_pass",
+    "path_redo_all": "test_gpu_paths.py::test_path_list_overflow_reruns",
+    "path_fp_mask": "test_gpu_parity.py::test_read_paths_with_colliding_fingerprints",
+    "path_edge_cap": "test_gpu_paths.py::RETRIES",
+    "path_redo_cap": "test_gpu_paths.py::RETRIES",
+    "path_ubc_cap": "test_gpu_paths.py::RETRIES",
+    "unitig_bc_cut": "test_gpu_parity.py::test_unitig_barcode_lists_two_derivations_200k_parity_unpinned_rust",
+    "dups_two_sorts": "test_gpu_paths.py::VARIANTS",
+    "hbv_dev_min": "test_gpu_parity.py::HBV_FLOODS",
+    "hbv_big": "test_gpu_parity.py::HBV_FLOODS",
+    "df_stream": "test_gpu_dfin.py::test_streamed_count_graph_equals_resident",
+}
+
+
+def _source_of(path, symbol):
+    """The text of a top-level function, fixture or assignment of a test module (up to the next top-level statement)."""
+    text = (ROOT / "tests" / path).read_text()
+    m = re.search(r"^(?:def %s\(|%s\s*=)" % (re.escape(symbol), re.escape(symbol)), text, re.M)
+    assert m, f"{path} has no top-level '{symbol}'"
+    rest = text[m.start():]
+    end = re.search(r"^(?=[^\s#)\]}])", rest[rest.index("\n") + 1:], re.M)
+    return rest[:rest.index("\n") + 1 + end.start()] if end else rest
+
+
+def test_every_option_is_classified(snk):
+    """Every registered option is in exactly one of: NEUTRAL (tests/test_gpu_option_invariance.py forces it and compares the results),
+    ALREADY_FORCED (an existing test does; its source names the option, in either spelling) or INVALIDATING (debug / probe / measurement
+    modes, whose description says so).  An option added without a test fails here."""
+    import test_gpu_option_invariance as inv
+    reg = _registry(snk)
+    groups = {"NEUTRAL": set(inv.NEUTRAL), "ALREADY_FORCED": set(ALREADY_FORCED), "INVALIDATING": set(INVALIDATING)}
+    for name in reg:
+        where = [g for g, s in groups.items() if name in s]
+        assert len(where) == 1, f"option '{name}' is in {where or 'no group'}"
+    for g, s in groups.items():
+        assert s <= set(reg), (g, s - set(reg))
+    for name in INVALIDATING:
+        assert re.search(r"debug|probe|measurement", reg[name][0]), (name, reg[name][0])
+    for name, where in ALREADY_FORCED.items():
+        path, symbol = where.split("::")
+        src = _source_of(path, symbol)
+        assert re.search(r"""["'](?:SNK_%s|%s)["']""" % (name.upper(), name), src) or re.search(r"\b%s=" % name, src), f"{where} does not set '{name}'"
+    for name, spec in inv.NEUTRAL.items():
+        assert spec["values"] and spec["legs"] and spec["evidence"], name

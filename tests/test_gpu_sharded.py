@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import goldens
+from sharded_cases import plasmid_case
 
 pytestmark = pytest.mark.gpu
 
@@ -315,35 +316,6 @@ def test_rccl_world1_exchange_multi_gib(snk):
         dist.destroy_process_group()
 
 
-def _plasmid_case(seed=5):
-    """A 600 kb linear genome + six circular replicons from 150 bp to 20 kb at 30x, error-free, two barcodes per locus:
-    thousands of fragments (the sparse-ruling-set ranking runs, not the small-input fallback) with circles that hold splitters
-    and circles that hold none."""
-    rng = np.random.default_rng(seed)
-    L = 150
-    reps = [(rng.integers(0, 4, 600_000, dtype=np.uint8), False)] + [(rng.integers(0, 4, n, dtype=np.uint8), True) for n in (150, 400, 1000, 3000, 8000, 20000)]
-    rows = []
-    for g, circular in reps:
-        G = len(g)
-        n = max(40, G * 30 // L)
-        ext = np.concatenate([g, g[:L]]) if circular else g
-        starts = rng.integers(0, G if circular else G - L + 1, n)
-        idx = starts[:, None] + np.arange(L)[None, :]
-        r = ext[idx]
-        flip = rng.random(n) < 0.5
-        r[flip] = (3 - r[flip][:, ::-1])
-        rows.append(r)
-    codes = np.concatenate(rows).astype(np.uint8)
-    perm = rng.permutation(codes.shape[0])
-    codes = codes[perm]
-    if codes.shape[0] & 1:
-        codes = codes[:-1]
-    n = codes.shape[0]
-    quals = np.full((n, L), 30, dtype=np.uint8)
-    bc = rng.integers(1, 50, n).astype(np.int32)
-    return codes, quals, bc, L
-
-
 @pytest.mark.parametrize("W", [1, 2, 3])
 def test_sharded_circles_at_scale_against_the_oracle(snk, W):
     """Circular replicons among tens of thousands of fragments: the partitioned ranking cuts them (splitter cycles by pointer
@@ -354,7 +326,7 @@ def test_sharded_circles_at_scale_against_the_oracle(snk, W):
     from supernova_amd import synth
     from supernova_amd.engine import Engine, Params
     from supernova_amd.sharded import ShardedEngine, SimWorld
-    codes, quals, bc, L = _plasmid_case()
+    codes, quals, bc, L = plasmid_case()
     n = codes.shape[0]
     o = oracle_lib.OracleResult(codes, np.full(n, L, np.uint32), bc, hbv=False)
     assert sum(1 for u in o.unitigs if len(u) >= 95 and u[:47] == u[-47:]) >= 6

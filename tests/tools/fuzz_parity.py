@@ -11,6 +11,16 @@ import oracle_lib
 from supernova_amd import synth
 from supernova_amd.engine import Engine, Params
 from supernova_amd.sharded import ShardedEngine, SimWorld
+from test_gpu_option_invariance import NEUTRAL
+
+# result-neutral options a case may pin (up to two, with one of the values the invariance tests list): the ones a context reads per call
+# and that need no companion option to matter.  Drawn AFTER every other draw of the case, so that the cases of older logs replay unchanged.
+FUZZ_NEUTRAL = sorted(o for o, s in NEUTRAL.items() if "with" not in s and o != "arena_vmm")
+
+
+def draw_neutral(rng):
+    names = rng.choice(FUZZ_NEUTRAL, size=int(rng.integers(0, 3)), replace=False)
+    return {str(o): int(rng.choice(NEUTRAL[str(o)]["values"])) for o in names}
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
 only = int(sys.argv[3]) if len(sys.argv) > 3 else -1      # replay one case of a sweep (same random stream)
@@ -70,6 +80,7 @@ for case in range(n_cases):
         if K == 48 and rng.random() < 0.4:
             ng_ = int(rng.choice([1, 2, 7])); rng.integers(0, ng_, n); rng.choice([1, 1000])
         rng.choice([2, 3, 5, 8])
+        draw_neutral(rng)
         continue
     if only >= 0:
         print(f"replaying case {case}: K={K} L={L} G={G} n={n} err={err} nbc={nbc} min_freq={min_freq} min_bc={min_bc} nb={nb} bc={use_bc} cap%={cap_pct}", flush=True)
@@ -139,6 +150,17 @@ for case in range(n_cases):
             ok = False; print("MISMATCH grouped NG=%d" % NG, tag, flush=True)
     W = int(rng.choice([2, 3, 5, 8]))
     if only >= 0: print("  sharded leg, W =", W, flush=True)
+    # the case once more through the one-GPU path (ungrouped, bucket-local stage) with the drawn options pinned; the ranks below are created
+    # under SNK_TUNING and carry them too
+    neutral = draw_neutral(rng)
+    tag += " opts=" + (",".join(f"{k}={v}" for k, v in neutral.items()) or "-")
+    for k, v in neutral.items():
+        eng.set_option(k, v)
+    os.environ["SNK_TUNING"] = ",".join([f"msp_cap_pct={cap_pct}"] + [f"{k}={v}" for k, v in neutral.items()])
+    if neutral:
+        r = eng.count_graph(rows, L, quals=dq, bc=dbc, lens=dl, params=Params(K=K, min_freq=min_freq, min_bc=min_bc, n_buckets=nb))
+        if not same(r.keys(), r.counts(), r.ctx(), r.unitigs(), o):
+            ok = False; print("MISMATCH single with options", tag, flush=True)
     world = SimWorld(W); bounds = [n * q // W for q in range(W + 1)]; out = [None] * W; errs = []
     def worker(q):
         try:
@@ -169,6 +191,8 @@ for case in range(n_cases):
             if out[0][3] != o.unitigs:
                 a, b = set(out[0][3]), set(o.unitigs)
                 print("   only in HIP:", len(a - b), "only in oracle:", len(b - a), "lens", sorted(len(x) for x in a - b)[:10], sorted(len(x) for x in b - a)[:10], flush=True)
+    for k in neutral:
+        eng.clear_option(k)
     bad += 0 if ok else 1
     print(("ok   " if ok else "FAIL ") + tag + f" (sharded W={W})", flush=True)
 print(f"{n_cases - bad} of {n_cases} cases bit-exact")
