@@ -563,6 +563,60 @@ int snk_write_paths_index(const char* path_inv, const char* path_countsb, uint64
                           const int32_t* counts, char* err, size_t errcap);
 int snk_write_dup(const char* path, uint64_t n_pairs, const uint8_t* dup, char* err, size_t errcap);
 
+/* ---- the compressed read paths: a.pathsX and a.hbx ------------------------------------------------------------------
+ * Right after StageBuildGraph the reference turns the graph into a HyperBasevectorX and the paths into a ReadPathVecX (10X/DF.cc:573-583,
+ * InitializePathsXFromPaths, 10X/DfTools.cc:24-69); every later consumer takes that form, and a DF entered at START=patch opens a.hbv,
+ * a.hbx, a.inv, a.pathsX and a.dup (DF.cc:612-630).  Per read, in read order, the record is (RPParser::LLzip,
+ * 10X/paths/ReadPathParser.cc:18-51,184-198):
+ *     u8 n = number of edges | n > 0: i16 offset (static_cast<int16_t>: beyond +-32767 it wraps), u32 first edge id,
+ *                              (n - 1 + 3) / 4 bytes of 2-bit branch ids, least significant bits first
+ * The branch id of a step e -> e' is the position of e' in From(ToRight(e)).  A step whose e' is not among them encodes nothing and does
+ * not move the bit cursor; the record's size still comes from n (the bytes left over are 0).  ZipIndex: the byte offset of every 10th
+ * read.
+ *   paths        of snk_dev_path_reads (edge ids = HBV edge ids); it stays valid across the call, as for snk_dev_paths_index
+ *   h            HOST: the graph the paths were made on.  Its From / To lists are derived by the function that snk_write_hbv takes them
+ *                from, in the order a.hbv has them
+ *   data         u8[n_bytes], index i64[n_index], n_index = ceil(n_reads / 10): device memory of the context, valid until its next
+ *                top-level call
+ * Refused: a path of more than 255 edges (SNK_E_UNSUPPORTED: the reference's own record is self-inconsistent there: one byte holds the
+ * count), a vertex with more than four out-edges (SNK_E_UNSUPPORTED: a branch id has two bits), an edge id outside the graph (SNK_E_ARG),
+ * start / n_edges that do not add up to n_edges_total (SNK_E_ARG: start must be the exclusive scan of n_edges -- no gaps, no overlaps -- and
+ * start[n_reads] = n_edges_total, as snk_dev_path_reads leaves them).  The result is bit-identical from call to call and depends on no
+ * tuning option. */
+typedef struct snk_dev_pathsx {
+    uint64_t n_reads, n_bytes, n_index;
+    const void* data;
+    const void* index;
+    uint64_t n_empty;                    /* reads without a path (one byte each) */
+    uint64_t n_steps_not_found;          /* steps e -> e' with e' not in From(ToRight(e)): nothing encoded for them */
+    uint64_t n_offsets_wrapped;          /* reads with a path whose offset does not fit an int16 */
+    float ms;                            /* time between two HIP events at the start and the end of the call's device work: not kernel time
+                                            alone -- it spans the upload of the per-edge arrays, one wait of the host in the middle (largest
+                                            edge id, flags and n_bytes come down before data is allocated) and that allocation.  The
+                                            host's derivation of the per-edge arrays from h comes before the first event */
+    uint32_t reserved0;
+    uint64_t reserved[6];
+} snk_dev_pathsx;
+int snk_dev_paths_zip(snk_ctx* ctx, const snk_dev_paths* paths, const snk_hbv* h, snk_dev_pathsx* out, void* stream, char* err, size_t errcap);
+/* The inverse (ReadPathVecX::unzip, LLunzip, ReadPathParser.cc:106-132): how a consumer starts from an a.pathsX file.  in->data and
+ * in->index are device memory (n_reads, n_bytes, n_index filled in; the counters are not read).  out: offset, n_edges, start, edges as
+ * from snk_dev_path_reads (context memory, valid until its next top-level call; path_ms = time of the call, the other fields 0); an
+ * offset comes back as the int16 it was stored as.  SNK_E_ARG: n_index is not ceil(n_reads / 10), the records do not follow the index or
+ * do not end exactly at n_bytes, a first edge outside the graph, a branch id that addresses no out-edge of its vertex. */
+int snk_dev_paths_unzip(snk_ctx* ctx, const snk_dev_pathsx* in, const snk_hbv* h, snk_dev_paths* out, void* stream, char* err, size_t errcap);
+/* The files (host arrays; no GPU needed), byte for byte what the reference writes:
+ *   snk_write_pathsx   a.pathsX = ReadPathVecX::writeBinary(std::string) (10X/paths/ReadPathVecX.cc:976-996), raw: skip = 10, start_rid = 0,
+ *                      next_start_rid = n_reads, the index size and the data size as int64, the index, the data
+ *   snk_read_pathsx    the same file back; *index and *data are malloc'ed (snk_host_free).  SNK_E_IO: a header that does not fit the file
+ *   snk_write_hbx      a.hbx = BinaryWriter::writeFile(HyperBasevectorX) (paths/HyperBasevector.cc:133-137, graph/DigraphTemplate.h:3107-3113):
+ *                      "BINWRITE", int K, from_, to_ (per vertex a u32 count and the vertices at the other end), from_edge_obj_,
+ *                      to_edge_obj_ (the edge ids), edges_ (as in a.hbv), to_left_, to_right_ (u64 count + ints).  The unitig arrays are
+ *                      the ones the snk_hbv was built from (BVComp order), as for snk_write_hbv */
+int snk_write_pathsx(const char* path, uint64_t n_reads, const int64_t* index, uint64_t n_index, const uint8_t* data, uint64_t n_bytes, char* err, size_t errcap);
+int snk_read_pathsx(const char* path, uint64_t* n_reads, uint64_t* n_index, int64_t** index, uint64_t* n_bytes, uint8_t** data, char* err, size_t errcap);
+int snk_write_hbx(const char* path, uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases, const snk_hbv* h, char* err,
+                  size_t errcap);
+
 /* ---- f3: barcode ids on the device --------------------------------------------------------------
  * BcIndexer, lib/tada/src/utils.rs:101-164: whitelist line -> index (identical lines: the last one wins); a read's
  * barcode field "SEQ[-gg][,raw]" (FASTH line 6, lib/tada/src/multifastq.rs:72-126) gets

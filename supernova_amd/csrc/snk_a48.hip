@@ -5,14 +5,20 @@
 //   a.paths.inv  feudal MasterVec<ULongVec>   10X/PathsIndex.cc:76,100-108
 //   a.countsb    BINWRITE vec<vec<int>>       10X/PathsIndex.cc:75,135 (one inner vector)
 //   a.dup        BINWRITE vec<Bool>           10X/DF.cc:599-600
+//   a.pathsX     raw ReadPathVecX             10X/paths/ReadPathVecX.cc:976-996 (five int64, the ZipIndex, the zipped data)
+//   a.hbx        BINWRITE HyperBasevectorX    paths/HyperBasevector.cc:133-137, graph/DigraphTemplate.h:3107-3113; 10X/DF.cc:573-576
 // A feudal file: 24-byte control block (feudal/FeudalControlBlock.h:157-166), the elements' variable-length data back to back, the
 // table of N + 1 file offsets, then the fixed-length data (none for these element types).
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+
+#include <new>
 
 #include <vector>
 
 #include "snk_ctx.h"
+#include "snk_hbvadj.h"
 
 namespace {
 
@@ -122,4 +128,98 @@ extern "C" int snk_write_dup(const char* path, uint64_t n_pairs, const uint8_t* 
     o.put(dup, (size_t)n_pairs);
     if (!o.close()) return snk_fail(SNK_E_IO, err, errcap, "snk_write_dup: write error on %s", path);
     return SNK_OK;
+}
+
+extern "C" int snk_write_pathsx(const char* path, uint64_t n_reads, const int64_t* index, uint64_t n_index, const uint8_t* data, uint64_t n_bytes, char* err, size_t errcap) {
+    if (!path || (n_index && !index) || (n_bytes && !data)) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_pathsx: NULL argument");
+    if (n_index != (n_reads + 9) / 10)
+        return snk_fail(SNK_E_ARG, err, errcap, "snk_write_pathsx: %llu index entries for %llu reads (one per 10)", (unsigned long long)n_index, (unsigned long long)n_reads);
+    out_file o(path);
+    if (!o.ok) return snk_fail(SNK_E_IO, err, errcap, "snk_write_pathsx: cannot create %s", path);
+    const int64_t head[5] = {10, 0, (int64_t)n_reads, (int64_t)n_index, (int64_t)n_bytes};      // skip, start_rid, next_start_rid, sizes
+    o.put(head, sizeof head);
+    o.put(index, (size_t)n_index * 8);
+    o.put(data, (size_t)n_bytes);
+    if (!o.close()) return snk_fail(SNK_E_IO, err, errcap, "snk_write_pathsx: write error on %s", path);
+    return SNK_OK;
+}
+
+extern "C" int snk_read_pathsx(const char* path, uint64_t* n_reads, uint64_t* n_index, int64_t** index, uint64_t* n_bytes, uint8_t** data, char* err, size_t errcap) {
+    if (!path || !n_reads || !n_index || !index || !n_bytes || !data) return snk_fail(SNK_E_ARG, err, errcap, "snk_read_pathsx: NULL argument");
+    *n_reads = *n_index = *n_bytes = 0;
+    *index = nullptr;
+    *data = nullptr;
+    FILE* f = fopen(path, "rb");
+    if (!f) return snk_fail(SNK_E_IO, err, errcap, "snk_read_pathsx: cannot open %s", path);
+    int64_t head[5];
+    bool ok = fread(head, 8, 5, f) == 5 && fseek(f, 0, SEEK_END) == 0;
+    const long long size = ok ? (long long)ftell(f) : -1;
+    // skip 10 and reads from 0: what DF writes; the sizes must be the file's
+    // (every count is bounded by the file's size before it is multiplied: a hostile header cannot overflow the sums)
+    ok = ok && head[0] == 10 && head[1] == 0 && head[2] >= 0 && head[2] <= size && head[3] >= 0 && head[3] <= size / 8 && head[4] >= 0 && head[4] <= size &&
+         head[3] == (head[2] + 9) / 10 && head[4] >= head[2] && head[4] <= head[2] * 71 && size == 40 + head[3] * 8 + head[4] && fseek(f, 40, SEEK_SET) == 0;
+    if (!ok) { fclose(f); return snk_fail(SNK_E_IO, err, errcap, "snk_read_pathsx: %s is not an a.pathsX file (header and size disagree)", path); }
+    int64_t* ix = (int64_t*)malloc((size_t)head[3] * 8 + 8);
+    uint8_t* d = (uint8_t*)malloc((size_t)head[4] + 8);
+    if (!ix || !d) { free(ix); free(d); fclose(f); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_read_pathsx: host allocation failed"); }
+    ok = fread(ix, 8, (size_t)head[3], f) == (size_t)head[3] && fread(d, 1, (size_t)head[4], f) == (size_t)head[4];
+    fclose(f);
+    if (!ok) { free(ix); free(d); return snk_fail(SNK_E_IO, err, errcap, "snk_read_pathsx: short read from %s", path); }
+    *n_reads = (uint64_t)head[2];
+    *n_index = (uint64_t)head[3];
+    *n_bytes = (uint64_t)head[4];
+    *index = ix;
+    *data = d;
+    return SNK_OK;
+}
+
+static int write_hbx_impl(const char* path, uint32_t K, uint64_t U, const uint64_t* off, const uint8_t* bases, const snk_hbv* h, char* err, size_t errcap) {
+    const int32_t N = h->n_vertices, E = h->n_edges;
+    for (int32_t e = 0; e < E; ++e)
+        if (h->src_unitig[e] < 0 || (uint64_t)h->src_unitig[e] >= U) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_hbx: edge %d is out of range", e);
+    snk_hbv_lists ls;
+    const int rc = snk_hbv_lists_build(h, &ls, "snk_write_hbx", err, errcap);
+    if (rc) return rc;
+    out_file o(path);
+    if (!o.ok) return snk_fail(SNK_E_IO, err, errcap, "snk_write_hbx: cannot create %s", path);
+    o.put("BINWRITE", 8);
+    const int32_t k32 = (int32_t)K;
+    o.put(&k32, 4);
+    // VecIntVec = MasterVec<SerfVec<int>>: u64 count, per element a u32 count and its ints (feudal/OuterVec.h:377-379, SmallVec.h:355-357)
+    auto put_lists = [&](const std::vector<uint64_t>& loff, const std::vector<int32_t>& vals) {
+        const uint64_t n = (uint64_t)N;
+        o.put(&n, 8);
+        for (int32_t v = 0; v < N; ++v) {
+            const uint32_t m = (uint32_t)(loff[(size_t)v + 1] - loff[v]);
+            o.put(&m, 4);
+            if (m) o.put(vals.data() + loff[v], (size_t)m * 4);
+        }
+    };
+    put_lists(ls.from_off, ls.from_v);
+    put_lists(ls.to_off, ls.to_v);
+    put_lists(ls.from_off, ls.from_e);
+    put_lists(ls.to_off, ls.to_e);
+    const uint64_t e64 = (uint64_t)E;
+    o.put(&e64, 8);
+    std::vector<uint8_t> buf;
+    for (int32_t e = 0; e < E; ++e) {
+        const uint64_t len64 = snk_hbv_edge_image(h, e, off, bases, buf);
+        if (len64 > 0xFFFFFFFFull) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_write_hbx: edge longer than 2^32 bases");
+        const uint32_t len = (uint32_t)len64;
+        o.put(&len, 4);
+        o.put(buf.data(), buf.size());
+    }
+    o.put(&e64, 8);
+    o.put(h->v_left, (size_t)E * 4);
+    o.put(&e64, 8);
+    o.put(h->v_right, (size_t)E * 4);
+    if (!o.close()) return snk_fail(SNK_E_IO, err, errcap, "snk_write_hbx: write error on %s", path);
+    return SNK_OK;
+}
+
+extern "C" int snk_write_hbx(const char* path, uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases, const snk_hbv* h, char* err,
+                             size_t errcap) {
+    if (!path || !h || (n_unitigs && (!unitig_off || !unitig_bases))) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_hbx: NULL argument");
+    try { return write_hbx_impl(path, K, n_unitigs, unitig_off, unitig_bases, h, err, errcap); }
+    catch (const std::bad_alloc&) { return snk_fail(SNK_E_NOMEM, err, errcap, "snk_write_hbx: host allocation failed"); }
 }

@@ -32,6 +32,7 @@
 #include "snk_ctx.h"
 #include "snk_common.h"
 #include "snk_kernels.h"
+#include "snk_hbvadj.h"
 
 namespace {
 
@@ -252,49 +253,93 @@ extern "C" int snk_hbv_involution(const snk_hbv* h, uint64_t n_unitigs, int32_t*
 // (paths/HyperBasevector.cc:121-125, graph/Digraph.h:381-382, graph/DigraphTemplate.h:3092-3097, feudal/BinaryStream.h:488-493).
 // Adjacency order is AddEdge's (DigraphTemplate.h:2572-2582): a vertex's out-edges ascending by target vertex, equal targets
 // in edge-id order (upper_bound insertion); in-edges likewise by source vertex.  a.inv = "BINWRITE", u64 E, E ints.
+// the shared derivation of the lists (snk_hbvadj.h): counting sort of the edges by vertex (edge-id order kept), then inside a vertex a
+// stable sort by the vertex at the other end (by insertion up to 16 edges, which every HBV vertex stays far below) -- what
+// upper_bound insertion in edge-id order leaves
+int snk_hbv_lists_build(const snk_hbv* h, snk_hbv_lists* out, const char* who, char* err, size_t errcap) {
+    const int32_t N = h->n_vertices, E = h->n_edges;
+    for (int32_t e = 0; e < E; ++e) {
+        const int32_t v = h->v_left[e], w = h->v_right[e];
+        if (v < 0 || w < 0 || v >= N || w >= N) return snk_fail(SNK_E_ARG, err, errcap, "%s: edge %d is out of range", who, e);
+    }
+    auto one_side = [&](const int32_t* own, const int32_t* other, std::vector<uint64_t>& off, std::vector<int32_t>& ov, std::vector<int32_t>& oe) {
+        off.assign((size_t)N + 1, 0);
+        for (int32_t e = 0; e < E; ++e) ++off[(size_t)own[e] + 1];
+        for (int32_t v = 0; v < N; ++v) off[(size_t)v + 1] += off[v];
+        ov.resize((size_t)E);
+        oe.resize((size_t)E);
+        std::vector<uint64_t> at(off.begin(), off.end() - 1);
+        for (int32_t e = 0; e < E; ++e) {
+            const uint64_t q = at[own[e]]++;
+            ov[q] = other[e];
+            oe[q] = e;
+        }
+        std::vector<std::pair<int32_t, int32_t>> big;
+        for (int32_t v = 0; v < N; ++v) {
+            const uint64_t b = off[v], m = off[(size_t)v + 1] - b;
+            if (m > 16) {              // (an HBV vertex has at most four edges a side; any other snk_hbv still sorts in n log n)
+                big.resize(m);
+                for (uint64_t i = 0; i < m; ++i) big[i] = {ov[b + i], oe[b + i]};
+                std::stable_sort(big.begin(), big.end(), [](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) { return x.first < y.first; });
+                for (uint64_t i = 0; i < m; ++i) { ov[b + i] = big[i].first; oe[b + i] = big[i].second; }
+                continue;
+            }
+            for (uint64_t i = off[v] + 1; i < off[(size_t)v + 1]; ++i) {
+                const int32_t kv = ov[i], ke = oe[i];
+                uint64_t j = i;
+                for (; j > off[v] && ov[j - 1] > kv; --j) { ov[j] = ov[j - 1]; oe[j] = oe[j - 1]; }
+                ov[j] = kv;
+                oe[j] = ke;
+            }
+        }
+    };
+    one_side(h->v_left, h->v_right, out->from_off, out->from_v, out->from_e);
+    one_side(h->v_right, h->v_left, out->to_off, out->to_v, out->to_e);
+    return SNK_OK;
+}
+
+uint64_t snk_hbv_edge_image(const snk_hbv* h, int32_t e, const uint64_t* off, const uint8_t* bases, std::vector<uint8_t>& buf) {
+    const uint64_t u = (uint64_t)h->src_unitig[e], len = off[u + 1] - off[u];
+    buf.clear();
+    if (len > 0xFFFFFFFFull) return len;
+    const uint8_t* b = bases + off[u];
+    buf.assign((len + 3) / 4, 0);
+    if (!h->is_rc[e]) for (uint64_t j = 0; j < len; ++j) buf[j >> 2] |= (uint8_t)((b[j] & 3u) << (2 * (j & 3)));
+    else for (uint64_t j = 0; j < len; ++j) buf[j >> 2] |= (uint8_t)(((b[len - 1 - j] & 3u) ^ 3u) << (2 * (j & 3)));
+    return len;
+}
+
 static int write_hbv_impl(const char* path_hbv, const char* path_inv, uint32_t K, uint64_t U, const uint64_t* off, const uint8_t* bases,
                           const snk_hbv* h, char* err, size_t errcap) {
     const int32_t N = h->n_vertices, E = h->n_edges;
-    std::vector<std::vector<std::pair<int32_t, int32_t>>> from(N), to(N);      // (other vertex, edge)
-    for (int32_t e = 0; e < E; ++e) {
-        const int32_t v = h->v_left[e], w = h->v_right[e];
-        if (v < 0 || w < 0 || v >= N || w >= N || h->src_unitig[e] < 0 || (uint64_t)h->src_unitig[e] >= U)
-            return snk_fail(SNK_E_ARG, err, errcap, "snk_write_hbv: edge %d is out of range", e);
-        from[v].push_back({w, e});
-        to[w].push_back({v, e});
-    }
-    for (auto& l : from) std::stable_sort(l.begin(), l.end(), [](const std::pair<int32_t, int32_t>& a, const std::pair<int32_t, int32_t>& b) { return a.first < b.first; });
-    for (auto& l : to) std::stable_sort(l.begin(), l.end(), [](const std::pair<int32_t, int32_t>& a, const std::pair<int32_t, int32_t>& b) { return a.first < b.first; });
+    for (int32_t e = 0; e < E; ++e)
+        if (h->src_unitig[e] < 0 || (uint64_t)h->src_unitig[e] >= U) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_hbv: edge %d is out of range", e);
+    snk_hbv_lists ls;
+    int lrc = snk_hbv_lists_build(h, &ls, "snk_write_hbv", err, errcap);
+    if (lrc) return lrc;
     FILE* f = fopen(path_hbv, "wb");
     if (!f) return snk_fail(SNK_E_IO, err, errcap, "snk_write_hbv: cannot open %s", path_hbv);
     bool ok = fwrite("BINWRITE", 1, 8, f) == 8;
     const int32_t k32 = (int32_t)K;
     ok = ok && fwrite(&k32, 4, 1, f) == 1;
-    auto put_lists = [&](const std::vector<std::vector<std::pair<int32_t, int32_t>>>& ls, bool second) {
-        const uint64_t n = ls.size();
+    auto put_lists = [&](const std::vector<uint64_t>& loff, const std::vector<int32_t>& vals) {
+        const uint64_t n = (uint64_t)N;
         ok = ok && fwrite(&n, 8, 1, f) == 1;
-        std::vector<int32_t> tmp;
-        for (const auto& l : ls) {
-            const uint64_t m = l.size();
-            tmp.resize(m);
-            for (uint64_t i = 0; i < m; ++i) tmp[i] = second ? l[i].second : l[i].first;
-            ok = ok && fwrite(&m, 8, 1, f) == 1 && (m == 0 || fwrite(tmp.data(), 4, m, f) == m);
+        for (int32_t v = 0; v < N; ++v) {
+            const uint64_t m = loff[(size_t)v + 1] - loff[v];
+            ok = ok && fwrite(&m, 8, 1, f) == 1 && (m == 0 || fwrite(vals.data() + loff[v], 4, m, f) == m);
         }
     };
-    put_lists(from, false);
-    put_lists(from, true);
-    put_lists(to, true);
+    put_lists(ls.from_off, ls.from_v);
+    put_lists(ls.from_off, ls.from_e);
+    put_lists(ls.to_off, ls.to_e);
     const uint64_t e64 = (uint64_t)E;
     ok = ok && fwrite(&e64, 8, 1, f) == 1;
     std::vector<uint8_t> buf;
     for (int32_t e = 0; ok && e < E; ++e) {
-        const uint64_t u = (uint64_t)h->src_unitig[e], len64 = off[u + 1] - off[u];
+        const uint64_t len64 = snk_hbv_edge_image(h, e, off, bases, buf);
         if (len64 > 0xFFFFFFFFull) { fclose(f); return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_write_hbv: edge longer than 2^32 bases"); }
         const uint32_t len = (uint32_t)len64;
-        const uint8_t* b = bases + off[u];
-        buf.assign((len + 3) / 4, 0);
-        if (!h->is_rc[e]) for (uint32_t j = 0; j < len; ++j) buf[j >> 2] |= (uint8_t)((b[j] & 3u) << (2 * (j & 3)));
-        else for (uint32_t j = 0; j < len; ++j) buf[j >> 2] |= (uint8_t)(((b[len - 1 - j] & 3u) ^ 3u) << (2 * (j & 3)));
         ok = fwrite(&len, 4, 1, f) == 1 && (buf.empty() || fwrite(buf.data(), 1, buf.size(), f) == buf.size());
     }
     if (fclose(f) != 0) ok = false;

@@ -133,7 +133,7 @@ class Result:
         return out
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
-                   paths_index=False):
+                   paths_index=False, pathsx=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -145,7 +145,10 @@ class Result:
         info['retries']: the lists that overflowed and were regrown (snk_dev_paths.retries: 1 redo list, 2 path edges, 4 barcode keys).
         paths_index: writePathsIndex over these paths (10X/PathsIndex.cc:23-145; snk_dev_paths_index) -> info['paths_index'] = (off u64[E+1],
         ids u64[...]): the reads of HBV edge e are ids[off[e]:off[e+1]], ascending, a read as often as its path holds e; info['countsb'] =
-        i32[E] read support, an edge and its reverse complement summed; info['inv'] = the involution; info['pidx'] = counters and time."""
+        i32[E] read support, an edge and its reverse complement summed; info['inv'] = the involution; info['pidx'] = counters and time.
+        pathsx: the paths as a ReadPathVecX (10X/DF.cc:579; snk_dev_paths_zip) -> info['pathsx'] = (index i64[ceil(n / 10)], data u8[...]):
+        per read its edge count, int16 offset, first edge and 2-bit branch ids; info['pathsx_stats'] = sizes, counters and time (download=False:
+        info['pathsx_dev'] = the SnkDevPathsx itself, valid until the engine's next count_graph or path_reads)."""
         e = self._e
         h = _lib.SnkHbv()
         ms = C.c_float(0)
@@ -194,6 +197,15 @@ class Result:
                 if download:
                     pidx_arrays = (self._dl(px.index_off, (ne_hbv + 1) * 8, np.uint64, (ne_hbv + 1,)), self._dl(px.index_ids, nent * 8, np.uint64, (nent,)),
                                    self._dl(px.counts, ne_hbv * 4, np.int32, (ne_hbv,)), inv[:ne_hbv].copy())
+            px_stats = None
+            if pathsx:
+                zx = _lib.SnkDevPathsx()
+                rc = e.lib.snk_dev_paths_zip(e._ctx, C.byref(out), C.byref(h), C.byref(zx), e._stream(), err, 512)
+                if rc:
+                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+                px_stats = _pathsx_stats(zx)
+                if download:
+                    px_arrays = (self._dl(zx.index, int(zx.n_index) * 8, np.int64, (int(zx.n_index),)), self._dl(zx.data, int(zx.n_bytes), np.uint8, (int(zx.n_bytes),)))
         finally:
             e.lib.snk_hbv_free(C.byref(h))
         n, tot = int(out.n_reads), int(out.n_edges_total)
@@ -205,6 +217,8 @@ class Result:
                 info["dups"] = {k: v for k, v in dups.items() if k != "dup"}
             if pidx is not None:
                 info["pidx"] = pidx
+            if px_stats is not None:
+                info["pathsx_stats"], info["pathsx_dev"] = px_stats, zx     # (zx: device memory of the context, for Engine.unzip_paths)
             return None, None, None, info
         off = self._dl(out.offset, n * 4, np.int32, (n,))
         ne = self._dl(out.n_edges, n * 4, np.uint32, (n,))
@@ -215,6 +229,8 @@ class Result:
             info["dups"] = dups
         if pidx is not None:
             info["pidx"], info["paths_index"], info["countsb"], info["inv"] = pidx, pidx_arrays[:2], pidx_arrays[2], pidx_arrays[3]
+        if px_stats is not None:
+            info["pathsx"], info["pathsx_stats"] = px_arrays, px_stats
         if unitig_bcs and out.unitig_bc_off:
             nb = int(out.n_unitig_bcs)
             info["unitig_bcs"] = (self._dl(out.unitig_bc_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,)),
@@ -240,6 +256,11 @@ class Result:
         us = [asc[int(off[i]):int(off[i + 1])] for i in range(self.n_unitigs)]
         us.sort(key=lambda s: (-len(s), s))
         return us
+
+
+def _pathsx_stats(zx: "_lib.SnkDevPathsx") -> dict:
+    return dict(n_reads=int(zx.n_reads), n_bytes=int(zx.n_bytes), n_index=int(zx.n_index), n_empty=int(zx.n_empty),
+                n_steps_not_found=int(zx.n_steps_not_found), n_offsets_wrapped=int(zx.n_offsets_wrapped), ms=float(zx.ms))
 
 
 import weakref as _weakref
@@ -350,6 +371,59 @@ class Engine:
 
     def _download(self, dptr, hptr, nbytes):
         _lib.check(self.lib.snk_dev_download(self._ctx, dptr, hptr, nbytes, self._stream()))
+
+    # ---- compressed read paths (ReadPathVecX) from and to device-resident paths
+    def zip_paths(self, h: "_lib.SnkHbv", offset: torch.Tensor, n_edges: torch.Tensor, edges: torch.Tensor, start: torch.Tensor | None = None,
+                  download: bool = True):
+        """snk_dev_paths_zip over paths held in torch tensors on this engine's device: offset i32[n], n_edges i32[n] (read as u32), edges
+        i32[sum], start i64[n + 1] (None: the paths follow each other), on the graph h (graphio.hbv_handle).  -> (index i64[], data u8[],
+        stats) on the host, or with download=False (SnkDevPathsx, stats): device memory of the context, valid until its next top-level call."""
+        n = int(n_edges.shape[0])
+        if start is None:
+            start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
+            start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
+        p = _lib.SnkDevPaths()
+        p.n_reads, p.n_edges_total = n, int(edges.shape[0])
+        p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
+        zx = _lib.SnkDevPathsx()
+        err = C.create_string_buffer(512)
+        rc = self.lib.snk_dev_paths_zip(self._ctx, C.byref(p), C.byref(h), C.byref(zx), self._stream(), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        stats = _pathsx_stats(zx)
+        if not download:
+            return zx, stats
+        index = np.empty(int(zx.n_index), np.int64)
+        data = np.empty(int(zx.n_bytes), np.uint8)
+        if index.size:
+            self._download(zx.index, index.ctypes.data, index.nbytes)
+        if data.size:
+            self._download(zx.data, data.ctypes.data, data.nbytes)
+        return index, data, stats
+
+    def unzip_paths(self, h: "_lib.SnkHbv", index, data=None, n_reads: int | None = None, download: bool = True):
+        """snk_dev_paths_unzip: a ReadPathVecX on the device -- index i64[] and data u8[] as torch tensors with n_reads, or the SnkDevPathsx
+        of zip_paths(download=False) -- back into paths on the graph h.  -> (offset i32[n], n_edges u32[n], edges i32[sum], ms) on the
+        host; download=False: (SnkDevPaths, ms)."""
+        if isinstance(index, _lib.SnkDevPathsx):
+            zx = index
+        else:
+            zx = _lib.SnkDevPathsx()
+            zx.n_reads, zx.n_bytes, zx.n_index = int(n_reads), int(data.shape[0]), int(index.shape[0])
+            zx.data, zx.index = data.data_ptr(), index.data_ptr()
+        out = _lib.SnkDevPaths()
+        err = C.create_string_buffer(512)
+        rc = self.lib.snk_dev_paths_unzip(self._ctx, C.byref(zx), C.byref(h), C.byref(out), self._stream(), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        if not download:
+            return out, float(out.path_ms)
+        n, tot = int(out.n_reads), int(out.n_edges_total)
+        off, ne, edges = np.empty(n, np.int32), np.empty(n, np.uint32), np.empty(tot, np.int32)
+        for a, ptr in ((off, out.offset), (ne, out.n_edges), (edges, out.edges)):
+            if a.size:
+                self._download(ptr, a.ctypes.data, a.nbytes)
+        return off, ne, edges, float(out.path_ms)
 
     # ---- synthetic reads straight into HBM
     def synth(self, sp: _lib.SnkSynthParams, first: int = 0, n: int | None = None, qstride: int | None = None):

@@ -6,9 +6,13 @@
   write_hbv            a.hbv / a.inv as DF keeps the graph (paths/HyperBasevector.cc:121-125)
   write_paths, write_paths_index, write_dup, write_a48
                        the rest of a.48/: a.paths, a.paths.inv, a.countsb, a.dup (10X/DF.cc:584-600, 10X/PathsIndex.cc:23-145)
+  write_pathsx / read_pathsx, write_hbx
+                       the compressed forms DF goes on working from: a.pathsX (10X/paths/ReadPathVecX.cc:976-996) and a.hbx
+                       (paths/HyperBasevector.cc:133-137); write_a48 adds them when the result holds 'pathsx'
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -82,6 +86,21 @@ def hbv_from_unitigs(K: int, off: np.ndarray, bases: np.ndarray) -> dict:
     return out
 
 
+@contextlib.contextmanager
+def hbv_handle(K: int, off: np.ndarray, bases: np.ndarray):
+    """The snk_hbv of unitigs in BVComp order as the C struct (lib.SnkHbv) the device calls take -- Engine.zip_paths / unzip_paths --
+    freed when the block ends."""
+    lib = _lib.load()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    h = _lib.SnkHbv()
+    _call(lib.snk_hbv_from_unitigs, K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h))
+    try:
+        yield h
+    finally:
+        lib.snk_hbv_free(C.byref(h))
+
+
 def write_hbv(path_hbv, path_inv, K: int, off: np.ndarray, bases: np.ndarray) -> np.ndarray:
     """Unitigs in BVComp order -> a.hbv (+ a.inv) as DF writes them; returns the involution."""
     lib = _lib.load()
@@ -145,10 +164,50 @@ def write_dup(path, dup: np.ndarray) -> None:
     _call(_lib.load().snk_write_dup, str(path).encode(), len(dup), dup.ctypes.data)
 
 
+def write_pathsx(path, index: np.ndarray, data: np.ndarray, n_reads: int) -> None:
+    """a.pathsX (ReadPathVecX::writeBinary, 10X/paths/ReadPathVecX.cc:976-996) from what snk_dev_paths_zip made: index i64[ceil(n_reads / 10)] =
+    the byte offset of every 10th read's record, data u8[...] = the records."""
+    index = np.ascontiguousarray(index, dtype=np.int64)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    _call(_lib.load().snk_write_pathsx, str(path).encode(), int(n_reads), index.ctypes.data, len(index), data.ctypes.data, len(data))
+
+
+def read_pathsx(path):
+    """a.pathsX -> (index i64[], data u8[], n_reads)."""
+    lib = _lib.load()
+    n, ni, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    pi = C.POINTER(C.c_int64)()
+    pd = C.POINTER(C.c_uint8)()
+    _call(lib.snk_read_pathsx, str(path).encode(), C.byref(n), C.byref(ni), C.byref(pi), C.byref(nb), C.byref(pd))
+    try:
+        index = np.ctypeslib.as_array(pi, shape=(ni.value,)).copy() if ni.value else np.zeros(0, np.int64)
+        data = np.ctypeslib.as_array(pd, shape=(nb.value,)).copy() if nb.value else np.zeros(0, np.uint8)
+    finally:
+        lib.snk_host_free(pi)
+        lib.snk_host_free(pd)
+    return index, data, int(n.value)
+
+
+def write_hbx(path, K: int, off: np.ndarray, bases: np.ndarray) -> None:
+    """Unitigs in BVComp order -> a.hbx, the HyperBasevectorX of the graph a.hbv holds (10X/DF.cc:573-576)."""
+    lib = _lib.load()
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    h = _lib.SnkHbv()
+    nu = len(off) - 1
+    _call(lib.snk_hbv_from_unitigs, K, nu, off.ctypes.data, bases.ctypes.data, C.byref(h))
+    try:
+        _call(lib.snk_write_hbx, str(path).encode(), K, nu, off.ctypes.data, bases.ctypes.data, C.byref(h))
+    finally:
+        lib.snk_hbv_free(C.byref(h))
+
+
 def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.ndarray, path_n_edges: np.ndarray, path_edges: np.ndarray, info: dict) -> np.ndarray:
     """The six files DF leaves in a.<K>/ after StageBuildGraph (10X/DF.cc:564-601) from one result: a.hbv, a.inv (the unitigs in BVComp
     order: graphio.unitigs_to_arrays(res.unitigs())), a.paths (what res.path_reads returned), a.paths.inv, a.countsb (info['paths_index'],
-    info['countsb']: path_reads(..., paths_index=True)) and a.dup (info['dups']['dup']: mark_dups=True).  Returns the involution."""
+    info['countsb']: path_reads(..., paths_index=True)) and a.dup (info['dups']['dup']: mark_dups=True).  With info['pathsx']
+    (path_reads(..., pathsx=True)) also a.hbx and a.pathsX, the two other files a DF entered at START=patch opens (10X/DF.cc:612-630).
+    Returns the involution."""
     from pathlib import Path
     d = Path(dir)
     d.mkdir(parents=True, exist_ok=True)
@@ -162,6 +221,9 @@ def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.n
     write_paths(d / "a.paths", path_offset, path_n_edges, path_edges)
     write_paths_index(d / "a.paths.inv", d / "a.countsb", info["paths_index"][0], info["paths_index"][1], info["countsb"])
     write_dup(d / "a.dup", info["dups"]["dup"])
+    if "pathsx" in info:
+        write_hbx(d / "a.hbx", K, off, bases)
+        write_pathsx(d / "a.pathsX", info["pathsx"][0], info["pathsx"][1], len(path_n_edges))
     return inv
 
 

@@ -93,6 +93,12 @@ class SnkDevPidx(C.Structure):
                 ("reserved", C.c_uint64 * 6)]
 
 
+class SnkDevPathsx(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("n_bytes", C.c_uint64), ("n_index", C.c_uint64), ("data", C.c_void_p), ("index", C.c_void_p),
+                ("n_empty", C.c_uint64), ("n_steps_not_found", C.c_uint64), ("n_offsets_wrapped", C.c_uint64), ("ms", C.c_float),
+                ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 6)]
+
+
 class SnkFasthBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("first_pair", C.c_uint64), ("file", C.c_uint32), ("max_len", C.c_uint32),
                 ("ascii", C.c_void_p), ("quals", C.c_void_p), ("lens", C.c_void_p), ("bc_fields", C.c_void_p),
@@ -252,6 +258,11 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_path_reads2": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), u32, P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_mark_dups": (C.c_int, [vp, P(SnkDevReads), P(SnkDevPaths), P(SnkDevDups), vp, cp, sz]),
         "snk_dev_paths_index": (C.c_int, [vp, P(SnkDevPaths), u64, vp, P(SnkDevPidx), vp, cp, sz]),
+        "snk_dev_paths_zip": (C.c_int, [vp, P(SnkDevPaths), P(SnkHbv), P(SnkDevPathsx), vp, cp, sz]),
+        "snk_dev_paths_unzip": (C.c_int, [vp, P(SnkDevPathsx), P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
+        "snk_write_pathsx": (C.c_int, [cp, u64, vp, u64, vp, u64, cp, sz]),
+        "snk_read_pathsx": (C.c_int, [cp, P(u64), P(u64), P(P(C.c_int64)), P(u64), P(P(C.c_uint8)), cp, sz]),
+        "snk_write_hbx": (C.c_int, [cp, u32, u64, vp, vp, P(SnkHbv), cp, sz]),
         "snk_write_paths": (C.c_int, [cp, u64, vp, vp, vp, vp, cp, sz]),
         "snk_write_paths_index": (C.c_int, [cp, cp, u64, vp, vp, vp, cp, sz]),
         "snk_write_dup": (C.c_int, [cp, u64, vp, cp, sz]),
