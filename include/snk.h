@@ -446,6 +446,10 @@ typedef struct snk_hbv {
 } snk_hbv;
 int snk_hbv_from_unitigs(uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases,
                          snk_hbv* out, char* err, size_t errcap);
+/* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
+ * snk_dev_paths_zip, snk_dev_paths_unzip and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
+ * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
 int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
                 snk_hbv* out, float* device_ms, void* stream, char* err, size_t errcap);

@@ -20,7 +20,7 @@
 //   final   per entry: visit marks, recount and shadow against the stored count and context
 #include <algorithm>
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 
 namespace {
 
@@ -531,111 +531,98 @@ extern "C" int snk_dev_check_graph(snk_ctx* ctx, const snk_check_input* in, cons
             return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_check_graph: reads need rows, quals or good_len, read_len <= 16 * row_words");
         if (grouped && !reads->group) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_check_graph: grouped reads without group ids");
     }
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-
     // scratch after the arrays under test, handed back on return: the result being checked stays valid
-    const uint64_t mark = ctx->alloc_serial;
-    uint64_t bytes = 0;
-    struct guard {
-        snk_ctx* c; uint64_t m;
-        ~guard() { snk_ctx_release_since(c, m, nullptr, 0); }
-    } g{ctx, mark};
-    auto alloc = [&](size_t nb, void** p) {
-        nb = std::max<size_t>(nb, 256);
-        bytes += nb;
-        return snk_ctx_alloc(ctx, nb, p, err, errcap);
-    };
-    int rc;
-    ck_acc* acc = nullptr;
-    if ((rc = alloc(sizeof(ck_acc), (void**)&acc))) return rc;
-    SNK_HIP_TRY(hipMemsetAsync(acc, 0, sizeof(ck_acc), st));
-    SNK_HIP_TRY(hipMemsetAsync(acc->first, 0xFF, sizeof(acc->first), st));
+    const int rc = snk_call_run(ctx, stream, "snk_dev_check_graph", out, err, errcap, [&](snk_call& c) -> int {
+        const hipStream_t st = c.st;
+        int rc;
+        ck_acc* acc = nullptr;
+        if ((rc = c.alloc(1, &acc))) return rc;
+        SNK_HIP_TRY(hipMemsetAsync(acc, 0, sizeof(ck_acc), st));
+        SNK_HIP_TRY(hipMemsetAsync(acc->first, 0xFF, sizeof(acc->first), st));
 
-    ck_args a{};
-    a.t.keys = (const uint64_t*)in->keys;
-    a.t.counts = (const uint32_t*)in->counts;
-    a.t.ctx = (const uint8_t*)in->ctx;
-    a.t.n = in->n_kmers;
-    a.t.K = K;
-    a.t.sh = 128 - 2 * K;
-    a.flags = flags;
-    a.min_freq = in->min_freq;
-    a.grouped = grouped;
-    a.pad_mask_lo = grouped ? 0u : (uint32_t)((1ull << a.t.sh) - 1);
-    a.t.kmask = grouped ? ~0xFFFFFFFFull : ~0ull;
-    a.n_unitigs = in->n_unitigs;
-    a.off = (const uint64_t*)in->unitig_off;
-    a.bases = (const uint8_t*)in->unitig_bases;
-    a.ugroup = grouped ? (const uint32_t*)in->unitig_group : nullptr;
-    a.acc = acc;
-    uint64_t total = 0;
-    if (in->n_unitigs) {
-        SNK_HIP_TRY(hipMemcpyAsync(&total, a.off + in->n_unitigs, 8, hipMemcpyDeviceToHost, st));
+        ck_args a{};
+        a.t.keys = (const uint64_t*)in->keys;
+        a.t.counts = (const uint32_t*)in->counts;
+        a.t.ctx = (const uint8_t*)in->ctx;
+        a.t.n = in->n_kmers;
+        a.t.K = K;
+        a.t.sh = 128 - 2 * K;
+        a.flags = flags;
+        a.min_freq = in->min_freq;
+        a.grouped = grouped;
+        a.pad_mask_lo = grouped ? 0u : (uint32_t)((1ull << a.t.sh) - 1);
+        a.t.kmask = grouped ? ~0xFFFFFFFFull : ~0ull;
+        a.n_unitigs = in->n_unitigs;
+        a.off = (const uint64_t*)in->unitig_off;
+        a.bases = (const uint8_t*)in->unitig_bases;
+        a.ugroup = grouped ? (const uint32_t*)in->unitig_group : nullptr;
+        a.acc = acc;
+        uint64_t total = 0;
+        if (in->n_unitigs) {
+            SNK_HIP_TRY(hipMemcpyAsync(&total, a.off + in->n_unitigs, 8, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(snk_sync(st));
+        }
+        a.total_bases = total;
+        const bool do_reads = reads && !digest_only && reads->n_reads;
+
+        SNK_HIP_TRY(c.stamp());
+        if (!digest_only) {
+            a.t.cap = std::max<uint64_t>(2 * a.t.n + 1, 64);     // load <= 0.5
+            uint32_t* slots = nullptr;
+            if ((rc = c.alloc(a.t.cap, &slots)) || (rc = c.alloc((a.t.n + 15) / 16, &a.vis))) return rc;
+            SNK_HIP_TRY(hipMemsetAsync(slots, 0xFF, a.t.cap * 4, st));
+            SNK_HIP_TRY(hipMemsetAsync(a.vis, 0, (a.t.n + 15) / 16 * 4, st));
+            a.t.slots = slots;
+        }
+        if (a.t.n) SNK_HIP_TRY(snk_launch(ck_table_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a, digest_only ? 0 : 1));
+        if (a.n_unitigs) SNK_HIP_TRY(snk_launch(ck_unitig_kernel, snk_blocks_capped(a.n_unitigs, CB / 64, CK_GRID_CAP), CB, 0, st, a, digest_only ? 1 : 0));
+        if (!digest_only) {
+            if (a.t.n) SNK_HIP_TRY(snk_launch(ck_ctx_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a));
+            if (a.n_unitigs && total) SNK_HIP_TRY(snk_launch(ck_pos_kernel, snk_blocks_capped(snk_blocks(total, CK_SEG), CB, CK_GRID_CAP), CB, 0, st, a));
+        }
+        SNK_HIP_TRY(c.stamp());
+        if (do_reads) {
+            if ((rc = c.alloc(a.t.n, &a.recount)) || (rc = c.alloc((a.t.n + 3) / 4, &a.shadow))) return rc;
+            SNK_HIP_TRY(hipMemsetAsync(a.recount, 0, std::max<uint64_t>(a.t.n * 4, 4), st));
+            SNK_HIP_TRY(hipMemsetAsync(a.shadow, 0, std::max<uint64_t>((a.t.n + 3) / 4 * 4, 4), st));
+            ck_reads r{};
+            r.rows = (const uint32_t*)reads->rows;
+            r.lens = (const uint16_t*)reads->lens;
+            r.quals = (const uint8_t*)reads->quals;
+            r.good_len = (const uint16_t*)reads->good_len;
+            r.group = grouped ? (const uint32_t*)reads->group : nullptr;
+            r.n = reads->n_reads;
+            r.row_words = reads->row_words;
+            r.read_len = reads->read_len;
+            r.qstride = reads->qstride;
+            r.min_qual = in->min_qual ? in->min_qual : 7;
+            SNK_HIP_TRY(snk_launch(ck_reads_kernel, snk_blocks_capped(r.n, CB, CK_GRID_CAP), CB, 0, st, a, r));
+        }
+        if (!digest_only && a.t.n) SNK_HIP_TRY(snk_launch(ck_final_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a, do_reads ? 1 : 0, in->min_freq > 1 ? 1 : 0));
+        SNK_HIP_TRY(c.stamp());
+        ck_acc h;
+        SNK_HIP_TRY(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
-    }
-    a.total_bases = total;
-    const bool do_reads = reads && !digest_only && reads->n_reads;
 
-    hipEvent_t ev[3];
-    for (auto& e : ev) SNK_HIP_TRY(hipEventCreate(&e));
-    struct evguard { hipEvent_t* e; ~evguard() { for (int i = 0; i < 3; ++i) (void)hipEventDestroy(e[i]); } } eg{ev};
-    SNK_HIP_TRY(hipEventRecord(ev[0], st));
-    if (!digest_only) {
-        a.t.cap = std::max<uint64_t>(2 * a.t.n + 1, 64);     // load <= 0.5
-        uint32_t* slots = nullptr;
-        if ((rc = alloc(a.t.cap * 4, (void**)&slots)) || (rc = alloc((a.t.n + 15) / 16 * 4, (void**)&a.vis))) return rc;
-        SNK_HIP_TRY(hipMemsetAsync(slots, 0xFF, a.t.cap * 4, st));
-        SNK_HIP_TRY(hipMemsetAsync(a.vis, 0, (a.t.n + 15) / 16 * 4, st));
-        a.t.slots = slots;
-    }
-    if (a.t.n) SNK_HIP_TRY(snk_launch(ck_table_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a, digest_only ? 0 : 1));
-    if (a.n_unitigs) SNK_HIP_TRY(snk_launch(ck_unitig_kernel, snk_blocks_capped(a.n_unitigs, CB / 64, CK_GRID_CAP), CB, 0, st, a, digest_only ? 1 : 0));
-    if (!digest_only) {
-        if (a.t.n) SNK_HIP_TRY(snk_launch(ck_ctx_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a));
-        if (a.n_unitigs && total) SNK_HIP_TRY(snk_launch(ck_pos_kernel, snk_blocks_capped(snk_blocks(total, CK_SEG), CB, CK_GRID_CAP), CB, 0, st, a));
-    }
-    SNK_HIP_TRY(hipEventRecord(ev[1], st));
-    if (do_reads) {
-        if ((rc = alloc(a.t.n * 4, (void**)&a.recount)) || (rc = alloc((a.t.n + 3) / 4 * 4, (void**)&a.shadow))) return rc;
-        SNK_HIP_TRY(hipMemsetAsync(a.recount, 0, std::max<uint64_t>(a.t.n * 4, 4), st));
-        SNK_HIP_TRY(hipMemsetAsync(a.shadow, 0, std::max<uint64_t>((a.t.n + 3) / 4 * 4, 4), st));
-        ck_reads r{};
-        r.rows = (const uint32_t*)reads->rows;
-        r.lens = (const uint16_t*)reads->lens;
-        r.quals = (const uint8_t*)reads->quals;
-        r.good_len = (const uint16_t*)reads->good_len;
-        r.group = grouped ? (const uint32_t*)reads->group : nullptr;
-        r.n = reads->n_reads;
-        r.row_words = reads->row_words;
-        r.read_len = reads->read_len;
-        r.qstride = reads->qstride;
-        r.min_qual = in->min_qual ? in->min_qual : 7;
-        SNK_HIP_TRY(snk_launch(ck_reads_kernel, snk_blocks_capped(r.n, CB, CK_GRID_CAP), CB, 0, st, a, r));
-    }
-    if (!digest_only && a.t.n) SNK_HIP_TRY(snk_launch(ck_final_kernel, snk_blocks_capped(a.t.n, CB, CK_GRID_CAP), CB, 0, st, a, do_reads ? 1 : 0, in->min_freq > 1 ? 1 : 0));
-    SNK_HIP_TRY(hipEventRecord(ev[2], st));
-    ck_acc h;
-    SNK_HIP_TRY(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-
-    for (int i = 0; i < SNK_CHECK_N_COUNTERS; ++i) {
-        out->count[i] = h.count[i];
-        out->first[i] = h.first[i];
-    }
-    if (do_reads && in->n_instances && h.n_instances != in->n_instances) { out->count[C_INST_MM] = 1; out->first[C_INST_MM] = 0; }
-    out->levels = digest_only ? 0u : (1u | (do_reads ? 2u : 0u));
-    out->n_kmers = in->n_kmers;
-    out->n_unitigs = in->n_unitigs;
-    out->n_bases = total;
-    out->n_circles = h.n_circles;
-    out->n_palindromes = h.n_palindromes;
-    out->n_instances = h.n_instances;
-    out->table_digest = h.table_digest;
-    out->unitig_digest = h.unitig_digest;
-    out->peak_bytes = bytes;
-    SNK_HIP_TRY(hipEventElapsedTime(&out->graph_ms, ev[0], ev[1]));
-    SNK_HIP_TRY(hipEventElapsedTime(&out->reads_ms, ev[1], ev[2]));
-    return SNK_OK;
+        for (int i = 0; i < SNK_CHECK_N_COUNTERS; ++i) {
+            out->count[i] = h.count[i];
+            out->first[i] = h.first[i];
+        }
+        if (do_reads && in->n_instances && h.n_instances != in->n_instances) { out->count[C_INST_MM] = 1; out->first[C_INST_MM] = 0; }
+        out->levels = digest_only ? 0u : (1u | (do_reads ? 2u : 0u));
+        out->n_kmers = in->n_kmers;
+        out->n_unitigs = in->n_unitigs;
+        out->n_bases = total;
+        out->n_circles = h.n_circles;
+        out->n_palindromes = h.n_palindromes;
+        out->n_instances = h.n_instances;
+        out->table_digest = h.table_digest;
+        out->unitig_digest = h.unitig_digest;
+        out->peak_bytes = c.bytes;
+        out->graph_ms = c.ms(0, 1);
+        out->reads_ms = c.ms(1, 2);
+        return c.end(SNK_OK);
+    });
+    out->struct_size = struct_size;
+    return rc;
 }

@@ -17,20 +17,12 @@
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_stages.h"
 #include "snk_common.h"
 
 
 namespace {
-
-template <typename T>
-int dev(snk_ctx* ctx, size_t n, T** out, char* err, size_t errcap) {
-    void* q = nullptr;
-    int rc = snk_ctx_alloc(ctx, (n ? n : 1) * sizeof(T) + 16, &q, err, errcap);
-    *out = (T*)q;
-    return rc;
-}
 
 struct dup_in {
     const uint32_t* rows; uint32_t row_words, read_len;
@@ -213,119 +205,96 @@ __global__ void __launch_bounds__(256) dup_count_kernel(const uint8_t* __restric
 
 }  // namespace
 
-static int mark_dups_impl(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_paths* paths, snk_dev_dups* out, void* stream, char* err, size_t errcap);
-
 extern "C" int snk_dev_mark_dups(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_paths* paths, snk_dev_dups* out, void* stream, char* err, size_t errcap) {
     if (!ctx || !in || !paths || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_mark_dups: NULL argument");
-    // sort keys, group heads, quality sums (~35 B per read + the sort's own scratch) go back to the arena with the call; the
-    // duplicate flags stay until the context's next snk_dev_count_graph / snk_shard_step
-    const uint64_t mark = ctx->alloc_serial;
-    const int rc = mark_dups_impl(ctx, in, paths, out, stream, err, errcap);
-    (void)hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream);
-    const void* keep[1] = {out->dup};
-    snk_ctx_release_since(ctx, mark, keep, rc ? 0 : 1);
-    if (rc) memset(out, 0, sizeof *out);
-    return rc;
-}
-
-static int mark_dups_impl(snk_ctx* ctx, const snk_dev_reads* in, const snk_dev_paths* paths, snk_dev_dups* out, void* stream, char* err, size_t errcap) {
+    memset(out, 0, sizeof *out);
     const uint64_t n = in->n_reads;
     if (n != paths->n_reads) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_mark_dups: %llu reads, paths of %llu", (unsigned long long)n, (unsigned long long)paths->n_reads);
     if (n & 1ull) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_mark_dups: reads come in pairs (2q, 2q+1); got an odd number");
     if (n >= (1ull << 32)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_mark_dups: more than 2^32 reads in one call");
     if (n && (!in->rows || !in->quals || in->read_len < 5 || in->row_words * 16 < in->read_len))
         return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_mark_dups: need packed rows and quality rows of reads with at least five bases");
-    memset(out, 0, sizeof *out);
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    hipEvent_t e0, e1;
-    SNK_HIP_TRY(hipEventCreate(&e0)); SNK_HIP_TRY(hipEventCreate(&e1));
-    struct evg { hipEvent_t a, b; ~evg() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } g{e0, e1};
-    SNK_HIP_TRY(hipEventRecord(e0, st));
-    int rc;
-    dup_in a;
-    a.rows = (const uint32_t*)in->rows; a.row_words = in->row_words; a.read_len = in->read_len; a.lens = (const uint16_t*)in->lens;
-    a.quals = (const uint8_t*)in->quals; a.qstride = in->qstride; a.bc = (const int32_t*)in->bc;
-    a.p_off = (const int32_t*)paths->offset; a.p_n = (const uint32_t*)paths->n_edges; a.p_start = (const unsigned long long*)paths->start;
-    a.p_edges = (const int32_t*)paths->edges; a.n = n;
-    unsigned long long *key, *key2, *stat;
-    uint32_t *head, *head2, *id, *id2, *qsum;
-    uint8_t *gstart, *multi, *dup, *art;
-    const uint64_t np = n / 2;
-    if ((rc = dev(ctx, n, &key, err, errcap)) || (rc = dev(ctx, n, &key2, err, errcap)) || (rc = dev(ctx, n, &head, err, errcap)) || (rc = dev(ctx, n, &head2, err, errcap)) ||
-        (rc = dev(ctx, n, &id, err, errcap)) || (rc = dev(ctx, n, &id2, err, errcap)) || (rc = dev(ctx, n, &qsum, err, errcap)) || (rc = dev(ctx, n, &gstart, err, errcap)) ||
-        (rc = dev(ctx, n, &multi, err, errcap)) || (rc = dev(ctx, np, &dup, err, errcap)) || (rc = dev(ctx, np, &art, err, errcap)) || (rc = dev(ctx, 8 + 256, &stat, err, errcap)))
-        return rc;
-    SNK_HIP_TRY(hipMemsetAsync(stat, 0, (8 + 256) * 8, st));
-    SNK_HIP_TRY(hipMemsetAsync(dup, 0, np ? np : 1, st));
-    SNK_HIP_TRY(hipMemsetAsync(art, 0, np ? np : 1, st));
-    unsigned long long h_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t n_placed_total = 0;
-    if (n) {
-        const uint64_t gn = snk_blocks(n, 256);
-        uint32_t* range;
-        if ((rc = dev(ctx, 768, &range, err, errcap))) return rc;
-        SNK_HIP_TRY(hipMemsetAsync(range, 0, 512 * 4, st));
-        SNK_HIP_TRY(hipMemsetAsync(range + 512, 0xFF, 256 * 4, st));
-        SNK_HIP_TRY(snk_launch(dup_key_kernel, gn, 256, 0, st, a, key, head, id, stat + 8, range));
-        unsigned long long h_placed[256];
-        uint32_t h_range[768];
-        SNK_HIP_TRY(hipMemcpyAsync(h_placed, stat + 8, sizeof h_placed, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
+    // sort keys, group heads, quality sums (~35 B per read + the sort's own scratch) go back to the arena with the call; the
+    // duplicate flags stay until the context's next snk_dev_count_graph / snk_shard_step
+    return snk_call_run(ctx, stream, "snk_dev_mark_dups", out, err, errcap, [&](snk_call& c) -> int {
+        const hipStream_t st = c.st;
+        SNK_HIP_TRY(c.stamp());
+        int rc;
+        dup_in a;
+        a.rows = (const uint32_t*)in->rows; a.row_words = in->row_words; a.read_len = in->read_len; a.lens = (const uint16_t*)in->lens;
+        a.quals = (const uint8_t*)in->quals; a.qstride = in->qstride; a.bc = (const int32_t*)in->bc;
+        a.p_off = (const int32_t*)paths->offset; a.p_n = (const uint32_t*)paths->n_edges; a.p_start = (const unsigned long long*)paths->start;
+        a.p_edges = (const int32_t*)paths->edges; a.n = n;
+        unsigned long long *key, *key2, *stat;
+        uint32_t *head, *head2, *id, *id2, *qsum;
+        uint8_t *gstart, *multi, *dup, *art;
+        const uint64_t np = n / 2;
+        if ((rc = c.alloc(n, &key)) || (rc = c.alloc(n, &key2)) || (rc = c.alloc(n, &head)) || (rc = c.alloc(n, &head2)) ||
+            (rc = c.alloc(n, &id)) || (rc = c.alloc(n, &id2)) || (rc = c.alloc(n, &qsum)) || (rc = c.alloc(n, &gstart)) ||
+            (rc = c.alloc(n, &multi)) || (rc = c.alloc(np, &dup)) || (rc = c.alloc(np, &art)) || (rc = c.alloc(8 + 256, &stat)))
+            return rc;
+        SNK_HIP_TRY(hipMemsetAsync(stat, 0, (8 + 256) * 8, st));
+        SNK_HIP_TRY(hipMemsetAsync(dup, 0, np ? np : 1, st));
+        SNK_HIP_TRY(hipMemsetAsync(art, 0, np ? np : 1, st));
+        unsigned long long h_stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        uint64_t n_placed_total = 0;
+        if (n) {
+            const uint64_t gn = snk_blocks(n, 256);
+            uint32_t* range;
+            if ((rc = c.alloc(768, &range))) return rc;
+            SNK_HIP_TRY(hipMemsetAsync(range, 0, 512 * 4, st));
+            SNK_HIP_TRY(hipMemsetAsync(range + 512, 0xFF, 256 * 4, st));
+            SNK_HIP_TRY(snk_launch(dup_key_kernel, gn, 256, 0, st, a, key, head, id, stat + 8, range));
+            unsigned long long h_placed[256];
+            uint32_t h_range[768];
+            SNK_HIP_TRY(hipMemcpyAsync(h_placed, stat + 8, sizeof h_placed, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(snk_sync(st));
+            uint64_t m = 0;                                     // placed reads: the front of the sorted array
+            uint32_t emax = 0, omax = 0, omin = 0xFFFFFFFFu;
+            for (int q = 0; q < 256; ++q) { m += h_placed[q]; emax = std::max(emax, h_range[q]); omax = std::max(omax, h_range[256 + q]); omin = std::min(omin, h_range[512 + q]); }
+            n_placed_total = m;
+            auto bits_of = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
+            const uint32_t ebits = bits_of(emax), obits = m ? bits_of((uint64_t)omax - omin) : 0u, total_bits = ebits + obits + 10u;
+            const unsigned long long* skey;
+            const uint32_t* sid;
+            const bool one_sort = total_bits <= 62 && !snk_opt_u32(ctx, SNK_OPT_dups_two_sorts);
+            if (one_sort) {
+                // the reference's record order (edge, offset, mate head, read id) in ONE stable sort over total_bits + 1 bits (the bench graph: 42)
+                SNK_HIP_TRY(snk_launch(dup_composite_kernel, gn, 256, 0, st, key, head, n, m ? omin : 0u, obits, total_bits));
+                if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, key, key2, id, id2, (size_t)n, 0u, total_bits + 1u, st); }))) return rc;
+                skey = key2; sid = id2;
+            } else {
+                auto by_head = [&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, head, head2, id, id2, (size_t)n, 0u, 10u, st); };     // id2 = ids by (head, id)
+                auto by_key = [&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, key2, key, id2, id, (size_t)n, 0u, 64u, st); };        // key / id = (edge, offset, head, id) order
+                snk_temp t;
+                if ((rc = c.temp(&t, by_head, by_key))) return rc;
+                SNK_HIP_TRY(by_head(t.p, t.bytes));
+                SNK_HIP_TRY(snk_launch(dup_gather_key_kernel, gn, 256, 0, st, id2, key, n, key2));
+                SNK_HIP_TRY(by_key(t.p, t.bytes));
+                skey = key; sid = id;
+            }
+            if (m) {
+                const uint64_t gm = snk_blocks(m, 256);
+                if (one_sort) SNK_HIP_TRY(snk_launch(dup_flag1_kernel, gm, 256, 0, st, skey, m, gstart, multi));
+                else SNK_HIP_TRY(snk_launch(dup_flag_kernel, gm, 256, 0, st, skey, sid, head, m, gstart, multi));
+                SNK_HIP_TRY(snk_launch(dup_qsum_kernel, gm, 256, 0, st, a, sid, multi, m, qsum));
+                SNK_HIP_TRY(snk_launch(dup_group_kernel, gm, 256, 0, st, a, skey, sid, head, gstart, qsum, m, dup, art, stat));
+            }
+            SNK_HIP_TRY(snk_launch(dup_count_kernel, snk_blocks(np, 256), 256, 0, st, dup, art, np, stat));
+            SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, 64, hipMemcpyDeviceToHost, st));
+        }
+        SNK_HIP_TRY(c.stamp());
         SNK_HIP_TRY(snk_sync(st));
-        uint64_t m = 0;                                     // placed reads: the front of the sorted array
-        uint32_t emax = 0, omax = 0, omin = 0xFFFFFFFFu;
-        for (int q = 0; q < 256; ++q) { m += h_placed[q]; emax = std::max(emax, h_range[q]); omax = std::max(omax, h_range[256 + q]); omin = std::min(omin, h_range[512 + q]); }
-        n_placed_total = m;
-        auto bits_of = [](uint64_t v) { uint32_t b = 0; while (v) { ++b; v >>= 1; } return b; };
-        const uint32_t ebits = bits_of(emax), obits = m ? bits_of((uint64_t)omax - omin) : 0u, total_bits = ebits + obits + 10u;
-        const unsigned long long* skey;
-        const uint32_t* sid;
-        const bool one_sort = total_bits <= 62 && !snk_opt_u32(ctx, SNK_OPT_dups_two_sorts);
-        if (one_sort) {
-            // the reference's record order (edge, offset, mate head, read id) in ONE stable sort over total_bits + 1 bits (the bench graph: 42)
-            SNK_HIP_TRY(snk_launch(dup_composite_kernel, gn, 256, 0, st, key, head, n, m ? omin : 0u, obits, total_bits));
-            size_t tb = 0;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, key, key2, id, id2, (size_t)n, 0u, total_bits + 1u, st));
-            uint8_t* tmp;
-            if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, key, key2, id, id2, (size_t)n, 0u, total_bits + 1u, st));
-            skey = key2; sid = id2;
-        } else {
-            size_t tb1 = 0, tb2 = 0;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb1, head, head2, id, id2, (size_t)n, 0u, 10u, st));
-            SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb2, key, key2, id, id2, (size_t)n, 0u, 64u, st));
-            size_t tb = tb1 > tb2 ? tb1 : tb2;
-            uint8_t* tmp;
-            if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-            size_t t = tb;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, t, head, head2, id, id2, (size_t)n, 0u, 10u, st));          // id2 = ids by (head, id)
-            SNK_HIP_TRY(snk_launch(dup_gather_key_kernel, gn, 256, 0, st, id2, key, n, key2));
-            t = tb;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, t, key2, key, id2, id, (size_t)n, 0u, 64u, st));            // key / id = (edge, offset, head, id) order
-            skey = key; sid = id;
-        }
-        if (m) {
-            const uint64_t gm = snk_blocks(m, 256);
-            if (one_sort) SNK_HIP_TRY(snk_launch(dup_flag1_kernel, gm, 256, 0, st, skey, m, gstart, multi));
-            else SNK_HIP_TRY(snk_launch(dup_flag_kernel, gm, 256, 0, st, skey, sid, head, m, gstart, multi));
-            SNK_HIP_TRY(snk_launch(dup_qsum_kernel, gm, 256, 0, st, a, sid, multi, m, qsum));
-            SNK_HIP_TRY(snk_launch(dup_group_kernel, gm, 256, 0, st, a, skey, sid, head, gstart, qsum, m, dup, art, stat));
-        }
-        SNK_HIP_TRY(snk_launch(dup_count_kernel, snk_blocks(np, 256), 256, 0, st, dup, art, np, stat));
-        SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, 64, hipMemcpyDeviceToHost, st));
-    }
-    SNK_HIP_TRY(hipEventRecord(e1, st));
-    SNK_HIP_TRY(snk_sync(st));
-    out->n_pairs = np;
-    out->dup = dup;
-    out->n_dup_reads = h_stat[0];
-    out->n_interdup_reads = h_stat[1];
-    out->n_dup_pairs = h_stat[2];
-    out->n_art_pairs = h_stat[3];
-    out->n_placed = n_placed_total;
-    out->interdup_rate = h_stat[0] ? (double)h_stat[1] / (double)h_stat[0] : 0.0;
-    (void)hipEventElapsedTime(&out->ms, e0, e1);
-    return SNK_OK;
+        out->n_pairs = np;
+        out->dup = dup;
+        out->n_dup_reads = h_stat[0];
+        out->n_interdup_reads = h_stat[1];
+        out->n_dup_pairs = h_stat[2];
+        out->n_art_pairs = h_stat[3];
+        out->n_placed = n_placed_total;
+        out->interdup_rate = h_stat[0] ? (double)h_stat[1] / (double)h_stat[0] : 0.0;
+        out->ms = c.ms(0, 1);
+        return c.end(SNK_OK, {dup});
+    });
 }

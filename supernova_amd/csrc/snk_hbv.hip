@@ -29,7 +29,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_common.h"
 #include "snk_kernels.h"
 #include "snk_hbvadj.h"
@@ -566,24 +566,6 @@ __global__ void __launch_bounds__(HB) hbv_flood_kernel(const uint32_t* __restric
     if (bad || tail != size) atomicOr(errflag, 4u);
 }
 
-// scratch of one call: handed back to the arena when the call returns (the unitigs it reads are scratch of the
-// preceding snk_dev_count_graph and must stay)
-struct scratch_list {
-    snk_ctx* ctx;
-    std::vector<void*> p;
-    ~scratch_list() { for (void* q : p) snk_ctx_release_block(ctx, q); }
-};
-
-
-template <typename T>
-int dalloc(scratch_list& sl, size_t n, T** out, char* err, size_t errcap) {
-    void* q = nullptr;
-    int rc = snk_ctx_alloc(sl.ctx, std::max<size_t>(n * sizeof(T), 16), &q, err, errcap);
-    if (!rc) sl.p.push_back(q);
-    *out = (T*)q;
-    return rc;
-}
-
 }  // namespace
 
 extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_unitig_off, const void* d_unitig_bases, snk_hbv* out,
@@ -595,198 +577,199 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     if (U == 0) return SNK_OK;
     if (!d_unitig_off || !d_unitig_bases) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_hbv: NULL unitig arrays");
     if (U >= (1ull << 30)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_hbv: too many unitigs");
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    const uint64_t* off = (const uint64_t*)d_unitig_off;
-    const uint8_t* bases = (const uint8_t*)d_unitig_bases;
-    const uint64_t n4 = 4 * U;
-    int rc;
-    scratch_list sl{ctx, {}};
-    uint64_t *lkey, *lkey2, *run_beg;
-    uint32_t *idx, *order, *codes, *codes2, *flag, *cls, *flags;
-    uint8_t *pal, *palr;
-    snk_u128 *keys, *keys2;
-    int32_t* vtx_of;
-    if ((rc = dalloc(sl, U, &lkey, err, errcap)) || (rc = dalloc(sl, U, &lkey2, err, errcap)) || (rc = dalloc(sl, U, &idx, err, errcap)) ||
-        (rc = dalloc(sl, U, &order, err, errcap)) || (rc = dalloc(sl, U, &pal, err, errcap)) || (rc = dalloc(sl, U, &palr, err, errcap)) ||
-        (rc = dalloc(sl, n4, &keys, err, errcap)) || (rc = dalloc(sl, n4, &keys2, err, errcap)) || (rc = dalloc(sl, n4, &codes, err, errcap)) ||
-        (rc = dalloc(sl, n4, &codes2, err, errcap)) || (rc = dalloc(sl, n4, &flag, err, errcap)) || (rc = dalloc(sl, n4, &cls, err, errcap)) ||
-        (rc = dalloc(sl, n4, &vtx_of, err, errcap)) || (rc = dalloc(sl, n4 + 1, &run_beg, err, errcap)) || (rc = dalloc(sl, 4, &flags, err, errcap)))
-        return rc;
-    hipEvent_t e0, e1;
-    SNK_HIP_TRY(hipEventCreate(&e0));
-    SNK_HIP_TRY(hipEventCreate(&e1));
-    SNK_HIP_TRY(hipEventRecord(e0, st));
-    SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
-    const uint64_t gU = snk_blocks(U, HB), g4 = snk_blocks(n4, HB);
-    SNK_HIP_TRY(snk_launch(hbv_head_kernel, gU, HB, 0, st, off, bases, U, K, keys, idx, pal, flags));
-    // BVComp rank: sort by first k-mer, then stable sort by descending length
-    size_t tmp_bytes = 0, tb2 = 0, tb3 = 0;
-    SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tmp_bytes, lkey, lkey2, idx, order, (size_t)U, 0u, 64u, st));
-    SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb2, keys, keys2, codes, codes2, (size_t)n4, 0u, 128u, st));
-    SNK_HIP_TRY(rocprim::inclusive_scan((void*)nullptr, tb3, flag, cls, (size_t)n4, rocprim::plus<uint32_t>(), st));
-    size_t tb4 = 0;
-    SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb4, flag, cls, 0u, (size_t)(2 * U), rocprim::plus<uint32_t>(), st));
-    tmp_bytes = std::max(std::max(tmp_bytes, tb4), std::max(tb2, tb3));
-    uint8_t* tmp = nullptr;
-    if ((rc = dalloc(sl, tmp_bytes, &tmp, err, errcap))) return rc;
-    size_t tbx = tmp_bytes;
-    SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, keys, keys2, idx, codes, (size_t)U, 0u, 128u, st));   // codes = first-k-mer order
-    SNK_HIP_TRY(snk_launch(hbv_lenkey_kernel, gU, HB, 0, st, off, codes, U, lkey));
-    tbx = tmp_bytes;
-    SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, lkey, lkey2, codes, order, (size_t)U, 0u, 64u, st));
-    SNK_HIP_TRY(snk_launch(hbv_ends_kernel, g4, HB, 0, st, off, bases, order, pal, U, K, keys, codes, palr));
-    // vertex-major order of the ends: stable sort by the (K-1)-mer; inside a vertex the generation order (rank, rc,
-    // position) is EEComp
-    tbx = tmp_bytes;
-    SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, keys, keys2, codes, codes2, (size_t)n4, 0u, 128u, st));
-    uint32_t h_flags[4] = {0, 0, 0, 0};
-    SNK_HIP_TRY(hipMemcpyAsync(h_flags, flags, 16, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    if (h_flags[0]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_hbv: a unitig is shorter than K");
-    const uint64_t n_ee = n4 - 2ull * h_flags[1];            // the missing ends of palindromes sorted last
-    const uint64_t ge = snk_blocks(n_ee, HB);
-    SNK_HIP_TRY(snk_launch(hbv_flag_kernel, ge, HB, 0, st, keys2, n_ee, flag));
-    tbx = tmp_bytes;
-    SNK_HIP_TRY(rocprim::inclusive_scan(tmp, tbx, flag, cls, (size_t)n_ee, rocprim::plus<uint32_t>(), st));
-    SNK_HIP_TRY(hipMemsetAsync(vtx_of, 0xFF, n4 * 4, st));
-    SNK_HIP_TRY(snk_launch(hbv_class_kernel, ge, HB, 0, st, cls, flag, codes2, n_ee, vtx_of, run_beg));
-    uint32_t nruns = 0;
-    SNK_HIP_TRY(hipMemcpyAsync(&nruns, cls + (n_ee - 1), 4, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
+    // What the asynchronous copies write on the host is declared in front of the frame: it is let go of after the frame's last wait,
+    // whichever way the call ends.  The call's scratch goes back to the arena with it (the unitigs it reads are scratch of the preceding
+    // snk_dev_count_graph and stay); the result is host memory, freed below after any failure.
     const bool huge = snk_opt_u32(ctx, SNK_OPT_hbv_huge_pages) != 0;
-    std::vector<uint32_t> h_order(U);
+    std::vector<uint32_t> h_order;
     huge_vec<uint32_t> h_ee(huge);
     huge_vec<int32_t> h_vtx(huge);
     huge_vec<uint8_t> h_pal(huge);
     huge_vec<uint64_t> h_run(huge);
-    auto fetch_tables = [&]() -> hipError_t {       // what a flood on the host reads
-        if (!h_ee.resize(n_ee) || !h_vtx.resize(n4) || !h_pal.resize(U) || !h_run.resize((size_t)nruns + 1)) return hipErrorOutOfMemory;
-        hipError_t e;
-        if ((e = hipMemcpyAsync(h_ee.data(), codes2, n_ee * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(h_vtx.data(), vtx_of, n4 * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(h_pal.data(), palr, U, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-        if ((e = hipMemcpyAsync(h_run.data(), run_beg, (size_t)nruns * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-        h_run[nruns] = n_ee;
-        return hipSuccess;
-    };
-    // small graphs (the hot path's few thousand unitigs) are flooded on the host in less time than the launches below take.
-    // Measured (tools/hbv_scale_probe.py, profiles/r04_hbv_scale.log): 9.5 M unitigs of per-barcode graphs (every component small) 4.8 s
-    // -> 0.19 s per call, the flood itself ~5 ms behind the 30 ms of sorts; 6.1 M unitigs of ONE genome (the connected bulk goes to
-    // the host either way) 3.15 -> 2.82 s.
-    const uint64_t dev_min = snk_opt_u64(ctx, SNK_OPT_hbv_dev_min);
-    if (U < dev_min) {
-        SNK_HIP_TRY(hipEventRecord(e1, st));
-        SNK_HIP_TRY(fetch_tables());
-        SNK_HIP_TRY(hipMemcpyAsync(h_order.data(), order, U * 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(snk_sync(st));
-        if (device_ms) (void)hipEventElapsedTime(device_ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap);
-        if (rc) return rc;
-    } else {
-        // the sort buffers are dead: node arrays live in `keys` (64 U bytes), the outputs in `keys2`, the vertex ids in `flag`
-        const uint64_t n2 = 2 * U;
-        uint32_t* par = (uint32_t*)keys;
-        uint32_t *ce = par + n2, *cv = ce + n2, *be = cv + n2, *bv = be + n2;
-        int32_t* d_fwd = (int32_t*)keys2;
-        int32_t *d_rev = d_fwd + U, *d_vl = d_rev + U, *d_vr = d_vl + n2, *d_src = d_vr + n2;
-        uint8_t* d_isrc = (uint8_t*)(d_src + n2);
-        int32_t* d_vid = (int32_t*)flag;
-        const uint32_t big_limit = snk_opt_u32(ctx, SNK_OPT_hbv_big);
-        const uint32_t big_cap = (uint32_t)(n2 / ((uint64_t)big_limit + 1) + 1);
-        hbv_big* d_big;
-        uint32_t* d_nbig;                      // [0] components for the host, [1] error flag
-        if ((rc = dalloc(sl, big_cap, &d_big, err, errcap)) || (rc = dalloc(sl, 4, &d_nbig, err, errcap))) return rc;
-        const uint64_t h_nee = n_ee;
-        SNK_HIP_TRY(hipMemcpyAsync(run_beg + nruns, &h_nee, 8, hipMemcpyHostToDevice, st));
-        SNK_HIP_TRY(hipMemsetAsync(ce, 0, n2 * 8, st));                       // ce, cv
-        SNK_HIP_TRY(hipMemsetAsync(d_fwd, 0xFF, U * 8, st));                  // fwd, rev
-        SNK_HIP_TRY(hipMemsetAsync(d_vid, 0xFF, (size_t)nruns * 4, st));
-        SNK_HIP_TRY(hipMemsetAsync(d_nbig, 0, 8, st));
-        const uint64_t g2 = snk_blocks(n2, HB), gr = snk_blocks(nruns, HB);
-        SNK_HIP_TRY(snk_launch(hbv_cc_init_kernel, g2, HB, 0, st, par, n2));
-        SNK_HIP_TRY(snk_launch(hbv_cc_union_kernel, ge, HB, 0, st, codes2, cls, run_beg, n_ee, (uint32_t)U, par, d_nbig + 1));
-        SNK_HIP_TRY(snk_launch(hbv_cc_nodes_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, d_nbig + 1));
-        SNK_HIP_TRY(snk_launch(hbv_cc_classes_kernel, gr, HB, 0, st, par, codes2, run_beg, (uint64_t)nruns, (uint32_t)U, cv, d_nbig + 1));
+    std::vector<hbv_big> h_big;
+    uint32_t h_flags[4] = {0, 0, 0, 0}, h_nb[2] = {0, 0}, nruns = 0;
+    uint64_t h_nee = 0;
+    const int rc = snk_call_guarded(ctx, stream, "snk_dev_hbv", err, errcap, [&](snk_call& c) -> int {
+        const hipStream_t st = c.st;
+        const uint64_t* off = (const uint64_t*)d_unitig_off;
+        const uint8_t* bases = (const uint8_t*)d_unitig_bases;
+        const uint64_t n4 = 4 * U;
+        int rc;
+        uint64_t *lkey, *lkey2, *run_beg;
+        uint32_t *idx, *order, *codes, *codes2, *flag, *cls, *flags;
+        uint8_t *pal, *palr;
+        snk_u128 *keys, *keys2;
+        int32_t* vtx_of;
+        if ((rc = c.alloc(U, &lkey)) || (rc = c.alloc(U, &lkey2)) || (rc = c.alloc(U, &idx)) ||
+            (rc = c.alloc(U, &order)) || (rc = c.alloc(U, &pal)) || (rc = c.alloc(U, &palr)) ||
+            (rc = c.alloc(n4, &keys)) || (rc = c.alloc(n4, &keys2)) || (rc = c.alloc(n4, &codes)) ||
+            (rc = c.alloc(n4, &codes2)) || (rc = c.alloc(n4, &flag)) || (rc = c.alloc(n4, &cls)) ||
+            (rc = c.alloc(n4, &vtx_of)) || (rc = c.alloc(n4 + 1, &run_beg)) || (rc = c.alloc(4, &flags)))
+            return rc;
+        SNK_HIP_TRY(c.stamp());
+        SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
+        const uint64_t gU = snk_blocks(U, HB), g4 = snk_blocks(n4, HB);
+        SNK_HIP_TRY(snk_launch(hbv_head_kernel, gU, HB, 0, st, off, bases, U, K, keys, idx, pal, flags));
+        // BVComp rank: sort by first k-mer, then stable sort by descending length
+        // (one scratch block for every sort and scan of the call: the largest of their sizes)
+        snk_temp t;
+        if ((rc = c.temp(&t, [&](void* p, size_t& b) { return rocprim::radix_sort_pairs(p, b, lkey, lkey2, idx, order, (size_t)U, 0u, 64u, st); },
+                         [&](void* p, size_t& b) { return rocprim::radix_sort_pairs(p, b, keys, keys2, codes, codes2, (size_t)n4, 0u, 128u, st); },
+                         [&](void* p, size_t& b) { return rocprim::inclusive_scan(p, b, flag, cls, (size_t)n4, rocprim::plus<uint32_t>(), st); },
+                         [&](void* p, size_t& b) { return rocprim::exclusive_scan(p, b, flag, cls, 0u, (size_t)(2 * U), rocprim::plus<uint32_t>(), st); })))
+            return rc;
+        void* const tmp = t.p;
+        const size_t tmp_bytes = t.bytes;
+        size_t tbx = tmp_bytes;
+        SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, keys, keys2, idx, codes, (size_t)U, 0u, 128u, st));   // codes = first-k-mer order
+        SNK_HIP_TRY(snk_launch(hbv_lenkey_kernel, gU, HB, 0, st, off, codes, U, lkey));
         tbx = tmp_bytes;
-        SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tbx, ce, be, 0u, (size_t)n2, rocprim::plus<uint32_t>(), st));
+        SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, lkey, lkey2, codes, order, (size_t)U, 0u, 64u, st));
+        SNK_HIP_TRY(snk_launch(hbv_ends_kernel, g4, HB, 0, st, off, bases, order, pal, U, K, keys, codes, palr));
+        // vertex-major order of the ends: stable sort by the (K-1)-mer; inside a vertex the generation order (rank, rc,
+        // position) is EEComp
         tbx = tmp_bytes;
-        SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tbx, cv, bv, 0u, (size_t)n2, rocprim::plus<uint32_t>(), st));
-        SNK_HIP_TRY(snk_launch(hbv_flood_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, be, bv, codes2, vtx_of, run_beg, big_limit,
-                               d_fwd, d_rev, d_vid, d_vl, d_vr, d_src, d_isrc, d_big, big_cap, d_nbig, nruns, d_nbig + 1));
-        SNK_HIP_TRY(hipEventRecord(e1, st));
-        uint32_t h_nb[2] = {0, 0};
-        SNK_HIP_TRY(hipMemcpyAsync(h_nb, d_nbig, 8, hipMemcpyDeviceToHost, st));
-        if ((rc = hbv_alloc_out(U, nruns, huge, out, err, errcap))) return rc;
-        SNK_HIP_TRY(hipMemcpyAsync(out->fwd_xlat, d_fwd, U * 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(out->rev_xlat, d_rev, U * 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(out->v_left, d_vl, n2 * 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(out->v_right, d_vr, n2 * 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(out->src_unitig, d_src, n2 * 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(out->is_rc, d_isrc, n2, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(hipMemcpyAsync(h_order.data(), order, U * 4, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tbx, keys, keys2, codes, codes2, (size_t)n4, 0u, 128u, st));
+        SNK_HIP_TRY(hipMemcpyAsync(h_flags, flags, 16, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
-        if (device_ms) (void)hipEventElapsedTime(device_ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        const uint32_t n_big = h_nb[0];
-        if (h_nb[1]) {              // a bounded loop of the device flood ran out (never seen; the flood on the host does not depend on it)
-            snk_hbv_free(out);
-            if (snk_opt_u32(ctx, SNK_OPT_hbv_strict)) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: the device flood gave up (flag %u)", h_nb[1]);
+        if (h_flags[0]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_hbv: a unitig is shorter than K");
+        const uint64_t n_ee = n4 - 2ull * h_flags[1];            // the missing ends of palindromes sorted last
+        const uint64_t ge = snk_blocks(n_ee, HB);
+        SNK_HIP_TRY(snk_launch(hbv_flag_kernel, ge, HB, 0, st, keys2, n_ee, flag));
+        tbx = tmp_bytes;
+        SNK_HIP_TRY(rocprim::inclusive_scan(tmp, tbx, flag, cls, (size_t)n_ee, rocprim::plus<uint32_t>(), st));
+        SNK_HIP_TRY(hipMemsetAsync(vtx_of, 0xFF, n4 * 4, st));
+        SNK_HIP_TRY(snk_launch(hbv_class_kernel, ge, HB, 0, st, cls, flag, codes2, n_ee, vtx_of, run_beg));
+        SNK_HIP_TRY(hipMemcpyAsync(&nruns, cls + (n_ee - 1), 4, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(snk_sync(st));
+        h_order.resize(U);
+        auto fetch_tables = [&]() -> hipError_t {       // what a flood on the host reads
+            if (!h_ee.resize(n_ee) || !h_vtx.resize(n4) || !h_pal.resize(U) || !h_run.resize((size_t)nruns + 1)) return hipErrorOutOfMemory;
+            hipError_t e;
+            if ((e = hipMemcpyAsync(h_ee.data(), codes2, n_ee * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(h_vtx.data(), vtx_of, n4 * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(h_pal.data(), palr, U, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+            if ((e = hipMemcpyAsync(h_run.data(), run_beg, (size_t)nruns * 8, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+            h_run[nruns] = n_ee;
+            return hipSuccess;
+        };
+        // small graphs (the hot path's few thousand unitigs) are flooded on the host in less time than the launches below take.
+        // Measured (tools/hbv_scale_probe.py, profiles/r04_hbv_scale.log): 9.5 M unitigs of per-barcode graphs (every component small) 4.8 s
+        // -> 0.19 s per call, the flood itself ~5 ms behind the 30 ms of sorts; 6.1 M unitigs of ONE genome (the connected bulk goes to
+        // the host either way) 3.15 -> 2.82 s.
+        const uint64_t dev_min = snk_opt_u64(ctx, SNK_OPT_hbv_dev_min);
+        if (U < dev_min) {
+            SNK_HIP_TRY(c.stamp());
             SNK_HIP_TRY(fetch_tables());
+            SNK_HIP_TRY(hipMemcpyAsync(h_order.data(), order, U * 4, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
-            if ((rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap))) return rc;
-            goto flooded;
-        }
-        out->n_edges = (int32_t)(n2 - h_flags[1]);
-        if (n_big) {               // the connected bulk: flooded here into the blocks the scans gave it
-            if (n_big > big_cap) { snk_hbv_free(out); return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: component list overflow"); }
-            std::vector<hbv_big> h_big(n_big);
-            SNK_HIP_TRY(hipMemcpyAsync(h_big.data(), d_big, (size_t)n_big * sizeof(hbv_big), hipMemcpyDeviceToHost, st));
-            SNK_HIP_TRY(fetch_tables());
+            if (device_ms) *device_ms = c.ms(0, 1);
+            rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap);
+            if (rc) return rc;
+        } else {
+            // the sort buffers are dead: node arrays live in `keys` (64 U bytes), the outputs in `keys2`, the vertex ids in `flag`
+            const uint64_t n2 = 2 * U;
+            uint32_t* par = (uint32_t*)keys;
+            uint32_t *ce = par + n2, *cv = ce + n2, *be = cv + n2, *bv = be + n2;
+            int32_t* d_fwd = (int32_t*)keys2;
+            int32_t *d_rev = d_fwd + U, *d_vl = d_rev + U, *d_vr = d_vl + n2, *d_src = d_vr + n2;
+            uint8_t* d_isrc = (uint8_t*)(d_src + n2);
+            int32_t* d_vid = (int32_t*)flag;
+            const uint32_t big_limit = snk_opt_u32(ctx, SNK_OPT_hbv_big);
+            const uint32_t big_cap = (uint32_t)(n2 / ((uint64_t)big_limit + 1) + 1);
+            hbv_big* d_big;
+            uint32_t* d_nbig;                      // [0] components for the host, [1] error flag
+            if ((rc = c.alloc(big_cap, &d_big)) || (rc = c.alloc(4, &d_nbig))) return rc;
+            h_nee = n_ee;
+            SNK_HIP_TRY(hipMemcpyAsync(run_beg + nruns, &h_nee, 8, hipMemcpyHostToDevice, st));
+            SNK_HIP_TRY(hipMemsetAsync(ce, 0, n2 * 8, st));                       // ce, cv
+            SNK_HIP_TRY(hipMemsetAsync(d_fwd, 0xFF, U * 8, st));                  // fwd, rev
+            SNK_HIP_TRY(hipMemsetAsync(d_vid, 0xFF, (size_t)nruns * 4, st));
+            SNK_HIP_TRY(hipMemsetAsync(d_nbig, 0, 8, st));
+            const uint64_t g2 = snk_blocks(n2, HB), gr = snk_blocks(nruns, HB);
+            SNK_HIP_TRY(snk_launch(hbv_cc_init_kernel, g2, HB, 0, st, par, n2));
+            SNK_HIP_TRY(snk_launch(hbv_cc_union_kernel, ge, HB, 0, st, codes2, cls, run_beg, n_ee, (uint32_t)U, par, d_nbig + 1));
+            SNK_HIP_TRY(snk_launch(hbv_cc_nodes_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, d_nbig + 1));
+            SNK_HIP_TRY(snk_launch(hbv_cc_classes_kernel, gr, HB, 0, st, par, codes2, run_beg, (uint64_t)nruns, (uint32_t)U, cv, d_nbig + 1));
+            tbx = tmp_bytes;
+            SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tbx, ce, be, 0u, (size_t)n2, rocprim::plus<uint32_t>(), st));
+            tbx = tmp_bytes;
+            SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tbx, cv, bv, 0u, (size_t)n2, rocprim::plus<uint32_t>(), st));
+            SNK_HIP_TRY(snk_launch(hbv_flood_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, be, bv, codes2, vtx_of, run_beg, big_limit,
+                                   d_fwd, d_rev, d_vid, d_vl, d_vr, d_src, d_isrc, d_big, big_cap, d_nbig, nruns, d_nbig + 1));
+            SNK_HIP_TRY(c.stamp());
+            SNK_HIP_TRY(hipMemcpyAsync(h_nb, d_nbig, 8, hipMemcpyDeviceToHost, st));
+            if ((rc = hbv_alloc_out(U, nruns, huge, out, err, errcap))) return rc;
+            SNK_HIP_TRY(hipMemcpyAsync(out->fwd_xlat, d_fwd, U * 4, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(out->rev_xlat, d_rev, U * 4, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(out->v_left, d_vl, n2 * 4, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(out->v_right, d_vr, n2 * 4, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(out->src_unitig, d_src, n2 * 4, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(out->is_rc, d_isrc, n2, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(h_order.data(), order, U * 4, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
-            huge_vec<int32_t> vidv(huge);
-            if (!vidv.resize((size_t)nruns + 1)) { snk_hbv_free(out); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_hbv: host allocation failed"); }
-            int32_t* vid = vidv.data();
-            for (uint64_t i = 0; i < nruns; ++i) vid[i] = -1;
-            const hbv_tables t{U, h_pal.data(), h_ee.data(), h_vtx.data(), h_run.data(), snk_opt_u32(ctx, SNK_OPT_hbv_short_queue) != 0};
-            // Components are independent once their id blocks are known (the device's scans): a host thread each, largest first.  The bulk
-            // of a genome graph is TWO components -- the forward copies' and its mirror image, the reverse copies' -- whose floods are NOT
-            // each other's mirror (a flood pushes the left vertex's edges before the right vertex's), so both are run, side by side.
-            // (Why not on the device: profiles/r05_hbv_depth.log -- 6.1 M edge copies in 1.3 M breadth-first levels, 4.7 per level: a
-            // level-synchronous reproduction is >= 1.3 M rounds of >= 3 us.)
-            std::vector<uint32_t> ord(n_big);
-            for (uint32_t i = 0; i < n_big; ++i) ord[i] = i;
-            std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return h_big[a].ce > h_big[b].ce; });
-            const uint32_t nthr = std::min<uint32_t>(n_big, std::min<uint32_t>(8u, std::max(1u, (uint32_t)snk_host_cpu_budget())));
-            std::atomic<uint32_t> next{0};
-            std::atomic<int> bad{0};
-            auto work = [&]() {
-                std::vector<uint64_t> q;
-                for (;;) {
-                    const uint32_t i = next.fetch_add(1);
-                    if (i >= n_big) break;
-                    const hbv_big& b = h_big[ord[i]];
-                    int32_t next_e = (int32_t)b.be, next_v = (int32_t)b.bv;
-                    hbv_flood_component(t, b.root >= U ? b.root - U : b.root, b.root >= U ? 1 : 0, vid, q, next_e, next_v, out);
-                    if ((uint32_t)next_e != b.be + b.ce) bad = 1;
-                }
-            };
-            if (nthr <= 1) work();
-            else {
-                std::vector<std::thread> th;
-                for (uint32_t i = 0; i < nthr; ++i) th.emplace_back(work);
-                for (auto& x : th) x.join();
+            if (device_ms) *device_ms = c.ms(0, 1);
+            const uint32_t n_big = h_nb[0];
+            if (h_nb[1]) {              // a bounded loop of the device flood ran out (never seen; the flood on the host does not depend on it)
+                snk_hbv_free(out);
+                if (snk_opt_u32(ctx, SNK_OPT_hbv_strict)) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: the device flood gave up (flag %u)", h_nb[1]);
+                SNK_HIP_TRY(fetch_tables());
+                SNK_HIP_TRY(snk_sync(st));
+                if ((rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap))) return rc;
+                goto flooded;
             }
-            if (bad) { snk_hbv_free(out); return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: a component's flood left its block"); }
+            out->n_edges = (int32_t)(n2 - h_flags[1]);
+            if (n_big) {               // the connected bulk: flooded here into the blocks the scans gave it
+                if (n_big > big_cap) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: component list overflow");
+                h_big.resize(n_big);
+                SNK_HIP_TRY(hipMemcpyAsync(h_big.data(), d_big, (size_t)n_big * sizeof(hbv_big), hipMemcpyDeviceToHost, st));
+                SNK_HIP_TRY(fetch_tables());
+                SNK_HIP_TRY(snk_sync(st));
+                huge_vec<int32_t> vidv(huge);
+                if (!vidv.resize((size_t)nruns + 1)) return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_hbv: host allocation failed");
+                int32_t* vid = vidv.data();
+                for (uint64_t i = 0; i < nruns; ++i) vid[i] = -1;
+                const hbv_tables t{U, h_pal.data(), h_ee.data(), h_vtx.data(), h_run.data(), snk_opt_u32(ctx, SNK_OPT_hbv_short_queue) != 0};
+                // Components are independent once their id blocks are known (the device's scans): a host thread each, largest first.  The bulk
+                // of a genome graph is TWO components -- the forward copies' and its mirror image, the reverse copies' -- whose floods are NOT
+                // each other's mirror (a flood pushes the left vertex's edges before the right vertex's), so both are run, side by side.
+                // (Why not on the device: profiles/r05_hbv_depth.log -- 6.1 M edge copies in 1.3 M breadth-first levels, 4.7 per level: a
+                // level-synchronous reproduction is >= 1.3 M rounds of >= 3 us.)
+                std::vector<uint32_t> ord(n_big);
+                for (uint32_t i = 0; i < n_big; ++i) ord[i] = i;
+                std::sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) { return h_big[a].ce > h_big[b].ce; });
+                const uint32_t nthr = std::min<uint32_t>(n_big, std::min<uint32_t>(8u, std::max(1u, (uint32_t)snk_host_cpu_budget())));
+                std::atomic<uint32_t> next{0};
+                std::atomic<int> bad{0};
+                auto work = [&]() {
+                    std::vector<uint64_t> q;
+                    for (;;) {
+                        const uint32_t i = next.fetch_add(1);
+                        if (i >= n_big) break;
+                        const hbv_big& b = h_big[ord[i]];
+                        int32_t next_e = (int32_t)b.be, next_v = (int32_t)b.bv;
+                        hbv_flood_component(t, b.root >= U ? b.root - U : b.root, b.root >= U ? 1 : 0, vid, q, next_e, next_v, out);
+                        if ((uint32_t)next_e != b.be + b.ce) bad = 1;
+                    }
+                };
+                if (nthr <= 1) work();
+                else {
+                    std::vector<std::thread> th;
+                    for (uint32_t i = 0; i < nthr; ++i) th.emplace_back(work);
+                    for (auto& x : th) x.join();
+                }
+                if (bad) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: a component's flood left its block");
+            }
         }
-    }
 flooded:
-    out->bvcomp_order = (int32_t*)malloc(U * 4);
-    if (!out->bvcomp_order) { snk_hbv_free(out); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_hbv: host allocation failed"); }
-    for (uint64_t i = 0; i < U; ++i) out->bvcomp_order[i] = (int32_t)h_order[i];
-    return SNK_OK;
+        out->bvcomp_order = (int32_t*)malloc(U * 4);
+        if (!out->bvcomp_order) return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_hbv: host allocation failed");
+        for (uint64_t i = 0; i < U; ++i) out->bvcomp_order[i] = (int32_t)h_order[i];
+        return c.end(SNK_OK);
+    });
+    if (rc) {                    // (after the frame's wait: no copy into these arrays is still running)
+        snk_hbv_free(out);
+        if (device_ms) *device_ms = 0.f;
+    }
+    return rc;
 }

@@ -13,7 +13,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_common.h"
 #include "snk_kernels.h"
 
@@ -385,13 +385,6 @@ int snk_unitigs_to_host(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t U, co
     SNK_HIP_TRY(snk_sync(st));
     return SNK_OK;
 }
-
-// No C++ exception leaves an extern "C" entry point: a failed host allocation maps to SNK_E_NOMEM (the caller's exit code 99,
-// system/RunTime.cc:195-221), anything else to SNK_E_INTERNAL.
-#define SNK_GUARD(body)                                                                                       \
-    try { body } catch (const std::bad_alloc&) { return snk_fail(SNK_E_NOMEM, err, errcap, "host allocation failed"); } \
-    catch (const std::exception& ex) { return snk_fail(SNK_E_INTERNAL, err, errcap, "%s", ex.what()); }               \
-    catch (...) { return snk_fail(SNK_E_INTERNAL, err, errcap, "unexpected exception"); }
 
 extern "C" int snk_count_graph(snk_ctx* ctx, const snk_reads* in, const snk_params* p, snk_result* out, char* err, size_t errcap) {
     // every error exit of the implementation leaves through here: uploads / kernels it queued are waited for (the caller may free

@@ -25,7 +25,7 @@
 #include <rocprim/rocprim.hpp>
 #include "snk_stages.h"
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_common.h"
 #include "snk_kernels.h"
 
@@ -875,30 +875,18 @@ __global__ void __launch_bounds__(256) widen_kernel(const uint32_t* __restrict__
     if (i <= n) out[i] = i < n ? in[i] : 0ull;
 }
 
+// (h belongs to path_host: it outlives the wait for this copy)
 template <typename T>
-int dev(snk_ctx* ctx, size_t n, T** out, char* err, size_t errcap) {
-    void* q = nullptr;
-    int rc = snk_ctx_alloc(ctx, (n ? n : 1) * sizeof(T) + 16, &q, err, errcap);
-    *out = (T*)q;
-    return rc;
-}
-template <typename T>
-int up(snk_ctx* ctx, hipStream_t st, const std::vector<T>& h, const T** out, char* err, size_t errcap) {
+int up(snk_call& c, const std::vector<T>& h, const T** out, char* err, size_t errcap) {
     T* d;
-    int rc = dev(ctx, h.size(), &d, err, errcap);
+    int rc = c.alloc(h.size(), &d);
     if (rc) return rc;
-    if (!h.empty()) SNK_HIP_TRY(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
+    if (!h.empty()) SNK_HIP_TRY(hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, c.st));
     *out = d;
     return SNK_OK;
 }
-int scan64(snk_ctx* ctx, hipStream_t st, const uint64_t* in, uint64_t* out, size_t count, char* err, size_t errcap) {
-    size_t tb = 0;
-    SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, in, out, (uint64_t)0, count, rocprim::plus<uint64_t>(), st));
-    void* tmp;
-    int rc = snk_ctx_alloc(ctx, tb + 16, &tmp, err, errcap);
-    if (rc) return rc;
-    SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, count, rocprim::plus<uint64_t>(), st));
-    return SNK_OK;
+int scan64(snk_call& c, const uint64_t* in, uint64_t* out, size_t count) {
+    return c.with_temp([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, count, rocprim::plus<uint64_t>(), c.st); });
 }
 
 // adjacency in AddEdge order: a vertex's edges ascending by the vertex at their other end, equal ones in edge-id order
@@ -985,19 +973,27 @@ __global__ void __launch_bounds__(64) ubc_cut_copy_kernel(const uint64_t* __rest
     for (uint64_t i = threadIdx.x; i < n; i += 64) out[noff[u] + i] = in[off[u] + i];
 }
 
+// the graph tables on the host: what the asynchronous uploads read.  The entry point declares them in front of the frame, which waits
+// for the stream before they are let go of, whichever way the call ends.
+struct path_host {
+    std::vector<int32_t> fwd, rev, eu, off_to, v_to, e_to, off_from, v_from, e_from, vl, vr;
+    std::vector<uint8_t> erc, drop;
+};
+
+// stamps: 0 start, 1 dictionary built, 2 paths done, 3 / 4 around the barcode lists
 template <int K>
-int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U, const uint64_t* d_uoff, const uint8_t* d_ubases, const snk_hbv* h,
-              uint32_t flags, snk_dev_paths* out, char* err, size_t errcap) {
+int path_impl(snk_call& c, path_host& H, const snk_dev_reads* in, uint64_t U, const uint64_t* d_uoff, const uint8_t* d_ubases, const snk_hbv* h, uint32_t flags,
+              snk_dev_paths* out, char* err, size_t errcap) {
+    snk_ctx* const ctx = c.ctx;
+    const hipStream_t st = c.st;
     int rc;
     const uint64_t n = in->n_reads;
-    hipEvent_t e0, e1, e2, e3, e2b;
-    SNK_HIP_TRY(hipEventCreate(&e0)); SNK_HIP_TRY(hipEventCreate(&e1)); SNK_HIP_TRY(hipEventCreate(&e2)); SNK_HIP_TRY(hipEventCreate(&e3)); SNK_HIP_TRY(hipEventCreate(&e2b));
-    struct evg { hipEvent_t a, b, c, d, e; ~evg() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); (void)hipEventDestroy(c); (void)hipEventDestroy(d); (void)hipEventDestroy(e); } } g{e0, e1, e2, e3, e2b};
-    SNK_HIP_TRY(hipEventRecord(e0, st));
+    SNK_HIP_TRY(c.stamp());
     // ---- graph tables (host: O(U + E)), in the device's unitig numbering
     const int32_t N = h->n_vertices, E = h->n_edges;
-    std::vector<int32_t> fwd(U), rev(U), eu((size_t)E), off_to, v_to, e_to, off_from, v_from, e_from;
-    std::vector<uint8_t> erc((size_t)E);
+    std::vector<int32_t> &fwd = H.fwd, &rev = H.rev, &eu = H.eu, &off_to = H.off_to, &v_to = H.v_to, &e_to = H.e_to, &off_from = H.off_from, &v_from = H.v_from, &e_from = H.e_from;
+    std::vector<uint8_t> &erc = H.erc, &drop = H.drop;
+    fwd.resize(U); rev.resize(U); eu.resize((size_t)E); erc.resize((size_t)E);
     for (uint64_t r = 0; r < U; ++r) {
         const uint64_t d = h->bvcomp_order ? (uint64_t)h->bvcomp_order[r] : r;
         fwd[d] = h->fwd_xlat[r];
@@ -1010,21 +1006,22 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     }
     adjacency(N, E, h->v_right, h->v_left, off_to, v_to, e_to);
     adjacency(N, E, h->v_left, h->v_right, off_from, v_from, e_from);
-    std::vector<int32_t> vl(h->v_left, h->v_left + E), vr(h->v_right, h->v_right + E);
+    std::vector<int32_t> &vl = H.vl, &vr = H.vr;
+    vl.assign(h->v_left, h->v_left + E); vr.assign(h->v_right, h->v_right + E);
     path_args a;
     memset(&a, 0, sizeof a);
     path_graph& G = a.G;
     G.uoff = d_uoff; G.ubases = d_ubases;
-    if ((rc = up(ctx, st, fwd, &G.fwd, err, errcap)) || (rc = up(ctx, st, rev, &G.rev, err, errcap)) || (rc = up(ctx, st, vl, &G.vleft, err, errcap)) ||
-        (rc = up(ctx, st, vr, &G.vright, err, errcap)) || (rc = up(ctx, st, eu, &G.e_unitig, err, errcap)) || (rc = up(ctx, st, erc, &G.e_rc, err, errcap)) ||
-        (rc = up(ctx, st, off_to, &G.to_off, err, errcap)) || (rc = up(ctx, st, v_to, &G.to_v, err, errcap)) || (rc = up(ctx, st, e_to, &G.to_e, err, errcap)) ||
-        (rc = up(ctx, st, off_from, &G.from_off, err, errcap)) || (rc = up(ctx, st, v_from, &G.from_v, err, errcap)) || (rc = up(ctx, st, e_from, &G.from_e, err, errcap)))
+    if ((rc = up(c, fwd, &G.fwd, err, errcap)) || (rc = up(c, rev, &G.rev, err, errcap)) || (rc = up(c, vl, &G.vleft, err, errcap)) ||
+        (rc = up(c, vr, &G.vright, err, errcap)) || (rc = up(c, eu, &G.e_unitig, err, errcap)) || (rc = up(c, erc, &G.e_rc, err, errcap)) ||
+        (rc = up(c, off_to, &G.to_off, err, errcap)) || (rc = up(c, v_to, &G.to_v, err, errcap)) || (rc = up(c, e_to, &G.to_e, err, errcap)) ||
+        (rc = up(c, off_from, &G.from_off, err, errcap)) || (rc = up(c, v_from, &G.from_v, err, errcap)) || (rc = up(c, e_from, &G.from_e, err, errcap)))
         return rc;
     // ---- per-unitig records + dictionary
     uint64_t h_off_last = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&h_off_last, d_uoff + U, 8, hipMemcpyDeviceToHost, st));
     // seeds on a short hanging edge are dropped (BuildReadQGraph48.cc:1240-1247): a property of the edge, decided here once
-    std::vector<uint8_t> drop((size_t)E + 1, 0);
+    drop.assign((size_t)E + 1, 0);
     SNK_HIP_TRY(snk_sync(st));
     {
         std::vector<uint64_t> h_uoff(U + 1);
@@ -1036,9 +1033,9 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         }
     }
     const uint8_t* d_drop;
-    if ((rc = up(ctx, st, drop, &d_drop, err, errcap))) return rc;
+    if ((rc = up(c, drop, &d_drop, err, errcap))) return rc;
     uint4* uinfo;
-    if ((rc = dev(ctx, 2 * U + 2, &uinfo, err, errcap))) return rc;
+    if ((rc = c.alloc(2 * U + 2, &uinfo))) return rc;
     SNK_HIP_TRY(snk_launch(uinfo_kernel, snk_blocks(U, 256), 256, 0, st, d_uoff, U, G.fwd, G.rev, d_drop, uinfo));
     G.uinfo = uinfo;
     const uint64_t total_bases = h_off_last;
@@ -1046,7 +1043,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         // the unitigs once more, 2 bits per base (a quarter of the byte array), UPAD bases of slack at either end
         const uint64_t n_words = (total_bases + 15) / 16 + 1;
         uint32_t* upack;
-        if ((rc = dev(ctx, n_words + 2 * (UPAD / 16) + 2, &upack, err, errcap))) return rc;
+        if ((rc = c.alloc(n_words + 2 * (UPAD / 16) + 2, &upack))) return rc;
         SNK_HIP_TRY(hipMemsetAsync(upack, 0, (UPAD / 16) * 4, st));
         SNK_HIP_TRY(hipMemsetAsync(upack + UPAD / 16 + n_words, 0, (UPAD / 16 + 2) * 4, st));
         SNK_HIP_TRY(snk_launch(upack_kernel, snk_blocks(n_words, 256), 256, 0, st, d_ubases, total_bases, upack + UPAD / 16, n_words));
@@ -1085,7 +1082,7 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_path_reads: the k-mer dictionary of this graph (%llu unitig k-mers, 3 slots of 8 B each) needs %.1f GB, "
                         "%.1f GB of HBM are free; let the minimiser index take the look-ups (option path_index unset or 1)", (unsigned long long)nk, cap * 8ull / 1e9, free_b / 1e9);
     if (snk_opt_is_set(ctx, SNK_OPT_path_fp_mask)) { const unsigned long long m = snk_opt_u64(ctx, SNK_OPT_path_fp_mask) & 0x3FFFFFFFull; if (m) fp_mask = m; }
-    if ((rc = dev(ctx, cap, &dslot, err, errcap))) return rc;
+    if ((rc = c.alloc(cap, &dslot))) return rc;
     SNK_HIP_TRY(hipMemsetAsync(dslot, 0xFF, cap * 8, st));
     SNK_HIP_TRY(snk_launch(dict_build_kernel<K>, snk_blocks(snk_blocks(total_bases, DB_RUN), 256), 256, 0, st, d_uoff, d_ubases, U, total_bases, dslot, cap, fp_mask));
     }
@@ -1096,37 +1093,30 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         uint32_t *wgc, *okey, *okey2, *mdir, *mhist;
         uint64_t *wg64, *wgo;
         unsigned long long *oval, *oval2;
-        if ((rc = dev(ctx, n_wg + 2, &wgc, err, errcap)) || (rc = dev(ctx, n_wg + 2, &wg64, err, errcap)) || (rc = dev(ctx, n_wg + 2, &wgo, err, errcap))) return rc;
+        if ((rc = c.alloc(n_wg + 2, &wgc)) || (rc = c.alloc(n_wg + 2, &wg64)) || (rc = c.alloc(n_wg + 2, &wgo))) return rc;
         if (n_wg) {
             SNK_HIP_TRY(snk_launch(mm_scan_kernel<K, false>, n_wg, 256, 0, st, d_uoff, G.upack, U, total_bases, wgc, (const uint64_t*)nullptr, (uint32_t*)nullptr,
                                    (unsigned long long*)nullptr));
             SNK_HIP_TRY(snk_launch(mm_widen_kernel, snk_blocks(n_wg + 1, 256), 256, 0, st, wgc, n_wg, wg64));
-            if ((rc = scan64(ctx, st, wg64, wgo, n_wg + 1, err, errcap))) return rc;
+            if ((rc = scan64(c, wg64, wgo, n_wg + 1))) return rc;
             SNK_HIP_TRY(hipMemcpyAsync(&n_ment, wgo + n_wg, 8, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
         }
         if (n_ment >= (1ull << 32) - 2) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_path_reads: more than 2^32 minimiser places");
-        if ((rc = dev(ctx, n_ment + 1, &okey, err, errcap)) || (rc = dev(ctx, n_ment + 1, &okey2, err, errcap)) || (rc = dev(ctx, n_ment + 1, &oval, err, errcap)) ||
-            (rc = dev(ctx, n_ment + 1, &oval2, err, errcap)))
+        if ((rc = c.alloc(n_ment + 1, &okey)) || (rc = c.alloc(n_ment + 1, &okey2)) || (rc = c.alloc(n_ment + 1, &oval)) ||
+            (rc = c.alloc(n_ment + 1, &oval2)))
             return rc;
         uint32_t bits = 8;
         while (bits < 26 && (2ull << bits) < n_ment) ++bits;             // ~2-4 places per directory entry
-        if ((rc = dev(ctx, (1ull << bits) + 2, &mdir, err, errcap)) || (rc = dev(ctx, (1ull << bits) + 2, &mhist, err, errcap))) return rc;
+        if ((rc = c.alloc((1ull << bits) + 2, &mdir)) || (rc = c.alloc((1ull << bits) + 2, &mhist))) return rc;
         SNK_HIP_TRY(hipMemsetAsync(mdir, 0, ((1ull << bits) + 2) * 4, st));
         SNK_HIP_TRY(hipMemsetAsync(mhist, 0, ((1ull << bits) + 2) * 4, st));
         if (n_ment) {
             SNK_HIP_TRY(snk_launch(mm_scan_kernel<K, true>, n_wg, 256, 0, st, d_uoff, G.upack, U, total_bases, wgc, (const uint64_t*)wgo, okey, oval));
-            size_t tb = 0;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, okey, okey2, oval, oval2, (size_t)n_ment, 0u, 32u, st));
-            void* tmp;
-            if ((rc = snk_ctx_alloc(ctx, tb + 64, &tmp, err, errcap))) return rc;
-            SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, okey, okey2, oval, oval2, (size_t)n_ment, 0u, 32u, st));
+            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, okey, okey2, oval, oval2, (size_t)n_ment, 0u, 32u, st); }))) return rc;
             SNK_HIP_TRY(snk_launch(mm_hist_kernel, snk_blocks(n_ment, 256), 256, 0, st, okey2, n_ment, 32u - bits, mhist));
-            size_t tb2 = 0;
-            SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb2, mhist, mdir, 0u, ((size_t)1 << bits) + 1, rocprim::plus<uint32_t>(), st));
-            void* tmp2;
-            if ((rc = snk_ctx_alloc(ctx, tb2 + 64, &tmp2, err, errcap))) return rc;
-            SNK_HIP_TRY(rocprim::exclusive_scan(tmp2, tb2, mhist, mdir, 0u, ((size_t)1 << bits) + 1, rocprim::plus<uint32_t>(), st));
+            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, mhist, mdir, 0u, ((size_t)1 << bits) + 1, rocprim::plus<uint32_t>(), st); })))
+                return rc;
         }
         G.ment = oval2; G.mdir = mdir; G.mdir_bits = bits; G.idx_dbg = snk_opt_u32(ctx, SNK_OPT_path_idx_dbg);
         if (!need_kdict) cap = n_ment;
@@ -1135,14 +1125,14 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     {
         const uint64_t n_blk = (total_bases >> 8) + 2;
         uint32_t* ublk;
-        if ((rc = dev(ctx, n_blk, &ublk, err, errcap))) return rc;
+        if ((rc = c.alloc(n_blk, &ublk))) return rc;
         if (U) SNK_HIP_TRY(snk_launch(ublk_kernel, snk_blocks(n_blk, 256), 256, 0, st, d_uoff, U, n_blk, ublk));
         else SNK_HIP_TRY(hipMemsetAsync(ublk, 0, n_blk * 4, st));
         G.ublk = ublk;
     }
     SNK_HIP_TRY(snk_sync(st));            // drop[] has been copied
     G.dslot = dslot; G.dcap = cap; G.fp_mask = fp_mask;
-    SNK_HIP_TRY(hipEventRecord(e1, st));
+    SNK_HIP_TRY(c.stamp());
     // ---- the reads
     a.rows = (const uint32_t*)in->rows; a.row_words = in->row_words; a.read_len = in->read_len;
     a.quals = (const uint8_t*)in->quals; a.qstride = in->qstride; a.lens = (const uint16_t*)in->lens; a.n_reads = n;
@@ -1150,8 +1140,8 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     unsigned long long *out_start, *cursor;
     int32_t *out_off, *out_e0, *scratch = nullptr, *edges = nullptr;
     uint64_t *n64, *pos;
-    if ((rc = dev(ctx, n + 1, &out_n, err, errcap)) || (rc = dev(ctx, n + 1, &out_start, err, errcap)) || (rc = dev(ctx, n + 1, &out_off, err, errcap)) || (rc = dev(ctx, n + 1, &out_e0, err, errcap)) ||
-        (rc = dev(ctx, 4, &cursor, err, errcap)) || (rc = dev(ctx, n + 2, &n64, err, errcap)) || (rc = dev(ctx, n + 2, &pos, err, errcap)))
+    if ((rc = c.alloc(n + 1, &out_n)) || (rc = c.alloc(n + 1, &out_start)) || (rc = c.alloc(n + 1, &out_off)) || (rc = c.alloc(n + 1, &out_e0)) ||
+        (rc = c.alloc(4, &cursor)) || (rc = c.alloc(n + 2, &n64)) || (rc = c.alloc(n + 2, &pos)))
         return rc;
     // first capacities of the three lists the passes fill through a cursor: a wrong guess costs one re-run (path_edge_cap, path_redo_cap and
     // path_ubc_cap set them for the tests of that re-run)
@@ -1164,18 +1154,18 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     ppart* gparts = nullptr;
     uint8_t* gm = nullptr;
     if (!snk_opt_u32(ctx, SNK_OPT_path_fused)) {          // default: split first pass (SNK_PATH_FUSED=1: the group kernel does it all)
-        if ((rc = dev(ctx, n * GPARTS + 1, &gparts, err, errcap)) || (rc = dev(ctx, n + 1, &gm, err, errcap))) return rc;
+        if ((rc = c.alloc(n * GPARTS + 1, &gparts)) || (rc = c.alloc(n + 1, &gm))) return rc;
     }
     uint32_t* redo = nullptr;
     uint64_t *slow_flag = nullptr, *slow_pos = nullptr;
     uint64_t rcap = cap0(SNK_OPT_path_redo_cap, n / 64 + 65536);
     for (int attempt = 0; attempt < 3; ++attempt) {
-        if (!scratch && (rc = dev(ctx, scap, &scratch, err, errcap))) return rc;
-        if (want_bcs && !ubk && (rc = dev(ctx, n + ubcap, &ubk, err, errcap))) return rc;
+        if (!scratch && (rc = c.alloc(scap, &scratch))) return rc;
+        if (want_bcs && !ubk && (rc = c.alloc(n + ubcap, &ubk))) return rc;
         SNK_HIP_TRY(hipMemsetAsync(cursor, 0, 32, st));
         a.out_off = out_off; a.out_n = out_n; a.out_e0 = out_e0; a.out_start = out_start; a.scratch = scratch; a.cursor = cursor; a.scratch_cap = scap;
         a.bc = want_bcs ? (const int32_t*)in->bc : nullptr; a.ub_first = ubk; a.ub_more = ubk ? ubk + n : nullptr; a.ub_cap = ubcap;
-        if (!redo && (rc = dev(ctx, rcap, &redo, err, errcap))) return rc;
+        if (!redo && (rc = c.alloc(rcap, &redo))) return rc;
         a.redo = redo; a.redo_cap = rcap; a.n_redo = 0; a.force_redo = snk_opt_u32(ctx, SNK_OPT_path_redo_all);
         a.gparts = gparts; a.gm = gm;
         if (n) {
@@ -1196,15 +1186,15 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
                 } else if (use_index) SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 0, 16, true>, grid, 256, 0, st, a));
                 else SNK_HIP_TRY(snk_launch(path_kernel<K, PCAP1, PMAX1, 0, 16, false>, grid, 256, 0, st, a));
                 // the reads it left, in read order
-                if (!slow_flag && ((rc = dev(ctx, n + 2, &slow_flag, err, errcap)) || (rc = dev(ctx, n + 2, &slow_pos, err, errcap)))) return rc;
+                if (!slow_flag && ((rc = c.alloc(n + 2, &slow_flag)) || (rc = c.alloc(n + 2, &slow_pos)))) return rc;
                 SNK_HIP_TRY(snk_launch(slow_flag_kernel, snk_blocks(n + 1, 256), 256, 0, st, gm, n, slow_flag));
-                if ((rc = scan64(ctx, st, slow_flag, slow_pos, n + 1, err, errcap))) return rc;
+                if ((rc = scan64(c, slow_flag, slow_pos, n + 1))) return rc;
                 uint64_t n_slow = 0;
                 SNK_HIP_TRY(hipMemcpyAsync(&n_slow, slow_pos + n, 8, hipMemcpyDeviceToHost, st));
                 SNK_HIP_TRY(snk_sync(st));
                 if (n_slow) {
                     uint32_t* slow;
-                    if ((rc = dev(ctx, n_slow + 1, &slow, err, errcap))) return rc;
+                    if ((rc = c.alloc(n_slow + 1, &slow))) return rc;
                     SNK_HIP_TRY(snk_launch(slow_fill_kernel, snk_blocks(n, 256), 256, 0, st, gm, slow_pos, n, slow));
                     a.slow = slow; a.n_slow = n_slow;
 #ifndef SNK_PATH_SLOW_GS
@@ -1244,13 +1234,13 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         if (b_over) { snk_ctx_release_block(ctx, ubk); ubk = nullptr; ubcap = h_cur[2] + 1024; out->retries |= 4u; }
     }
     SNK_HIP_TRY(snk_launch(widen_kernel, snk_blocks(n + 1, 256), 256, 0, st, out_n, n, n64));
-    if ((rc = scan64(ctx, st, n64, pos, n + 1, err, errcap))) return rc;
+    if ((rc = scan64(c, n64, pos, n + 1))) return rc;
     uint64_t total = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&total, pos + n, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
-    if ((rc = dev(ctx, total + 1, &edges, err, errcap))) return rc;
+    if ((rc = c.alloc(total + 1, &edges))) return rc;
     SNK_HIP_TRY(snk_launch(path_gather_kernel, snk_blocks(n, 256), 256, 0, st, out_n, out_e0, out_start, pos, scratch, n, edges));
-    SNK_HIP_TRY(hipEventRecord(e2, st));
+    SNK_HIP_TRY(c.stamp());
     SNK_HIP_TRY(snk_sync(st));
     snk_ctx_release_block(ctx, scratch);
     out->n_reads = n;
@@ -1260,15 +1250,15 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
     out->start = pos;
     out->edges = edges;
     out->dict_slots = cap;
-    (void)hipEventElapsedTime(&out->dict_ms, e0, e1);
-    (void)hipEventElapsedTime(&out->path_ms, e1, e2);
+    out->dict_ms = c.ms(0, 1);
+    out->path_ms = c.ms(1, 2);
     if (want_bcs) {
         // sort the keys, keep the first of every run, count per unitig: sorted distinct barcodes per unitig
         uint64_t nkeys = n + h_cur[2];
         if (flags & SNK_PATH_UNITIG_BCS_EXHAUSTIVE) {
             const uint64_t xcap = n * 16 + 1024;
             unsigned long long* xk;
-            if ((rc = dev(ctx, xcap, &xk, err, errcap))) return rc;
+            if ((rc = c.alloc(xcap, &xk))) return rc;
             SNK_HIP_TRY(hipMemsetAsync(cursor, 0, 8, st));
             SNK_HIP_TRY(snk_launch(ubc_exhaustive_kernel<K>, snk_blocks(n, 256), 256, 0, st, G, a.rows, a.row_words, a.read_len, a.lens,
                                    (const int32_t*)in->bc, n, xk, xcap, cursor));
@@ -1290,27 +1280,24 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         unsigned ubits = 1;
         while (ubits < 32 && (1ull << ubits) < U + 2) ++ubits;
         const unsigned end_bit = 32 + ubits;
-        size_t tb = 0;
-        uint8_t* tmp = nullptr;
-        if ((rc = dev(ctx, nkeys + 1, &ks, err, errcap)) || (rc = dev(ctx, nkeys + 2, &flag, err, errcap)) || (rc = dev(ctx, nkeys + 2, &upos, err, errcap)) ||
-            (rc = dev(ctx, U + 2, &per_u, err, errcap)) || (rc = dev(ctx, U + 2, &uoff_out, err, errcap)) || (rc = dev(ctx, nkeys + 1, &bcs, err, errcap)))
+        auto sort_keys = [&](void* tmp, size_t& tb) { return rocprim::radix_sort_keys(tmp, tb, ubk, ks, (size_t)nkeys, 0u, end_bit, st); };
+        snk_temp t;
+        if ((rc = c.alloc(nkeys + 1, &ks)) || (rc = c.alloc(nkeys + 2, &flag)) || (rc = c.alloc(nkeys + 2, &upos)) ||
+            (rc = c.alloc(U + 2, &per_u)) || (rc = c.alloc(U + 2, &uoff_out)) || (rc = c.alloc(nkeys + 1, &bcs)))
             return rc;
-        if (nkeys) {
-            SNK_HIP_TRY(rocprim::radix_sort_keys((void*)nullptr, tb, ubk, ks, (size_t)nkeys, 0u, end_bit, st));
-            if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-        }
-        SNK_HIP_TRY(hipEventRecord(e2b, st));
+        if (nkeys && (rc = c.temp(&t, sort_keys))) return rc;
+        SNK_HIP_TRY(c.stamp());
         uint64_t n_unique = 0;
         if (nkeys) {
-            SNK_HIP_TRY(rocprim::radix_sort_keys(tmp, tb, ubk, ks, (size_t)nkeys, 0u, end_bit, st));
+            SNK_HIP_TRY(sort_keys(t.p, t.bytes));
             SNK_HIP_TRY(snk_launch(ubc_flag_kernel, snk_blocks(nkeys + 1, 256), 256, 0, st, ks, nkeys, flag));
-            if ((rc = scan64(ctx, st, flag, upos, nkeys + 1, err, errcap))) return rc;
+            if ((rc = scan64(c, flag, upos, nkeys + 1))) return rc;
             SNK_HIP_TRY(hipMemcpyAsync(&n_unique, upos + nkeys, 8, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
         }
         SNK_HIP_TRY(hipMemsetAsync(per_u, 0, (U + 2) * 8, st));
         SNK_HIP_TRY(snk_launch(ubc_scatter_kernel, snk_blocks(nkeys, 256), 256, 0, st, ks, flag, upos, nkeys, bcs, per_u));
-        if ((rc = scan64(ctx, st, per_u, uoff_out, U + 1, err, errcap))) return rc;
+        if ((rc = scan64(c, per_u, uoff_out, U + 1))) return rc;
         SNK_HIP_TRY(hipGetLastError());
         SNK_HIP_TRY(snk_sync(st));
         if (!(flags & SNK_PATH_UNITIG_BCS_NOCUT) && U) {
@@ -1320,19 +1307,19 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
             const uint64_t cut = snk_opt_u32(ctx, SNK_OPT_unitig_bc_cut);
             uint64_t *clen, *noff2;
             uint32_t* any;
-            if ((rc = dev(ctx, U + 2, &clen, err, errcap)) || (rc = dev(ctx, U + 2, &noff2, err, errcap)) || (rc = dev(ctx, 4, &any, err, errcap))) return rc;
+            if ((rc = c.alloc(U + 2, &clen)) || (rc = c.alloc(U + 2, &noff2)) || (rc = c.alloc(4, &any))) return rc;
             SNK_HIP_TRY(hipMemsetAsync(any, 0, 4, st));
             SNK_HIP_TRY(snk_launch(ubc_cut_len_kernel, snk_blocks(U + 1, 256), 256, 0, st, uoff_out, U, cut, clen, any));
             uint32_t h_any = 0;
             SNK_HIP_TRY(hipMemcpyAsync(&h_any, any, 4, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
             if (h_any) {
-                if ((rc = scan64(ctx, st, clen, noff2, U + 1, err, errcap))) return rc;
+                if ((rc = scan64(c, clen, noff2, U + 1))) return rc;
                 uint64_t n_cut = 0;
                 SNK_HIP_TRY(hipMemcpyAsync(&n_cut, noff2 + U, 8, hipMemcpyDeviceToHost, st));
                 SNK_HIP_TRY(snk_sync(st));
                 uint32_t* bcs2;
-                if ((rc = dev(ctx, n_cut + 1, &bcs2, err, errcap))) return rc;
+                if ((rc = c.alloc(n_cut + 1, &bcs2))) return rc;
                 SNK_HIP_TRY(snk_launch(ubc_cut_copy_kernel, U, 64, 0, st, uoff_out, noff2, U, bcs, bcs2));
                 uoff_out = noff2; bcs = bcs2; n_unique = n_cut;
             }
@@ -1340,9 +1327,9 @@ int path_impl(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, uint64_t U,
         out->unitig_bc_off = uoff_out;
         out->unitig_bcs = bcs;
         out->n_unitig_bcs = n_unique;
-        SNK_HIP_TRY(hipEventRecord(e3, st));
+        SNK_HIP_TRY(c.stamp());
         SNK_HIP_TRY(snk_sync(st));
-        (void)hipEventElapsedTime(&out->bcs_ms, e2b, e3);
+        out->bcs_ms = c.ms(3, 4);
     }
     return SNK_OK;
 }
@@ -1357,26 +1344,18 @@ extern "C" int snk_dev_path_reads(snk_ctx* ctx, uint32_t K, const snk_dev_reads*
 extern "C" int snk_dev_path_reads2(snk_ctx* ctx, uint32_t K, const snk_dev_reads* in, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
                                    const snk_hbv* h, uint32_t flags, snk_dev_paths* out, void* stream, char* err, size_t errcap) {
     if (!ctx || !in || !h || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_path_reads: NULL argument");
+    memset(out, 0, sizeof *out);
     if (K != 48 && K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", K);
     if (in->n_reads && (!in->rows || !in->quals || in->read_len == 0 || in->read_len > 256 || in->row_words * 16 < in->read_len || in->row_words > 16))
         return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_path_reads: need packed rows and quality rows, reads of at most 256 bases");
     if (n_unitigs && (!d_unitig_off || !d_unitig_bases)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_path_reads: NULL unitig arrays");
     if (n_unitigs >= (1ull << 31)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_path_reads: too many unitigs");
-    memset(out, 0, sizeof *out);
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
     // the call's scratch (graph tables, dictionary, parts, sort buffers: ~0.3 KB per read + 40 B per unitig k-mer) goes back to the
     // arena when it returns; only the paths (and barcode lists) stay, until the context's next snk_dev_count_graph / snk_shard_step
-    const uint64_t mark = ctx->alloc_serial;
-    int rc;
-    try {
-        if (K == 48) rc = path_impl<48>(ctx, st, in, n_unitigs, (const uint64_t*)d_unitig_off, (const uint8_t*)d_unitig_bases, h, flags, out, err, errcap);
-        else rc = path_impl<60>(ctx, st, in, n_unitigs, (const uint64_t*)d_unitig_off, (const uint8_t*)d_unitig_bases, h, flags, out, err, errcap);
-    } catch (const std::bad_alloc&) { rc = snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_path_reads: host allocation failed"); }
-    (void)hipStreamSynchronize(st);          // also on the error paths: nothing of this call is still running when its scratch is handed back
-    const void* keep[6] = {out->offset, out->n_edges, out->start, out->edges, out->unitig_bc_off, out->unitig_bcs};
-    snk_ctx_release_since(ctx, mark, keep, rc ? 0 : 6);
-    if (rc) memset(out, 0, sizeof *out);
-    return rc;
+    path_host H;
+    return snk_call_run(ctx, stream, "snk_dev_path_reads", out, err, errcap, [&](snk_call& c) -> int {
+        const int rc = K == 48 ? path_impl<48>(c, H, in, n_unitigs, (const uint64_t*)d_unitig_off, (const uint8_t*)d_unitig_bases, h, flags, out, err, errcap)
+                               : path_impl<60>(c, H, in, n_unitigs, (const uint64_t*)d_unitig_off, (const uint8_t*)d_unitig_bases, h, flags, out, err, errcap);
+        return c.end(rc, {out->offset, out->n_edges, out->start, out->edges, out->unitig_bc_off, out->unitig_bcs});
+    });
 }

@@ -12,7 +12,7 @@
 // From(v_left)) -- so that a step is found iff v_left[e'] == v_right[e], and its id is from_pos[e'].
 //   px_size_kernel     record size per read (u8), the empty reads, the offsets that wrap, a path table that does not add up (start must
 //                      be the exclusive scan of n_edges and end at n_edges_total), n > 255
-//   px_range_kernel    the largest edge id (one outside the graph would index outside the three arrays: refused before the encoder runs)
+//   snk_max_edge_id    the largest edge id (one outside the graph would index outside the three arrays: refused before the encoder runs)
 //   exclusive scan     64-bit byte offsets (rocPRIM)
 //   px_index_kernel    ZipIndex: every 10th offset
 //   px_encode_kernel   a workgroup takes 256 consecutive reads (at most 71 bytes each: a static LDS tile); one lane per read walks its
@@ -31,7 +31,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_common.h"
 #include "snk_hbvadj.h"
 
@@ -44,14 +44,6 @@ constexpr unsigned X_TILE = XB * X_MAX_REC + 16;      // + the tile's misalignme
 constexpr uint64_t PX_GRID_CAP = 1u << 20;
 // bits of the flag word
 constexpr uint32_t F_TABLE = 1, F_LONG = 2, F_WALK = 4, F_BRANCH = 8, F_EDGE = 16;
-
-template <typename T>
-int dev(snk_ctx* ctx, size_t n, T** out, char* err, size_t errcap) {
-    void* q = nullptr;
-    int rc = snk_ctx_alloc(ctx, (n ? n : 1) * sizeof(T) + 16, &q, err, errcap);
-    *out = (T*)q;
-    return rc;
-}
 
 __host__ __device__ __forceinline__ uint32_t rec_bytes(uint32_t n) { return n ? 7u + (n + 2u) / 4u : 1u; }
 
@@ -96,20 +88,6 @@ __global__ void __launch_bounds__(XB) px_size_kernel(const unsigned long long* _
     const uint32_t slot = blockIdx.x & 255u;
     if (threadIdx.x == 0 && wg_empty) atomicAdd(&stat[slot], (unsigned long long)wg_empty);
     if (threadIdx.x == 0 && wg_wrap) atomicAdd(&stat[256 + slot], (unsigned long long)wg_wrap);
-}
-
-// edge ids compared as unsigned: a negative one is the largest
-__global__ void __launch_bounds__(XB) px_range_kernel(const uint32_t* __restrict__ edges, uint64_t n, uint32_t* __restrict__ range /* [256] */) {
-    uint32_t m = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * XB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * XB) m = max(m, edges[i]);
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-    __shared__ uint32_t wg_max;
-    if (threadIdx.x == 0) wg_max = 0;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(&wg_max, m);
-    __syncthreads();
-    const uint32_t slot = blockIdx.x & 255u;
-    if (threadIdx.x == 0 && wg_max > range[slot]) atomicMax(&range[slot], wg_max);
 }
 
 __global__ void __launch_bounds__(XB) px_index_kernel(const unsigned long long* __restrict__ off, uint64_t n_index, long long* __restrict__ index) {
@@ -225,15 +203,11 @@ __global__ void __launch_bounds__(XB) px_decode_kernel(const uint8_t* __restrict
     }
 }
 
-struct ev_pair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~ev_pair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
+}  // namespace
 
-// What the asynchronous uploads read on the host -- the lists and from_pos -- belongs to the caller (the extern "C" wrappers), which waits
-// for the stream before it lets go of them, whichever way the call ends.
-int zip_impl(snk_ctx* ctx, const snk_dev_paths* paths, const snk_hbv* h, snk_hbv_lists& ls, std::vector<uint8_t>& h_pos, snk_dev_pathsx* out, void* stream, char* err,
-             size_t errcap) {
+extern "C" int snk_dev_paths_zip(snk_ctx* ctx, const snk_dev_paths* paths, const snk_hbv* h, snk_dev_pathsx* out, void* stream, char* err, size_t errcap) {
+    if (!ctx || !paths || !h || !out || (h->n_edges > 0 && (!h->v_left || !h->v_right))) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: NULL argument");
+    memset(out, 0, sizeof *out);
     const uint64_t n = paths->n_edges_total, n_reads = paths->n_reads;
     const uint64_t E = (uint64_t)(h->n_edges > 0 ? h->n_edges : 0);
     if (n_reads && (!paths->start || !paths->n_edges || !paths->offset)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: paths without their device arrays");
@@ -241,101 +215,99 @@ int zip_impl(snk_ctx* ctx, const snk_dev_paths* paths, const snk_hbv* h, snk_hbv
     if (n && !E) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: %llu path entries on a graph without edges", (unsigned long long)n);
     if (!n_reads && n) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: start / n_edges do not add up to n_edges_total = %llu", (unsigned long long)n);
     if (n_reads >= (1ull << 40)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_zip: too many reads");
-    // the three per-edge arrays from the shared lists
-    int rc = snk_hbv_lists_build(h, &ls, "snk_dev_paths_zip", err, errcap);
-    if (rc) return rc;
-    h_pos.assign((size_t)E + 1, 0);
-    for (int32_t v = 0; v < h->n_vertices; ++v)
-        for (uint64_t i = ls.from_off[v]; i < ls.from_off[(size_t)v + 1]; ++i) {
-            const uint64_t j = i - ls.from_off[v];
-            if (j > 3)
-                return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_zip: vertex %d has more than four out-edges (a branch id has two bits)", v);
-            h_pos[ls.from_e[i]] = (uint8_t)j;
+    // What the asynchronous uploads read on the host -- from_pos here, the lists in unzip -- is declared in front of the frame: it is
+    // let go of after the frame's last wait, whichever way the call ends.
+    std::vector<uint8_t> h_pos;
+    // sizes, offsets, the per-edge arrays and the scan's scratch go back to the arena with the call; data and index stay until the
+    // context's next top-level call
+    return snk_call_run(ctx, stream, "snk_dev_paths_zip", out, err, errcap, [&](snk_call& c) -> int {
+        // the three per-edge arrays from the shared lists
+        snk_hbv_lists ls;
+        int rc = snk_hbv_lists_build(h, &ls, "snk_dev_paths_zip", err, errcap);
+        if (rc) return rc;
+        h_pos.assign((size_t)E + 1, 0);
+        for (int32_t v = 0; v < h->n_vertices; ++v)
+            for (uint64_t i = ls.from_off[v]; i < ls.from_off[(size_t)v + 1]; ++i) {
+                const uint64_t j = i - ls.from_off[v];
+                if (j > 3)
+                    return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_zip: vertex %d has more than four out-edges (a branch id has two bits)", v);
+                h_pos[ls.from_e[i]] = (uint8_t)j;
+            }
+        const hipStream_t st = c.st;
+        SNK_HIP_TRY(c.stamp());
+        const uint64_t n_index = (n_reads + X_SKIP - 1) / X_SKIP, n_tiles = snk_blocks(n_reads, XB);
+        long long* index;
+        unsigned long long *off, *stat;
+        uint8_t *sz, *d_pos;
+        int32_t *d_vl, *d_vr;
+        uint32_t *range, *tile_nf;
+        // (the result first: what is handed back behind it coalesces; data follows when its size is known)
+        if ((rc = c.alloc(n_index, &index)) || (rc = c.alloc(n_reads + 1, &off)) || (rc = c.alloc(n_reads + 1, &sz)) || (rc = c.alloc(E, &d_vl)) || (rc = c.alloc(E, &d_vr)) ||
+            (rc = c.alloc(E, &d_pos)) || (rc = c.alloc(512 + 1, &stat)) || (rc = c.alloc(256 + 1, &range)) || (rc = c.alloc(n_tiles, &tile_nf)))
+            return rc;
+        SNK_HIP_TRY(hipMemsetAsync(stat, 0, 513 * 8, st));
+        SNK_HIP_TRY(hipMemsetAsync(range, 0, 257 * 4, st));
+        if (E) {
+            SNK_HIP_TRY(hipMemcpyAsync(d_vl, h->v_left, E * 4, hipMemcpyHostToDevice, st));
+            SNK_HIP_TRY(hipMemcpyAsync(d_vr, h->v_right, E * 4, hipMemcpyHostToDevice, st));
+            SNK_HIP_TRY(hipMemcpyAsync(d_pos, h_pos.data(), E, hipMemcpyHostToDevice, st));
         }
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    ev_pair ev;
-    SNK_HIP_TRY(hipEventCreate(&ev.a)); SNK_HIP_TRY(hipEventCreate(&ev.b));
-    SNK_HIP_TRY(hipEventRecord(ev.a, st));
-    const uint64_t n_index = (n_reads + X_SKIP - 1) / X_SKIP, n_tiles = snk_blocks(n_reads, XB);
-    long long* index;
-    unsigned long long *off, *stat;
-    uint8_t *sz, *d_pos;
-    int32_t *d_vl, *d_vr;
-    uint32_t *range, *tile_nf;
-    // (the result first: what is handed back behind it coalesces; data follows when its size is known)
-    if ((rc = dev(ctx, n_index, &index, err, errcap)) || (rc = dev(ctx, n_reads + 1, &off, err, errcap)) || (rc = dev(ctx, n_reads + 1, &sz, err, errcap)) ||
-        (rc = dev(ctx, E, &d_vl, err, errcap)) || (rc = dev(ctx, E, &d_vr, err, errcap)) || (rc = dev(ctx, E, &d_pos, err, errcap)) ||
-        (rc = dev(ctx, 512 + 1, &stat, err, errcap)) || (rc = dev(ctx, 256 + 1, &range, err, errcap)) || (rc = dev(ctx, n_tiles, &tile_nf, err, errcap)))
-        return rc;
-    SNK_HIP_TRY(hipMemsetAsync(stat, 0, 513 * 8, st));
-    SNK_HIP_TRY(hipMemsetAsync(range, 0, 257 * 4, st));
-    if (E) {
-        SNK_HIP_TRY(hipMemcpyAsync(d_vl, h->v_left, E * 4, hipMemcpyHostToDevice, st));
-        SNK_HIP_TRY(hipMemcpyAsync(d_vr, h->v_right, E * 4, hipMemcpyHostToDevice, st));
-        SNK_HIP_TRY(hipMemcpyAsync(d_pos, h_pos.data(), E, hipMemcpyHostToDevice, st));
-    }
-    uint32_t* flags = range + 256;
-    SNK_HIP_TRY(snk_launch(px_size_kernel, snk_blocks_capped(n_reads + 1, XB, PX_GRID_CAP), XB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges,
-                           (const int32_t*)paths->offset, n_reads, n, sz, stat, flags));
-    if (n) SNK_HIP_TRY(snk_launch(px_range_kernel, snk_blocks_capped(n, XB * 8, PX_GRID_CAP), XB, 0, st, (const uint32_t*)paths->edges, n, range));
-    {
-        rocprim::transform_iterator<const uint8_t*, u8_to_u64, unsigned long long> in(sz, u8_to_u64());
-        size_t tb = 0;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, in, off, 0ull, (size_t)(n_reads + 1), rocprim::plus<unsigned long long>(), st));
-        uint8_t* tmp;
-        if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)tmp, tb, in, off, 0ull, (size_t)(n_reads + 1), rocprim::plus<unsigned long long>(), st));
-    }
-    uint32_t h_range[257];
-    unsigned long long n_bytes = 0;
-    SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(hipMemcpyAsync(&n_bytes, off + n_reads, 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    uint32_t emax = 0;
-    for (int q = 0; q < 256; ++q) emax = std::max(emax, h_range[q]);
-    if (h_range[256] & F_TABLE) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: start / n_edges do not add up to n_edges_total = %llu", (unsigned long long)n);
-    if (n && emax >= E)
-        return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: a path holds edge id %lld, the graph has %llu edges", (long long)(int32_t)emax, (unsigned long long)E);
-    if (h_range[256] & F_LONG)
-        return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_zip: a path of more than 255 edges (the record's edge count is one byte)");
-    if (n_bytes > n_reads * (unsigned long long)X_MAX_REC) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_paths_zip: the scan's total is out of range");
-    uint8_t* data;
-    if ((rc = dev(ctx, (size_t)n_bytes, &data, err, errcap))) return rc;
-    if ((uintptr_t)data & 15u) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_paths_zip: the arena handed out a block that is not 16-byte aligned");
-    SNK_HIP_TRY(snk_launch(px_index_kernel, snk_blocks_capped(n_index, XB, PX_GRID_CAP), XB, 0, st, (const unsigned long long*)off, n_index, index));
-    if (n_tiles)
-        SNK_HIP_TRY(snk_launch(px_encode_kernel, snk_blocks_capped(n_tiles, 1, PX_GRID_CAP), XB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges,
-                               (const int32_t*)paths->offset, (const uint32_t*)paths->edges, (const int32_t*)d_vl, (const int32_t*)d_vr, (const uint8_t*)d_pos,
-                               (const unsigned long long*)off, n_reads, n_tiles, data, tile_nf));
-    if (n_tiles) {
-        rocprim::transform_iterator<const uint32_t*, u32_to_u64, unsigned long long> in(tile_nf, u32_to_u64());
-        size_t tb = 0;
-        SNK_HIP_TRY(rocprim::reduce((void*)nullptr, tb, in, stat + 512, 0ull, (size_t)n_tiles, rocprim::plus<unsigned long long>(), st));
-        uint8_t* tmp;
-        if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-        SNK_HIP_TRY(rocprim::reduce((void*)tmp, tb, in, stat + 512, 0ull, (size_t)n_tiles, rocprim::plus<unsigned long long>(), st));
-    }
-    unsigned long long h_stat[513];
-    SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(hipEventRecord(ev.b, st));
-    SNK_HIP_TRY(snk_sync(st));
-    uint64_t n_empty = 0, n_wrap = 0;
-    for (int q = 0; q < 256; ++q) { n_empty += h_stat[q]; n_wrap += h_stat[256 + q]; }
-    out->n_reads = n_reads;
-    out->n_bytes = n_bytes;
-    out->n_index = n_index;
-    out->data = data;
-    out->index = index;
-    out->n_empty = n_empty;
-    out->n_steps_not_found = h_stat[512];
-    out->n_offsets_wrapped = n_wrap;
-    (void)hipEventElapsedTime(&out->ms, ev.a, ev.b);
-    return SNK_OK;
+        uint32_t* flags = range + 256;
+        SNK_HIP_TRY(snk_launch(px_size_kernel, snk_blocks_capped(n_reads + 1, XB, PX_GRID_CAP), XB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges,
+                               (const int32_t*)paths->offset, n_reads, n, sz, stat, flags));
+        if (n) SNK_HIP_TRY(snk_max_edge_id((const uint32_t*)paths->edges, n, range, st));
+        {
+            rocprim::transform_iterator<const uint8_t*, u8_to_u64, unsigned long long> in(sz, u8_to_u64());
+            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, in, off, 0ull, (size_t)(n_reads + 1), rocprim::plus<unsigned long long>(), st); })))
+                return rc;
+        }
+        uint32_t h_range[257];
+        unsigned long long n_bytes = 0;
+        SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(hipMemcpyAsync(&n_bytes, off + n_reads, 8, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(snk_sync(st));
+        uint32_t emax = 0;
+        for (int q = 0; q < 256; ++q) emax = std::max(emax, h_range[q]);
+        if (h_range[256] & F_TABLE) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: start / n_edges do not add up to n_edges_total = %llu", (unsigned long long)n);
+        if (n && emax >= E)
+            return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: a path holds edge id %lld, the graph has %llu edges", (long long)(int32_t)emax, (unsigned long long)E);
+        if (h_range[256] & F_LONG)
+            return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_zip: a path of more than 255 edges (the record's edge count is one byte)");
+        if (n_bytes > n_reads * (unsigned long long)X_MAX_REC) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_paths_zip: the scan's total is out of range");
+        uint8_t* data;
+        if ((rc = c.alloc((size_t)n_bytes, &data))) return rc;
+        if ((uintptr_t)data & 15u) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_paths_zip: the arena handed out a block that is not 16-byte aligned");
+        SNK_HIP_TRY(snk_launch(px_index_kernel, snk_blocks_capped(n_index, XB, PX_GRID_CAP), XB, 0, st, (const unsigned long long*)off, n_index, index));
+        if (n_tiles) {
+            SNK_HIP_TRY(snk_launch(px_encode_kernel, snk_blocks_capped(n_tiles, 1, PX_GRID_CAP), XB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges,
+                                   (const int32_t*)paths->offset, (const uint32_t*)paths->edges, (const int32_t*)d_vl, (const int32_t*)d_vr, (const uint8_t*)d_pos,
+                                   (const unsigned long long*)off, n_reads, n_tiles, data, tile_nf));
+            rocprim::transform_iterator<const uint32_t*, u32_to_u64, unsigned long long> in(tile_nf, u32_to_u64());
+            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::reduce(tmp, tb, in, stat + 512, 0ull, (size_t)n_tiles, rocprim::plus<unsigned long long>(), st); })))
+                return rc;
+        }
+        unsigned long long h_stat[513];
+        SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(c.stamp());
+        SNK_HIP_TRY(snk_sync(st));
+        uint64_t n_empty = 0, n_wrap = 0;
+        for (int q = 0; q < 256; ++q) { n_empty += h_stat[q]; n_wrap += h_stat[256 + q]; }
+        out->n_reads = n_reads;
+        out->n_bytes = n_bytes;
+        out->n_index = n_index;
+        out->data = data;
+        out->index = index;
+        out->n_empty = n_empty;
+        out->n_steps_not_found = h_stat[512];
+        out->n_offsets_wrapped = n_wrap;
+        out->ms = c.ms(0, 1);
+        return c.end(SNK_OK, {data, index});
+    });
 }
 
-int unzip_impl(snk_ctx* ctx, const snk_dev_pathsx* in, const snk_hbv* h, snk_hbv_lists& ls, snk_dev_paths* out, void* stream, char* err, size_t errcap) {
+extern "C" int snk_dev_paths_unzip(snk_ctx* ctx, const snk_dev_pathsx* in, const snk_hbv* h, snk_dev_paths* out, void* stream, char* err, size_t errcap) {
+    if (!ctx || !in || !h || !out || (h->n_edges > 0 && (!h->v_left || !h->v_right))) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: NULL argument");
+    memset(out, 0, sizeof *out);
     const uint64_t n_reads = in->n_reads, n_bytes = in->n_bytes, n_index = in->n_index;
     const uint64_t E = (uint64_t)(h->n_edges > 0 ? h->n_edges : 0), N = (uint64_t)(h->n_vertices > 0 ? h->n_vertices : 0);
     if (n_index != (n_reads + X_SKIP - 1) / X_SKIP)
@@ -343,95 +315,55 @@ int unzip_impl(snk_ctx* ctx, const snk_dev_pathsx* in, const snk_hbv* h, snk_hbv
     if ((n_bytes && !in->data) || (n_index && !in->index)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: NULL data or index");
     if (n_bytes < n_reads || n_bytes > n_reads * (uint64_t)X_MAX_REC)
         return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: %llu bytes cannot hold %llu records", (unsigned long long)n_bytes, (unsigned long long)n_reads);
-    int rc = snk_hbv_lists_build(h, &ls, "snk_dev_paths_unzip", err, errcap);
-    if (rc) return rc;
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    ev_pair ev;
-    SNK_HIP_TRY(hipEventCreate(&ev.a)); SNK_HIP_TRY(hipEventCreate(&ev.b));
-    SNK_HIP_TRY(hipEventRecord(ev.a, st));
-    int32_t *offset, *edges, *d_vr, *d_fe;
-    uint32_t *ne, *flags;
-    unsigned long long *start, *rec_off, *d_fo;
-    if ((rc = dev(ctx, n_reads, &offset, err, errcap)) || (rc = dev(ctx, n_reads + 1, &ne, err, errcap)) || (rc = dev(ctx, n_reads + 1, &start, err, errcap)) ||
-        (rc = dev(ctx, n_reads, &rec_off, err, errcap)) || (rc = dev(ctx, E, &d_vr, err, errcap)) || (rc = dev(ctx, E, &d_fe, err, errcap)) ||
-        (rc = dev(ctx, N + 1, &d_fo, err, errcap)) || (rc = dev(ctx, 4, &flags, err, errcap)))
-        return rc;
-    SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
-    SNK_HIP_TRY(hipMemcpyAsync(d_fo, ls.from_off.data(), (N + 1) * 8, hipMemcpyHostToDevice, st));
-    if (E) {
-        SNK_HIP_TRY(hipMemcpyAsync(d_vr, h->v_right, E * 4, hipMemcpyHostToDevice, st));
-        SNK_HIP_TRY(hipMemcpyAsync(d_fe, ls.from_e.data(), E * 4, hipMemcpyHostToDevice, st));
-    }
-    SNK_HIP_TRY(snk_launch(px_walk_kernel, snk_blocks_capped(n_index + 1, XB, PX_GRID_CAP), XB, 0, st, (const uint8_t*)in->data, n_bytes, (const long long*)in->index, n_index, n_reads,
-                           rec_off, ne, flags));
-    {
-        rocprim::transform_iterator<const uint32_t*, u32_to_u64, unsigned long long> it(ne, u32_to_u64());
-        size_t tb = 0;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, it, start, 0ull, (size_t)(n_reads + 1), rocprim::plus<unsigned long long>(), st));
-        uint8_t* tmp;
-        if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)tmp, tb, it, start, 0ull, (size_t)(n_reads + 1), rocprim::plus<unsigned long long>(), st));
-    }
-    uint32_t h_flags = 0;
-    unsigned long long total = 0;
-    SNK_HIP_TRY(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(hipMemcpyAsync(&total, start + n_reads, 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    if (h_flags & F_WALK)
-        return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: the records do not follow the index or do not end at n_bytes = %llu", (unsigned long long)n_bytes);
-    if (total > n_reads * 255ull) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_paths_unzip: the scan's total is out of range");
-    if (total && !E) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: %llu path entries on a graph without edges", total);
-    if ((rc = dev(ctx, (size_t)total, &edges, err, errcap))) return rc;
-    SNK_HIP_TRY(snk_launch(px_decode_kernel, snk_blocks_capped(n_reads, XB, PX_GRID_CAP), XB, 0, st, (const uint8_t*)in->data, (const unsigned long long*)rec_off, (const uint32_t*)ne,
-                           (const unsigned long long*)start, n_reads, E, (const int32_t*)d_vr, (const unsigned long long*)d_fo, (const int32_t*)d_fe, offset, edges, flags));
-    SNK_HIP_TRY(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(hipEventRecord(ev.b, st));
-    SNK_HIP_TRY(snk_sync(st));
-    if (h_flags & F_EDGE) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: a record's first edge id is outside the graph (%llu edges)", (unsigned long long)E);
-    if (h_flags & F_BRANCH) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: a branch id points past the out-edges of its vertex");
-    out->n_reads = n_reads;
-    out->n_edges_total = total;
-    out->offset = offset;
-    out->n_edges = ne;
-    out->start = start;
-    out->edges = edges;
-    (void)hipEventElapsedTime(&out->path_ms, ev.a, ev.b);
-    return SNK_OK;
-}
-
-}  // namespace
-
-extern "C" int snk_dev_paths_zip(snk_ctx* ctx, const snk_dev_paths* paths, const snk_hbv* h, snk_dev_pathsx* out, void* stream, char* err, size_t errcap) {
-    if (!ctx || !paths || !h || !out || (h->n_edges > 0 && (!h->v_left || !h->v_right))) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_zip: NULL argument");
-    // sizes, offsets, the per-edge arrays and the scan's scratch go back to the arena with the call; data and index stay until the
-    // context's next top-level call
-    const uint64_t mark = ctx->alloc_serial;
-    memset(out, 0, sizeof *out);
-    int rc;
     snk_hbv_lists ls;
-    std::vector<uint8_t> h_pos;
-    try { rc = zip_impl(ctx, paths, h, ls, h_pos, out, stream, err, errcap); }
-    catch (const std::bad_alloc&) { rc = snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_paths_zip: host allocation failed"); }
-    (void)hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream);
-    const void* keep[2] = {out->data, out->index};
-    snk_ctx_release_since(ctx, mark, keep, rc ? 0 : 2);
-    if (rc) memset(out, 0, sizeof *out);
-    return rc;
-}
-
-extern "C" int snk_dev_paths_unzip(snk_ctx* ctx, const snk_dev_pathsx* in, const snk_hbv* h, snk_dev_paths* out, void* stream, char* err, size_t errcap) {
-    if (!ctx || !in || !h || !out || (h->n_edges > 0 && (!h->v_left || !h->v_right))) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: NULL argument");
-    const uint64_t mark = ctx->alloc_serial;
-    memset(out, 0, sizeof *out);
-    int rc;
-    snk_hbv_lists ls;
-    try { rc = unzip_impl(ctx, in, h, ls, out, stream, err, errcap); }
-    catch (const std::bad_alloc&) { rc = snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_paths_unzip: host allocation failed"); }
-    (void)hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream);
-    const void* keep[4] = {out->offset, out->n_edges, out->start, out->edges};
-    snk_ctx_release_since(ctx, mark, keep, rc ? 0 : 4);
-    if (rc) memset(out, 0, sizeof *out);
-    return rc;
+    return snk_call_run(ctx, stream, "snk_dev_paths_unzip", out, err, errcap, [&](snk_call& c) -> int {
+        int rc = snk_hbv_lists_build(h, &ls, "snk_dev_paths_unzip", err, errcap);
+        if (rc) return rc;
+        const hipStream_t st = c.st;
+        SNK_HIP_TRY(c.stamp());
+        int32_t *offset, *edges, *d_vr, *d_fe;
+        uint32_t *ne, *flags;
+        unsigned long long *start, *rec_off, *d_fo;
+        if ((rc = c.alloc(n_reads, &offset)) || (rc = c.alloc(n_reads + 1, &ne)) || (rc = c.alloc(n_reads + 1, &start)) || (rc = c.alloc(n_reads, &rec_off)) ||
+            (rc = c.alloc(E, &d_vr)) || (rc = c.alloc(E, &d_fe)) || (rc = c.alloc(N + 1, &d_fo)) || (rc = c.alloc(4, &flags)))
+            return rc;
+        SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));
+        SNK_HIP_TRY(hipMemcpyAsync(d_fo, ls.from_off.data(), (N + 1) * 8, hipMemcpyHostToDevice, st));
+        if (E) {
+            SNK_HIP_TRY(hipMemcpyAsync(d_vr, h->v_right, E * 4, hipMemcpyHostToDevice, st));
+            SNK_HIP_TRY(hipMemcpyAsync(d_fe, ls.from_e.data(), E * 4, hipMemcpyHostToDevice, st));
+        }
+        SNK_HIP_TRY(snk_launch(px_walk_kernel, snk_blocks_capped(n_index + 1, XB, PX_GRID_CAP), XB, 0, st, (const uint8_t*)in->data, n_bytes, (const long long*)in->index, n_index, n_reads,
+                               rec_off, ne, flags));
+        {
+            rocprim::transform_iterator<const uint32_t*, u32_to_u64, unsigned long long> it(ne, u32_to_u64());
+            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, it, start, 0ull, (size_t)(n_reads + 1), rocprim::plus<unsigned long long>(), st); })))
+                return rc;
+        }
+        uint32_t h_flags = 0;
+        unsigned long long total = 0;
+        SNK_HIP_TRY(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(hipMemcpyAsync(&total, start + n_reads, 8, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(snk_sync(st));
+        if (h_flags & F_WALK)
+            return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: the records do not follow the index or do not end at n_bytes = %llu", (unsigned long long)n_bytes);
+        if (total > n_reads * 255ull) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_paths_unzip: the scan's total is out of range");
+        if (total && !E) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: %llu path entries on a graph without edges", total);
+        if ((rc = c.alloc((size_t)total, &edges))) return rc;
+        SNK_HIP_TRY(snk_launch(px_decode_kernel, snk_blocks_capped(n_reads, XB, PX_GRID_CAP), XB, 0, st, (const uint8_t*)in->data, (const unsigned long long*)rec_off, (const uint32_t*)ne,
+                               (const unsigned long long*)start, n_reads, E, (const int32_t*)d_vr, (const unsigned long long*)d_fo, (const int32_t*)d_fe, offset, edges, flags));
+        SNK_HIP_TRY(hipMemcpyAsync(&h_flags, flags, 4, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(c.stamp());
+        SNK_HIP_TRY(snk_sync(st));
+        if (h_flags & F_EDGE) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: a record's first edge id is outside the graph (%llu edges)", (unsigned long long)E);
+        if (h_flags & F_BRANCH) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_unzip: a branch id points past the out-edges of its vertex");
+        out->n_reads = n_reads;
+        out->n_edges_total = total;
+        out->offset = offset;
+        out->n_edges = ne;
+        out->start = start;
+        out->edges = edges;
+        out->path_ms = c.ms(0, 1);
+        return c.end(SNK_OK, {offset, ne, start, edges});
+    });
 }

@@ -9,7 +9,7 @@
 // entries by edge id that carries the read id:
 //   pidx_fill_kernel     read id of every entry (one thread per read writes its own n_edges ids: entries of neighbouring reads are
 //                        neighbours, the stores coalesce)
-//   pidx_range_kernel    the largest edge id (an id outside [0, E) would index outside the offset table: refused before anything is written)
+//   max_edge_id_kernel   the largest edge id (an id outside [0, E) would index outside the offset table: refused before anything is written)
 //   radix sort           stable LSD over the ceil(log2 E) key bits there are (14 on the bench graph's 7 605 unitigs, 24 at 12 M edges):
 //                        digit histograms in LDS per workgroup, no atomic per entry anywhere -- a handful of edges hold most entries.
 //                        rocPRIM's radix_sort_pairs, as in MarkDups (snk_dups.hip): the whole call runs at 2.9 TB/s of the data it has
@@ -23,20 +23,12 @@
 #include <vector>
 #include <rocprim/rocprim.hpp>
 
-#include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_common.h"
 
 namespace {
 
 constexpr unsigned PB = 256;
-
-template <typename T>
-int dev(snk_ctx* ctx, size_t n, T** out, char* err, size_t errcap) {
-    void* q = nullptr;
-    int rc = snk_ctx_alloc(ctx, (n ? n : 1) * sizeof(T) + 16, &q, err, errcap);
-    *out = (T*)q;
-    return rc;
-}
 
 // every launch of this file: a grid that covers its work items at PB a workgroup, cut at 2^20 workgroups -- the kernels stride over
 // what is left, with 64-bit indices
@@ -51,16 +43,22 @@ __global__ void __launch_bounds__(PB) pidx_fill_kernel(const unsigned long long*
     }
 }
 
-// 16 bytes per lane: four edge ids per load; slot = one of 256 words, looked at before it is touched (it stops moving early)
-__global__ void __launch_bounds__(PB) pidx_range_kernel(const uint32_t* __restrict__ edges, uint64_t n, uint32_t* __restrict__ range /* [256] */) {
+// The largest edge id, compared as unsigned.  16 bytes per lane where the pointer allows: the (up to three) ids before the first 16-byte
+// boundary and behind the last whole uint4 are peeled by workgroup 0.  slot = one of 256 words, looked at before it is touched (it
+// stops moving early).
+__global__ void __launch_bounds__(PB) max_edge_id_kernel(const uint32_t* __restrict__ edges, uint64_t n, uint32_t* __restrict__ range /* [256] */) {
     uint32_t m = 0;
-    const uint64_t n4 = n / 4;
-    const uint4* e4 = reinterpret_cast<const uint4*>(edges);
+    const uint64_t head = min(n, (uint64_t)((0u - (uint32_t)((uintptr_t)edges >> 2)) & 3u));
+    const uint64_t n4 = (n - head) / 4, tail = head + n4 * 4;
+    const uint4* e4 = reinterpret_cast<const uint4*>(edges + head);
     for (uint64_t i = (uint64_t)blockIdx.x * PB + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * PB) {
         const uint4 v = e4[i];
         m = max(max(m, v.x), max(max(v.y, v.z), v.w));
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3ull)) m = max(m, edges[n4 * 4 + threadIdx.x]);
+    if (blockIdx.x == 0) {
+        if (threadIdx.x < head) m = max(m, edges[threadIdx.x]);
+        if (threadIdx.x < n - tail) m = max(m, edges[tail + threadIdx.x]);
+    }
     for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
     __shared__ uint32_t wg_max;
     if (threadIdx.x == 0) wg_max = 0;
@@ -129,24 +127,14 @@ __global__ void __launch_bounds__(PB) pidx_counts_kernel(const unsigned long lon
 
 }  // namespace
 
-static int paths_index_impl(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E, const int32_t* inv, snk_dev_pidx* out, void* stream, char* err, size_t errcap);
-
-extern "C" int snk_dev_paths_index(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t n_hbv_edges, const int32_t* inv, snk_dev_pidx* out, void* stream,
-                                   char* err, size_t errcap) {
-    if (!ctx || !paths || !out || (n_hbv_edges && !inv)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: NULL argument");
-    // the read ids in path order, the sorted keys, the involution and the sort's own scratch go back to the arena with the call; offsets,
-    // ids and counts stay until the context's next top-level call
-    const uint64_t mark = ctx->alloc_serial;
-    memset(out, 0, sizeof *out);
-    const int rc = paths_index_impl(ctx, paths, n_hbv_edges, inv, out, stream, err, errcap);
-    (void)hipStreamSynchronize(stream ? (hipStream_t)stream : ctx->stream);
-    const void* keep[3] = {out->index_off, out->index_ids, out->counts};
-    snk_ctx_release_since(ctx, mark, keep, rc ? 0 : 3);
-    if (rc) memset(out, 0, sizeof *out);
-    return rc;
+hipError_t snk_max_edge_id(const uint32_t* edges, uint64_t n, uint32_t* range, hipStream_t st) {
+    return snk_launch(max_edge_id_kernel, snk_blocks_capped(n / 4 + 1, PB, PIDX_GRID_CAP), PB, 0, st, edges, n, range);
 }
 
-static int paths_index_impl(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E, const int32_t* inv, snk_dev_pidx* out, void* stream, char* err, size_t errcap) {
+extern "C" int snk_dev_paths_index(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E, const int32_t* inv, snk_dev_pidx* out, void* stream, char* err,
+                                   size_t errcap) {
+    if (!ctx || !paths || !out || (E && !inv)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: NULL argument");
+    memset(out, 0, sizeof *out);
     const uint64_t n = paths->n_edges_total, n_reads = paths->n_reads;
     if (E > 0x7FFFFFFFull) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: %llu HBV edges (edge ids are int32)", (unsigned long long)E);
     if (n && (!paths->start || !paths->n_edges || !paths->edges)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: paths without their device arrays");
@@ -158,64 +146,59 @@ static int paths_index_impl(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E
         if (r < 0 || (uint64_t)r >= E || (uint64_t)inv[r] != e)
             return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: inv is not an involution of [0, %llu) at edge %llu", (unsigned long long)E, (unsigned long long)e);
     }
-    SNK_HIP_TRY(snk_enter(ctx));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    hipEvent_t e0, e1;
-    SNK_HIP_TRY(hipEventCreate(&e0)); SNK_HIP_TRY(hipEventCreate(&e1));
-    struct evg { hipEvent_t a, b; ~evg() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } g{e0, e1};
-    SNK_HIP_TRY(hipEventRecord(e0, st));
-    int rc;
-    unsigned long long *off, *ids, *rid, *stat;
-    int32_t *counts, *d_inv;
-    uint32_t *skey, *range;
-    // (results first: what is handed back behind them coalesces)
-    if ((rc = dev(ctx, E + 1, &off, err, errcap)) || (rc = dev(ctx, n, &ids, err, errcap)) || (rc = dev(ctx, E, &counts, err, errcap)) ||
-        (rc = dev(ctx, n, &rid, err, errcap)) || (rc = dev(ctx, n + 4, &skey, err, errcap)) || (rc = dev(ctx, E, &d_inv, err, errcap)) ||
-        (rc = dev(ctx, 512, &stat, err, errcap)) || (rc = dev(ctx, 256 + 1, &range, err, errcap)))
-        return rc;
-    SNK_HIP_TRY(hipMemsetAsync(stat, 0, 512 * 8, st));
-    SNK_HIP_TRY(hipMemsetAsync(range, 0, 257 * 4, st));
-    if (E) SNK_HIP_TRY(hipMemcpyAsync(d_inv, inv, E * 4, hipMemcpyHostToDevice, st));
-    uint32_t key_bits = 0;
-    while (key_bits < 32 && (1ull << key_bits) < E) ++key_bits;
-    if (n) {
-        SNK_HIP_TRY(snk_launch(pidx_fill_kernel, snk_blocks_capped(n_reads, PB, PIDX_GRID_CAP), PB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges, n_reads, n, rid,
-                               range + 256));
-        SNK_HIP_TRY(snk_launch(pidx_range_kernel, snk_blocks_capped(n / 4 + 1, PB, PIDX_GRID_CAP), PB, 0, st, (const uint32_t*)paths->edges, n, range));
-        uint32_t h_range[257];
-        SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
+    // the read ids in path order, the sorted keys, the involution and the sort's own scratch go back to the arena with the call; offsets,
+    // ids and counts stay until the context's next top-level call
+    return snk_call_run(ctx, stream, "snk_dev_paths_index", out, err, errcap, [&](snk_call& c) -> int {
+        const hipStream_t st = c.st;
+        SNK_HIP_TRY(c.stamp());
+        int rc;
+        unsigned long long *off, *ids, *rid, *stat;
+        int32_t *counts, *d_inv;
+        uint32_t *skey, *range;
+        // (results first: what is handed back behind them coalesces)
+        if ((rc = c.alloc(E + 1, &off)) || (rc = c.alloc(n, &ids)) || (rc = c.alloc(E, &counts)) || (rc = c.alloc(n, &rid)) || (rc = c.alloc(n + 4, &skey)) ||
+            (rc = c.alloc(E, &d_inv)) || (rc = c.alloc(512, &stat)) || (rc = c.alloc(256 + 1, &range)))
+            return rc;
+        SNK_HIP_TRY(hipMemsetAsync(stat, 0, 512 * 8, st));
+        SNK_HIP_TRY(hipMemsetAsync(range, 0, 257 * 4, st));
+        if (E) SNK_HIP_TRY(hipMemcpyAsync(d_inv, inv, E * 4, hipMemcpyHostToDevice, st));
+        uint32_t key_bits = 0;
+        while (key_bits < 32 && (1ull << key_bits) < E) ++key_bits;
+        if (n) {
+            SNK_HIP_TRY(snk_launch(pidx_fill_kernel, snk_blocks_capped(n_reads, PB, PIDX_GRID_CAP), PB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges, n_reads, n,
+                                   rid, range + 256));
+            SNK_HIP_TRY(snk_max_edge_id((const uint32_t*)paths->edges, n, range, st));
+            uint32_t h_range[257];
+            SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(snk_sync(st));
+            uint32_t emax = 0;
+            for (int q = 0; q < 256; ++q) emax = std::max(emax, h_range[q]);
+            if (h_range[256]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: start / n_edges do not add up to n_edges_total = %llu", (unsigned long long)n);
+            if (emax >= E)
+                return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: a path holds edge id %lld, the graph has %llu edges", (long long)(int32_t)emax, (unsigned long long)E);
+            const uint32_t bits = std::max(1u, key_bits);
+            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)paths->edges, skey, rid, ids, (size_t)n, 0u, bits, st); })))
+                return rc;
+        }
+        SNK_HIP_TRY(snk_launch(pidx_offsets_kernel, snk_blocks_capped(n ? (n + 3) / 4 : E + 1, PB, PIDX_GRID_CAP), PB, 0, st, skey, n, E, off));
+        if (E) SNK_HIP_TRY(snk_launch(pidx_counts_kernel, snk_blocks_capped(E, PB, PIDX_GRID_CAP), PB, 0, st, off, d_inv, E, counts, stat));
+        unsigned long long h_stat[512];
+        SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(c.stamp());
         SNK_HIP_TRY(snk_sync(st));
-        uint32_t emax = 0;
-        for (int q = 0; q < 256; ++q) emax = std::max(emax, h_range[q]);
-        if (h_range[256]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: start / n_edges do not add up to n_edges_total = %llu", (unsigned long long)n);
-        if (emax >= E)
-            return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: a path holds edge id %lld, the graph has %llu edges", (long long)(int32_t)emax, (unsigned long long)E);
-        const uint32_t bits = std::max(1u, key_bits);
-        size_t tb = 0;
-        SNK_HIP_TRY(rocprim::radix_sort_pairs((void*)nullptr, tb, (const uint32_t*)paths->edges, skey, rid, ids, (size_t)n, 0u, bits, st));
-        uint8_t* tmp;
-        if ((rc = dev(ctx, tb, &tmp, err, errcap))) return rc;
-        SNK_HIP_TRY(rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)paths->edges, skey, rid, ids, (size_t)n, 0u, bits, st));
-    }
-    SNK_HIP_TRY(snk_launch(pidx_offsets_kernel, snk_blocks_capped(n ? (n + 3) / 4 : E + 1, PB, PIDX_GRID_CAP), PB, 0, st, skey, n, E, off));
-    if (E) SNK_HIP_TRY(snk_launch(pidx_counts_kernel, snk_blocks_capped(E, PB, PIDX_GRID_CAP), PB, 0, st, off, d_inv, E, counts, stat));
-    unsigned long long h_stat[512];
-    SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(hipEventRecord(e1, st));
-    SNK_HIP_TRY(snk_sync(st));
-    uint64_t n_empty = 0, n_over = 0;
-    for (int q = 0; q < 256; ++q) { n_empty += h_stat[q]; n_over += h_stat[256 + q]; }
-    if (n_over)
-        return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_index: the read support of %llu edge(s) and their reverse complements passes 2^31 - 1 (a.countsb holds int)",
-                        (unsigned long long)n_over);
-    out->n_hbv_edges = E;
-    out->n_entries = n;
-    out->index_off = off;
-    out->index_ids = ids;
-    out->counts = counts;
-    out->n_empty_edges = n_empty;
-    out->key_bits = key_bits;
-    (void)hipEventElapsedTime(&out->ms, e0, e1);
-    return SNK_OK;
+        uint64_t n_empty = 0, n_over = 0;
+        for (int q = 0; q < 256; ++q) { n_empty += h_stat[q]; n_over += h_stat[256 + q]; }
+        if (n_over)
+            return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_paths_index: the read support of %llu edge(s) and their reverse complements passes 2^31 - 1 (a.countsb holds int)",
+                            (unsigned long long)n_over);
+        out->n_hbv_edges = E;
+        out->n_entries = n;
+        out->index_off = off;
+        out->index_ids = ids;
+        out->counts = counts;
+        out->n_empty_edges = n_empty;
+        out->key_bits = key_bits;
+        out->ms = c.ms(0, 1);
+        return c.end(SNK_OK, {off, ids, counts});
+    });
 }

@@ -166,4 +166,7 @@ def test_verifier_source_is_independent():
     includes = re.findall(r'#include\s+"([^"]+)"', src)
     for banned in ("snk_count", "snk_graph", "snk_local", "snk_kernels", "snk_stages"):
         assert not any(banned in i for i in includes), includes
-    assert set(includes) <= {"snk_ctx.h", "snk_common.h"}
+    assert set(includes) <= {"snk_call.h", "snk_common.h"}
+    # the call frame it runs in brings nothing but the context with it
+    frame = (ROOT / "supernova_amd" / "csrc" / "snk_call.h").read_text()
+    assert re.findall(r'#include\s+"([^"]+)"', frame) == ["snk_ctx.h"]
