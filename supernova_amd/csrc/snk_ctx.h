@@ -11,6 +11,7 @@
 #include "../../include/snk.h"
 #include "snk_launch.h"
 #include "snk_opts.h"
+#include "snk_plan.h"
 
 struct snk_ctx {
     int device = 0;
@@ -57,13 +58,9 @@ struct snk_ctx {
     uint32_t last_ovf = 0, last_ovf_nb = 0;             // overflow supermers of the last partition pass and its bucket count
     uint64_t last_ovf_reads = 0;
     uint64_t last_dense = 0;                            // supermer records of the last dense partition pass (last_ovf_nb == 0xD0000000)
-    double retain_ratio = 0.0;                         // retained k-mers per k-mer instance of the last call (same key as claim_ratio)
     uint32_t count_screen = 0;                         // ungrouped call: the count launches run their instances through the bit filter first (level; snk_count.hip SCREEN)
     uint32_t count_tight = 0;                          // this call's count launches book their table slots (error-rich data, per-barcode groups: fuller tables, fewer buckets)
-    double screen_ratio = 0.0;                         // the distinct-per-instance ratio an ungrouped screened call was decided on
-    double claim_ratio = 0.0;                          // distinct k-mers per k-mer instance the count kernel saw in the last call ...
-    uint64_t claim_ratio_reads = 0;                    // ... over this many reads ...
-    uint32_t claim_ratio_k = 0;                        // ... in this mode (2 K + grouped + 256 x minimiser length)
+    snk_sizing_history sizing;                         // what the last call's tables held per k-mer instance: the next call's bucket plan starts from it (snk_plan.h)
     uint32_t mlen = 16;                                // minimiser length of the top-level call at hand (snk_set_mlen)
     uint32_t last_extra = 0;                           // split sub-passes the previous call recorded
     uint64_t last_input_fp = 0;                        // fingerprint of the last resident call's reads (snk_pipeline.hip): other data of the same size must not inherit its sizing history

@@ -133,7 +133,11 @@ void snk_opts_init(snk_opts* o);                     // nothing set
 int snk_opts_parse(snk_opts* o, const char* text, char* bad, unsigned badcap);      // "name=value,name=value"; 0 ok, else the offending item in `bad`
 bool snk_opt_valid(int id, long long value);         // the option's range; every setter refuses what lies outside
 const char* snk_opt_doc(int id);                     // the registry's text and, in brackets, the range
-// the context's value if it set one, else the registry's default (ctx NULL: the defaults)
+// the value that was set, else the registry's default: over a set of options (host code without HIP: snk_opts.hip with SNK_OPTS_NO_CTX) ...
+bool snk_opts_is_set(const snk_opts& o, snk_opt_id id);
+unsigned long long snk_opts_u64(const snk_opts& o, snk_opt_id id);
+inline uint32_t snk_opts_u32(const snk_opts& o, snk_opt_id id) { return (uint32_t)snk_opts_u64(o, id); }
+// ... and over a context's (ctx NULL: the defaults)
 struct snk_ctx;
 bool snk_opt_is_set(const snk_ctx* ctx, snk_opt_id id);
 uint32_t snk_opt_u32(const snk_ctx* ctx, snk_opt_id id);

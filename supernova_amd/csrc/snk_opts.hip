@@ -1,12 +1,16 @@
 // snk_opts.hip -- the option registry behind snk_ctx_set_option / snk_ctx_set_tuning (snk_opts.h).
+// With SNK_OPTS_NO_CTX defined this file is the registry alone -- names, defaults, ranges, parsing, the value of an option in a set of
+// options: host code without a HIP header or a context, which the host-only checks link (tests/plan_host.cc).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <string>
 
-#include "snk_ctx.h"
 #include "snk_opts.h"
+#ifndef SNK_OPTS_NO_CTX
+#include "snk_ctx.h"
+#endif
 
 const snk_opt_def snk_opt_defs[SNK_OPT_COUNT] = {
 #define X(name, dflt, range, doc) {#name, dflt, range, doc},
@@ -74,11 +78,13 @@ const char* snk_opt_doc(int id) {
     return id >= 0 && id < SNK_OPT_COUNT ? all.text[id].c_str() : nullptr;
 }
 
-bool snk_opt_is_set(const snk_ctx* ctx, snk_opt_id id) { return ctx && ctx->opts.set[id]; }
+bool snk_opts_is_set(const snk_opts& o, snk_opt_id id) { return o.set[id]; }
+unsigned long long snk_opts_u64(const snk_opts& o, snk_opt_id id) { return (unsigned long long)(o.set[id] ? o.v[id] : snk_opt_defs[id].dflt); }
+
+#ifndef SNK_OPTS_NO_CTX
+bool snk_opt_is_set(const snk_ctx* ctx, snk_opt_id id) { return ctx && snk_opts_is_set(ctx->opts, id); }
 uint32_t snk_opt_u32(const snk_ctx* ctx, snk_opt_id id) { return (uint32_t)snk_opt_u64(ctx, id); }
-unsigned long long snk_opt_u64(const snk_ctx* ctx, snk_opt_id id) {
-    return (unsigned long long)(snk_opt_is_set(ctx, id) ? ctx->opts.v[id] : snk_opt_defs[id].dflt);
-}
+unsigned long long snk_opt_u64(const snk_ctx* ctx, snk_opt_id id) { return ctx ? snk_opts_u64(ctx->opts, id) : (unsigned long long)snk_opt_defs[id].dflt; }
 
 // ---- C ABI
 extern "C" int snk_ctx_set_option(snk_ctx* ctx, const char* name, long long value, char* err, size_t errcap) {
@@ -178,3 +184,4 @@ extern "C" void snk_ctx_get_tuning(const snk_ctx* ctx, snk_tuning* t) {
     t->last_partition_passes = ctx->last_partition_passes;
     t->last_minimiser_len = ctx->mlen;
 }
+#endif  // SNK_OPTS_NO_CTX

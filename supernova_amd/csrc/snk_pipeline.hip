@@ -64,8 +64,11 @@ static int graph_tail(snk_ctx* ctx, hipStream_t st, const snk_params* p, uint32_
                       snk_table& tab, const snk_partition& part, snk_dev_result* out, phase_timer& tm, char* err, size_t errcap) {
     int rc;
     void* records = part.records;
-    if (h_ninst) { ctx->claim_ratio = (ctx->count_screen && !grouped && ctx->screen_ratio > 0.0) ? ctx->screen_ratio : (double)tab.distinct / (double)h_ninst; ctx->claim_ratio_reads = n_reads; ctx->claim_ratio_k = K * 2 + (grouped ? 1u : 0u) + 256u * ctx->mlen;
-                   ctx->retain_ratio = (double)tab.n / (double)h_ninst; }
+    if (h_ninst) {
+        snk_sizing_history& H = ctx->sizing;
+        H.store(snk_sizing_key(K, grouped, ctx->mlen), n_reads, (ctx->count_screen && !grouped && H.screen_ratio > 0.0) ? H.screen_ratio : (double)tab.distinct / (double)h_ninst,
+                (double)tab.n / (double)h_ninst);
+    }
     snk_ctx_release_block(ctx, records);       // the fixed-capacity supermer slots: the graph stage may reuse the memory
     const uint64_t n_kmers = tab.n;
     out->buckets_split = tab.buckets_split;
@@ -184,12 +187,6 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     if (rc) return rc;
     unsigned long long h_ninst = h_plan[0];
     out->n_instances = h_ninst;
-    // instances per bucket: sized so that the DISTINCT k-mers of a bucket fit the LDS table (1216 claims).  At 56x coverage and
-    // 0.2 % errors 5000 instances hold ~800 distinct k-mers; per-barcode groups see every locus once or twice, so nearly every
-    // instance is distinct there.  Error-rich or shallow data have more distinct k-mers per instance: with the default size
-    // nearly every bucket would overflow its table and be counted in two to four hash-split sub-passes (0.6 % errors: count
-    // 46 -> 133 ms).  The ratio is a property of the data set: the previous call's is used if there is one, else the count stage
-    // looks at its first 1/64 of the buckets and asks for a second partition when they overflow as a rule.
     // ---- is this the data set the context's sizing history was made on?  (one 8-byte read-back: ~40 us)
     bool same_data = true;
     if (n_reads && p->n_buckets == 0 && snk_opt_u32(ctx, SNK_OPT_input_fp)) {
@@ -209,62 +206,19 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         ctx->last_input_fp = h_fp; ctx->have_input_fp = true;
         if (!same_data) { ctx->last_n_kmers = 0; ctx->last_bnd = 0; ctx->last_region_max = 0; }       // (the count regions' and the boundary index's sizes were that data's)
     }
-    // The count kernel has two ways to keep its probe loops supplied with free slots (snk_count.hip): a margin of one round of every wave
-    // (1216 of 2048 slots usable, nothing to pay per round) or booked slots (15/16 usable, one LDS atomic round trip per wave and round:
-    // 45.1 instead of 43.0 ms on the bench model).  Data whose tables run full -- sequencing errors, per-barcode groups -- are counted the
-    // second way: fewer, fuller buckets (1.5 % errors: 8.4 M -> 5.6 M buckets, 218 -> 188 ms; 0.6 %: 149 -> 136; groups: 183 -> 177).
-    // SNK_COUNT_TIGHT = 0 never, = n always with n usable slots.
-    ctx->count_tight = 0;
-    const uint32_t plain_target = K == 48 ? 5000u : 3500u;
-    auto tight_for = [&](double ratio) -> uint32_t {
-        const uint32_t tries = snk_opt_u32(ctx, SNK_OPT_tight_tries) << 16;
-        if (snk_opt_is_set(ctx, SNK_OPT_count_tight)) {
-            const uint32_t v = snk_opt_u32(ctx, SNK_OPT_count_tight);
-            return v ? (std::min(std::max(v, 256u), snk_count_slots(K) - 64u) | tries) : 0u;
-        }
-        const bool full = grouped || (ratio > 0.0 && 0.65 * (double)snk_count_limit(K, 0u, 0u) / ratio < (double)plain_target);
-        return full ? ((snk_count_slots(K) - snk_count_slots(K) / 16u) | tries) : 0u;
-    };
-    // (per-barcode groups: nearly every instance is a distinct entry, the bucket IS the table: three quarters of its capacity on average)
-    // (... unless the bit filter in front of the table is on -- min_freq >= 2: then the table only sees the (group, k-mer) pairs that can be retained,
-    // one in ten, and a bucket is as large as one batch of 512 records and ten instances per lane allow: beyond 6000 buckets start to fall out
-    // of the filter -- 92.9 ms at 4800, 92.2 at 5600, 94.6 at 6400, `profiles/r05_count_screen_groups.log`)
-    const bool group_screen = grouped && snk_opt_u32(ctx, SNK_OPT_count_screen) != 0 && p->min_freq >= (snk_opt_u32(ctx, SNK_OPT_count_screen) >= 2 ? 2u : 3u);
-    auto default_target_now = [&]() -> uint32_t { return grouped ? ((group_screen && ctx->count_tight) ? 5200u : (uint32_t)(0.74 * snk_count_limit(K, 1u, ctx->count_tight))) : plain_target; };
+    // ---- the bucket plan (snk_plan.h): bucket count, count kernel, usable table slots; from the context's history of this data set if there
+    // is one, else the count stage looks at its first buckets and may ask for a second partition (SNK_RETARGET)
     const bool target_forced = snk_opt_is_set(ctx, SNK_OPT_target_inst);
-    // ... and the RETAINED k-mers of a bucket are one chunk of the bucket-local graph stage, whose one-wave kernels hold 256 of them
-    // (larger chunks take the slower big-chunk variants): at half the coverage twice as many k-mers survive per instance, every other
-    // chunk was over the line and the graph stage took 81 instead of ~58 ms.  From the previous call's retained share: chunks of ~180 (28x coverage, with merged chunks behind it: 153.2 ms at 120, 149.5 at 150, 147.7 at 180, 147.5 at 210).
-    const double retain = (same_data && ctx->retain_ratio > 0.0 && ctx->claim_ratio_reads == n_reads && ctx->claim_ratio_k == K * 2 + (grouped ? 1u : 0u) + 256u * ctx->mlen) ? ctx->retain_ratio : 0.0;
-    auto target_for = [&](double ratio) -> uint32_t {
-        const uint32_t default_target = default_target_now();
-        if (target_forced) return snk_opt_u32(ctx, SNK_OPT_target_inst);
-        if (ctx->count_screen && !grouped) return snk_opt_u32(ctx, SNK_OPT_screen_target);
-        if (retain > 0.0 && (!grouped || group_screen)) {       // (groups behind the bit filter: buckets of 5200 instances, unless that many would retain more than a graph chunk holds)
-            const double t = (double)snk_opt_u32(ctx, SNK_OPT_chunk_kmers) / retain;
-            if (t < (double)default_target) {
-                uint32_t tt = t < 600.0 ? 600u : (uint32_t)t;
-                if (ratio > 0.0) {           // the tighter of the two limits
-                    const double lim = (double)snk_count_limit(K, 0u, ctx->count_tight);
-                    if (0.65 * lim / ratio < (double)default_target) {
-                        const double t2 = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ratio;
-                        if (t2 < (double)tt) tt = t2 < 600.0 ? 600u : (uint32_t)t2;
-                    }
-                }
-                return tt;
-            }
-        }
-        if (!(ratio > 0.0)) return default_target;
-        // measured: the default size is right while the tables run up to ~65 % full on average (the bench model: 800 of 1216); data
-        // that would fill them further do best at ~50 % (0.6 % errors: 239 ms with the default size, 186 at 80 %, 154 at 50 %)
-        const double lim = (double)snk_count_limit(K, grouped ? 1u : 0u, ctx->count_tight);
-        if (0.65 * lim / ratio >= (double)default_target) return default_target;
-        const double t = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ratio;
-        return t >= (double)default_target ? default_target : (t < 600.0 ? 600u : (uint32_t)t);
-    };
-    const bool have_hint = same_data && ctx->claim_ratio > 0.0 && ctx->claim_ratio_reads == n_reads && ctx->claim_ratio_k == K * 2 + (grouped ? 1u : 0u) + 256u * ctx->mlen;
-    double ratio = have_hint ? ctx->claim_ratio : 0.0;
+    const bool my_history = same_data && ctx->sizing.lookup(snk_sizing_key(K, grouped, ctx->mlen), n_reads);
+    const bool have_hint = my_history && ctx->sizing.ratio > 0.0;
+    double ratio = have_hint ? ctx->sizing.ratio : 0.0;
     const bool adaptive = p->n_buckets == 0 && !target_forced && !grouped && snk_opt_u32(ctx, SNK_OPT_adaptive_buckets) != 0;      // (the per-barcode default is tuned at ratio ~1)
+    snk_plan_in pin;
+    pin.K = K; pin.grouped = grouped; pin.has_bc = in->bc != nullptr; pin.min_freq = p->min_freq; pin.min_bc = p->min_bc;
+    pin.n_buckets = p->n_buckets; pin.inst_ub = h_plan[0]; pin.may_adapt = adaptive; pin.opts = &ctx->opts;
+    pin.retain = (my_history && ctx->sizing.retain > 0.0) ? ctx->sizing.retain : 0.0;
+    pin.slots = snk_count_slots(K); pin.plain_limit = snk_count_limit(K, 0u, 0u); pin.screen_limit = snk_count_screen_limit();
+    pin.nb_max = 1ull << 25; pin.use_retain = true;
     uint32_t NB = 0;
     snk_partition part;
     snk_table tab;
@@ -273,37 +227,13 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     const uint64_t mark = ctx->alloc_serial;
     const unsigned long long ub_inst = h_plan[0], ub_live = h_plan[1];
     for (int pass = 0; pass < 2; ++pass) {
-        NB = p->n_buckets;
-        ctx->count_tight = tight_for(adaptive ? ratio : (have_hint ? ctx->claim_ratio : 0.0));
-        // ungrouped reads whose tables run very full (1.5 % errors: 0.41 distinct k-mers per instance, most of them seen once or twice): the bit
-        // filter of the per-barcode groups in front of a 1024-slot table -- the table then sees what can be retained and the bucket is as large
-        // as one batch of records and ten instances per lane allow.  SNK_COUNT_SCREEN_NG: 0 never, 2 always, default: ratio above 0.3
-        // (0.6 % errors, ratio 0.21, lose with it: a fifth of their instances are singletons, the first pass costs more than it saves)
-        {
-            const double r_now = adaptive ? ratio : (have_hint ? ctx->claim_ratio : 0.0);
-            const uint32_t ng = snk_opt_u32(ctx, SNK_OPT_count_screen_ng);
-            ctx->count_screen = (!grouped && K == 48 && p->min_freq >= 3 && (!in->bc || p->min_bc <= 2) && ng && (ng >= 2 || r_now > 0.01 * snk_opt_u32(ctx, SNK_OPT_screen_ratio_pct))) ? 3u : 0u;
-            if (snk_opt_is_set(ctx, SNK_OPT_count_tight) && snk_opt_u32(ctx, SNK_OPT_count_tight) == 0u) ctx->count_screen = 0;      // (the filter comes with booked slots)
-            if (ctx->count_screen && !ctx->count_tight) ctx->count_tight = (snk_count_slots(K) - snk_count_slots(K) / 16u) | (snk_opt_u32(ctx, SNK_OPT_tight_tries) << 16);
-            if (ctx->count_screen && r_now > 0.0) ctx->screen_ratio = r_now;      // (what the screened call reports is the table's view: the decision keeps the ratio it was made on)
-            ctx->last_count_limit = snk_count_limit(K, grouped ? 1u : 0u, ctx->count_tight);
-            if ((ctx->count_screen || (group_screen && ctx->count_tight)) && K == 48) ctx->last_count_limit = std::min(ctx->last_count_limit, snk_count_screen_limit());
-        }
-        if (NB == 0) {
-            const uint32_t target = target_for(adaptive ? ratio : 0.0);
-            uint64_t nb = (ub_inst + target - 1) / target;
-            const uint64_t nb_max = 1ull << 25;      // (2^23 until round 6: at 800 M reads that is 9700 instances per bucket, a third of the buckets split; 1.2 B reads as per-barcode graphs want 23.5 M)
-            if (nb < 1) nb = 1;
-            if (nb > nb_max) nb = nb_max;
-            NB = (uint32_t)nb;
-        }
-        {
-            // a caller's bucket count is honoured down to ~1 M k-mer instances per bucket: a bucket is counted by ONE
-            // workgroup that re-reads all its records in every hash-split sub-pass, so 20 M instances in one bucket would be
-            // thousands of passes over a million records (finite, but minutes)
-            const uint64_t nb_floor = (ub_inst >> 20) + 1;
-            if (NB < nb_floor) NB = (uint32_t)nb_floor;
-        }
+        pin.ratio = ratio;
+        const snk_plan_out plan = snk_bucket_plan(pin);
+        NB = plan.NB;
+        ctx->count_tight = plan.tight;
+        ctx->count_screen = plan.screen;
+        if (plan.screen && ratio > 0.0) ctx->sizing.screen_ratio = ratio;      // (what the screened call reports is the table's view: the decision keeps the ratio it was made on)
+        ctx->last_count_limit = plan.count_limit;
         out->n_buckets = NB;
         if (pass == 0) tm.mark();  // 2
         h_plan[0] = ub_inst; h_plan[1] = ub_live;
@@ -463,26 +393,16 @@ extern "C" int snk_dev_stream_begin(snk_ctx* ctx, const snk_params* p, uint32_t 
     const uint32_t K = p->K;
     const unsigned long long kpr = read_len >= K ? read_len - K + 1 : 0;
     const unsigned long long ub_inst = total_reads_ub * kpr;
-    // bucket count: as snk_dev_count_graph sizes it; the distinct-k-mers-per-instance ratio of the previous call on this context (same
-    // read total) is used if there is one -- a streamed job cannot look at its first buckets and partition again, its slabs are gone:
-    // error-rich data without that history are counted in hash-split sub-passes (slower, same result)
-    uint32_t NB = p->n_buckets;
-    if (NB == 0) {
-        uint32_t target = K == 48 ? 5000u : 3500u;
-        if (snk_opt_is_set(ctx, SNK_OPT_target_inst)) target = snk_opt_u32(ctx, SNK_OPT_target_inst);
-        else if (ctx->claim_ratio > 0.0 && ctx->claim_ratio_reads == total_reads_ub && ctx->claim_ratio_k == K * 2 + 256u * ctx->mlen) {
-            const double lim = (double)snk_count_limit(K, 0u, ctx->count_tight);
-            if (0.65 * lim / ctx->claim_ratio < (double)target) {
-                const double t = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ctx->claim_ratio;
-                target = t < 600.0 ? 600u : (uint32_t)t;
-            }
-        }
-        uint64_t nb = (ub_inst + target - 1) / target;
-        if (nb < 1) nb = 1;
-        if (nb > (1ull << 23)) nb = 1ull << 23;
-        NB = (uint32_t)nb;
-    }
-    { const uint64_t nb_floor = (ub_inst >> 20) + 1; if (NB < nb_floor) NB = (uint32_t)nb_floor; }
+    // bucket count: the plan of snk_dev_count_graph (snk_plan.h); the distinct-k-mers-per-instance ratio of the previous call on this context
+    // (same read total) is used if there is one -- a streamed job cannot look at its first buckets and partition again, its slabs are
+    // gone: error-rich data without that history are counted in hash-split sub-passes (slower, same result)
+    snk_plan_in pin;
+    pin.K = K; pin.has_bc = has_bc != 0; pin.min_freq = p->min_freq; pin.min_bc = p->min_bc; pin.n_buckets = p->n_buckets; pin.inst_ub = ub_inst; pin.opts = &ctx->opts;
+    pin.ratio = ctx->sizing.lookup(snk_sizing_key(K, false, ctx->mlen), total_reads_ub) ? ctx->sizing.ratio : 0.0;
+    pin.may_adapt = true;
+    pin.slots = snk_count_slots(K); pin.plain_limit = snk_count_limit(K, 0u, 0u); pin.screen_limit = snk_count_screen_limit();
+    pin.nb_max = 1ull << 23; pin.may_book = false; pin.fill_unclamped = true;
+    const uint32_t NB = snk_bucket_plan(pin).NB;
     j->NB = NB;
     void* q;
     int rc;

@@ -179,37 +179,16 @@ int all_ranges_ready(void* user) {       // the whole exchange has landed (the h
     return 0;
 }
 
-uint32_t plan_buckets(const snk_ctx* ctx, uint64_t inst_ub, uint32_t world, uint32_t K, uint32_t forced, double ratio, uint32_t* tight_out = nullptr, uint32_t* screen_out = nullptr) {
-    uint64_t nb = forced;
-    if (tight_out) *tight_out = 0;
-    const bool screen_ok = screen_out && *screen_out;       // (in: the call's parameters allow the bit filter; out: it is taken)
-    if (screen_out) *screen_out = 0;
-    if (!nb) {
-        const uint32_t dflt = K == 48 ? 5000u : 3500u;
-        const bool target_forced = snk_opt_is_set(ctx, SNK_OPT_target_inst);
-        uint64_t target = target_forced ? snk_opt_u32(ctx, SNK_OPT_target_inst) : dflt;
-        if (!target_forced && ratio > 0.0 && snk_opt_u32(ctx, SNK_OPT_adaptive_buckets)) {
-            // (the rule of the one-GPU path, snk_pipeline.hip: smaller buckets when the tables would run more than ~65 % full)
-            double lim = (double)snk_count_limit(K, 0u, 0u);
-            // (tables that run full are counted with booked slots, as on the one-GPU path: every rank takes the same turn, the ratio is job-wide)
-            const bool tight_off = snk_opt_is_set(ctx, SNK_OPT_count_tight) && snk_opt_u32(ctx, SNK_OPT_count_tight) == 0u;
-            if (tight_out && 0.65 * lim / ratio < (double)dflt && !tight_off) {
-                *tight_out = (snk_count_slots(K) - snk_count_slots(K) / 16u) | (snk_opt_u32(ctx, SNK_OPT_tight_tries) << 16);
-                lim = (double)snk_count_limit(K, 0u, *tight_out);
-            }
-            if (0.65 * lim / ratio < (double)dflt) { const double t = 0.01 * snk_opt_u32(ctx, SNK_OPT_bucket_fill_pct) * lim / ratio; target = t < 600.0 ? 600u : (uint64_t)t; if (target > dflt) target = dflt; }
-            // (... and above 0.3 distinct k-mers per instance behind the bit filter, whose table only sees what can be retained: snk_pipeline.hip)
-            const uint32_t ng = snk_opt_u32(ctx, SNK_OPT_count_screen_ng);
-            if (screen_ok && tight_out && *tight_out && ng && (ng >= 2 || ratio > 0.01 * snk_opt_u32(ctx, SNK_OPT_screen_ratio_pct))) { *screen_out = 3; target = snk_opt_u32(ctx, SNK_OPT_screen_target); }
-        }
-        nb = (inst_ub + target - 1) / target;
-        if (nb < 1) nb = 1;
-        if (nb > (1ull << 26)) nb = 1ull << 26;
-    }
-    const uint64_t floor_ = (inst_ub >> 20) + 1;       // at most ~1 M instances per bucket (one workgroup counts a bucket)
-    if (nb < floor_) nb = floor_;
-    nb = (nb + world - 1) / world * world;
-    return (uint32_t)nb;
+// the inputs of the job's bucket plan (snk_plan.h).  Every rank fills them from the same exchanged words and the same group history, so
+// every rank reaches the same plan: tables that run full are counted with booked slots, and above 0.3 distinct k-mers per instance behind
+// the bit filter, as on the one-GPU path -- every rank takes the same turn, the ratio is job-wide.
+snk_plan_in shard_plan_in(const snk_ctx* ctx, const snk_params* p, uint32_t W, bool has_bc, uint64_t inst_ub, double ratio, bool may_adapt, bool may_book) {
+    snk_plan_in pin;
+    pin.K = p->K; pin.has_bc = has_bc; pin.min_freq = p->min_freq; pin.min_bc = p->min_bc; pin.n_buckets = p->n_buckets; pin.inst_ub = inst_ub; pin.world = W;
+    pin.ratio = ratio; pin.may_adapt = may_adapt; pin.opts = &ctx->opts;
+    pin.slots = snk_count_slots(p->K); pin.plain_limit = snk_count_limit(p->K, 0u, 0u); pin.screen_limit = snk_count_screen_limit();
+    pin.nb_max = 1ull << 26; pin.may_book = may_book; pin.book_only_adapting = true; pin.screen_needs_tight = true;
+    return pin;
 }
 
 template <typename In, typename Out>
@@ -257,12 +236,13 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             for (ull v : all) inst_ub += v * kpr;
         }
     }
-    const bool have_ratio = inst_ub && comm->claim_ratio > 0.0 && comm->claim_ratio_reads == inst_ub && comm->claim_ratio_k == K * 2 + 256u * ctx->mlen;      // (the group's history: snk_comm.h)
+    const uint32_t hkey = snk_sizing_key(K, false, ctx->mlen);
+    const bool have_ratio = inst_ub && comm->sizing.ratio > 0.0 && comm->sizing.lookup(hkey, inst_ub);      // (the group's history: snk_comm.h)
     // Bucket size: from the job-wide ratio of distinct k-mers per instance the previous step exchanged; without that history the
     // count stage looks at its first buckets, the ranks agree on what they saw (one more exchange), and if the tables overflow as
     // a rule the reads are partitioned and exchanged once more into smaller buckets (error-rich reads: see snk_pipeline.hip).
     const bool adaptive = inst_ub && !snk_opt_is_set(ctx, SNK_OPT_target_inst) && snk_opt_u32(ctx, SNK_OPT_adaptive_buckets) != 0;
-    double ratio = have_ratio ? comm->claim_ratio : 0.0;
+    double ratio = have_ratio ? comm->sizing.ratio : 0.0;
     uint32_t NB_total = 0, NBl = 0;
     uint64_t n_inst = 0, inst_hint = 0, exch_records = 0;
     snk_shard_state* S = nullptr;
@@ -407,12 +387,13 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
         // (a streamed step sized its buckets when it was opened -- the same rule on the same job-wide figures -- and cannot partition twice: its
         // slabs are gone; error-rich data without the group's history are counted in hash-split sub-passes then)
         {
-            uint32_t tight = 0, screen = (K == 48 && p->min_freq >= 3 && (!has_bc || p->min_bc <= 2)) ? 1u : 0u;
-            NB_total = X.streamed ? snk_shard_state_of(ctx)->NB_total : plan_buckets(ctx, inst_ub, W, K, p->n_buckets, adaptive ? ratio : 0.0, &tight, &screen);
-            if (X.streamed) screen = 0;
-            ctx->count_tight = tight; ctx->count_screen = screen;
-            ctx->last_count_limit = screen ? std::min(snk_count_limit(K, 0u, tight), snk_count_screen_limit()) : snk_count_limit(K, 0u, tight);
-            if (screen && ratio > 0.0) { comm->claim_ratio = ratio; comm->claim_ratio_reads = inst_ub; comm->claim_ratio_k = K * 2 + 256u * ctx->mlen; }      // (a screened step reports the table's view: the group keeps the ratio the decision was made on)
+            snk_plan_out plan;
+            if (X.streamed) { plan.NB = snk_shard_state_of(ctx)->NB_total; plan.count_limit = snk_count_limit(K, 0u, 0u); }
+            else plan = snk_bucket_plan(shard_plan_in(ctx, p, W, has_bc != 0, inst_ub, ratio, adaptive, true));
+            NB_total = plan.NB;
+            ctx->count_tight = plan.tight; ctx->count_screen = plan.screen;
+            ctx->last_count_limit = plan.count_limit;
+            if (plan.screen && ratio > 0.0) comm->sizing.store(hkey, inst_ub, ratio);      // (a screened step reports the table's view: the group keeps the ratio the decision was made on)
         }
         NBl = NB_total / W;
         tm.n = 1;
@@ -453,7 +434,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             q_send[q] = qall[(size_t)me * (W + QX) + q]; q_recv[q] = qall[(size_t)q * (W + QX) + me]; all_n[q] = qall[(size_t)q * (W + QX) + W];
             dsum += qall[(size_t)q * (W + QX) + W + 1]; isum += qall[(size_t)q * (W + QX) + W + 2];
         }
-        if (isum && !X.ctx->count_screen) { comm->claim_ratio = (double)dsum / (double)isum; comm->claim_ratio_reads = inst_ub; comm->claim_ratio_k = K * 2 + 256u * ctx->mlen; }      // (job-wide figures, kept with the group: every rank takes the same decision next time)
+        if (isum && !X.ctx->count_screen) comm->sizing.store(hkey, inst_ub, (double)dsum / (double)isum);      // (job-wide figures, kept with the group: every rank takes the same decision next time)
     }
     uint64_t nq = 0, nq_in = 0;
     for (uint32_t q = 0; q < W; ++q) { nq += q_send[q]; nq_in += q_recv[q]; }
@@ -829,8 +810,9 @@ extern "C" int snk_shard_stream_begin(snk_ctx* ctx, snk_comm* comm, const snk_pa
     const uint64_t kpr = read_len >= K ? read_len - K + 1 : 0;
     const uint64_t inst_ub = total_reads * kpr;
     const bool adaptive = inst_ub && !snk_opt_is_set(ctx, SNK_OPT_target_inst) && snk_opt_u32(ctx, SNK_OPT_adaptive_buckets) != 0;
-    const bool have_ratio = inst_ub && comm->claim_ratio > 0.0 && comm->claim_ratio_reads == inst_ub && comm->claim_ratio_k == K * 2 + 256u * ctx->mlen;
-    const uint32_t NB_total = plan_buckets(ctx, inst_ub, W, K, p->n_buckets, adaptive && have_ratio ? comm->claim_ratio : 0.0);
+    const bool have_ratio = inst_ub && comm->sizing.ratio > 0.0 && comm->sizing.lookup(snk_sizing_key(K, false, ctx->mlen), inst_ub);
+    // (a streamed step cannot partition twice and keeps the default kernel: the bucket rule alone follows the group's history)
+    const uint32_t NB_total = snk_bucket_plan(shard_plan_in(ctx, p, W, has_bc != 0, inst_ub, have_ratio ? comm->sizing.ratio : 0.0, adaptive, false)).NB;
     return snk_shard_job_open(ctx, p, comm->rank, W, NB_total, read_len, rank_reads_ub, total_reads, has_bc, st, err, errcap);
 }
 extern "C" int snk_shard_stream_append(snk_ctx* ctx, const snk_dev_reads* slab, void* stream, char* err, size_t errcap) {

@@ -177,6 +177,8 @@ class TorchComm:
 
 # ------------------------------------------------------------------------------------------------ planning helpers
 def plan_buckets(total_inst_upper: int, world: int, K: int, target_inst: int = 0) -> int:
+    """The default bucket count of a sharded job without sizing history (a planning helper for callers and tests).  The library's own rule,
+    which also follows the data and chooses the count kernel, is snk_bucket_plan (csrc/snk_plan.h)."""
     target = int(target_inst) or (5000 if K == 48 else 3500)
     nb = max(1, -(-total_inst_upper // target))
     nb = min(nb, 1 << 26)

@@ -182,6 +182,25 @@ def _grouped_case():
     return c, group, want
 
 
+def _check_groups(res, want, tag):
+    """A grouped result against the oracle's run on every group's reads alone (want: group id -> OracleResult)."""
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    k, cnt, ctx = res.keys(), res.counts(), res.ctx()
+    off, bases = res.unitig_arrays()
+    ug = res.unitig_groups()
+    assert np.all(np.diff(ug.astype(np.int64)) >= 0)
+    total = 0
+    for gid, o in want.items():
+        m = k[:, 3] == gid
+        kk, cc, xx = k[m], cnt[m], ctx[m]
+        order = np.lexsort((kk[:, 2], kk[:, 1], kk[:, 0]))
+        assert np.array_equal(kk[order][:, :3], o.keys[:, :3]) and np.array_equal(cc[order], o.counts) and np.array_equal(xx[order], o.ctx), tag + (gid,)
+        us = sorted((lut[bases[int(off[u]):int(off[u + 1])]].tobytes().decode() for u in np.nonzero(ug == gid)[0]), key=lambda t: (-len(t), t))
+        assert us == o.unitigs, tag + (gid,)
+        total += int(m.sum())
+    assert total == k.shape[0]
+
+
 @pytest.mark.parametrize("name,value", _pairs("grouped"))
 def test_local_stage_options_per_group(engine, tune, name, value):
     import torch
@@ -189,27 +208,12 @@ def test_local_stage_options_per_group(engine, tune, name, value):
     c, group, want = _grouped_case()
     rows, quals, bc, lens = _dev(c)
     g_dev = torch.from_numpy(group).to(rows.device)
-    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
     for nb, merged in ((0, False), (4099, True)):
         tune("count_persist", 1 if merged else 32)
         tune(name, value)
         res = engine.count_graph(rows, c.read_len, quals=quals, bc=None, lens=lens, group=g_dev,
                                  params=Params(K=48, min_freq=3, min_bc=0, grouped=True, sorted_table=False, n_buckets=nb))
-        k, cnt, ctx = res.keys(), res.counts(), res.ctx()
-        off, bases = res.unitig_arrays()
-        ug = res.unitig_groups()
-        assert np.all(np.diff(ug.astype(np.int64)) >= 0)
-        total = 0
-        for gid, o in want.items():
-            m = k[:, 3] == gid
-            kk, cc, xx = k[m], cnt[m], ctx[m]
-            order = np.lexsort((kk[:, 2], kk[:, 1], kk[:, 0]))
-            tag = (name, value, nb, gid)
-            assert np.array_equal(kk[order][:, :3], o.keys[:, :3]) and np.array_equal(cc[order], o.counts) and np.array_equal(xx[order], o.ctx), tag
-            us = sorted((lut[bases[int(off[u]):int(off[u + 1])]].tobytes().decode() for u in np.nonzero(ug == gid)[0]), key=lambda t: (-len(t), t))
-            assert us == o.unitigs, tag
-            total += int(m.sum())
-        assert total == k.shape[0]
+        _check_groups(res, want, (name, value, nb))
 
 
 # ---- list ranking on tens of thousands of fragments with circles (sharded_cases.plasmid_case), against the C oracle
