@@ -735,7 +735,16 @@ uint64_t snk_fasth_file_pairs(snk_fasth_stream* s, uint32_t file);   /* known on
 void snk_fasth_close(snk_fasth_stream* s);
 /* ... and into HBM: packed rows (snk_dev_pack_ascii), quality rows, lengths and -- with a whitelist index -- barcode ids
  * (snk_dev_bc_ids, one per read), in file-major order; uploads, pack and id lookup overlap the decode.  The arrays are plain
- * device allocations (not the context's arena: they are the INPUT of snk_dev_count_graph); snk_dev_ingest_free releases them. */
+ * device allocations (not the context's arena: they are the INPUT of snk_dev_count_graph); snk_dev_ingest_free releases them.
+ *   read_len  1..256: the row length in bases, i.e. the longest read the lane may hold.  Rows are padded to 16 bases (row_words =
+ *             ceil(read_len / 16), qstride = 16 * row_words); shorter reads are fine (lens[] has their lengths, packed codes and
+ *             quality bytes behind a read's own length are 0).  A read LONGER than read_len is refused by both entry points:
+ *             SNK_E_UNSUPPORTED, the message names the file, the record, the read's length and read_len.  Nothing is ever cut:
+ *             every kernel downstream takes min(lens[], read_len) as a read's length, so a cut read would lose its last k-mers
+ *             silently.  (snk_fasth_open itself takes whatever fits its stride.)
+ *   SNK_INGEST_TRACE=1 prints where the consumer thread's time went, the number of batches, how many times the device arrays had
+ *             to grow (their first size is a guess from the compressed sizes) and whether the batches had to be put into file-major
+ *             order afterwards (1) or arrived in it (0). */
 typedef struct snk_dev_ingest {
     uint64_t n_reads;
     uint32_t read_len, row_words, qstride, max_len;
@@ -755,8 +764,15 @@ void snk_dev_ingest_free(snk_dev_ingest* r);
 /* FASTH files -> unitigs with the reads never resident as a whole: every decoded batch is uploaded, packed, given its barcode ids and
  * appended to a streamed job (snk_dev_stream_*) -- partitioned while the next batches are being inflated; the wall time is
  * max(ingest, partition) + count + graph.  res: as snk_dev_count_graph's (good_len in arrival order: batches arrive in any order).
- * total_reads_hint: an upper bound of the job's reads (sizes the bucket slots), 0 = from the compressed sizes.  stats: rows / quals /
- * lens / bc stay NULL.  The reading half + MSP of tada in one pass (lib/tada/src/cmd_msp.rs:55-69,100-190). */
+ * read_len and the refusal of longer reads: as snk_dev_ingest_fasth.
+ * total_reads_hint: an upper bound of the job's reads (sizes the bucket slots).  A lane with more reads than the hint is refused
+ * (SNK_E_ARG) as soon as a batch crosses it; the message names total_reads_hint and the reads decoded so far.  0 = the library's own
+ * guess from the compressed sizes and the gzip trailers.  It is a guess: files of several gzip members (cat a.gz b.gz), lanes of
+ * reads much shorter than read_len and lanes that deflate unusually well hold more reads than it.  Then nothing more is uploaded, the
+ * decode runs to the end to count the reads, and the job is run again from the files with that count: the same result, at the price
+ * of decoding the lane twice (and the device work done up to the crossing).  Callers that know the read count should pass it.
+ * stats: rows / quals / lens / bc stay NULL; seconds covers both passes.  The reading half + MSP of tada in one pass
+ * (lib/tada/src/cmd_msp.rs:55-69,100-190). */
 int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths, uint32_t n_files, uint32_t read_len, const snk_bc_index* ix, uint32_t threads,
                                uint32_t batch_pairs, uint64_t total_reads_hint, const snk_params* p, snk_dev_result* res, snk_dev_ingest* stats, char* err,
                                size_t errcap);

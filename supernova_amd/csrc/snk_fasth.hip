@@ -42,6 +42,8 @@ struct snk_fasth_stream {
     };
     std::vector<std::string> paths;
     uint32_t stride = 0, batch_pairs = 0;
+    uint32_t max_read = 0;                 // longest read a row takes: the stride for host callers, read_len for the device entry points
+    bool by_read_len = false;              // (max_read is a caller's read_len: the refusal names it)
     std::vector<batch> pool;
     std::deque<int> free_q, ready_q;
     std::mutex mu;
@@ -159,6 +161,7 @@ bool decode_file(snk_fasth_stream* s, uint32_t fi) {
     uint32_t li = 0;              // line of the record, 0..8
     uint32_t r_len[2] = {0, 0};
     bool ok = true, eof_in = false, first_byte = true, mid_member = false;
+    int what_rc = SNK_E_IO;
     std::string what;
     auto flush = [&](bool last) {
         if (cur < 0) return;
@@ -180,7 +183,12 @@ bool decode_file(snk_fasth_stream* s, uint32_t fi) {
             }
         } else if (li == 1 || li == 3) {
             snk_fasth_stream::batch& b = s->pool[cur];
-            if (n > stride) { what = path + ": a read of " + std::to_string(n) + " bases does not fit rows of " + std::to_string(stride); return false; }
+            if (n > s->max_read) {
+                what_rc = SNK_E_UNSUPPORTED;
+                if (s->by_read_len) what = path + ": record " + std::to_string(pairs_in_file) + ": a read of " + std::to_string(n) + " bases is longer than read_len = " + std::to_string(s->max_read) + " (reads are not cut: give the lane's longest read as read_len)";
+                else what = path + ": a read of " + std::to_string(n) + " bases does not fit rows of " + std::to_string(stride);
+                return false;
+            }
             uint8_t* row = b.ascii + (2 * b.n_pairs + (li >> 1)) * (size_t)stride;
             memcpy(row, p, n);
             memset(row + n, 'A', stride - n);
@@ -314,7 +322,7 @@ bool decode_file(snk_fasth_stream* s, uint32_t fi) {
     }
     if (ok && li != 0) { what = path + ": truncated record " + std::to_string(pairs_in_file); ok = false; }
     if (!ok) {
-        if (!what.empty()) fail(s, what.find("does not fit") != std::string::npos ? SNK_E_UNSUPPORTED : SNK_E_IO, what);
+        if (!what.empty()) fail(s, what_rc, what);
         return false;
     }
     flush(true);
@@ -343,10 +351,15 @@ void free_batch(snk_fasth_stream::batch& b) {
 
 extern "C" uint32_t snk_host_cpu_budget(void) { return host_cpu_budget(); }
 
-extern "C" int snk_fasth_open(const char* const* paths, uint32_t n_files, uint32_t stride, uint32_t batch_pairs, uint32_t threads, uint32_t flags,
-                              snk_fasth_stream** out, char* err, size_t errcap) {
+namespace {
+// max_read: reads longer than this are refused (SNK_E_UNSUPPORTED), 0 = whatever fits a row.  The device entry points pass their read_len:
+// every kernel behind them takes a read's length as min(lens[], read_len), so a longer read would lose its tail without a word.
+int fasth_open(const char* const* paths, uint32_t n_files, uint32_t stride, uint32_t max_read, uint32_t batch_pairs, uint32_t threads, uint32_t flags,
+               snk_fasth_stream** out, char* err, size_t errcap) {
     if (!paths || !out || n_files == 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_fasth_open: no files");
     if (stride == 0 || stride > 65535) return snk_fail(SNK_E_ARG, err, errcap, "snk_fasth_open: bad row stride");
+    const bool by_read_len = max_read != 0;
+    if (max_read == 0 || max_read > stride) max_read = stride;
     if (batch_pairs == 0) batch_pairs = 32768;
     if (threads == 0) { const uint32_t b = host_cpu_budget(); threads = b > 3 ? b - 2 : b; }       // (the consumer and the HIP runtime's helpers want CPUs too)
     if (threads > n_files) threads = n_files;
@@ -354,6 +367,8 @@ extern "C" int snk_fasth_open(const char* const* paths, uint32_t n_files, uint32
     snk_fasth_stream* s = new snk_fasth_stream();
     for (uint32_t i = 0; i < n_files; ++i) s->paths.push_back(paths[i] ? paths[i] : "");
     s->stride = stride;
+    s->max_read = max_read;
+    s->by_read_len = by_read_len;
     s->batch_pairs = batch_pairs;
     s->file_pairs.assign(n_files, 0);
     const bool want_pinned = (flags & 1u) != 0;
@@ -386,6 +401,12 @@ extern "C" int snk_fasth_open(const char* const* paths, uint32_t n_files, uint32
     for (uint32_t t = 0; t < threads; ++t) s->workers.emplace_back(worker_main, s);
     *out = s;
     return SNK_OK;
+}
+}  // namespace
+
+extern "C" int snk_fasth_open(const char* const* paths, uint32_t n_files, uint32_t stride, uint32_t batch_pairs, uint32_t threads, uint32_t flags,
+                              snk_fasth_stream** out, char* err, size_t errcap) {
+    return fasth_open(paths, n_files, stride, 0, batch_pairs, threads, flags, out, err, errcap);
 }
 
 extern "C" int snk_fasth_next(snk_fasth_stream* s, snk_fasth_batch* out, char* err, size_t errcap) {
@@ -521,7 +542,7 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
     for (uint32_t i = 0; i < n_files; ++i) { FILE* f = fopen(paths[i], "rb"); if (f) { fseek(f, 0, SEEK_END); const long n = ftell(f); if (n > 0) comp += (uint64_t)n; fclose(f); } }
     uint64_t cap = comp / 70 + 4ull * batch_pairs;
     snk_fasth_stream* fs = nullptr;
-    int rc = snk_fasth_open(paths, n_files, stride, batch_pairs, threads, 1u, &fs, err, errcap);
+    int rc = fasth_open(paths, n_files, stride, read_len, batch_pairs, threads, 1u, &fs, err, errcap);
     if (rc) return rc;
     hipStream_t cs = nullptr;
     constexpr int NST = 4;
@@ -537,7 +558,7 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
     std::deque<pend> pending;
     std::vector<hipEvent_t> ev_pool;
     uint64_t n_reads = 0, text = 0;
-    uint32_t max_len = 0;
+    uint32_t max_len = 0, n_grown = 0;
     auto cleanup = [&]() {
         if (cs) (void)hipStreamSynchronize(cs);
         for (auto& p : pending) { (void)hipEventDestroy(p.ev); snk_fasth_release(fs, &p.b); }
@@ -590,6 +611,7 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
             ING_TRY(hipStreamSynchronize(cs));
             A.release();
             A = N;
+            ++n_grown;
         }
         const double s0 = now_s();
         if (st_busy[slot]) { ING_TRY(hipEventSynchronize(st_ev[slot])); st_busy[slot] = false; }
@@ -621,14 +643,15 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
     }
     const double t_loop = now_s();
     ING_TRY(hipStreamSynchronize(cs));
-    if (trace) fprintf(stderr, "[snk ingest] setup %.3f s | loop %.3f s: wait for decode %.3f, wait for copies (batch hand-back) %.3f, wait for a staging slot %.3f, issue %.3f | drain %.3f s | %zu batches\n",
-                       t_ready - t0, t_loop - t_ready, wait_s, t_pend, t_slot, t_issue, now_s() - t_loop, pieces.size());
+    const double t_drained = now_s();
     while (!pending.empty()) { (void)hipEventDestroy(pending.front().ev); snk_fasth_release(fs, &pending.front().b); pending.pop_front(); }
     // ---- file-major order
     std::vector<uint64_t> fbase(n_files + 1, 0);
     for (uint32_t i = 0; i < n_files; ++i) fbase[i + 1] = fbase[i] + 2 * snk_fasth_file_pairs(fs, i);
     bool in_order = true;
     for (auto& p : pieces) if (fbase[p.file] + 2 * p.first_pair != p.at) { in_order = false; break; }
+    if (trace) fprintf(stderr, "[snk ingest] setup %.3f s | loop %.3f s: wait for decode %.3f, wait for copies (batch hand-back) %.3f, wait for a staging slot %.3f, issue %.3f | drain %.3f s | %zu batches | arrays grown %u times | reordered %d\n",
+                       t_ready - t0, t_loop - t_ready, wait_s, t_pend, t_slot, t_issue, t_drained - t_loop, pieces.size(), n_grown, in_order ? 0 : 1);
     if (!in_order) {
         ING_RC(alloc_arrays(Bf, n_reads, row_words, qstride, ix != nullptr, err, errcap));
         for (auto& p : pieces) {
@@ -657,33 +680,18 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
 // and is appended to a streamed job (snk_dev_stream_*, snk_pipeline.hip) -- partitioned into the job's minimiser buckets while the
 // workers inflate the next batches; finish() counts and builds the graph.  Wall time = max(ingest, partition) + count + graph, not
 // their sum; the device holds the supermer records, not the reads.  total_reads_hint: an upper bound of the job's reads (it sizes the
-// bucket slots); 0 = derived from the compressed sizes.
-extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths, uint32_t n_files, uint32_t read_len, const snk_bc_index* ix, uint32_t threads,
-                                          uint32_t batch_pairs, uint64_t total_reads_hint, const snk_params* p, snk_dev_result* res, snk_dev_ingest* out, char* err,
-                                          size_t errcap) {
-    if (!ctx || !paths || !out || !p || !res || n_files == 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: NULL argument");
-    if (read_len == 0 || read_len > 256) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: read_len must be 1..256");
-    memset(out, 0, sizeof *out);
-    SNK_HIP_TRY(snk_enter(ctx));
+// bucket slots); 0 = derived from the compressed sizes, a guess: when the files hold more reads than it, the job is run a second time.
+namespace {
+// One pass over the files with the job sized for `ub` reads.  A batch that would cross the bound: with the caller's own hint the job is
+// refused there and then; with the derived bound (hint 0) nothing more is uploaded, the decode goes on to the end to count the reads, and
+// *need is their number (res is not filled): the caller runs the job again with it.
+int ingest_count_graph_once(snk_ctx* ctx, const char* const* paths, uint32_t n_files, uint32_t read_len, const snk_bc_index* ix, uint32_t threads, uint32_t batch_pairs,
+                            uint64_t total_reads_hint, uint64_t ub, uint64_t comp, double t0, const snk_params* p, snk_dev_result* res, snk_dev_ingest* out, uint64_t* need,
+                            char* err, size_t errcap) {
     const uint32_t stride = (read_len + 15) / 16 * 16, row_words = (read_len + 15) / 16, qstride = stride;
-    if (batch_pairs == 0) batch_pairs = 65536;
-    const double t0 = now_s();
-    uint64_t comp = 0;
-    uint64_t isize_sum = 0;      // text bytes by the files' gzip trailers (exact for the one-member files the reference writes, below 4 GB each)
-    for (uint32_t i = 0; i < n_files; ++i) {
-        struct stat sb;
-        if (stat(paths[i], &sb) == 0 && sb.st_size > 0) {
-            comp += (uint64_t)sb.st_size;
-            if (sb.st_size >= 18) { FILE* f = fopen(paths[i], "rb"); if (f) { uint32_t is = 0; if (fseek(f, -4, SEEK_END) == 0 && fread(&is, 4, 1, f) == 1) isize_sum += is; fclose(f); } }
-        }
-    }
-    // a read pair is ~650 bytes of text that deflate to ~130; 45 compressed bytes per read is a bound with a margin of a third -- unless the
-    // files compress better than usual (binned qualities): the trailers' text sizes bound the reads as well (a read is at least its bases
-    // and qualities with their line ends), and the larger bound counts (the job used to fail late on such files)
-    const uint64_t ub_isize = isize_sum / (2ull * read_len + 2);
-    const uint64_t ub = total_reads_hint ? total_reads_hint : std::max(comp / 45, ub_isize) + 8ull * batch_pairs;
+    *need = 0;
     snk_fasth_stream* fs = nullptr;
-    int rc = snk_fasth_open(paths, n_files, stride, batch_pairs, threads, 1u, &fs, err, errcap);
+    int rc = fasth_open(paths, n_files, stride, read_len, batch_pairs, threads, 1u, &fs, err, errcap);
     if (rc) return rc;
     hipStream_t cs = nullptr;
     constexpr int NST = 4;
@@ -720,6 +728,7 @@ extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths
     double wait_s = 0;
     uint64_t n_reads = 0, text = 0;
     uint32_t max_len = 0, n_batches = 0;
+    bool counting = false;          // the derived bound was crossed: no more uploads, the rest of the decode only counts
     const double t_ready = now_s();
     for (;;) {
         while (!pending.empty() && (pending.size() > 2 || hipEventQuery(pending.front().ev) == hipSuccess)) {
@@ -734,6 +743,18 @@ extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths
         wait_s += now_s() - w0;
         if (b.n_pairs == 0) break;
         const uint64_t nr = 2 * b.n_pairs;
+        if (counting || n_reads + nr > ub) {
+            if (total_reads_hint) {
+                snk_fasth_release(fs, &b);
+                cleanup();
+                return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: more reads than the job's upper bound: total_reads_hint = %llu, %llu reads decoded so far and more to come",
+                                (unsigned long long)total_reads_hint, (unsigned long long)(n_reads + nr));
+            }
+            counting = true;
+            n_reads += nr;
+            snk_fasth_release(fs, &b);
+            continue;
+        }
         slot_t& q = S[slot];
         if (q.busy) { ING_TRY(hipEventSynchronize(q.ev)); q.busy = false; }        // the partition launch that read this slot is done
         ING_TRY(hipMemcpyAsync(q.ascii, b.ascii, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
@@ -764,6 +785,11 @@ extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths
         ++n_batches;
         if (b.max_len > max_len) max_len = b.max_len;
     }
+    if (counting) {
+        cleanup();          // (the open job stays with the context: the next snk_dev_stream_begin drops it)
+        *need = n_reads;
+        return SNK_OK;
+    }
     const double t_decoded = now_s();
     ING_RC(snk_dev_stream_finish(ctx, res, cs, err, errcap));
     ING_TRY(hipStreamSynchronize(cs));
@@ -776,6 +802,44 @@ extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths
     return SNK_OK;
 #undef ING_TRY
 #undef ING_RC
+}
+}  // namespace
+
+extern "C" int snk_dev_ingest_count_graph(snk_ctx* ctx, const char* const* paths, uint32_t n_files, uint32_t read_len, const snk_bc_index* ix, uint32_t threads,
+                                          uint32_t batch_pairs, uint64_t total_reads_hint, const snk_params* p, snk_dev_result* res, snk_dev_ingest* out, char* err,
+                                          size_t errcap) {
+    if (!ctx || !paths || !out || !p || !res || n_files == 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: NULL argument");
+    if (read_len == 0 || read_len > 256) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: read_len must be 1..256");
+    memset(out, 0, sizeof *out);
+    SNK_HIP_TRY(snk_enter(ctx));
+    if (batch_pairs == 0) batch_pairs = 65536;
+    const double t0 = now_s();
+    uint64_t comp = 0;
+    uint64_t isize_sum = 0;      // text bytes by the files' gzip trailers (exact for the one-member files the reference writes, below 4 GB each)
+    for (uint32_t i = 0; i < n_files; ++i) {
+        struct stat sb;
+        if (stat(paths[i], &sb) == 0 && sb.st_size > 0) {
+            comp += (uint64_t)sb.st_size;
+            if (sb.st_size >= 18) { FILE* f = fopen(paths[i], "rb"); if (f) { uint32_t is = 0; if (fseek(f, -4, SEEK_END) == 0 && fread(&is, 4, 1, f) == 1) isize_sum += is; fclose(f); } }
+        }
+    }
+    // a read pair is ~650 bytes of text that deflate to ~130; 45 compressed bytes per read is a bound with a margin of a third -- unless the
+    // files compress better than usual (binned qualities): the trailers' text sizes bound the reads as well (a read is at least its bases
+    // and qualities with their line ends), and the larger bound counts.  Both are guesses: a trailer speaks for the last gzip member of
+    // its file only, reads shorter than read_len take less text, repetitive lanes deflate further.
+    const uint64_t ub_isize = isize_sum / (2ull * read_len + 2);
+    const uint64_t ub = total_reads_hint ? total_reads_hint : std::max(comp / 45, ub_isize) + 8ull * batch_pairs;
+    const bool trace = getenv("SNK_INGEST_TRACE") && *getenv("SNK_INGEST_TRACE") == '1';
+    uint64_t need = 0;
+    int rc = ingest_count_graph_once(ctx, paths, n_files, read_len, ix, threads, batch_pairs, total_reads_hint, ub, comp, t0, p, res, out, &need, err, errcap);
+    if (rc || need == 0) return rc;
+    // the guess was too small and the files are still there: the same job sized by the count of the first pass (one more decode of the lane)
+    if (trace) fprintf(stderr, "[snk ingest] derived bound of %llu reads too small for %llu: job restarted\n", (unsigned long long)ub, (unsigned long long)need);
+    const uint64_t counted = need;
+    rc = ingest_count_graph_once(ctx, paths, n_files, read_len, ix, threads, batch_pairs, 0, counted, comp, t0, p, res, out, &need, err, errcap);
+    if (rc) return rc;
+    if (need) return snk_fail(SNK_E_IO, err, errcap, "snk_dev_ingest_count_graph: the files changed while they were read (%llu reads, then %llu)", (unsigned long long)counted, (unsigned long long)need);
+    return SNK_OK;
 }
 
 extern "C" void snk_dev_ingest_free(snk_dev_ingest* r) {

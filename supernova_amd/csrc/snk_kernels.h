@@ -65,6 +65,10 @@ struct snk_msp_args {
     // over the same slot memory, the reads scanned once per pass (what the reference's MapReduce engine does when its records do not
     // fit: lib/assembly/src/MapReduceEngine.h:452-468)
     uint32_t b_lo, b_hi;
+    // added to the wave number that picks the overflow sub-list.  A job that partitions many small slabs (snk_partition_add) steps it
+    // from launch to launch: the few waves of a small launch would otherwise fill the same few sub-lists, slab after slab, and a
+    // sub-list overruns at a sixty-fourth of what the list holds
+    uint32_t ovf_rot;
 };
 constexpr int SNK_MSP_PLAN_SLOTS = 256;
 constexpr uint32_t SNK_OVF_SUBLISTS = 64;

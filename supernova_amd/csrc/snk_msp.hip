@@ -340,7 +340,7 @@ __global__ void __launch_bounds__(BD, K == 48 ? SNK_MSP_OCC48 : 4) snk_msp_kerne
                         const int lane = tid & 63, leader = __ffsll((long long)m) - 1;
                         // ... on one of SNK_OVF_SUBLISTS cursors, by wave: with a repeat-rich genome a few per cent of all supermers
                         // overflow, nearly every wave has one in every turn, and ten million reservations on ONE address were 108 ms
-                        const uint32_t sub = (blockIdx.x * (BD / 64) + ((uint32_t)tid >> 6)) & (SNK_OVF_SUBLISTS - 1u);
+                        const uint32_t sub = (a.ovf_rot + blockIdx.x * (BD / 64) + ((uint32_t)tid >> 6)) & (SNK_OVF_SUBLISTS - 1u);
                         uint32_t o = 0;
                         if (lane == leader) o = atomicAdd(&a.ovf_cursor[sub * SNK_OVF_CUR_STRIDE], (uint32_t)__popcll(m));
                         o = __shfl(o, leader) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));

@@ -1063,6 +1063,7 @@ int snk_partition_add(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, const 
     ma.cursor = J->cursor; ma.records = (uint4*)J->records; ma.cap = J->cap; ma.ovf_cap = (uint32_t)(J->ovf_cap / SNK_OVF_SUBLISTS);
     ma.ovf_base = (uint64_t)J->NB * J->cap; ma.ovf_bucket = J->ovf_bucket; ma.ovf_cursor = J->ovf_cur;
     ma.hot_tab = J->cursor + J->NB + 1; ma.hot_thr = msp_hot_thr(ctx, J->cap);
+    ma.ovf_rot = (uint32_t)(J->n_slabs * 17u);          // (17 is odd: 64 slabs in a row start at 64 different sub-lists)
     if (ft) {
         ma.good_len = ft->good_out; ma.quals = (const uint8_t*)ft->quals; ma.qstride = ft->qstride; ma.min_qual = ft->min_qual;
         ma.lens = (const uint16_t*)ft->lens; ma.good_out = ft->good_out; ma.plan = J->d_plan;

@@ -367,3 +367,73 @@ def test_host_api_count_graph_and_hbv():
     assert us == c.exp_unitigs                    # same order as the reference's BVComp sort
     assert stats["n_kmers"] == len(c.exp_keys)
     assert graphio.hbv_text(us, graphio.hbv_from_unitigs(48, off, bases)) == c.exp_hbv
+
+
+def test_damaged_fasth_files_raise_or_read_alike(snk, tmp_path, monkeypatch):
+    """One valid file of 300 ragged pairs and some 250 damaged copies of it -- one byte replaced, at positions spread over the gzip header,
+    the deflate body and the trailer; the file cut at some 50 lengths.  For each copy snk_fasth_open/_next (1 and 2 threads, batches of
+    7 pairs, whole-file and streaming inflate) either raises or returns exactly what Python's gzip followed by the restatement of
+    MultiFastqIter returns; where the restatement cannot read the file, the library raises.  Both outcomes occur: an edit in MTIME,
+    XFL or OS reads alike on both sides, an edit in the body or the trailer does not read at all."""
+    import zlib
+    import fasthgen
+    from supernova_amd.lib import SnkError
+    from supernova_amd.martian import BcIndexer, read_fasth, read_fasth_stream
+    rng = np.random.default_rng(0xDA11)
+    wl, seqs = fasthgen.odd_whitelist(rng)
+    ix = BcIndexer(fasthgen.whitelist_lines(wl))
+    good = Path(fasthgen.write_fasth(tmp_path / "good.fasth.gz", fasthgen.odd_records(rng, 300, 200, seqs)))
+    whole = good.read_bytes()
+    n = len(whole)
+    assert whole[:4] == b"\x1f\x8b\x08\x00" and n > 2000
+    copies = []
+    body = np.linspace(10, n - 9, 170).astype(int).tolist()
+    for pos in sorted(set(list(range(10)) + body + list(range(n - 8, n)))):
+        for _ in range(2 if pos < 10 or pos >= n - 8 else 1):
+            v = int(rng.integers(0, 256))
+            while v == whole[pos]:
+                v = int(rng.integers(0, 256))
+            copies.append((f"byte {pos} = {v:#x}", whole[:pos] + bytes([v]) + whole[pos + 1:]))
+    cuts = sorted(set([0, 1, 2, 3, 9, 10, 11, 17, 18, 19, n - 9, n - 8, n - 7, n - 4, n - 1] + np.linspace(20, n - 10, 37).astype(int).tolist()))
+    copies += [(f"cut at {c}", whole[:c]) for c in cuts]
+    copies.append(("intact", whole))
+    assert 240 <= len(copies) <= 280
+
+    def fields_ids(fields):
+        return np.array([ix.get_bc_id(bytes(f[:int(np.argmax(f == 0)) if (f == 0).any() else 64]).decode()) or 0 for f in fields], dtype=np.int32)
+
+    alike, refused_both, refused_lib_only = 0, 0, 0
+    p = tmp_path / "damaged.fasth.gz"
+    for what, data in copies:
+        p.write_bytes(data)
+        try:
+            exp = read_fasth([str(p)], ix)
+        except (OSError, EOFError, zlib.error, ValueError, OverflowError):
+            exp = None
+        outcomes = set()
+        for whole_mb in (None, "0"):              # libdeflate's whole-file inflate where the host has it, zlib's streaming inflate
+            if whole_mb is None:
+                monkeypatch.delenv("SNK_FASTH_WHOLE_MAX_MB", raising=False)
+            else:
+                monkeypatch.setenv("SNK_FASTH_WHOLE_MAX_MB", whole_mb)
+            for threads in (1, 2):
+                try:
+                    asc, qa, lens, fields, st = read_fasth_stream([str(p)] * threads, threads=threads, batch_pairs=7)
+                except SnkError:
+                    outcomes.add("raised")
+                    continue
+                assert exp is not None, f"{what}: the library read a file that gzip + the restatement cannot read"
+                e_asc, e_qa, e_lens, e_bc = (np.concatenate([x] * threads) for x in exp)
+                assert np.array_equal(lens, e_lens) and asc.shape == e_asc.shape, what
+                assert np.array_equal(asc, e_asc) and np.array_equal(qa, e_qa), what
+                assert np.array_equal(np.repeat(fields_ids(fields), 2), e_bc), what
+                outcomes.add("alike")
+        assert len(outcomes) == 1, (what, outcomes)          # the same file, the same answer from every reader
+        if "alike" in outcomes:
+            alike += 1
+        elif exp is None:
+            refused_both += 1
+        else:
+            refused_lib_only += 1
+    monkeypatch.delenv("SNK_FASTH_WHOLE_MAX_MB", raising=False)
+    assert alike >= 8 and refused_both >= 150, (alike, refused_both, refused_lib_only)
