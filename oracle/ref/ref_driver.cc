@@ -19,7 +19,7 @@
 // Built only by oracle/ref/build_ref.sh from the sources where they lie in
 // /root/reference; the binary lands in oracle/_ref/ (git-ignored).
 //
-// usage: snref_driver <in.snkr> <outdir> [threads=8] [mode=dump|time] [minQual=7 minFreq=3 minBC=2]
+// usage: snref_driver <in.snkr> <outdir> [threads=8] [mode=dump|graph|time|formats] [minQual=7 minFreq=3 minBC=2]
 
 #ifdef SNK_REF_K60
 // K=60 variant of the reference (paths/long/BuildReadQGraph60.cc: createDict :148, buildEdges :378); it has no
@@ -90,7 +90,7 @@ std::string bvstr(bvec const& b) {
 
 int main(int argc, char** argv) {
     RunTime();
-    if (argc < 3) die("usage: snref_driver <in.snkr> <outdir> [threads] [dump|time] [minQual minFreq minBC]");
+    if (argc < 3) die("usage: snref_driver <in.snkr> <outdir> [threads] [dump|graph|time|formats] [minQual minFreq minBC]");
     std::string inpath = argv[1], outdir = argv[2];
     unsigned nt = argc > 3 ? atoi(argv[3]) : 8;
     std::string mode = argc > 4 ? argv[4] : "dump";
@@ -228,8 +228,9 @@ int main(int argc, char** argv) {
     buildEdges(*pDict, &edges);
 #ifndef SNK_REF_K60
     // ---- read paths: the pPaths != nullptr branch of buildReadQGraph48 (:1749-1769) -- graph from the edges as built, then
-    //      pathReads with the new aligner (RunStages.cc:405-406 passes useNewAligner = True)
-    {
+    //      pathReads with the new aligner (RunStages.cc:405-406 passes useNewAligner = True).  Mode "graph" stops before it:
+    //      the table, unitigs and graph files only, for read sets whose paths nobody stores (tens of millions of edge entries)
+    if (mode != "graph") {
         HyperBasevector hbvp;
         vec<int> fwdp, revp;
         buildHBVFromEdges(edges, K, &hbvp, &fwdp, &revp);

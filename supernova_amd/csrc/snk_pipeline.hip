@@ -226,6 +226,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     const bool local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32(ctx, SNK_OPT_global_graph);
     const uint64_t mark = ctx->alloc_serial;
     const unsigned long long ub_inst = h_plan[0], ub_live = h_plan[1];
+    uint64_t ovf_floor = 0;          // bucket-range passes: the overflow list a pass asked for (SNK_OVF_RETRY)
     for (int pass = 0; pass < 2; ++pass) {
         pin.ratio = ratio;
         const snk_plan_out plan = snk_bucket_plan(pin);
@@ -235,7 +236,7 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         if (plan.screen && ratio > 0.0) ctx->sizing.screen_ratio = ratio;      // (what the screened call reports is the table's view: the decision keeps the ratio it was made on)
         ctx->last_count_limit = plan.count_limit;
         out->n_buckets = NB;
-        if (pass == 0) tm.mark();  // 2
+        if (pass == 0 && !ovf_floor) tm.mark();  // 2
         h_plan[0] = ub_inst; h_plan[1] = ub_live;
         // ---- a job whose slots would not fit: bucket-range passes over one slot array (snk_stages.h); the count stage's range hook
         //      partitions range r right before range r is counted
@@ -243,8 +244,8 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
         ctx->last_partition_passes = n_passes;
         if (n_passes > 1) {
             snk_partition_passes PS;
-            if ((rc = snk_partition_passes_open(ctx, st, K, in, good_len, fused ? &ft : nullptr, NB, n_passes, ub_inst, ub_live, grouped, &PS, err, errcap))) return rc;
-            if (pass == 0) tm.mark();  // 3 (the partition's time is inside the count stage's here)
+            if ((rc = snk_partition_passes_open(ctx, st, K, in, good_len, fused ? &ft : nullptr, NB, n_passes, ub_inst, ub_live, grouped, &PS, err, errcap, ovf_floor))) return rc;
+            if (pass == 0 && !ovf_floor) tm.mark();  // 3 (the partition's time is inside the count stage's here)
             std::vector<snk_hot> pass_hots;
             PS.hots = &pass_hots;
             snk_count_ranges rgs{n_passes, PS.bounds, snk_partition_passes_run, &PS, true, &pass_hots};
@@ -259,6 +260,15 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
             const bool want_pilot_p = adaptive && pass == 0 && !have_hint;
             rc = snk_stage_count_table(ctx, st, K, PS.records, PS.seg, PS.seg + NB, 2 * NB, 2u, NB, p->min_freq, (in->bc && !grouped) ? p->min_bc : 0u, grouped ? 1u : 0u,
                                        ub_inst, status, !local_graph, &tab, err, errcap, &rgs, want_pilot_p ? &pilot_p : nullptr, nullptr, local_graph, nullptr);
+            if (rc == SNK_OVF_RETRY) {
+                // a pass's overflow list was too short for this data (snk_stages.h): everything since the mark goes back, the passes once more
+                // with a list that holds what the pass asked for -- this plan again, so the loop's counter stays
+                ovf_floor = PS.ovf_want;
+                snk_ctx_release_since(ctx, mark, nullptr, 0);
+                SNK_HIP_TRY(hipMemsetAsync(status, 0, 64, st));
+                --pass;
+                continue;
+            }
             if (rc == SNK_RETARGET) {
                 const unsigned long long inst_now = PS.h_plan[0] ? PS.h_plan[0] : ub_inst;
                 snk_ctx_release_since(ctx, mark, nullptr, 0);

@@ -123,9 +123,17 @@ struct snk_partition_passes {
     unsigned long long h_plan[2]; uint64_t n_supermers, n_overflow; float kernel_ms; uint32_t runs;
     std::vector<snk_hot>* hots; uint32_t n_hot;          // the passes' hot buckets, expanded while their records were there (owned by the caller)
     char* err; size_t errcap;
+    bool ovf_retried;             // opened with a floor: the next overflow is final
+    uint64_t ovf_want;            // set with SNK_OVF_RETRY: the overflow list that would have held the pass
 };
+// a pass whose supermers beyond their buckets' capacity did not fit the overflow list (a few minimisers carry a large share of the data: a
+// homopolymer, a satellite) returns SNK_OVF_RETRY through the count stage (S->ovf_want says how large a list holds them); the caller gives
+// everything since its mark back and opens the passes again with ovf_floor = that figure, as the one-pass partition runs again with a
+// longer list.  A pass that fails with the floor set fails for good (SNK_E_NOMEM).
+constexpr int SNK_OVF_RETRY = 1001;
 int snk_partition_passes_open(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_reads* in, const uint16_t* good_len, const snk_fused_trim* ft, uint32_t NB,
-                              uint32_t passes, unsigned long long n_inst, unsigned long long n_live, bool grouped, snk_partition_passes* S, char* err, size_t errcap);
+                              uint32_t passes, unsigned long long n_inst, unsigned long long n_live, bool grouped, snk_partition_passes* S, char* err, size_t errcap,
+                              uint64_t ovf_floor = 0);
 int snk_partition_passes_run(void* user, uint32_t r);
 // passes a job of this size needs so that its slots take at most ~a quarter of the device (1: the one-pass partition)
 uint32_t snk_partition_passes_needed(snk_ctx* ctx, uint32_t K, uint32_t NB, unsigned long long n_inst, unsigned long long n_live, bool grouped);

@@ -891,7 +891,8 @@ uint32_t snk_partition_passes_needed(snk_ctx* ctx, uint32_t K, uint32_t NB, unsi
 }
 
 int snk_partition_passes_open(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_dev_reads* in, const uint16_t* good_len, const snk_fused_trim* ft, uint32_t NB,
-                              uint32_t passes, unsigned long long n_inst, unsigned long long n_live, bool grouped, snk_partition_passes* S, char* err, size_t errcap) {
+                              uint32_t passes, unsigned long long n_inst, unsigned long long n_live, bool grouped, snk_partition_passes* S, char* err, size_t errcap,
+                              uint64_t ovf_floor) {
     if (passes < 1 || passes > 64 || passes > NB) return snk_fail(SNK_E_ARG, err, errcap, "partition passes: 1..64 (and at most one per bucket)");
     S->ctx = ctx; S->st = st; S->K = K; S->NB = NB; S->P = passes; S->grouped = grouped; S->in = *in; S->good_len = good_len; S->fused = ft != nullptr;
     if (ft) S->ft = *ft;
@@ -906,8 +907,11 @@ int snk_partition_passes_open(snk_ctx* ctx, hipStream_t st, uint32_t K, const sn
     for (uint32_t r = 0; r <= passes; ++r) S->bounds[r] = (uint32_t)((uint64_t)NB * r / passes);
     for (uint32_t r = 0; r < passes; ++r) widest = std::max(widest, S->bounds[r + 1] - S->bounds[r]);
     S->slots_per_pass = (uint64_t)widest * S->cap;
-    // (nothing can be looked at and run again with a larger list: a generous one, as for a streamed job)
+    // (a generous list, as for a streamed job: a pass that overflows it all the same costs the whole run once more, SNK_OVF_RETRY)
     S->ovf_cap = ((uint64_t)(est_super / passes / 6) + (1u << 20) + SNK_OVF_SUBLISTS - 1) / SNK_OVF_SUBLISTS * SNK_OVF_SUBLISTS;
+    S->ovf_want = 0;
+    S->ovf_retried = ovf_floor != 0;
+    if (ovf_floor > S->ovf_cap) S->ovf_cap = (ovf_floor + SNK_OVF_SUBLISTS - 1) / SNK_OVF_SUBLISTS * SNK_OVF_SUBLISTS;
     if (S->ovf_cap >= (1ull << 31)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "supermer overflow list too large");
     int rc;
     void* q;
@@ -974,9 +978,13 @@ int snk_partition_passes_run(void* user, uint32_t r) {
     uint64_t want = 0, mx = 0, tot = 0;
     for (uint32_t q = 0; q < SNK_OVF_SUBLISTS; ++q) { h_sub[q] = h_cur[q * SNK_OVF_CUR_STRIDE]; want += h_sub[q]; if (h_sub[q] > mx) mx = h_sub[q]; }
     for (int q = 0; q < 64; ++q) tot += h_tot64[q];
-    if (mx > S->ovf_cap / SNK_OVF_SUBLISTS)
-        return snk_fail(SNK_E_NOMEM, err, errcap, "partition pass %u of %u: %llu supermers beyond their buckets' capacity, the overflow list holds %llu (a few minimisers carry a "
-                        "large share of the data): more passes (SNK_PARTITION_PASSES) give the list more room", r, S->P, (unsigned long long)want, (unsigned long long)S->ovf_cap);
+    if (mx > S->ovf_cap / SNK_OVF_SUBLISTS) {
+        snk_fail(SNK_E_NOMEM, err, errcap, "partition pass %u of %u: %llu supermers beyond their buckets' capacity, the overflow list holds %llu (a few minimisers carry a "
+                 "large share of the data)", r, S->P, (unsigned long long)want, (unsigned long long)S->ovf_cap);
+        if (S->ovf_retried) return SNK_E_NOMEM;
+        S->ovf_want = (mx + mx / 8 + 1024) * SNK_OVF_SUBLISTS;      // (the cursors counted every supermer that asked; sized as the one-pass partition sizes its second run)
+        return SNK_OVF_RETRY;
+    }
     S->n_supermers += tot + want;
     S->n_overflow += want;
     S->kernel_ms += kt.ms(0, 1);

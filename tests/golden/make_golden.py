@@ -157,7 +157,16 @@ def dups_case(n_reads=4000, seed=0x5EED00D0):
     return out
 
 
+def big_groups_case():
+    """tests/pathgen.big_group_reads: duplicate groups of 7 to 257 pairs with interleaved runs among ordinary pairs (full dump)."""
+    import pathgen
+    codes, quals, lens, bc, _groups = pathgen.big_group_reads()
+    return dict(lens=lens.astype(np.uint16), ascii=synth.codes_to_ascii(codes), quals=quals, bc=bc.astype(np.int32), ign_bc_below=0,
+                meta=dict(kind="big_groups", generator="pathgen.big_group_reads"))
+
+
 CASES = {
+    "dup_groups": big_groups_case,
     "synth_4k_dups": lambda: dups_case(),
     "synth_2k_err": lambda: synth_case(2000, 0x5EED0001, False),
     "synth_6k_clean": lambda: synth_case(6000, 0x5EED0002, True),
@@ -213,6 +222,35 @@ def make(name: str) -> None:
 GOLD = Path(__file__).resolve().parent
 
 
+def make_hot() -> None:
+    """hot_kmers.npz / hot_kmers_k60.npz: the reference's table, unitigs, graph files and spectrum for the saturating read set of
+    tests/hotgen.py (one k-mer above 2^24-1 instances, one exactly one below).  Lean layout: the reads are not stored (their digest is),
+    the spectrum is stored sparse (its dense form has 2^24 bins), and the driver stops after the graph (mode "graph": nobody stores
+    the paths of 170 k homopolymer reads)."""
+    import hotgen
+    codes, quals, lens, bc = hotgen.reads()
+    dg = np.frombuffer(hotgen.digest(codes, quals, lens, bc), dtype=np.uint8)
+    asc = synth.codes_to_ascii(codes)
+    with tempfile.TemporaryDirectory() as td:
+        td = Path(td)
+        refio.write_snkrd(td / "in.snkrd", lens, asc, quals, bc, 0)
+        for K, out in ((48, "hot_kmers"), (60, "hot_kmers_k60")):
+            log = refio.run_ref(td / "in.snkrd", td / f"out{K}", mode="graph", K=K)
+            d = refio.read_ref_dump(td / f"out{K}", K=K)
+            summary = [l for l in log.splitlines() if l.startswith("SNREF_DUMP")][-1]
+            hist = np.asarray(d["hist"]["vals"] if d["hist"] else [], dtype=np.int64)
+            bins = np.nonzero(hist)[0]
+            f = GOLD / f"{out}.npz"
+            np.savez_compressed(
+                f, reads_digest=dg, exp_goodlens_digest=np.frombuffer(hotgen.digest(d["goodlens"], [], [], []), dtype=np.uint8),
+                exp_keys=d["kmers"]["k"], exp_counts=d["kmers"]["count"], exp_ctx=d["kmers"]["ctx"],
+                exp_unitigs=np.frombuffer("\n".join(d["unitigs"]).encode(), dtype=np.uint8),
+                exp_ahbv=d["a.hbv"], exp_ainv=d["a.inv"],
+                exp_hist_len=np.int64(len(hist)), exp_hist_bins=bins.astype(np.int64), exp_hist_vals=hist[bins],
+                ref_summary=np.frombuffer(summary.encode(), dtype=np.uint8))
+            print(f"{out}: {summary} max count {int(d['kmers']['count'].max())} hist bins {len(hist)} -> {f.name} ({f.stat().st_size/1024:.0f} KiB)")
+
+
 def make_formats() -> None:
     """tests/golden/formats/: the ASSEMBLER_DF stage inputs (reads.fastb / reads.qualp / reads.bci) of the
     synth_2k_err reads sorted by barcode, written by the REFERENCE's own writers (vecbvec::WriteAll,
@@ -232,6 +270,6 @@ def make_formats() -> None:
 
 
 if __name__ == "__main__":
-    names = sys.argv[1:] or list(CASES) + ["formats"]
+    names = sys.argv[1:] or list(CASES) + ["formats", "hot_kmers"]
     for nm in names:
-        make_formats() if nm == "formats" else make(nm)
+        make_formats() if nm == "formats" else make_hot() if nm == "hot_kmers" else make(nm)

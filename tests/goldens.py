@@ -67,3 +67,37 @@ class Case60:
 
 
 K60_CASES = ["adversarial", "synth_20k_err"]
+
+
+class HotCase:
+    """hot_kmers / hot_kmers_k60: the reference's results for the saturating read set of tests/hotgen.py, in a lean layout -- no reads
+    (generated, and checked against the stored digest), no paths, the spectrum sparse.  Not in CASES: it has no a48 files."""
+
+    def __init__(self, K: int):
+        import hotgen
+        z = np.load(GOLD / ("hot_kmers.npz" if K == 48 else "hot_kmers_k60.npz"))
+        self.K = K
+        self.codes, self.quals, self.lens, self.bc = hotgen.reads(expect_digest=bytes(z["reads_digest"]))
+        self.read_len = hotgen.L
+        self.rows = synth.pack_rows(self.codes)
+        self.exp_goodlens_digest = bytes(z["exp_goodlens_digest"])
+        self.exp_keys = z["exp_keys"]          # [n, 3 or 4] u32
+        self.exp_counts = z["exp_counts"]
+        self.exp_ctx = z["exp_ctx"]
+        self.exp_unitigs = bytes(z["exp_unitigs"]).decode().split("\n") if len(z["exp_unitigs"]) else []
+        self.exp_ahbv = bytes(z["exp_ahbv"])
+        self.exp_ainv = bytes(z["exp_ainv"])
+        # stats/histogram_kmer_count.json as (length, nonzero bins, their values); the K=60 reference writes none (length 0)
+        self.exp_hist_len = int(z["exp_hist_len"])
+        self.exp_hist_bins = z["exp_hist_bins"]
+        self.exp_hist_vals = z["exp_hist_vals"]
+        self.ref_summary = bytes(z["ref_summary"]).decode()
+
+
+_hot: dict[int, HotCase] = {}
+
+
+def load_hot(K: int) -> HotCase:
+    if K not in _hot:
+        _hot[K] = HotCase(K)
+    return _hot[K]

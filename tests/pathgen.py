@@ -98,6 +98,108 @@ def plant_dups(rng, codes, quals, lens, bc, frac: float, nbc: int):
     return codes[idx].copy(), quals[idx].copy(), lens[idx].copy(), bc[idx].copy()
 
 
+def plant_big_groups(rng, codes, quals, lens, bc, sizes):
+    """Duplicate groups of exactly sizes[i] pairs each (far beyond plant_dups' 2-6), every group built from one seed pair: an existing
+    full-length pair without a low quality, so that every copy keeps the seed's (first edge, offset, mate head).  The pairs are then
+    shuffled, so the runs of a group interleave by read id.  -> (codes, quals, lens, bc, groups), groups[i] = the final pair indices
+    of group i, ascending.
+
+    Copy c of a group is, by c mod 10: 0-4 one of five variants tied in their quality sum -- the seed itself, two neighbouring
+    qualities swapped in read 0, in read 1, in both, at another place of read 0 (tied but not identical: several runs per read, three
+    or more exact copies each from size 25 on); 5 a variant again, in another barcode where the group mixes barcodes; 6 a lower
+    quality sum; 7 the same sum with another base behind the mate head (each at a place of its own: never a solid k-mer); 8 a ragged
+    mate (shorter, garbage behind); 9 the seed again.  Kinds 6-8 also swap two qualities of the other read at a place of their own.  By the group's index g mod 7:
+      0  the member with the smallest read id has barcode 0 (the barcode walk starts at 0 and adopts the next)
+      1  the seed is replaced by a fragment that is its own reverse complement (both mates the same read, same qualities: both mates
+         of every pair sit in ONE group of 2 sizes[i] records, and in one run where they are exact copies); two barcodes
+      2  three barcodes
+      3  the member with the largest read id has the one larger quality sum: the best copy is the last member, after ties
+      4  the member with the smallest read id has the one larger sum: the tie never fires, no artifact in the whole group
+      5  two identical copies with the larger sum (a tie among the best); copies of kind 5 in another barcode
+      6  0 and 2 and 3 together"""
+    L = codes.shape[1]
+    n_pairs = codes.shape[0] // 2
+    full = [t for t in range(n_pairs) if lens[2 * t] == L and lens[2 * t + 1] == L and quals[2 * t:2 * t + 2].min() >= 15 and bc[2 * t] > 0]
+    seeds = rng.choice(full, len(sizes), replace=False)
+    codes, quals, lens, bc = codes.copy(), quals.copy(), lens.copy(), bc.copy()
+    extra, members = [], []
+    at = n_pairs
+
+    def swap(q, m, j):
+        while q[m, j] == q[m, j + 1]:
+            j += 1
+        q[m, j], q[m, j + 1] = q[m, j + 1], q[m, j]
+
+    for g, (t, size) in enumerate(zip(seeds, sizes)):
+        kind_g = g % 7
+        if kind_g == 1:
+            x = rng.integers(0, 4, L // 2, dtype=np.uint8)
+            codes[2 * t] = codes[2 * t + 1] = np.concatenate([x, rc(x)])
+            quals[2 * t + 1] = quals[2 * t]
+        a0, q0, b0 = codes[2 * t:2 * t + 2], quals[2 * t:2 * t + 2], int(bc[2 * t])
+        variants = []
+        for v in range(5):
+            q = q0.copy()
+            if v in (1, 3): swap(q, 0, 10)
+            if v in (2, 3): swap(q, 1, 20)
+            if v == 4: swap(q, 0, 80)
+            variants.append(q)
+        members.append([int(t)])
+        for c in range(1, size):
+            a, q, ln, b = a0.copy(), q0.copy(), np.array([L, L], dtype=lens.dtype), b0
+            k, m = c % 10, (c // 10) & 1
+            if k <= 5:
+                q = variants[(k + c // 10) % 5].copy()
+                if k == 5 and kind_g == 5: b = b0 + 1
+            elif k == 6:
+                q[m, 30 + c % 100] -= 1
+            elif k == 7:
+                a[m, 60 + (c // 10) % (L - 60)] ^= 1 + (c // 20) % 3
+            elif k == 8:
+                cut = 60 + (7 * c) % (L - 60); a[m, cut:] = 0; q[m, cut:] = rng.integers(0, 42, L - cut, dtype=np.uint8); ln[m] = cut
+            if k in (6, 7, 8):                    # ... and a quality layout of its own in the other read: an artifact in neither of its two groups
+                swap(q, 1 - m, 5 + (5 * (c // 10) + k) % (L - 8))
+            if kind_g in (2, 6): b = b0 + c % 3
+            if kind_g == 1: b = b0 + c % 2
+            if kind_g == 5 and c in (size // 3, size // 2):
+                q = q0.copy(); q[0, 40] += 2
+            extra.append((a, q, ln, b))
+            members[-1].append(at); at += 1
+    codes = np.concatenate([codes] + [x[0] for x in extra])
+    quals = np.concatenate([quals] + [x[1] for x in extra])
+    lens = np.concatenate([lens] + [x[2] for x in extra])
+    bc = np.concatenate([bc] + [np.array([x[3], x[3]], dtype=np.int32) for x in extra])
+    perm = rng.permutation(codes.shape[0] // 2)
+    idx = np.stack([2 * perm, 2 * perm + 1], axis=1).reshape(-1)
+    codes, quals, lens, bc = codes[idx].copy(), quals[idx].copy(), lens[idx].copy(), bc[idx].copy()
+    inv = np.argsort(perm)
+    groups = [np.sort(inv[np.asarray(m)]) for m in members]
+
+    def better(p, seed):          # pair p becomes the seed pair with a larger quality sum
+        for a in (codes, quals, lens):
+            a[2 * p:2 * p + 2] = a[2 * seed:2 * seed + 2]
+        quals[2 * p + (p & 1), 40] += 2
+
+    for g, mem in enumerate(groups):
+        kind_g, seed = g % 7, int(inv[members[g][0]])
+        if kind_g in (3, 6):
+            better(mem[-1], seed)
+        if kind_g == 4:
+            better(mem[0], seed)
+        if kind_g in (0, 6):
+            bc[2 * mem[0]:2 * mem[0] + 2] = 0
+    return codes, quals, lens, bc, groups
+
+
+def big_group_reads(seed=0xB16D0B5, sizes=(7, 63, 64, 65, 255, 256, 257), n_pairs=400, L=150, G=3000):
+    """The dup_groups read set (tests/golden/dup_groups.npz): about 400 ordinary pairs over a plain 3 kb genome with the planted groups
+    mixed in.  -> (codes, quals, lens, bc, groups)"""
+    rng = np.random.default_rng(seed)
+    g, _ = genome(rng, G, plants=False)
+    codes, quals, lens, bc = pairs(rng, g, n_pairs, L, 0.001, 12)
+    return plant_big_groups(rng, codes, quals, lens, bc, sizes)
+
+
 def to_device(codes, quals, lens, bc, pad_seed=None):
     """-> (rows i32, quals u8, lens i16, bc i32) on cuda:0.  pad_seed: quality rows padded to a multiple of four bytes (and four more
     every other time) with garbage behind the read length, the layout the readers produce."""

@@ -208,3 +208,103 @@ def test_oracle_matches_reference_digest_off_the_operating_point(name):
     dg = bighash.digest(gl.astype(np.uint32), o.keys, np.minimum(o.counts, (1 << 24) - 1), o.ctx, o.unitigs, hist, kw=3)
     bad = [f for f in ("n_reads", "n_kmers", "n_unitigs", "unitig_bases", "goodlens", "keys", "counts", "ctx", "hist", "unitigs") if dg[f] != exp[f]]
     assert not bad, {f: (dg[f], exp[f]) for f in bad}
+
+
+@pytest.fixture(scope="module", params=[48, 60])
+def hot(request):
+    """The saturating read set (tests/hotgen.py) through the C restatement, once per K: (fixture, good lengths, oracle result)."""
+    K = request.param
+    c = goldens.load_hot(K)
+    gl = oracle_lib.good_lens(c.quals, c.lens, K=K, min_qual=7)
+    return c, gl, oracle_lib.OracleResult(c.codes, gl, c.bc if K == 48 else None, K=K, min_freq=3, min_bc=2)
+
+
+def test_oracle_saturates_as_the_reference_does(hot):
+    """The 24-bit count field (kmers/ReadPather.h:127-131,145) reached by data: one k-mer with 17.9 M (K=48) / 16.8 M (K=60)
+    instances, one with exactly 2^24-2 at K=48.  The restatement's RAW counts equal the reference's -- nothing is clamped on the
+    oracle's side of the comparison -- and so do keys, contexts, unitigs, the spectrum and the graph."""
+    import hotgen
+    import a48xref
+    c, gl, o = hot
+    K = c.K
+    assert hotgen.digest(gl.astype(np.uint32), [], [], []) == c.exp_goodlens_digest
+    assert np.array_equal(o.keys[:, :c.exp_keys.shape[1]], c.exp_keys) and np.all(o.keys[:, c.exp_keys.shape[1]:] == 0)
+    assert np.array_equal(o.counts, c.exp_counts)
+    assert np.array_equal(o.ctx, c.exp_ctx)
+    assert o.unitigs == c.exp_unitigs
+    # the fixture is what it is for: the over family saturated, the under family exact, one entry in the last bin
+    for fam in ("over", "under"):
+        i = np.nonzero((o.keys == hotgen.homopolymer_key(fam, K)).all(axis=1))[0]
+        assert len(i) == 1 and int(c.exp_counts[i[0]]) == min(hotgen.true_count(fam, K), hotgen.SAT), (fam, i)
+    assert int((c.exp_counts == hotgen.SAT).sum()) == 1 and int(c.exp_counts.max()) == hotgen.SAT
+    # lengths K (the homopolymer's self-loop), K+1 (the dinucleotide circle, where the solo family survives) and the background
+    lens = sorted(len(u) for u in c.exp_unitigs)
+    assert lens[:2] == [K, K] and (K + 1 in lens) == (K == 60) and lens[-1] > 2000
+    hist = np.bincount(o.counts)
+    if c.exp_hist_len:          # stats/histogram_kmer_count.json (BuildReadQGraph48.cc:199-216; the K=60 variant writes none)
+        assert len(hist) == c.exp_hist_len == hotgen.SAT + 1
+        assert np.array_equal(np.nonzero(hist)[0], c.exp_hist_bins) and np.array_equal(hist[c.exp_hist_bins], c.exp_hist_vals)
+    assert len(hist) == hotgen.SAT + 1 and hist[-1] == 1
+    g = a48xref.parse_hbv(c.exp_ahbv)
+    h = o.hbv
+    assert (h["n_vertices"], h["n_edges"]) == (g.N, g.E)
+    assert np.array_equal(h["v_left"], g.v_left) and np.array_equal(h["v_right"], g.v_right)
+
+
+def test_hot_hbv_files_match_the_reference_writers(snk, tmp_path, hot):
+    """a.hbv / a.inv of the saturating set byte for byte (self-loop edges of the homopolymers, the two-k-mer circle)."""
+    from supernova_amd import graphio
+    c, _gl, o = hot
+    off, bases = graphio.unitigs_to_arrays(o.unitigs)
+    graphio.write_hbv(tmp_path / "a.hbv", tmp_path / "a.inv", c.K, off, bases)
+    assert (tmp_path / "a.hbv").read_bytes() == c.exp_ahbv and (tmp_path / "a.inv").read_bytes() == c.exp_ainv
+
+
+def big_group_sizes(codes, path_off, path_n, path_edges):
+    """Record count of every duplicate group of MarkDups: placed reads by (first edge, offset, first five bases of the mate)."""
+    n = len(path_n)
+    start = np.zeros(n + 1, np.int64)
+    start[1:] = np.cumsum(path_n)
+    placed = np.asarray(path_n) > 0
+    first = np.asarray(path_edges)[start[:-1][placed]]
+    head = np.zeros(n, np.int64)
+    for j in range(5):
+        head = head * 4 + codes[np.arange(n) ^ 1, j]
+    key = np.stack([first, np.asarray(path_off)[placed], head[placed]], axis=1)
+    return np.sort(np.unique(key, axis=0, return_counts=True)[1])
+
+
+BIG_GROUP_RECORDS = [7, 7, 64, 64, 65, 65, 126, 255, 255, 256, 256, 257, 257]      # both mates' groups; the self-complementary seed: one of 2 x 63
+
+
+def test_big_duplicate_groups_match_reference():
+    """MarkDups on groups of 7 to 257 pairs with interleaved runs (tests/pathgen.plant_big_groups; dup_groups.npz holds the
+    reference's own paths and flags): the generator still makes the fixture's reads, the restated pathing and marking reproduce the
+    reference, the groups have exactly the planted sizes and none is larger (the device walks a group with one thread, quadratic
+    in its size: 257 is a bound by construction), and the plants do what they are for."""
+    import pathgen
+    c = goldens.load("dup_groups")
+    codes, quals, lens, bc, groups = pathgen.big_group_reads()
+    assert np.array_equal(codes, c.codes) and np.array_equal(quals, c.quals) and np.array_equal(lens, c.lens) and np.array_equal(bc, c.bc)
+    gl = oracle_lib.good_lens(c.quals, c.lens)
+    assert np.array_equal(gl, c.exp_goodlens)
+    o = oracle_lib.OracleResult(c.codes, gl, c.bc)
+    assert np.array_equal(o.keys[:, :3], c.exp_keys) and np.array_equal(o.counts, c.exp_counts) and o.unitigs == c.exp_unitigs
+    off, n, edges = oracle_lib.path_reads(c.codes, c.quals, c.lens, o.unitigs)
+    assert np.array_equal(n, c.exp_path_n) and np.array_equal(edges, c.exp_path_edges) and np.array_equal(off, c.exp_path_off)
+    sizes = big_group_sizes(c.codes, off, n, edges)
+    assert sizes[sizes >= 7].tolist() == BIG_GROUP_RECORDS and sizes.max() == 257
+    dup, art, rate, nd, ni = oracle_lib.mark_dups(c.codes, c.quals, c.lens, off, n, edges, bc=c.bc)
+    assert np.array_equal(dup, c.exp_dup), np.nonzero(dup != c.exp_dup)[0][:10]
+    assert rate == c.exp_interdup and 0.0 < rate < 1.0
+    assert _art_matches_log(int(art.sum()), len(dup), c.exp_art_perc), (int(art.sum()), len(dup), c.exp_art_perc)
+    # what the plants are for, on the reference's flags: one survivor per group -- the first member, or the planted best copy (the last
+    # member of groups 3 and 6, a copy in the middle of group 5) -- except where both mates share a group (group 1: the survivor's own
+    # mate is a duplicate of it); no artifact at all where the best copy comes first and the tie never fires (group 4)
+    surv = [np.nonzero(c.exp_dup[g] == 0)[0].tolist() for g in groups]
+    assert [len(g) for g in groups] == [7, 63, 64, 65, 255, 256, 257]
+    assert surv[0] == [0] and surv[1] == [] and surv[2] == [0] and surv[3] == [64] and surv[4] == [0] and surv[6] == [256]
+    assert len(surv[5]) == 1 and 0 < surv[5][0] < 255
+    assert art[groups[4]].sum() == 0 and all(art[g].sum() > len(g) // 2 for i, g in enumerate(groups) if i != 4)
+    assert all(0 < art[g].sum() < dup[g].sum() for i, g in enumerate(groups) if i != 4)       # tied but not identical copies are not artifacts
+    assert bc[2 * groups[0][0]] == 0 and bc[2 * groups[6][0]] == 0 and len(np.unique(bc[2 * groups[2]])) == 3
