@@ -447,7 +447,7 @@ typedef struct snk_hbv {
 int snk_hbv_from_unitigs(uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases,
                          snk_hbv* out, char* err, size_t errcap);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_paths_zip, snk_dev_paths_unzip and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -620,6 +620,55 @@ int snk_write_pathsx(const char* path, uint64_t n_reads, const int64_t* index, u
 int snk_read_pathsx(const char* path, uint64_t* n_reads, uint64_t* n_index, int64_t** index, uint64_t* n_bytes, uint8_t** data, char* err, size_t errcap);
 int snk_write_hbx(const char* path, uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases, const snk_hbv* h, char* err,
                   size_t errcap);
+
+/* ---- the edge -> barcode lists: a.ebcx ------------------------------------------------------------------------------
+ * computeEdgeToBarcodeX, lib/assembly/src/10X/PathsIndex.cc:297-358 (StageEBC, 10X/runstages/RunStages.cc:31-38): per HBV edge the
+ * barcodes whose reads visit it -- stored as a.ebcx, the file every scaffolding step of the reference opens first.  The reference takes
+ * the reads one barcode's run at a time (bci: the start of every run; reads sorted by barcode), collects {e, inv[e]} over the path
+ * entries of a run whose first read has bc > 0, UniqueSorts them (:313-322) and appends the run's barcode to the list of every edge of
+ * that set, run by run (:344-355).  Here every path entry of a read with bc > 0 gives the two keys (e, bc) and (inv[e], bc); one stable
+ * radix sort and a distinct step leave the lists.
+ *   paths        of snk_dev_path_reads (edge ids = HBV edge ids; edges 4-byte aligned); it stays valid across the call, as for
+ *                snk_dev_paths_index
+ *   d_bc         DEVICE array, int32[n_reads]: the barcode of every read (<= 0: none, the read contributes nothing)
+ *   inv          HOST array, int32[n_hbv_edges], of snk_hbv_involution
+ *   flags        0 or SNK_EBC_GENERAL_SORT
+ * Contract: the list of edge e is the ascending set of the distinct bc[r] > 0 over the reads r whose path holds e or inv[e].  It is a
+ * pure function of (paths, bc, inv): independent of the order of the reads, of `flags` and of every tuning option, and bit-identical
+ * from call to call.
+ *   - On reads sorted by barcode with one value per run (what 10X/DF.cc:464-469 makes: bc is the run's ordinal) this IS the reference's
+ *     output, list by list.
+ *   - Two separate runs that carry the same value: the reference would list the value twice, here it is listed once.  DF never makes
+ *     that input.
+ *   - An empty run contributes nothing (there are no runs here, only reads).  The reference reads bc[bci[b]] of an empty last run out of
+ *     bounds (:311,345).
+ * Device memory of the context, valid until its next top-level call.  SNK_E_ARG: a NULL argument, an inv that is not an involution, an
+ * edge id outside [0, n_hbv_edges), start / n_edges that do not add up to n_edges_total (a read outside the entry table, or more entries
+ * in the reads with a barcode than the table has), unknown flag bits.  SNK_E_UNSUPPORTED: n_edges_total >= 2^31 (two keys are sorted per
+ * path entry).  *out is all zero after any refusal. */
+typedef struct snk_dev_ebcx {
+    uint64_t n_hbv_edges, n_ebc;         /* n_ebc = sum of the list lengths */
+    const void* ebc_off;                 /* u64[n_hbv_edges + 1] */
+    const void* ebc;                     /* i32[n_ebc]: the barcodes of edge e are ebc[ebc_off[e] .. ebc_off[e + 1]), strictly ascending */
+    uint64_t n_keys;                     /* (edge, barcode) keys that went into the sort: two per path entry of a read with bc > 0 */
+    uint64_t n_empty_edges, max_list;    /* edges without a barcode; the longest list */
+    uint32_t bc_sorted;                  /* 1: bc was non-decreasing over the reads with bc > 0 */
+    uint32_t general_sort;               /* 1: the full (edge, barcode) key was sorted; 0: the edge bits only (bc_sorted and no flag) */
+    uint32_t key_bits;                   /* bits of an edge id the sort looked at */
+    float ms;                            /* HIP events around the whole call (the upload of inv and the sizing read-back included) */
+    uint64_t reserved[6];
+} snk_dev_ebcx;
+#define SNK_EBC_GENERAL_SORT 1u          /* take the full-key sort even when bc is sorted */
+int snk_dev_edge_barcodes(snk_ctx* ctx, const snk_dev_paths* paths, const void* d_bc, uint64_t n_hbv_edges, const int32_t* inv, uint32_t flags,
+                          snk_dev_ebcx* out, void* stream, char* err, size_t errcap);
+/* The file (host arrays; no GPU needed), byte for byte what VecIntVec::WriteAll leaves:
+ *   snk_write_ebcx   a.ebcx = feudal MasterVec<SerfVec<int>> in its single-file form (the family of a.paths.inv): control block (count,
+ *                    flags 1, no fixed-length data, sizeof(SerfVec<int>) = 16, sizeof(int) = 4), the lists back to back as int32, the
+ *                    table of n_hbv_edges + 1 file offsets
+ *   snk_read_ebcx    the same file back; *ebc_off and *ebc are malloc'ed (snk_host_free).  SNK_E_IO: a file that does not add up (control
+ *                    block, offset table and size disagree, or the offsets decrease or leave the data) */
+int snk_write_ebcx(const char* path, uint64_t n_hbv_edges, const uint64_t* ebc_off, const int32_t* ebc, char* err, size_t errcap);
+int snk_read_ebcx(const char* path, uint64_t* n_hbv_edges, uint64_t** ebc_off, int32_t** ebc, char* err, size_t errcap);
 
 /* ---- f3: barcode ids on the device --------------------------------------------------------------
  * BcIndexer, lib/tada/src/utils.rs:101-164: whitelist line -> index (identical lines: the last one wins); a read's

@@ -1,4 +1,4 @@
-// snk_a48.hip -- host writers for the files DF leaves in a.48/ beside a.hbv and a.inv (those: snk_hbv.hip).  No device code.
+// snk_a48.hip -- host writers for the files DF leaves in a.48/ beside a.hbv and a.inv (those: snk_hbv.hip), and for a.ebcx.  No device code.
 //   a.paths      feudal MasterVec<ReadPath>   paths/long/ReadPath.h:61-63 (writeFeudal: offset, last skip, the edge ids),
 //                                             IncrementalWriter, feudal/FeudalFileWriter.cc:18-140; written as tmp.paths by pathReads
 //                                             (BuildReadQGraph48.cc:1441-1469), renamed at 10X/DF.cc:584
@@ -7,6 +7,7 @@
 //   a.dup        BINWRITE vec<Bool>           10X/DF.cc:599-600
 //   a.pathsX     raw ReadPathVecX             10X/paths/ReadPathVecX.cc:976-996 (five int64, the ZipIndex, the zipped data)
 //   a.hbx        BINWRITE HyperBasevectorX    paths/HyperBasevector.cc:133-137, graph/DigraphTemplate.h:3107-3113; 10X/DF.cc:573-576
+//   a.ebcx       feudal MasterVec<SerfVec<int>> VecIntVec::WriteAll of computeEdgeToBarcodeX's result (10X/PathsIndex.cc:297-358); not in a.48/
 // A feudal file: 24-byte control block (feudal/FeudalControlBlock.h:157-166), the elements' variable-length data back to back, the
 // table of N + 1 file offsets, then the fixed-length data (none for these element types).
 #include <stdio.h>
@@ -170,6 +171,61 @@ extern "C" int snk_read_pathsx(const char* path, uint64_t* n_reads, uint64_t* n_
     *n_bytes = (uint64_t)head[4];
     *index = ix;
     *data = d;
+    return SNK_OK;
+}
+
+extern "C" int snk_write_ebcx(const char* path, uint64_t E, const uint64_t* ebc_off, const int32_t* ebc, char* err, size_t errcap) {
+    if (!path || !ebc_off) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_ebcx: NULL argument");
+    if (ebc_off[0] != 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_ebcx: ebc_off does not start at 0");
+    for (uint64_t e = 0; e < E; ++e)
+        if (ebc_off[e + 1] < ebc_off[e]) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_ebcx: ebc_off decreases at edge %llu", (unsigned long long)e);
+    const uint64_t n = ebc_off[E];
+    if (n && !ebc) return snk_fail(SNK_E_ARG, err, errcap, "snk_write_ebcx: NULL argument");
+    out_file o(path);
+    if (!o.ok) return snk_fail(SNK_E_IO, err, errcap, "snk_write_ebcx: cannot create %s", path);
+    const uint64_t var = sizeof(fcb_t) + n * 4;
+    const fcb_t h = {(uint32_t)E, 1, 0, 16, 4, var, var + (E + 1) * 8};                   // sizeof(SerfVec<int>) = 16, sizeof(int) = 4
+    o.put(&h, sizeof h);
+    o.put(ebc, (size_t)n * 4);
+    for (uint64_t e = 0; e <= E; ++e) {
+        const uint64_t at = sizeof(fcb_t) + ebc_off[e] * 4;
+        o.put(&at, 8);
+    }
+    if (!o.close()) return snk_fail(SNK_E_IO, err, errcap, "snk_write_ebcx: write error on %s", path);
+    return SNK_OK;
+}
+
+extern "C" int snk_read_ebcx(const char* path, uint64_t* n_hbv_edges, uint64_t** ebc_off, int32_t** ebc, char* err, size_t errcap) {
+    if (!path || !n_hbv_edges || !ebc_off || !ebc) return snk_fail(SNK_E_ARG, err, errcap, "snk_read_ebcx: NULL argument");
+    *n_hbv_edges = 0;
+    *ebc_off = nullptr;
+    *ebc = nullptr;
+    FILE* f = fopen(path, "rb");
+    if (!f) return snk_fail(SNK_E_IO, err, errcap, "snk_read_ebcx: cannot open %s", path);
+    fcb_t h;
+    bool ok = fread(&h, sizeof h, 1, f) == 1 && fseek(f, 0, SEEK_END) == 0;
+    const long long size = ok ? (long long)ftell(f) : -1;
+    // the control block of a MasterVec<SerfVec<int>> without fixed-length data, and sizes that are the file's: the lists fill
+    // [24, var_offset), the table of E + 1 offsets [var_offset, fixed_offset = size)
+    ok = ok && h.flags == 1 && h.sizeof_fixed == 0 && h.sizeof_x == 16 && h.sizeof_a == 4 && h.fixed_offset == (uint64_t)size && h.var_offset >= sizeof(fcb_t) &&
+         h.var_offset <= h.fixed_offset - 8 && (h.var_offset - sizeof(fcb_t)) % 4 == 0 && (h.fixed_offset - h.var_offset) % 8 == 0;
+    const uint64_t E = ok ? (h.fixed_offset - h.var_offset) / 8 - 1 : 0, n = ok ? (h.var_offset - sizeof(fcb_t)) / 4 : 0;
+    ok = ok && (uint32_t)E == h.n && fseek(f, sizeof(fcb_t), SEEK_SET) == 0;
+    if (!ok) { fclose(f); return snk_fail(SNK_E_IO, err, errcap, "snk_read_ebcx: %s is not an a.ebcx file (control block and size disagree)", path); }
+    uint64_t* off = (uint64_t*)malloc((size_t)(E + 1) * 8);
+    int32_t* d = (int32_t*)malloc((size_t)n * 4 + 8);
+    if (!off || !d) { free(off); free(d); fclose(f); return snk_fail(SNK_E_NOMEM, err, errcap, "snk_read_ebcx: host allocation failed"); }
+    ok = fread(d, 4, (size_t)n, f) == (size_t)n && fread(off, 8, (size_t)(E + 1), f) == (size_t)(E + 1);
+    fclose(f);
+    if (!ok) { free(off); free(d); return snk_fail(SNK_E_IO, err, errcap, "snk_read_ebcx: short read from %s", path); }
+    // file offsets -> entries: they start at the control block's end, end at the table, never decrease and fall on whole ints
+    ok = off[0] == sizeof(fcb_t) && off[E] == h.var_offset;
+    for (uint64_t e = 0; ok && e < E; ++e) ok = off[e + 1] >= off[e] && off[e + 1] <= h.var_offset && (off[e + 1] - sizeof(fcb_t)) % 4 == 0;
+    if (!ok) { free(off); free(d); return snk_fail(SNK_E_IO, err, errcap, "snk_read_ebcx: the offset table of %s does not add up", path); }
+    for (uint64_t e = 0; e <= E; ++e) off[e] = (off[e] - sizeof(fcb_t)) / 4;
+    *n_hbv_edges = E;
+    *ebc_off = off;
+    *ebc = d;
     return SNK_OK;
 }
 

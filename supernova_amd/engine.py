@@ -133,7 +133,7 @@ class Result:
         return out
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
-                   paths_index=False, pathsx=False):
+                   paths_index=False, pathsx=False, ebcx=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -148,7 +148,13 @@ class Result:
         i32[E] read support, an edge and its reverse complement summed; info['inv'] = the involution; info['pidx'] = counters and time.
         pathsx: the paths as a ReadPathVecX (10X/DF.cc:579; snk_dev_paths_zip) -> info['pathsx'] = (index i64[ceil(n / 10)], data u8[...]):
         per read its edge count, int16 offset, first edge and 2-bit branch ids; info['pathsx_stats'] = sizes, counters and time (download=False:
-        info['pathsx_dev'] = the SnkDevPathsx itself, valid until the engine's next count_graph or path_reads)."""
+        info['pathsx_dev'] = the SnkDevPathsx itself, valid until the engine's next count_graph or path_reads).
+        ebcx (needs bc): the edge -> barcode lists of computeEdgeToBarcodeX (10X/PathsIndex.cc:297-358; snk_dev_edge_barcodes) ->
+        info['ebcx'] = (off u64[E+1], bcs i32[...]): the ascending distinct barcodes > 0 of the reads whose path holds HBV edge e or its
+        reverse complement are bcs[off[e]:off[e+1]]; info['ebcx_stats'] = sizes, which sort ran and time; ebcx="general" asks for the full-key
+        sort even when bc is sorted (SNK_EBC_GENERAL_SORT).  download=False: the stats only."""
+        if ebcx and bc is None:
+            raise ValueError("path_reads(ebcx=...) needs bc: the barcode of every read, on the device")
         e = self._e
         h = _lib.SnkHbv()
         ms = C.c_float(0)
@@ -197,6 +203,20 @@ class Result:
                 if download:
                     pidx_arrays = (self._dl(px.index_off, (ne_hbv + 1) * 8, np.uint64, (ne_hbv + 1,)), self._dl(px.index_ids, nent * 8, np.uint64, (nent,)),
                                    self._dl(px.counts, ne_hbv * 4, np.int32, (ne_hbv,)), inv[:ne_hbv].copy())
+            eb_stats = None
+            if ebcx:
+                ne_hbv = int(h.n_edges)
+                inv = np.zeros(max(ne_hbv, 1), dtype=np.int32)
+                rc = e.lib.snk_hbv_involution(C.byref(h), self.n_unitigs, inv.ctypes.data, err, 512)
+                eb = _lib.SnkDevEbcx()
+                if not rc:
+                    rc = e.lib.snk_dev_edge_barcodes(e._ctx, C.byref(out), bc.data_ptr(), ne_hbv, inv.ctypes.data,
+                                                     _lib.EBC_GENERAL_SORT if ebcx == "general" else 0, C.byref(eb), e._stream(), err, 512)
+                if rc:
+                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+                eb_stats = _ebcx_stats(eb)
+                if download:
+                    eb_arrays = (self._dl(eb.ebc_off, (ne_hbv + 1) * 8, np.uint64, (ne_hbv + 1,)), self._dl(eb.ebc, int(eb.n_ebc) * 4, np.int32, (int(eb.n_ebc),)))
             px_stats = None
             if pathsx:
                 zx = _lib.SnkDevPathsx()
@@ -219,6 +239,8 @@ class Result:
                 info["pidx"] = pidx
             if px_stats is not None:
                 info["pathsx_stats"], info["pathsx_dev"] = px_stats, zx     # (zx: device memory of the context, for Engine.unzip_paths)
+            if eb_stats is not None:
+                info["ebcx_stats"] = eb_stats
             return None, None, None, info
         off = self._dl(out.offset, n * 4, np.int32, (n,))
         ne = self._dl(out.n_edges, n * 4, np.uint32, (n,))
@@ -231,6 +253,8 @@ class Result:
             info["pidx"], info["paths_index"], info["countsb"], info["inv"] = pidx, pidx_arrays[:2], pidx_arrays[2], pidx_arrays[3]
         if px_stats is not None:
             info["pathsx"], info["pathsx_stats"] = px_arrays, px_stats
+        if eb_stats is not None:
+            info["ebcx"], info["ebcx_stats"] = eb_arrays, eb_stats
         if unitig_bcs and out.unitig_bc_off:
             nb = int(out.n_unitig_bcs)
             info["unitig_bcs"] = (self._dl(out.unitig_bc_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,)),
@@ -256,6 +280,11 @@ class Result:
         us = [asc[int(off[i]):int(off[i + 1])] for i in range(self.n_unitigs)]
         us.sort(key=lambda s: (-len(s), s))
         return us
+
+
+def _ebcx_stats(eb: "_lib.SnkDevEbcx") -> dict:
+    return dict(n_hbv_edges=int(eb.n_hbv_edges), n_ebc=int(eb.n_ebc), n_keys=int(eb.n_keys), n_empty_edges=int(eb.n_empty_edges), max_list=int(eb.max_list),
+                bc_sorted=int(eb.bc_sorted), general_sort=int(eb.general_sort), key_bits=int(eb.key_bits), ms=float(eb.ms))
 
 
 def _pathsx_stats(zx: "_lib.SnkDevPathsx") -> dict:

@@ -188,6 +188,32 @@ def read_pathsx(path):
     return index, data, int(n.value)
 
 
+def write_ebcx(path, off: np.ndarray, bcs: np.ndarray) -> None:
+    """a.ebcx (VecIntVec::WriteAll of computeEdgeToBarcodeX's result, 10X/PathsIndex.cc:297-358) from the lists of snk_dev_edge_barcodes:
+    the barcodes of edge e are bcs[off[e]:off[e+1]].  Not one of the files of a.48/: write_a48 leaves it alone."""
+    off = np.ascontiguousarray(off, dtype=np.uint64)
+    bcs = np.ascontiguousarray(bcs, dtype=np.int32)
+    E = len(off) - 1
+    assert E >= 0 and len(bcs) == int(off[-1])
+    _call(_lib.load().snk_write_ebcx, str(path).encode(), E, off.ctypes.data, bcs.ctypes.data)
+
+
+def read_ebcx(path):
+    """a.ebcx -> (off u64[E+1], bcs i32[])."""
+    lib = _lib.load()
+    E = C.c_uint64(0)
+    po = C.POINTER(C.c_uint64)()
+    pb = C.POINTER(C.c_int32)()
+    _call(lib.snk_read_ebcx, str(path).encode(), C.byref(E), C.byref(po), C.byref(pb))
+    try:
+        off = np.ctypeslib.as_array(po, shape=(E.value + 1,)).copy()
+        bcs = np.ctypeslib.as_array(pb, shape=(int(off[-1]),)).copy() if off[-1] else np.zeros(0, np.int32)
+    finally:
+        lib.snk_host_free(po)
+        lib.snk_host_free(pb)
+    return off, bcs
+
+
 def write_hbx(path, K: int, off: np.ndarray, bases: np.ndarray) -> None:
     """Unitigs in BVComp order -> a.hbx, the HyperBasevectorX of the graph a.hbv holds (10X/DF.cc:573-576)."""
     lib = _lib.load()

@@ -93,6 +93,15 @@ class SnkDevPidx(C.Structure):
                 ("reserved", C.c_uint64 * 6)]
 
 
+class SnkDevEbcx(C.Structure):
+    _fields_ = [("n_hbv_edges", C.c_uint64), ("n_ebc", C.c_uint64), ("ebc_off", C.c_void_p), ("ebc", C.c_void_p), ("n_keys", C.c_uint64),
+                ("n_empty_edges", C.c_uint64), ("max_list", C.c_uint64), ("bc_sorted", C.c_uint32), ("general_sort", C.c_uint32),
+                ("key_bits", C.c_uint32), ("ms", C.c_float), ("reserved", C.c_uint64 * 6)]
+
+
+EBC_GENERAL_SORT = 1             # SNK_EBC_GENERAL_SORT
+
+
 class SnkDevPathsx(C.Structure):
     _fields_ = [("n_reads", C.c_uint64), ("n_bytes", C.c_uint64), ("n_index", C.c_uint64), ("data", C.c_void_p), ("index", C.c_void_p),
                 ("n_empty", C.c_uint64), ("n_steps_not_found", C.c_uint64), ("n_offsets_wrapped", C.c_uint64), ("ms", C.c_float),
@@ -258,6 +267,9 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_path_reads2": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), u32, P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_mark_dups": (C.c_int, [vp, P(SnkDevReads), P(SnkDevPaths), P(SnkDevDups), vp, cp, sz]),
         "snk_dev_paths_index": (C.c_int, [vp, P(SnkDevPaths), u64, vp, P(SnkDevPidx), vp, cp, sz]),
+        "snk_dev_edge_barcodes": (C.c_int, [vp, P(SnkDevPaths), vp, u64, vp, u32, P(SnkDevEbcx), vp, cp, sz]),
+        "snk_write_ebcx": (C.c_int, [cp, u64, vp, vp, cp, sz]),
+        "snk_read_ebcx": (C.c_int, [cp, P(u64), P(P(u64)), P(P(i32)), cp, sz]),
         "snk_dev_paths_zip": (C.c_int, [vp, P(SnkDevPaths), P(SnkHbv), P(SnkDevPathsx), vp, cp, sz]),
         "snk_dev_paths_unzip": (C.c_int, [vp, P(SnkDevPathsx), P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
         "snk_write_pathsx": (C.c_int, [cp, u64, vp, u64, vp, u64, cp, sz]),
