@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -108,5 +109,38 @@ void snk_ctx_release_block(snk_ctx* ctx, const void* p);   // return one block t
 void snk_ctx_release_since(snk_ctx* ctx, uint64_t mark, const void* const* keep, size_t n_keep);
 void snk_ctx_trim_cache(snk_ctx* ctx);        // hipFree every unused cached block
 void snk_ctx_plan_mem(snk_ctx* ctx);          // ctx->plan_mem from the device's free memory + what the arena already holds (call it with the arena released)
+
+// The owner of a call's PLAIN device allocations (hipMalloc, not the arena): buffers that outlive the call or belong to a side stream,
+// where snk_call's frame does not apply.  On every way out the destructor waits for `st` when one is given (nothing enqueued by the
+// call still uses the memory), frees what the call has not taken out with keep(), and takes `st` out of ctx->cur_stream.
+struct snk_dev_owner {
+    snk_ctx* ctx;
+    hipStream_t st;
+    std::vector<void*> mine;
+    snk_dev_owner(snk_ctx* c, hipStream_t s) : ctx(c), st(s) {}
+    snk_dev_owner(const snk_dev_owner&) = delete;
+    snk_dev_owner& operator=(const snk_dev_owner&) = delete;
+    ~snk_dev_owner() {
+        if (st) (void)hipStreamSynchronize(st);
+        for (void* p : mine) (void)hipFree(p);
+        if (st && ctx->cur_stream == st) ctx->cur_stream = nullptr;
+    }
+    template <typename T>
+    hipError_t alloc(T** out, size_t bytes) {
+        mine.reserve(mine.size() + 1);
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) mine.push_back(p);
+        *out = (T*)p;
+        return e;
+    }
+    // what the call returns to its caller (mirrors snk_call::end(rc, keep))
+    void keep(std::initializer_list<const void*> ps) {
+        for (const void* p : ps)
+            for (void*& m : mine)
+                if (m == p) m = nullptr;
+    }
+};
+
 void snk_shard_state_free(void* p);
 void snk_shard_state_invalidate_job(void* p);   // an open streamed step dies with the arena it lives in (snk_ctx_release_scratch)

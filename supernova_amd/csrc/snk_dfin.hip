@@ -625,6 +625,13 @@ int decode_compact(snk_ctx* ctx, df_io* io, const snk_df_files* f, uint64_t firs
     return rc;
 }
 
+// the fields every DF entry point reports (the arrays, where there are any, are the caller's to set)
+void fill_ingest(snk_dev_ingest* out, uint64_t n, uint32_t max_len, const df_stats& st, uint32_t n_files, double t0, double t_ready) {
+    out->n_reads = n; out->read_len = max_len; out->row_words = (max_len + 15) / 16; out->qstride = (max_len + 15) / 16 * 16; out->max_len = max_len;
+    out->text_bytes = st.file_bytes; out->compressed_bytes = st.file_bytes; out->n_files = n_files; out->n_batches = st.n_slabs;
+    out->seconds = now_s() - t0; out->decode_wait_seconds = st.wait_io; out->setup_seconds = t_ready - t0;
+}
+
 }  // namespace
 
 extern "C" int snk_df_max_len(snk_ctx* ctx, snk_df_files* f, uint64_t first, uint64_t n, uint32_t* out, char* err, size_t errcap) {
@@ -650,24 +657,24 @@ extern "C" int snk_dev_ingest_df(snk_ctx* ctx, snk_df_files* f, uint64_t first, 
     if (rc) return rc;
     const uint32_t row_words = (max_len + 15) / 16, qstride = row_words * 16;
     uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr;
-    auto drop = [&]() { (void)hipStreamSynchronize(io->cs); (void)hipFree(rows); (void)hipFree(quals); (void)hipFree(lens); (void)hipFree(bc); };
-#define DF_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { drop(); return snk_fail(_e == hipErrorOutOfMemory ? SNK_E_NOMEM : SNK_E_HIP, err, errcap, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
-    DF_TRY(hipMalloc((void**)&rows, (n + 1) * row_words * 4ull));
-    DF_TRY(hipMalloc((void**)&quals, (n + 16) * (uint64_t)qstride));
-    DF_TRY(hipMalloc((void**)&lens, (n + 8) * 2ull));
-    if (f->have_bci) DF_TRY(hipMalloc((void**)&bc, (n + 2) * 4ull));
-#undef DF_TRY
-    const double t_ready = now_s();
     df_stats st;
-    rc = run_slabs(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride,
-                   [&](int, uint64_t at, uint64_t, slab_dev* sd) { sd->rows = rows + at * row_words; sd->quals = quals + at * qstride; sd->lens = lens + at; sd->bc = bc ? bc + at : nullptr; return SNK_OK; },
-                   [&](int, const slab_dev&) { return SNK_OK; }, &st, err, errcap);
-    if (!rc) rc = check_errs(io, f, qstride, err, errcap);
-    if (rc) { drop(); return rc; }
-    out->n_reads = n; out->read_len = max_len; out->row_words = row_words; out->qstride = qstride; out->max_len = max_len;
+    double t_ready;
+    {
+        snk_dev_owner mem(ctx, io->cs);
+        SNK_HIP_TRY(mem.alloc(&rows, (n + 1) * row_words * 4ull));
+        SNK_HIP_TRY(mem.alloc(&quals, (n + 16) * (uint64_t)qstride));
+        SNK_HIP_TRY(mem.alloc(&lens, (n + 8) * 2ull));
+        if (f->have_bci) SNK_HIP_TRY(mem.alloc(&bc, (n + 2) * 4ull));
+        t_ready = now_s();
+        rc = run_slabs(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride,
+                       [&](int, uint64_t at, uint64_t, slab_dev* sd) { sd->rows = rows + at * row_words; sd->quals = quals + at * qstride; sd->lens = lens + at; sd->bc = bc ? bc + at : nullptr; return SNK_OK; },
+                       [&](int, const slab_dev&) { return SNK_OK; }, &st, err, errcap);
+        if (!rc) rc = check_errs(io, f, qstride, err, errcap);
+        if (rc) return rc;
+        mem.keep({rows, quals, lens, bc});
+    }
     out->rows = rows; out->quals = quals; out->lens = lens; out->bc = bc;
-    out->text_bytes = st.file_bytes; out->compressed_bytes = st.file_bytes; out->n_files = 3; out->n_batches = st.n_slabs;
-    out->seconds = now_s() - t0; out->decode_wait_seconds = st.wait_io; out->setup_seconds = t_ready - t0;
+    fill_ingest(out, n, max_len, st, 3, t0, t_ready);
     return SNK_OK;
 }
 
@@ -687,27 +694,25 @@ extern "C" int snk_dev_ingest_df_trimmed(snk_ctx* ctx, snk_df_files* f, uint64_t
     if (rc) return rc;
     const uint32_t row_words = (max_len + 15) / 16, qstride = row_words * 16;
     uint32_t* rows = nullptr; uint16_t* gl = nullptr; int32_t* bc = nullptr;
-    uint8_t* qb[NSLOT] = {nullptr, nullptr, nullptr}; uint16_t* lb[NSLOT] = {nullptr, nullptr, nullptr};
-    auto drop_slots = [&]() { (void)hipStreamSynchronize(io->cs); for (int q = 0; q < NSLOT; ++q) { (void)hipFree(qb[q]); (void)hipFree(lb[q]); } if (ctx->cur_stream == io->cs) ctx->cur_stream = nullptr; };
-    auto drop = [&]() { drop_slots(); (void)hipFree(rows); (void)hipFree(gl); (void)hipFree(bc); };
-#define DF_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { drop(); return snk_fail(_e == hipErrorOutOfMemory ? SNK_E_NOMEM : SNK_E_HIP, err, errcap, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
-    DF_TRY(hipMalloc((void**)&rows, (n + 1) * row_words * 4ull));
-    DF_TRY(hipMalloc((void**)&gl, (n + 8) * 2ull));
-    if (f->have_bci) DF_TRY(hipMalloc((void**)&bc, (n + 2) * 4ull));
-    for (int q = 0; q < NSLOT; ++q) {
-        DF_TRY(hipMalloc((void**)&qb[q], (slab_reads + 16) * (uint64_t)qstride));
-        DF_TRY(hipMalloc((void**)&lb[q], (slab_reads + 8) * 2ull));
-    }
-#undef DF_TRY
-    const double t_ready = now_s();
     df_stats st;
-    rc = decode_compact(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride, K, min_qual, qb, lb, rows, gl, bc, &st, err, errcap);
-    if (rc) { drop(); return rc; }
-    drop_slots();
-    out->n_reads = n; out->read_len = max_len; out->row_words = row_words; out->qstride = qstride; out->max_len = max_len;
+    double t_ready;
+    {
+        snk_dev_owner mem(ctx, io->cs);          // the result and the per-slot quality rows and lengths, which die with the call
+        uint8_t* qb[NSLOT]; uint16_t* lb[NSLOT];
+        SNK_HIP_TRY(mem.alloc(&rows, (n + 1) * row_words * 4ull));
+        SNK_HIP_TRY(mem.alloc(&gl, (n + 8) * 2ull));
+        if (f->have_bci) SNK_HIP_TRY(mem.alloc(&bc, (n + 2) * 4ull));
+        for (int q = 0; q < NSLOT; ++q) {
+            SNK_HIP_TRY(mem.alloc(&qb[q], (slab_reads + 16) * (uint64_t)qstride));
+            SNK_HIP_TRY(mem.alloc(&lb[q], (slab_reads + 8) * 2ull));
+        }
+        t_ready = now_s();
+        rc = decode_compact(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride, K, min_qual, qb, lb, rows, gl, bc, &st, err, errcap);
+        if (rc) return rc;
+        mem.keep({rows, gl, bc});
+    }
     out->rows = rows; out->good_len = gl; out->bc = bc;
-    out->text_bytes = st.file_bytes; out->compressed_bytes = st.file_bytes; out->n_files = 3; out->n_batches = st.n_slabs;
-    out->seconds = now_s() - t0; out->decode_wait_seconds = st.wait_io; out->setup_seconds = t_ready - t0;
+    fill_ingest(out, n, max_len, st, 3, t0, t_ready);
     return SNK_OK;
 }
 
@@ -738,68 +743,61 @@ extern "C" int snk_dev_ingest_df_count_graph(snk_ctx* ctx, snk_df_files* f, uint
     // 382 small partition launches on the copies' stream cost 52 ms, one resident launch 30 -- and on error-rich data much faster.  So the
     // compact form is what runs unless the caller asks for the streamed job, whose point is that the reads are never resident in any form.)
     const bool streamed = snk_opt_u32(ctx, SNK_OPT_df_stream) == 2 && !(p->flags & SNK_F_GROUPED);
-    struct obuf { uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr; } O[NSLOT];
-    auto drop = [&]() {
-        (void)hipStreamSynchronize(io->cs);
-        for (auto& o : O) { (void)hipFree(o.rows); (void)hipFree(o.quals); (void)hipFree(o.lens); (void)hipFree(o.bc); }
-        if (ctx->cur_stream == io->cs) ctx->cur_stream = nullptr;
-    };
-#define DF_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { drop(); return snk_fail(_e == hipErrorOutOfMemory ? SNK_E_NOMEM : SNK_E_HIP, err, errcap, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
-    for (auto& o : O) {
-        if (streamed) DF_TRY(hipMalloc((void**)&o.rows, (slab_reads + 1) * row_words * 4ull));
-        DF_TRY(hipMalloc((void**)&o.quals, (slab_reads + 16) * (uint64_t)qstride));
-        DF_TRY(hipMalloc((void**)&o.lens, (slab_reads + 8) * 2ull));
-        if (streamed && f->have_bci) DF_TRY(hipMalloc((void**)&o.bc, (slab_reads + 2) * 4ull));
-    }
-    if (!streamed && (io->c_reads < n || io->c_row_words != row_words || (f->have_bci && !io->c_bc))) {
-        DF_TRY(hipStreamSynchronize(io->cs));
-        io->release_compact();
-        DF_TRY(hipMalloc((void**)&io->c_rows, (n + 1) * row_words * 4ull));
-        DF_TRY(hipMalloc((void**)&io->c_gl, (n + 8) * 2ull));
-        DF_TRY(hipMalloc((void**)&io->c_bc, (n + 2) * 4ull));
-        io->c_reads = n; io->c_row_words = row_words;
-    }
-#undef DF_TRY
     df_stats st;
     double t_ready;
-    if (streamed) {
-        if ((rc = snk_dev_stream_begin(ctx, p, max_len, n, f->have_bci ? 1 : 0, io->cs, err, errcap))) { drop(); return rc; }
-        t_ready = now_s();
-        rc = run_slabs(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride,
-                       [&](int s, uint64_t, uint64_t, slab_dev* sd) { sd->rows = O[s].rows; sd->quals = O[s].quals; sd->lens = O[s].lens; sd->bc = O[s].bc; return SNK_OK; },
-                       [&](int, const slab_dev& sd) {
-                           snk_dev_reads slab;
-                           memset(&slab, 0, sizeof slab);
-                           slab.n_reads = sd.n; slab.rows = sd.rows; slab.row_words = row_words; slab.read_len = max_len; slab.lens = sd.lens; slab.quals = sd.quals;
-                           slab.qstride = qstride; slab.bc = sd.bc; slab.ign_bc_below = ign_bc_below; slab.read_index_base = sd.first;
-                           return snk_dev_stream_append(ctx, &slab, io->cs, err, errcap);
-                       },
-                       &st, err, errcap);
-        // a bad file must not reach the count: the flags are read before the job is finished
-        if (!rc) rc = check_errs(io, f, qstride, err, errcap);
-        if (!rc) rc = snk_dev_stream_finish(ctx, res, io->cs, err, errcap);
-    } else {
-        t_ready = now_s();
-        uint8_t* qb[NSLOT]; uint16_t* lb[NSLOT];
-        for (int q = 0; q < NSLOT; ++q) { qb[q] = O[q].quals; lb[q] = O[q].lens; }
-        rc = decode_compact(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride, p->K, p->min_qual, qb, lb, io->c_rows, io->c_gl, f->have_bci ? io->c_bc : nullptr, &st, err, errcap);
-        if (!rc) {
-            snk_dev_reads in;
-            memset(&in, 0, sizeof in);
-            in.n_reads = n; in.rows = io->c_rows; in.row_words = row_words; in.read_len = max_len; in.good_len = io->c_gl; in.bc = f->have_bci ? io->c_bc : nullptr;
-            in.ign_bc_below = ign_bc_below; in.read_index_base = first;
-            // per-barcode graphs (SNK_F_GROUPED, BASELINE config 5): the group of a read is its barcode's ordinal in reads.bci (reads outside
-            // every range -- ordinal -1 -- are one group of their own)
-            if (p->flags & SNK_F_GROUPED) { in.group = in.bc; in.bc = nullptr; }
-            rc = snk_dev_count_graph(ctx, &in, p, res, io->cs, err, errcap);
+    {
+        snk_dev_owner mem(ctx, io->cs);          // what a slot's slab is decoded into
+        struct obuf { uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr; } O[NSLOT];
+        for (auto& o : O) {
+            if (streamed) SNK_HIP_TRY(mem.alloc(&o.rows, (slab_reads + 1) * row_words * 4ull));
+            SNK_HIP_TRY(mem.alloc(&o.quals, (slab_reads + 16) * (uint64_t)qstride));
+            SNK_HIP_TRY(mem.alloc(&o.lens, (slab_reads + 8) * 2ull));
+            if (streamed && f->have_bci) SNK_HIP_TRY(mem.alloc(&o.bc, (slab_reads + 2) * 4ull));
         }
+        if (!streamed && (io->c_reads < n || io->c_row_words != row_words || (f->have_bci && !io->c_bc))) {      // (the context's, not the call's)
+            SNK_HIP_TRY(hipStreamSynchronize(io->cs));
+            io->release_compact();
+            SNK_HIP_TRY(hipMalloc((void**)&io->c_rows, (n + 1) * row_words * 4ull));
+            SNK_HIP_TRY(hipMalloc((void**)&io->c_gl, (n + 8) * 2ull));
+            SNK_HIP_TRY(hipMalloc((void**)&io->c_bc, (n + 2) * 4ull));
+            io->c_reads = n; io->c_row_words = row_words;
+        }
+        if (streamed) {
+            if ((rc = snk_dev_stream_begin(ctx, p, max_len, n, f->have_bci ? 1 : 0, io->cs, err, errcap))) return rc;
+            t_ready = now_s();
+            rc = run_slabs(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride,
+                           [&](int s, uint64_t, uint64_t, slab_dev* sd) { sd->rows = O[s].rows; sd->quals = O[s].quals; sd->lens = O[s].lens; sd->bc = O[s].bc; return SNK_OK; },
+                           [&](int, const slab_dev& sd) {
+                               snk_dev_reads slab;
+                               memset(&slab, 0, sizeof slab);
+                               slab.n_reads = sd.n; slab.rows = sd.rows; slab.row_words = row_words; slab.read_len = max_len; slab.lens = sd.lens; slab.quals = sd.quals;
+                               slab.qstride = qstride; slab.bc = sd.bc; slab.ign_bc_below = ign_bc_below; slab.read_index_base = sd.first;
+                               return snk_dev_stream_append(ctx, &slab, io->cs, err, errcap);
+                           },
+                           &st, err, errcap);
+            // a bad file must not reach the count: the flags are read before the job is finished
+            if (!rc) rc = check_errs(io, f, qstride, err, errcap);
+            if (!rc) rc = snk_dev_stream_finish(ctx, res, io->cs, err, errcap);
+        } else {
+            t_ready = now_s();
+            uint8_t* qb[NSLOT]; uint16_t* lb[NSLOT];
+            for (int q = 0; q < NSLOT; ++q) { qb[q] = O[q].quals; lb[q] = O[q].lens; }
+            rc = decode_compact(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride, p->K, p->min_qual, qb, lb, io->c_rows, io->c_gl, f->have_bci ? io->c_bc : nullptr, &st, err, errcap);
+            if (!rc) {
+                snk_dev_reads in;
+                memset(&in, 0, sizeof in);
+                in.n_reads = n; in.rows = io->c_rows; in.row_words = row_words; in.read_len = max_len; in.good_len = io->c_gl; in.bc = f->have_bci ? io->c_bc : nullptr;
+                in.ign_bc_below = ign_bc_below; in.read_index_base = first;
+                // per-barcode graphs (SNK_F_GROUPED, BASELINE config 5): the group of a read is its barcode's ordinal in reads.bci (reads outside
+                // every range -- ordinal -1 -- are one group of their own)
+                if (p->flags & SNK_F_GROUPED) { in.group = in.bc; in.bc = nullptr; }
+                rc = snk_dev_count_graph(ctx, &in, p, res, io->cs, err, errcap);
+            }
+        }
+        if (!rc && hipStreamSynchronize(io->cs) != hipSuccess) rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dev_ingest_df_count_graph: the stream failed");
+        if (rc) return rc;
     }
-    if (!rc && hipStreamSynchronize(io->cs) != hipSuccess) rc = snk_fail(SNK_E_HIP, err, errcap, "snk_dev_ingest_df_count_graph: the stream failed");
-    drop();
-    if (rc) return rc;
-    out->n_reads = n; out->read_len = max_len; out->row_words = row_words; out->qstride = qstride; out->max_len = max_len;
-    out->text_bytes = st.file_bytes; out->compressed_bytes = st.file_bytes; out->n_files = streamed ? 3 : 4; out->n_batches = st.n_slabs;
-    out->seconds = now_s() - t0; out->decode_wait_seconds = st.wait_io; out->setup_seconds = t_ready - t0;
+    fill_ingest(out, n, max_len, st, streamed ? 3 : 4, t0, t_ready);
     return SNK_OK;
 }
 

@@ -512,10 +512,21 @@ __global__ void __launch_bounds__(256) pair_ids_kernel(const int32_t* __restrict
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < 2 * n_pairs) read_ids[i] = pair_ids[i >> 1];
 }
-struct ingest_arrays {
+struct ingest_arrays {          // the resident arrays while they grow: move-only, so that growing and reordering are "allocate new, copy, move-assign"
     uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr;
     uint64_t cap = 0;
+    ingest_arrays() = default;
+    ingest_arrays(const ingest_arrays&) = delete;
+    ingest_arrays& operator=(const ingest_arrays&) = delete;
+    ingest_arrays& operator=(ingest_arrays&& o) {
+        release();
+        rows = o.rows; quals = o.quals; lens = o.lens; bc = o.bc; cap = o.cap;
+        o.rows = nullptr; o.quals = nullptr; o.lens = nullptr; o.bc = nullptr; o.cap = 0;
+        return *this;
+    }
+    ~ingest_arrays() { release(); }
     void release() { (void)hipFree(rows); (void)hipFree(quals); (void)hipFree(lens); (void)hipFree(bc); rows = nullptr; quals = nullptr; lens = nullptr; bc = nullptr; cap = 0; }
+    void hand_to(snk_dev_ingest* out) { out->rows = rows; out->quals = quals; out->lens = lens; out->bc = bc; rows = nullptr; quals = nullptr; lens = nullptr; bc = nullptr; cap = 0; }
 };
 int alloc_arrays(ingest_arrays& a, uint64_t cap, uint32_t row_words, uint32_t qstride, bool want_bc, char* err, size_t errcap) {
     a.cap = cap;
@@ -526,6 +537,126 @@ int alloc_arrays(ingest_arrays& a, uint64_t cap, uint32_t row_words, uint32_t qs
     return SNK_OK;
 }
 double now_s() { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
+
+constexpr int NST = 4;
+// what the pump counts: reads seen (skipped batches included), and of the batches that went up their text, number and longest read;
+// where the consumer thread's time went (SNK_INGEST_TRACE=1)
+struct pump_stats { uint64_t n_reads = 0, text = 0; uint32_t max_len = 0, n_batches = 0; double wait_decode = 0, hand_back = 0, wait_slot = 0, issue = 0; };
+struct batch_dst { uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr; bool skip = false; };
+
+// The consumer of the decode workers, for both device entry points: the FASTH stream, the copy stream, the staging ring (ASCII rows and
+// barcode fields, from which snk_dev_pack_ascii / snk_dev_bc_ids take them), the batches whose copies are in flight and the event pool.
+struct fasth_pump {
+    snk_ctx* ctx;
+    const snk_bc_index* ix;
+    uint32_t read_len, stride, row_words;
+    snk_fasth_stream* fs = nullptr;
+    hipStream_t cs = nullptr;
+    struct slot_t { uint8_t *ascii = nullptr, *bcf = nullptr; int32_t* ids = nullptr; hipEvent_t ev = nullptr; bool busy = false; } S[NST];
+    struct pend { hipEvent_t ev; snk_fasth_batch b; };
+    std::deque<pend> pending;
+    std::vector<hipEvent_t> ev_pool;
+    pump_stats st;
+
+    fasth_pump(snk_ctx* c, uint32_t rl, const snk_bc_index* x) : ctx(c), ix(x), read_len(rl), stride((rl + 15) / 16 * 16), row_words((rl + 15) / 16) {}
+    fasth_pump(const fasth_pump&) = delete;
+    fasth_pump& operator=(const fasth_pump&) = delete;
+    // The order matters.  The page-locked batches are the SOURCE of asynchronous copies: the stream is waited for before a batch is
+    // handed back or anything is freed.  snk_fasth_close joins the workers and frees the page-locked memory: it runs last of all.
+    ~fasth_pump() {
+        if (cs) (void)hipStreamSynchronize(cs);
+        for (auto& p : pending) { (void)hipEventDestroy(p.ev); snk_fasth_release(fs, &p.b); }
+        for (auto e : ev_pool) (void)hipEventDestroy(e);
+        for (auto& q : S) { (void)hipFree(q.ascii); (void)hipFree(q.bcf); (void)hipFree(q.ids); if (q.ev) (void)hipEventDestroy(q.ev); }
+        if (cs) { if (ctx->cur_stream == cs) ctx->cur_stream = nullptr; (void)hipStreamDestroy(cs); }
+        if (fs) snk_fasth_close(fs);
+    }
+
+    int open(const char* const* paths, uint32_t n_files, uint32_t threads, uint32_t batch_pairs, char* err, size_t errcap) {
+        const int rc = fasth_open(paths, n_files, stride, read_len, batch_pairs, threads, 1u, &fs, err, errcap);
+        if (rc) return rc;
+        SNK_HIP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+        for (auto& q : S) {
+            SNK_HIP_TRY(hipMalloc((void**)&q.ascii, 2ull * batch_pairs * stride));
+            SNK_HIP_TRY(hipMalloc((void**)&q.bcf, (size_t)batch_pairs * 64));
+            SNK_HIP_TRY(hipMalloc((void**)&q.ids, (size_t)batch_pairs * 4));
+            SNK_HIP_TRY(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
+        }
+        return SNK_OK;
+    }
+
+    // Every batch of the stream, as it is decoded: target(slot, n, batch, &dst) says where the batch's packed rows, quality rows, lengths
+    // and barcode ids go (the resident reader: their place in the growing arrays; the streamed job: the slot's own buffers), or that the
+    // batch is only counted (dst.skip), or fails; quality rows and lengths are copied straight there, the ASCII rows and barcode fields
+    // through the slot; consume(slot, dst, batch) runs after the pack and barcode-id kernels are enqueued on cs.
+    template <typename Target, typename Consume>
+    int run(Target target, Consume consume, char* err, size_t errcap) {
+        int slot = 0, rc;
+        for (;;) {
+            // hand back the batches whose copies are done (never more than two outstanding: the workers need them)
+            const double p0 = now_s();
+            while (!pending.empty() && (pending.size() > 2 || hipEventQuery(pending.front().ev) == hipSuccess)) {
+                SNK_HIP_TRY(hipEventSynchronize(pending.front().ev));
+                ev_pool.push_back(pending.front().ev);
+                snk_fasth_release(fs, &pending.front().b);
+                pending.pop_front();
+            }
+            snk_fasth_batch b;
+            const double w0 = now_s();
+            st.hand_back += w0 - p0;
+            if ((rc = snk_fasth_next(fs, &b, err, errcap))) return rc;
+            st.wait_decode += now_s() - w0;
+            if (b.n_pairs == 0) return SNK_OK;
+            const uint64_t nr = 2 * b.n_pairs;
+            batch_dst d;
+            if ((rc = target(slot, nr, b, &d))) return rc;
+            if (d.skip) {
+                st.n_reads += nr;
+                snk_fasth_release(fs, &b);
+                continue;
+            }
+            slot_t& q = S[slot];
+            const double s0 = now_s();
+            if (q.busy) { SNK_HIP_TRY(hipEventSynchronize(q.ev)); q.busy = false; }        // whatever read this slot last is done
+            const double s1 = now_s();
+            st.wait_slot += s1 - s0;
+            SNK_HIP_TRY(hipMemcpyAsync(q.ascii, b.ascii, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
+            SNK_HIP_TRY(hipMemcpyAsync(d.quals, b.quals, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
+            SNK_HIP_TRY(hipMemcpyAsync(d.lens, b.lens, nr * 2ull, hipMemcpyHostToDevice, cs));
+            if (ix) SNK_HIP_TRY(hipMemcpyAsync(q.bcf, b.bc_fields, b.n_pairs * 64ull, hipMemcpyHostToDevice, cs));
+            // the batch's event stays the pool's until it is recorded, then it is the pending list's: no exit between the two
+            if (ev_pool.empty()) {
+                hipEvent_t e;
+                SNK_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                ev_pool.push_back(e);
+            }
+            SNK_HIP_TRY(hipEventRecord(ev_pool.back(), cs));
+            pending.push_back({ev_pool.back(), b});
+            ev_pool.pop_back();
+            if ((rc = snk_dev_pack_ascii(ctx, q.ascii, stride, read_len, nr, d.rows, row_words, cs))) return rc;
+            if (ix) {
+                if ((rc = snk_dev_bc_ids(ctx, ix, q.bcf, 64, b.n_pairs, q.ids, cs, err, errcap))) return rc;
+                SNK_HIP_TRY(snk_launch(pair_ids_kernel, snk_blocks(nr, 256), 256, 0, cs, q.ids, b.n_pairs, d.bc));
+            }
+            if ((rc = consume(slot, d, b))) return rc;
+            SNK_HIP_TRY(hipEventRecord(q.ev, cs));
+            q.busy = true;
+            slot = (slot + 1) % NST;
+            st.n_reads += nr;
+            st.text += b.text_bytes;
+            ++st.n_batches;
+            if (b.max_len > st.max_len) st.max_len = b.max_len;
+            st.issue += now_s() - s1;
+        }
+    }
+};
+
+// the fields every FASTH entry point reports (the arrays, where there are any, are the caller's to set)
+void fill_ingest(snk_dev_ingest* out, const pump_stats& st, uint32_t read_len, uint64_t comp, uint32_t n_files, double t0, double t_ready) {
+    out->n_reads = st.n_reads; out->read_len = read_len; out->row_words = (read_len + 15) / 16; out->qstride = (read_len + 15) / 16 * 16; out->max_len = st.max_len;
+    out->text_bytes = st.text; out->compressed_bytes = comp; out->n_files = n_files; out->n_batches = st.n_batches;
+    out->seconds = now_s() - t0; out->decode_wait_seconds = st.wait_decode; out->setup_seconds = t_ready - t0;
+}
 }  // namespace
 
 extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint32_t n_files, uint32_t read_len, const snk_bc_index* ix, uint32_t threads,
@@ -534,146 +665,74 @@ extern "C" int snk_dev_ingest_fasth(snk_ctx* ctx, const char* const* paths, uint
     if (read_len == 0 || read_len > 256) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_fasth: read_len must be 1..256");
     memset(out, 0, sizeof *out);
     SNK_HIP_TRY(snk_enter(ctx));
-    const uint32_t stride = (read_len + 15) / 16 * 16, row_words = (read_len + 15) / 16, qstride = stride;
+    const uint32_t row_words = (read_len + 15) / 16, qstride = row_words * 16;
     if (batch_pairs == 0) batch_pairs = 65536;       // (the consumer's per-batch cost -- a dozen runtime calls -- is what limits it once the decode is fast)
     const double t0 = now_s();
     // capacity guess from the compressed sizes (a read is ~330 bytes of text, FASTH deflates ~4x); the arrays grow if it is wrong
     uint64_t comp = 0;
     for (uint32_t i = 0; i < n_files; ++i) { FILE* f = fopen(paths[i], "rb"); if (f) { fseek(f, 0, SEEK_END); const long n = ftell(f); if (n > 0) comp += (uint64_t)n; fclose(f); } }
-    uint64_t cap = comp / 70 + 4ull * batch_pairs;
-    snk_fasth_stream* fs = nullptr;
-    int rc = fasth_open(paths, n_files, stride, read_len, batch_pairs, threads, 1u, &fs, err, errcap);
-    if (rc) return rc;
-    hipStream_t cs = nullptr;
-    constexpr int NST = 4;
-    uint8_t* st_ascii[NST] = {nullptr, nullptr, nullptr, nullptr};
-    uint8_t* st_bcf[NST] = {nullptr, nullptr, nullptr, nullptr};
-    int32_t* st_ids[NST] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t st_ev[NST] = {nullptr, nullptr, nullptr, nullptr};
-    bool st_busy[NST] = {false, false, false, false};
-    ingest_arrays A, Bf;
-    struct piece { uint32_t file; uint64_t first_pair, n_pairs, at; };
-    std::vector<piece> pieces;
-    struct pend { hipEvent_t ev; snk_fasth_batch b; };
-    std::deque<pend> pending;
-    std::vector<hipEvent_t> ev_pool;
-    uint64_t n_reads = 0, text = 0;
-    uint32_t max_len = 0, n_grown = 0;
-    auto cleanup = [&]() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        for (auto& p : pending) { (void)hipEventDestroy(p.ev); snk_fasth_release(fs, &p.b); }
-        pending.clear();
-        for (auto e : ev_pool) (void)hipEventDestroy(e);
-        ev_pool.clear();
-        for (int q = 0; q < NST; ++q) { (void)hipFree(st_ascii[q]); (void)hipFree(st_bcf[q]); (void)hipFree(st_ids[q]); if (st_ev[q]) (void)hipEventDestroy(st_ev[q]); }
-        if (cs) { if (ctx->cur_stream == cs) ctx->cur_stream = nullptr; (void)hipStreamDestroy(cs); }
-        if (fs) snk_fasth_close(fs);
-    };
-#define ING_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); A.release(); Bf.release(); return snk_fail(_e == hipErrorOutOfMemory ? SNK_E_NOMEM : SNK_E_HIP, err, errcap, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
-#define ING_RC(expr) do { int _r = (expr); if (_r) { cleanup(); A.release(); Bf.release(); return _r; } } while (0)
-    ING_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    for (int q = 0; q < NST; ++q) {
-        ING_TRY(hipMalloc((void**)&st_ascii[q], 2ull * batch_pairs * stride));
-        ING_TRY(hipMalloc((void**)&st_bcf[q], (size_t)batch_pairs * 64));
-        ING_TRY(hipMalloc((void**)&st_ids[q], (size_t)batch_pairs * 4));
-        ING_TRY(hipEventCreateWithFlags(&st_ev[q], hipEventDisableTiming));
+    ingest_arrays A;          // (before the pump: they die after its destructor has waited for the copies into them)
+    pump_stats st;
+    double t_ready = t0;
+    {
+        fasth_pump P(ctx, read_len, ix);
+        int rc = P.open(paths, n_files, threads, batch_pairs, err, errcap);
+        if (rc) return rc;
+        if ((rc = alloc_arrays(A, comp / 70 + 4ull * batch_pairs, row_words, qstride, ix != nullptr, err, errcap))) return rc;
+        struct piece { uint32_t file; uint64_t first_pair, n_pairs, at; };
+        std::vector<piece> pieces;
+        uint32_t n_grown = 0;
+        const bool trace = getenv("SNK_INGEST_TRACE") && *getenv("SNK_INGEST_TRACE") == '1';
+        t_ready = now_s();          // decode threads running, page-locked batches and device arrays allocated
+        rc = P.run(
+            [&](int, uint64_t nr, const snk_fasth_batch& b, batch_dst* d) -> int {
+                const uint64_t at = P.st.n_reads;
+                if (at + nr > A.cap) {
+                    ingest_arrays N;
+                    const int r2 = alloc_arrays(N, A.cap + A.cap / 2 + nr, row_words, qstride, ix != nullptr, err, errcap);
+                    if (r2) return r2;
+                    SNK_HIP_TRY(hipMemcpyAsync(N.rows, A.rows, at * row_words * 4ull, hipMemcpyDeviceToDevice, P.cs));
+                    SNK_HIP_TRY(hipMemcpyAsync(N.quals, A.quals, at * (uint64_t)qstride, hipMemcpyDeviceToDevice, P.cs));
+                    SNK_HIP_TRY(hipMemcpyAsync(N.lens, A.lens, at * 2ull, hipMemcpyDeviceToDevice, P.cs));
+                    if (ix) SNK_HIP_TRY(hipMemcpyAsync(N.bc, A.bc, at * 4ull, hipMemcpyDeviceToDevice, P.cs));
+                    SNK_HIP_TRY(hipStreamSynchronize(P.cs));
+                    A = std::move(N);
+                    ++n_grown;
+                }
+                d->rows = A.rows + at * row_words; d->quals = A.quals + at * (uint64_t)qstride; d->lens = A.lens + at; d->bc = ix ? A.bc + at : nullptr;
+                pieces.push_back({b.file, b.first_pair, b.n_pairs, at});
+                return SNK_OK;
+            },
+            [](int, const batch_dst&, const snk_fasth_batch&) { return SNK_OK; }, err, errcap);
+        if (rc) return rc;
+        const double t_loop = now_s();
+        SNK_HIP_TRY(hipStreamSynchronize(P.cs));
+        const double t_drained = now_s();
+        // ---- file-major order
+        std::vector<uint64_t> fbase(n_files + 1, 0);
+        for (uint32_t i = 0; i < n_files; ++i) fbase[i + 1] = fbase[i] + 2 * snk_fasth_file_pairs(P.fs, i);
+        bool in_order = true;
+        for (auto& p : pieces) if (fbase[p.file] + 2 * p.first_pair != p.at) { in_order = false; break; }
+        if (trace) fprintf(stderr, "[snk ingest] setup %.3f s | loop %.3f s: wait for decode %.3f, wait for copies (batch hand-back) %.3f, wait for a staging slot %.3f, issue %.3f | drain %.3f s | %zu batches | arrays grown %u times | reordered %d\n",
+                           t_ready - t0, t_loop - t_ready, P.st.wait_decode, P.st.hand_back, P.st.wait_slot, P.st.issue, t_drained - t_loop, pieces.size(), n_grown, in_order ? 0 : 1);
+        if (!in_order) {
+            ingest_arrays B;
+            if ((rc = alloc_arrays(B, P.st.n_reads, row_words, qstride, ix != nullptr, err, errcap))) return rc;
+            for (auto& p : pieces) {
+                const uint64_t d = fbase[p.file] + 2 * p.first_pair, s = p.at, nr = 2 * p.n_pairs;
+                SNK_HIP_TRY(hipMemcpyAsync(B.rows + d * row_words, A.rows + s * row_words, nr * row_words * 4ull, hipMemcpyDeviceToDevice, P.cs));
+                SNK_HIP_TRY(hipMemcpyAsync(B.quals + d * qstride, A.quals + s * qstride, nr * (uint64_t)qstride, hipMemcpyDeviceToDevice, P.cs));
+                SNK_HIP_TRY(hipMemcpyAsync(B.lens + d, A.lens + s, nr * 2ull, hipMemcpyDeviceToDevice, P.cs));
+                if (ix) SNK_HIP_TRY(hipMemcpyAsync(B.bc + d, A.bc + s, nr * 4ull, hipMemcpyDeviceToDevice, P.cs));
+            }
+            SNK_HIP_TRY(hipStreamSynchronize(P.cs));
+            A = std::move(B);
+        }
+        st = P.st;
     }
-    ING_RC(alloc_arrays(A, cap, row_words, qstride, ix != nullptr, err, errcap));
-    int slot = 0;
-    double wait_s = 0, t_pend = 0, t_slot = 0, t_issue = 0;      // SNK_INGEST_TRACE=1: where the consumer thread's time goes
-    const bool trace = getenv("SNK_INGEST_TRACE") && *getenv("SNK_INGEST_TRACE") == '1';
-    const double t_ready = now_s();          // decode threads running, page-locked batches and device arrays allocated
-    for (;;) {
-        // hand back the batches whose copies are done (never more than two outstanding: the workers need them)
-        const double p0 = now_s();
-        while (!pending.empty() && (pending.size() > 2 || hipEventQuery(pending.front().ev) == hipSuccess)) {
-            ING_TRY(hipEventSynchronize(pending.front().ev));
-            ev_pool.push_back(pending.front().ev);
-            snk_fasth_release(fs, &pending.front().b);
-            pending.pop_front();
-        }
-        snk_fasth_batch b;
-        const double w0 = now_s();
-        t_pend += w0 - p0;
-        ING_RC(snk_fasth_next(fs, &b, err, errcap));
-        wait_s += now_s() - w0;
-        if (b.n_pairs == 0) break;
-        const uint64_t nr = 2 * b.n_pairs;
-        if (n_reads + nr > A.cap) {
-            ingest_arrays N;
-            const uint64_t ncap = A.cap + A.cap / 2 + nr;
-            int r2 = alloc_arrays(N, ncap, row_words, qstride, ix != nullptr, err, errcap);
-            if (r2) { N.release(); snk_fasth_release(fs, &b); cleanup(); A.release(); return r2; }
-            ING_TRY(hipMemcpyAsync(N.rows, A.rows, n_reads * row_words * 4ull, hipMemcpyDeviceToDevice, cs));
-            ING_TRY(hipMemcpyAsync(N.quals, A.quals, n_reads * (uint64_t)qstride, hipMemcpyDeviceToDevice, cs));
-            ING_TRY(hipMemcpyAsync(N.lens, A.lens, n_reads * 2ull, hipMemcpyDeviceToDevice, cs));
-            if (ix) ING_TRY(hipMemcpyAsync(N.bc, A.bc, n_reads * 4ull, hipMemcpyDeviceToDevice, cs));
-            ING_TRY(hipStreamSynchronize(cs));
-            A.release();
-            A = N;
-            ++n_grown;
-        }
-        const double s0 = now_s();
-        if (st_busy[slot]) { ING_TRY(hipEventSynchronize(st_ev[slot])); st_busy[slot] = false; }
-        const double s1 = now_s();
-        t_slot += s1 - s0;
-        ING_TRY(hipMemcpyAsync(st_ascii[slot], b.ascii, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
-        ING_TRY(hipMemcpyAsync(A.quals + n_reads * (uint64_t)qstride, b.quals, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
-        ING_TRY(hipMemcpyAsync(A.lens + n_reads, b.lens, nr * 2ull, hipMemcpyHostToDevice, cs));
-        if (ix) ING_TRY(hipMemcpyAsync(st_bcf[slot], b.bc_fields, b.n_pairs * 64ull, hipMemcpyHostToDevice, cs));
-        pend pe;
-        if (!ev_pool.empty()) { pe.ev = ev_pool.back(); ev_pool.pop_back(); }
-        else ING_TRY(hipEventCreateWithFlags(&pe.ev, hipEventDisableTiming));
-        ING_TRY(hipEventRecord(pe.ev, cs));
-        pe.b = b;
-        pending.push_back(pe);
-        ING_RC(snk_dev_pack_ascii(ctx, st_ascii[slot], stride, read_len, nr, A.rows + n_reads * row_words, row_words, cs));
-        if (ix) {
-            ING_RC(snk_dev_bc_ids(ctx, ix, st_bcf[slot], 64, b.n_pairs, st_ids[slot], cs, err, errcap));
-            ING_TRY(snk_launch(pair_ids_kernel, snk_blocks(nr, 256), 256, 0, cs, st_ids[slot], b.n_pairs, A.bc + n_reads));
-        }
-        ING_TRY(hipEventRecord(st_ev[slot], cs));
-        st_busy[slot] = true;
-        slot = (slot + 1) % NST;
-        pieces.push_back({b.file, b.first_pair, b.n_pairs, n_reads});
-        n_reads += nr;
-        text += b.text_bytes;
-        if (b.max_len > max_len) max_len = b.max_len;
-        t_issue += now_s() - s1;
-    }
-    const double t_loop = now_s();
-    ING_TRY(hipStreamSynchronize(cs));
-    const double t_drained = now_s();
-    while (!pending.empty()) { (void)hipEventDestroy(pending.front().ev); snk_fasth_release(fs, &pending.front().b); pending.pop_front(); }
-    // ---- file-major order
-    std::vector<uint64_t> fbase(n_files + 1, 0);
-    for (uint32_t i = 0; i < n_files; ++i) fbase[i + 1] = fbase[i] + 2 * snk_fasth_file_pairs(fs, i);
-    bool in_order = true;
-    for (auto& p : pieces) if (fbase[p.file] + 2 * p.first_pair != p.at) { in_order = false; break; }
-    if (trace) fprintf(stderr, "[snk ingest] setup %.3f s | loop %.3f s: wait for decode %.3f, wait for copies (batch hand-back) %.3f, wait for a staging slot %.3f, issue %.3f | drain %.3f s | %zu batches | arrays grown %u times | reordered %d\n",
-                       t_ready - t0, t_loop - t_ready, wait_s, t_pend, t_slot, t_issue, t_drained - t_loop, pieces.size(), n_grown, in_order ? 0 : 1);
-    if (!in_order) {
-        ING_RC(alloc_arrays(Bf, n_reads, row_words, qstride, ix != nullptr, err, errcap));
-        for (auto& p : pieces) {
-            const uint64_t d = fbase[p.file] + 2 * p.first_pair, s = p.at, nr = 2 * p.n_pairs;
-            ING_TRY(hipMemcpyAsync(Bf.rows + d * row_words, A.rows + s * row_words, nr * row_words * 4ull, hipMemcpyDeviceToDevice, cs));
-            ING_TRY(hipMemcpyAsync(Bf.quals + d * qstride, A.quals + s * qstride, nr * (uint64_t)qstride, hipMemcpyDeviceToDevice, cs));
-            ING_TRY(hipMemcpyAsync(Bf.lens + d, A.lens + s, nr * 2ull, hipMemcpyDeviceToDevice, cs));
-            if (ix) ING_TRY(hipMemcpyAsync(Bf.bc + d, A.bc + s, nr * 4ull, hipMemcpyDeviceToDevice, cs));
-        }
-        ING_TRY(hipStreamSynchronize(cs));
-        A.release();
-        A = Bf;
-        Bf = ingest_arrays();
-    }
-    cleanup();
-    out->n_reads = n_reads; out->read_len = read_len; out->row_words = row_words; out->qstride = qstride; out->max_len = max_len;
-    out->rows = A.rows; out->quals = A.quals; out->lens = A.lens; out->bc = A.bc;
-    out->text_bytes = text; out->compressed_bytes = comp; out->n_files = n_files;
-    out->seconds = now_s() - t0; out->decode_wait_seconds = wait_s; out->setup_seconds = t_ready - t0; out->n_batches = (uint32_t)pieces.size();
+    A.hand_to(out);
+    fill_ingest(out, st, read_len, comp, n_files, t0, t_ready);
     return SNK_OK;
-#undef ING_TRY
-#undef ING_RC
 }
 
 // FASTH files -> count + graph with the reads never resident as a whole: every decoded batch goes up, is packed, gets its barcode ids
@@ -688,120 +747,58 @@ namespace {
 int ingest_count_graph_once(snk_ctx* ctx, const char* const* paths, uint32_t n_files, uint32_t read_len, const snk_bc_index* ix, uint32_t threads, uint32_t batch_pairs,
                             uint64_t total_reads_hint, uint64_t ub, uint64_t comp, double t0, const snk_params* p, snk_dev_result* res, snk_dev_ingest* out, uint64_t* need,
                             char* err, size_t errcap) {
-    const uint32_t stride = (read_len + 15) / 16 * 16, row_words = (read_len + 15) / 16, qstride = stride;
+    const uint32_t row_words = (read_len + 15) / 16, qstride = row_words * 16;
     *need = 0;
-    snk_fasth_stream* fs = nullptr;
-    int rc = fasth_open(paths, n_files, stride, read_len, batch_pairs, threads, 1u, &fs, err, errcap);
-    if (rc) return rc;
-    hipStream_t cs = nullptr;
-    constexpr int NST = 4;
-    struct slot_t { uint8_t *ascii = nullptr, *bcf = nullptr, *quals = nullptr; int32_t *ids = nullptr, *bc = nullptr; uint32_t* rows = nullptr; uint16_t* lens = nullptr; hipEvent_t ev = nullptr; bool busy = false; };
-    slot_t S[NST];
-    struct pend { hipEvent_t ev; snk_fasth_batch b; };
-    std::deque<pend> pending;
-    std::vector<hipEvent_t> ev_pool;
-    auto cleanup = [&]() {
-        if (cs) (void)hipStreamSynchronize(cs);
-        for (auto& q : pending) { (void)hipEventDestroy(q.ev); snk_fasth_release(fs, &q.b); }
-        pending.clear();
-        for (auto e : ev_pool) (void)hipEventDestroy(e);
-        for (auto& q : S) { (void)hipFree(q.ascii); (void)hipFree(q.bcf); (void)hipFree(q.quals); (void)hipFree(q.ids); (void)hipFree(q.bc); (void)hipFree(q.rows); (void)hipFree(q.lens); if (q.ev) (void)hipEventDestroy(q.ev); }
-        if (cs) { if (ctx->cur_stream == cs) ctx->cur_stream = nullptr; (void)hipStreamDestroy(cs); }
-        if (fs) snk_fasth_close(fs);
-    };
-#define ING_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { cleanup(); return snk_fail(_e == hipErrorOutOfMemory ? SNK_E_NOMEM : SNK_E_HIP, err, errcap, "%s failed: %s", #expr, hipGetErrorString(_e)); } } while (0)
-#define ING_RC(expr) do { int _r = (expr); if (_r) { cleanup(); return _r; } } while (0)
-    ING_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    const uint64_t nrb = 2ull * batch_pairs;
-    for (auto& q : S) {
-        ING_TRY(hipMalloc((void**)&q.ascii, nrb * stride));
-        ING_TRY(hipMalloc((void**)&q.quals, nrb * qstride));
-        ING_TRY(hipMalloc((void**)&q.rows, nrb * row_words * 4ull));
-        ING_TRY(hipMalloc((void**)&q.lens, nrb * 2 + 16));
-        ING_TRY(hipMalloc((void**)&q.bcf, (size_t)batch_pairs * 64));
-        ING_TRY(hipMalloc((void**)&q.ids, (size_t)batch_pairs * 4));
-        ING_TRY(hipMalloc((void**)&q.bc, nrb * 4));
-        ING_TRY(hipEventCreateWithFlags(&q.ev, hipEventDisableTiming));
-    }
-    ING_RC(snk_dev_stream_begin(ctx, p, read_len, ub, ix ? 1 : 0, cs, err, errcap));
-    int slot = 0;
-    double wait_s = 0;
-    uint64_t n_reads = 0, text = 0;
-    uint32_t max_len = 0, n_batches = 0;
-    bool counting = false;          // the derived bound was crossed: no more uploads, the rest of the decode only counts
-    const double t_ready = now_s();
-    for (;;) {
-        while (!pending.empty() && (pending.size() > 2 || hipEventQuery(pending.front().ev) == hipSuccess)) {
-            ING_TRY(hipEventSynchronize(pending.front().ev));
-            ev_pool.push_back(pending.front().ev);
-            snk_fasth_release(fs, &pending.front().b);
-            pending.pop_front();
+    pump_stats st;
+    double t_ready = t0;
+    {
+        fasth_pump P(ctx, read_len, ix);
+        int rc = P.open(paths, n_files, threads, batch_pairs, err, errcap);
+        if (rc) return rc;
+        // what a slot's batch is decoded into; the owner waits for the stream and frees them before the pump destroys the stream
+        snk_dev_owner mem(ctx, P.cs);
+        struct obuf { uint32_t* rows = nullptr; uint8_t* quals = nullptr; uint16_t* lens = nullptr; int32_t* bc = nullptr; } O[NST];
+        const uint64_t nrb = 2ull * batch_pairs;
+        for (auto& o : O) {
+            SNK_HIP_TRY(mem.alloc(&o.quals, nrb * qstride));
+            SNK_HIP_TRY(mem.alloc(&o.rows, nrb * row_words * 4ull));
+            SNK_HIP_TRY(mem.alloc(&o.lens, nrb * 2 + 16));
+            SNK_HIP_TRY(mem.alloc(&o.bc, nrb * 4));
         }
-        snk_fasth_batch b;
-        const double w0 = now_s();
-        ING_RC(snk_fasth_next(fs, &b, err, errcap));
-        wait_s += now_s() - w0;
-        if (b.n_pairs == 0) break;
-        const uint64_t nr = 2 * b.n_pairs;
-        if (counting || n_reads + nr > ub) {
-            if (total_reads_hint) {
-                snk_fasth_release(fs, &b);
-                cleanup();
-                return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: more reads than the job's upper bound: total_reads_hint = %llu, %llu reads decoded so far and more to come",
-                                (unsigned long long)total_reads_hint, (unsigned long long)(n_reads + nr));
-            }
-            counting = true;
-            n_reads += nr;
-            snk_fasth_release(fs, &b);
-            continue;
+        if ((rc = snk_dev_stream_begin(ctx, p, read_len, ub, ix ? 1 : 0, P.cs, err, errcap))) return rc;
+        bool counting = false;          // the derived bound was crossed: no more uploads, the rest of the decode only counts
+        t_ready = now_s();
+        rc = P.run(
+            [&](int slot, uint64_t nr, const snk_fasth_batch&, batch_dst* d) -> int {
+                if (counting || P.st.n_reads + nr > ub) {
+                    if (total_reads_hint)
+                        return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_ingest_count_graph: more reads than the job's upper bound: total_reads_hint = %llu, %llu reads decoded so far and more to come",
+                                        (unsigned long long)total_reads_hint, (unsigned long long)(P.st.n_reads + nr));
+                    counting = d->skip = true;
+                    return SNK_OK;
+                }
+                d->rows = O[slot].rows; d->quals = O[slot].quals; d->lens = O[slot].lens; d->bc = O[slot].bc;
+                return SNK_OK;
+            },
+            [&](int, const batch_dst& d, const snk_fasth_batch& b) {
+                snk_dev_reads slab;
+                memset(&slab, 0, sizeof slab);
+                slab.n_reads = 2 * b.n_pairs; slab.rows = d.rows; slab.row_words = row_words; slab.read_len = read_len; slab.lens = d.lens; slab.quals = d.quals; slab.qstride = qstride;
+                slab.bc = ix ? d.bc : nullptr;
+                return snk_dev_stream_append(ctx, &slab, P.cs, err, errcap);
+            },
+            err, errcap);
+        if (rc) return rc;
+        if (counting) {          // (the open job stays with the context: the next snk_dev_stream_begin drops it)
+            *need = P.st.n_reads;
+            return SNK_OK;
         }
-        slot_t& q = S[slot];
-        if (q.busy) { ING_TRY(hipEventSynchronize(q.ev)); q.busy = false; }        // the partition launch that read this slot is done
-        ING_TRY(hipMemcpyAsync(q.ascii, b.ascii, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
-        ING_TRY(hipMemcpyAsync(q.quals, b.quals, nr * (uint64_t)stride, hipMemcpyHostToDevice, cs));
-        ING_TRY(hipMemcpyAsync(q.lens, b.lens, nr * 2ull, hipMemcpyHostToDevice, cs));
-        if (ix) ING_TRY(hipMemcpyAsync(q.bcf, b.bc_fields, b.n_pairs * 64ull, hipMemcpyHostToDevice, cs));
-        pend pe;
-        if (!ev_pool.empty()) { pe.ev = ev_pool.back(); ev_pool.pop_back(); }
-        else ING_TRY(hipEventCreateWithFlags(&pe.ev, hipEventDisableTiming));
-        ING_TRY(hipEventRecord(pe.ev, cs));
-        pe.b = b;
-        pending.push_back(pe);
-        ING_RC(snk_dev_pack_ascii(ctx, q.ascii, stride, read_len, nr, q.rows, row_words, cs));
-        if (ix) {
-            ING_RC(snk_dev_bc_ids(ctx, ix, q.bcf, 64, b.n_pairs, q.ids, cs, err, errcap));
-            ING_TRY(snk_launch(pair_ids_kernel, snk_blocks(nr, 256), 256, 0, cs, q.ids, b.n_pairs, q.bc));
-        }
-        snk_dev_reads slab;
-        memset(&slab, 0, sizeof slab);
-        slab.n_reads = nr; slab.rows = q.rows; slab.row_words = row_words; slab.read_len = read_len; slab.lens = q.lens; slab.quals = q.quals; slab.qstride = qstride;
-        slab.bc = ix ? q.bc : nullptr;
-        ING_RC(snk_dev_stream_append(ctx, &slab, cs, err, errcap));
-        ING_TRY(hipEventRecord(q.ev, cs));
-        q.busy = true;
-        slot = (slot + 1) % NST;
-        n_reads += nr;
-        text += b.text_bytes;
-        ++n_batches;
-        if (b.max_len > max_len) max_len = b.max_len;
+        if ((rc = snk_dev_stream_finish(ctx, res, P.cs, err, errcap))) return rc;
+        SNK_HIP_TRY(hipStreamSynchronize(P.cs));
+        st = P.st;
     }
-    if (counting) {
-        cleanup();          // (the open job stays with the context: the next snk_dev_stream_begin drops it)
-        *need = n_reads;
-        return SNK_OK;
-    }
-    const double t_decoded = now_s();
-    ING_RC(snk_dev_stream_finish(ctx, res, cs, err, errcap));
-    ING_TRY(hipStreamSynchronize(cs));
-    while (!pending.empty()) { (void)hipEventDestroy(pending.front().ev); snk_fasth_release(fs, &pending.front().b); pending.pop_front(); }
-    cleanup();
-    out->n_reads = n_reads; out->read_len = read_len; out->row_words = row_words; out->qstride = qstride; out->max_len = max_len;
-    out->text_bytes = text; out->compressed_bytes = comp; out->n_files = n_files; out->n_batches = n_batches;
-    out->seconds = now_s() - t0; out->decode_wait_seconds = wait_s; out->setup_seconds = t_ready - t0;
-    (void)t_decoded;
+    fill_ingest(out, st, read_len, comp, n_files, t0, t_ready);
     return SNK_OK;
-#undef ING_TRY
-#undef ING_RC
 }
 }  // namespace
 

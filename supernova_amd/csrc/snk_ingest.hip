@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -119,27 +120,24 @@ extern "C" int snk_bc_index_create(snk_ctx* ctx, const char* whitelist, size_t b
         if (i + 1 < v.size() && v[i + 1].h == v[i].h && v[i + 1].s == v[i].s) continue;
         u.push_back(v[i]);
     }
-    snk_bc_index* ix = new snk_bc_index();
+    std::unique_ptr<snk_bc_index, void (*)(snk_bc_index*)> own(new snk_bc_index(), snk_bc_index_destroy);      // (with its device buffers, on every failing exit)
+    snk_bc_index* ix = own.get();
     ix->n = (uint32_t)u.size();
     ix->num_bcs = nlines;
     std::vector<uint64_t> hh(u.size());
     std::vector<uint32_t> ll(u.size());
     std::vector<uint8_t> tt(u.size() * BC_MAXLEN + 16, 0);
     for (size_t i = 0; i < u.size(); ++i) { hh[i] = u[i].h; ll[i] = u[i].line; memcpy(&tt[i * BC_MAXLEN], u[i].s.data(), u[i].s.size()); }
-    hipError_t e1 = hipMalloc((void**)&ix->d_hash, std::max<size_t>(hh.size() * 8, 16));
-    hipError_t e2 = hipMalloc((void**)&ix->d_line, std::max<size_t>(ll.size() * 4, 16));
-    hipError_t e3 = hipMalloc((void**)&ix->d_text, tt.size());
-    hipError_t e4 = hipMalloc((void**)&ix->d_err, 16);
-    if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) {
-        snk_bc_index_destroy(ix);
-        return snk_fail(SNK_E_NOMEM, err, errcap, "snk_bc_index_create: hipMalloc failed");
-    }
+    SNK_HIP_TRY(hipMalloc((void**)&ix->d_hash, std::max<size_t>(hh.size() * 8, 16)));
+    SNK_HIP_TRY(hipMalloc((void**)&ix->d_line, std::max<size_t>(ll.size() * 4, 16)));
+    SNK_HIP_TRY(hipMalloc((void**)&ix->d_text, tt.size()));
+    SNK_HIP_TRY(hipMalloc((void**)&ix->d_err, 16));
     if (!hh.empty()) {
         SNK_HIP_TRY(hipMemcpy(ix->d_hash, hh.data(), hh.size() * 8, hipMemcpyHostToDevice));
         SNK_HIP_TRY(hipMemcpy(ix->d_line, ll.data(), ll.size() * 4, hipMemcpyHostToDevice));
     }
     SNK_HIP_TRY(hipMemcpy(ix->d_text, tt.data(), tt.size(), hipMemcpyHostToDevice));
-    *out = ix;
+    *out = own.release();
     return SNK_OK;
 }
 

@@ -255,9 +255,9 @@ def _trace(capfd):
     return lines
 
 
-@pytest.fixture(scope="module")
-def compressible_lane(tmp_path_factory):
-    """About 4 000 copies of one pair (120 and 100 bases) at gzip level 9: a few bytes per read."""
+def _compressible_files(d, over_long=0):
+    """Two files of 2 000 copies of one pair (120 and 100 bases) at gzip level 9: a few bytes per read.  over_long: the last record of the
+    last file gets an R1 of that many bases."""
     rng = np.random.default_rng(99)
     wl, seqs = fasthgen.odd_whitelist(rng)
     g, _ = pathgen.genome(rng, 600, plants=False)
@@ -265,8 +265,15 @@ def compressible_lane(tmp_path_factory):
     b = "".join("ACGT"[3 - i] for i in g[449:349:-1])
     rec = fasthgen.record(a, np.full(120, 30), b, np.full(100, 30), seqs[5] + "-1")
     rec2 = fasthgen.record(a, np.full(120, 30), b, np.full(100, 30), seqs[6] + "-1")          # (two barcodes: the k-mers pass min_bc = 2)
-    d = tmp_path_factory.mktemp("comp")
-    paths = [fasthgen.write_fasth(d / f"c{i}.fasth.gz", [rec, rec2] * 1000, level=9) for i in range(2)]
+    files = [[rec, rec2] * 1000 for _ in range(2)]
+    if over_long:
+        files[-1][-1] = _with_read(files[-1][-1], 0, over_long, rng)
+    return [fasthgen.write_fasth(d / f"c{i}.fasth.gz", recs, level=9) for i, recs in enumerate(files)], wl
+
+
+@pytest.fixture(scope="module")
+def compressible_lane(tmp_path_factory):
+    paths, wl = _compressible_files(tmp_path_factory.mktemp("comp"))
     return paths, wl, fasthgen.Expected(paths, wl, 150)
 
 
@@ -288,6 +295,23 @@ def test_array_growth_ran(engine, compressible_lane, capfd, monkeypatch):
         assert int(m.group(1)) >= 3, lines[-1]
     finally:
         dr.close()
+
+
+def test_over_long_read_after_growth_is_refused(engine, good_lane, tmp_path):
+    """The refusal of an over-long read when the resident arrays have already been replaced by larger ones several times: the last record
+    of the compressible lane has an R1 of 151 bases.  One decode thread has four batches (threads + threads + 2), so all but four batches
+    have been given their place in the arrays -- which two growths cannot hold -- when the refusal arrives."""
+    from supernova_amd import ingest
+    from supernova_amd.lib import SnkError
+    paths, wl = _compressible_files(tmp_path, over_long=151)
+    bp, n, pool = 16, 8000, 1 + 1 + 2
+    cap0 = sum(os.path.getsize(p) for p in paths) // 70 + 4 * bp
+    assert cap0 * 1.5 ** 2 + 2 * 2 * bp * 2.5 < n - pool * 2 * bp, cap0
+    with pytest.raises(SnkError) as ei:
+        ingest.ingest_fasth(engine, paths, 150, wl, threads=1, batch_pairs=bp)
+    assert ei.value.code == SNK_E_UNSUPPORTED, str(ei.value)
+    assert re.search(r"\b151\b", str(ei.value)) and re.search(r"read_len = 150\b", str(ei.value)), str(ei.value)
+    _good_after(engine, good_lane, 150)
 
 
 def test_reorder_ran(engine, tmp_path, capfd, monkeypatch):
