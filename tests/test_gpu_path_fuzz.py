@@ -1,6 +1,8 @@
 """Two fixed-seed slices of the randomised read-pathing sweep (tests/tools/fuzz_paths.py): random genomes with long homopolymers and
 short-period repeats, read pairs of up to 256 bases with planted duplicate groups, random K / filters / pathing variant, every read's
-path, every pair's duplicate flag and the per-unitig barcode lists against the C oracle."""
+path, every pair's duplicate flag and the per-unitig barcode lists against the C oracle; and on every case's paths the four other stages that
+run after the pather -- the paths index, the compressed paths and their unzip, the edge -> barcode lists on both sort paths -- against
+their numpy restatements (a48ref.paths_index, a48xref.zip_paths, ebcxref.edge_barcodes)."""
 import subprocess
 import sys
 from pathlib import Path

@@ -2,18 +2,31 @@
 (oracle/snk_oracle.c): random genomes with the plants of tests/pathgen.py (repeats, a tandem run, a palindrome, a long homopolymer, a
 short-period repeat), read pairs of up to 256 bases with planted duplicate groups, a device graph of drawn K / filters / buckets, and a
 drawn pathing variant (look-up structure, passes, lanes, dictionary load, fingerprint mask, first list capacities, MarkDups sort).
-Per case: every read's (offset, edges) == oracle_lib.path_reads on the device's unitigs; the dup flag of every pair and the counters ==
-oracle_lib.mark_dups on those paths; on small cases the per-unitig barcode lists == oracle_lib.unitig_barcodes, uncut and cut.
-Test infrastructure, like tests/: it may use the oracle.
+Per case, the five stages that run after the pather, each on the paths the pather just made:
+  1. snk_dev_mark_dups: the dup flag of every pair and the counters == oracle_lib.mark_dups on those paths
+  2. snk_dev_paths_index: index, read support and counters == a48ref.paths_index
+  3. snk_dev_paths_zip: index, data and counters == a48xref.zip_paths on the graph parsed from the a.hbv the library writes, no step
+     outside the graph
+  4. snk_dev_paths_unzip of that result: edge counts and edges back exactly, offsets after the int16 wrap
+  5. snk_dev_edge_barcodes: == ebcxref.edge_barcodes, again with SNK_EBC_GENERAL_SORT, and (when the case counts with barcodes) again on
+     the reads reordered by barcode, the fast sort path
+-- after every read's (offset, edges) == oracle_lib.path_reads on the device's unitigs; on small cases also the per-unitig barcode lists
+== oracle_lib.unitig_barcodes, uncut and cut.  The restatements are pinned to the reference's own files by test_a48_files.py,
+test_a48x_files.py and test_ebcx_files.py.  Test infrastructure, like tests/: it may use the oracle.
 usage: python tests/tools/fuzz_paths.py [n_cases] [seed] [replay_case]"""
 import sys
 from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))
+import tempfile
 import numpy as np
+import a48ref
+import a48xref
+import ebcxref
+import handpaths
 import oracle_lib
 import pathgen
-from supernova_amd import lib as _lib
+from supernova_amd import graphio, lib as _lib
 from supernova_amd.engine import Engine, Params
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
@@ -53,6 +66,57 @@ def reads_for(rng, c):
     return codes, quals, lens, bc
 
 
+def later_stages(c, us, off, ne, edges, bc, info):
+    """The paths index, the zip, its unzip and the edge -> barcode lists of one case against their numpy restatements -> mismatch lines."""
+    import torch
+    bad = []
+    K, inv = c["K"], info["inv"]
+    u = graphio.unitigs_to_arrays(us)
+    with tempfile.TemporaryDirectory() as td:
+        graphio.write_hbv(Path(td) / "g.hbv", None, K, *u)
+        g = a48xref.parse_hbv((Path(td) / "g.hbv").read_bytes())
+    # the paths index
+    x_off, x_ids, x_counts = a48ref.paths_index(ne, edges, inv)
+    p = info["pidx"]
+    got = (p["n_entries"], p["n_hbv_edges"], p["n_empty_edges"], p["key_bits"])
+    want = (len(edges), len(inv), int((np.diff(x_off.astype(np.int64)) == 0).sum()), int(len(inv) - 1).bit_length() if len(inv) > 1 else 0)
+    same = [np.array_equal(a, b) for a, b in zip(info["paths_index"] + (info["countsb"],), (x_off, x_ids, x_counts))]
+    if not all(same) or got != want or g.E != len(inv):
+        bad.append(f"paths index: offsets / ids / counts {['equal' if x else 'differ' for x in same]}; counters {got} vs {want}; {g.E} edges in a.hbv")
+    # the compressed paths, and back
+    x_index, x_data, x_stats = a48xref.zip_paths(off, ne, edges, g)
+    index, data = info["pathsx"]
+    st = info["pathsx_stats"]
+    got = {k: st[k] for k in x_stats}
+    if not (np.array_equal(index, x_index) and np.array_equal(data, x_data)) or got != x_stats or x_stats["n_steps_not_found"] != 0:
+        bad.append(f"pathsX: index {'equal' if np.array_equal(index, x_index) else 'differs'}, data {'equal' if np.array_equal(data, x_data) else 'differ'}"
+                   f" ({len(data)} vs {len(x_data)} bytes); counters {got} vs {x_stats}")
+    dev = torch.device("cuda", 0)
+    with graphio.hbv_handle(K, *u) as h:
+        u_off, u_ne, u_edges, _ = eng.unzip_paths(h, torch.from_numpy(index.copy()).to(dev), torch.from_numpy(data.copy()).to(dev), len(ne))
+    back = (np.array_equal(u_ne, ne), np.array_equal(u_edges, edges), np.array_equal(u_off, np.where(ne > 0, a48xref.wrap16(off), 0)))
+    if not all(back):
+        bad.append(f"unzip: edge counts / edges / wrapped offsets {['equal' if x else 'differ' for x in back]}")
+    # the edge -> barcode lists: as path_reads ran them, with the full-key sort, and on the reads reordered by barcode
+    x_off, x_bcs = ebcxref.edge_barcodes(ne, edges, bc, inv)
+    runs = [("path_reads", True, info["ebcx"][0], info["ebcx"][1])]
+    gen = handpaths.EbcxCall(eng, ne, edges, bc, inv, flags=_lib.EBC_GENERAL_SORT)
+    runs.append(("general sort", gen.rc == 0 and gen.out.general_sort == 1, gen.off, gen.bcs))
+    if c["use_bc"]:
+        order = np.argsort(bc, kind="stable")
+        n_o = ne[order].astype(np.int64)
+        start = np.concatenate([[0], np.cumsum(ne.astype(np.int64))])
+        at = np.repeat(start[order] - (np.cumsum(n_o) - n_o), n_o) + np.arange(int(n_o.sum()))      # the entries of the reads in their new order
+        srt = handpaths.EbcxCall(eng, ne[order], edges[at], bc[order], inv)
+        runs.append(("reads by barcode", srt.rc == 0 and srt.out.bc_sorted == 1 and srt.out.general_sort == 0, srt.off, srt.bcs))
+    for name, ran, e_off, e_bcs in runs:
+        if not ran:
+            bad.append(f"edge barcodes ({name}): refused, or not the sort path it was to take")
+        elif not (np.array_equal(e_off, x_off) and np.array_equal(e_bcs, x_bcs)):
+            bad.append(f"edge barcodes ({name}): offsets {'equal' if np.array_equal(e_off, x_off) else 'differ'}, {len(e_bcs)} vs {len(x_bcs)} barcodes")
+    return bad
+
+
 def run_case(case, c, v, codes, quals, lens, bc):
     """-> list of mismatch descriptions (empty: bit-exact)."""
     K, L = c["K"], c["L"]
@@ -65,7 +129,7 @@ def run_case(case, c, v, codes, quals, lens, bc):
                           params=Params(K=K, min_freq=c["min_freq"], min_bc=c["min_bc"], n_buckets=c["nb"]))
     us = res.unitigs()
     small = codes.shape[0] <= BC_LISTS_MAX_READS
-    off, ne, edges, info = res.path_reads(rows, L, dq, lens=dl, mark_dups=True, bc=dbc, unitig_bcs=small)
+    off, ne, edges, info = res.path_reads(rows, L, dq, lens=dl, mark_dups=True, bc=dbc, unitig_bcs=small, paths_index=True, pathsx=True, ebcx=True)
     bad = []
     o_off, o_n, o_edges = oracle_lib.path_reads(codes, quals, lens, us, K=K)
     if not (np.array_equal(ne.astype(np.int64), o_n) and np.array_equal(edges, o_edges) and np.array_equal(off, o_off)):
@@ -78,6 +142,7 @@ def run_case(case, c, v, codes, quals, lens, bc):
     want = (o_nd, o_ni, int(o_dup.sum()), int(o_art.sum()), int((o_n > 0).sum()), o_rate)
     if not np.array_equal(d["dup"], o_dup) or got != want:
         bad.append(f"dups: {int((d['dup'] != o_dup).sum())} flags differ; counters {got} vs {want}")
+    bad += later_stages(c, us, off, ne, edges, bc, info)
     if small:
         uoff, ubases = res.unitig_arrays()
         asc = np.frombuffer(b"ACGT", dtype=np.uint8)[ubases].tobytes().decode()
