@@ -432,7 +432,9 @@ int snk_dev_bv_image(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d
  * (K-1)-mer end keys, their sort and the vertex classes are computed on the device (what the reference runs through
  * its MapReduce engine, HBVFromEdges.cc:136-168,257-262); the id hand-out, a breadth-first flood whose ids ARE the
  * visiting order (:170-238), runs per connected component: components and their id blocks on the device, one thread per
- * component; a component above SNK_HBV_BIG (1024) nodes, and any graph below SNK_HBV_DEV_MIN (65536) unitigs, on the host. */
+ * component; a component above SNK_HBV_BIG (1024) nodes, and any graph below SNK_HBV_DEV_MIN (65536) unitigs, on the host.
+ * snk_ctx_last_hbv_flood says which of the two ran.  The input must be the unitig set of a de Bruijn graph (no K-mer twice, at most 8
+ * ends per (K-1)-mer); other input is not refused. */
 typedef struct snk_hbv {
     int32_t n_vertices, n_edges;
     int32_t* v_left;            /* per HBV edge */
@@ -446,6 +448,12 @@ typedef struct snk_hbv {
 } snk_hbv;
 int snk_hbv_from_unitigs(uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases,
                          snk_hbv* out, char* err, size_t errcap);
+/* Which id flood the last snk_dev_hbv on the context ran: 0 = the host flood (the graph was below hbv_dev_min unitigs), 1 = the device
+ * flood, 2 = the device flood gave up and the host flood redid the graph (never with hbv_strict, which fails the call instead).
+ * *device_components / *host_components (either may be NULL): the connected components of the (unitig, strand) graph that device threads
+ * flooded (one thread each: those of at most hbv_big nodes) and those that host threads flooded (all of them after 0 and 2).  After a
+ * call that failed or had no unitigs: 0 and no components. */
+uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components, uint64_t* host_components);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
  * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has

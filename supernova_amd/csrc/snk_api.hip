@@ -414,6 +414,11 @@ void snk_ctx_release_scratch(snk_ctx* ctx) {
     snk_ctx_plan_mem(ctx);      // what this call's plans may count on (everything the arena holds is free at this point)
 }
 extern "C" uint32_t snk_ctx_last_partition_passes(const snk_ctx* ctx) { return ctx ? ctx->last_partition_passes : 0u; }
+extern "C" uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components, uint64_t* host_components) {
+    if (device_components) *device_components = ctx ? ctx->last_hbv_dev_components : 0;
+    if (host_components) *host_components = ctx ? ctx->last_hbv_host_components : 0;
+    return ctx ? ctx->last_hbv_flood : 0u;
+}
 extern "C" uint32_t snk_ctx_last_count_limit(const snk_ctx* ctx) { return ctx ? ctx->last_count_limit : 0u; }
 extern "C" int snk_ctx_reserve(snk_ctx* ctx, uint64_t bytes, char* err, size_t errcap) {
     if (!ctx) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_reserve: NULL context");

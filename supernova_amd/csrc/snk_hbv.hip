@@ -158,8 +158,9 @@ void hbv_flood_component(const hbv_tables& t, uint64_t e0, int rc0, int32_t* vid
         fprintf(stderr, "[snk hbv] component of %llu edge copies: %u breadth-first levels (%.1f copies per level)\n", (unsigned long long)visited, depth + 1, (double)visited / (depth + 1));
 }
 // Fills every array of `out`: every component in seed order.  ctx NULL (snk_hbv_from_unitigs has none): the options' defaults.
+// n_components (optional): how many components were flooded.
 int hbv_flood(const snk_ctx* ctx, uint64_t U, const uint8_t* pal, const uint32_t* ee, uint64_t n_ee, const int32_t* vtx_of, const uint64_t* run_beg,
-              uint64_t nruns, snk_hbv* out, char* err, size_t errcap) {
+              uint64_t nruns, snk_hbv* out, char* err, size_t errcap, uint64_t* n_components = nullptr) {
     const bool huge = snk_opt_u32(ctx, SNK_OPT_hbv_huge_pages) != 0;
     int rc = hbv_alloc_out(U, nruns, huge, out, err, errcap);
     if (rc) return rc;
@@ -172,10 +173,12 @@ int hbv_flood(const snk_ctx* ctx, uint64_t U, const uint8_t* pal, const uint32_t
     std::vector<uint64_t> q;
     const hbv_tables t{U, pal, ee, vtx_of, run_beg, snk_opt_u32(ctx, SNK_OPT_hbv_short_queue) != 0};
     (void)n_ee;
+    uint64_t ncomp = 0;
     for (int pass = 0; pass < 2; ++pass)
         for (uint64_t e0 = 0; e0 < U; ++e0)
-            if ((pass ? out->rev_xlat : out->fwd_xlat)[e0] == -1) hbv_flood_component(t, e0, pass, vid, q, next_e, next_v, out);
+            if ((pass ? out->rev_xlat : out->fwd_xlat)[e0] == -1) { hbv_flood_component(t, e0, pass, vid, q, next_e, next_v, out); ++ncomp; }
     out->n_edges = next_e;
+    if (n_components) *n_components = ncomp;
     return SNK_OK;
 }
 
@@ -421,7 +424,7 @@ __global__ void __launch_bounds__(HB) hbv_ends_kernel(const uint64_t* __restrict
     const uint32_t kl = K - 1;
     codes[t] = (uint32_t)t;
     if ((t & 3) == 0) pal_ranked[r] = pal[u];
-    if (rc && pal[u]) { keys[t] = ~(snk_u128)0; return; }
+    if ((rc && pal[u]) || len < K) { keys[t] = ~(snk_u128)0; return; }     // (shorter than K: the call fails once the flag is read; no base before its start is touched)
     // forward strand: bases [p0, p0+kl); reverse strand: complement of the mirrored range, read backwards
     const uint64_t p0 = distal ? len - kl : 0;
     snk_u128 k = 0;
@@ -517,7 +520,8 @@ __global__ void __launch_bounds__(HB) hbv_cc_classes_kernel(uint32_t* par, const
     hbv_count_root(cv, valid, valid ? uf_find(par, hbv_node(ee[run_beg[r]], U), errflag) : 0u);
 }
 struct hbv_big { uint32_t root, be, bv, ce; };
-// one thread per root: floods its component when that is small, lists it for the host otherwise
+// one thread per root: floods its component when that is small, lists it for the host otherwise; n_big[2] counts the roots (one atomic
+// per wave)
 __global__ void __launch_bounds__(HB) hbv_flood_kernel(const uint32_t* __restrict__ par, const uint8_t* __restrict__ palr, uint32_t U,
                                                        const uint32_t* __restrict__ ce, const uint32_t* __restrict__ be,
                                                        const uint32_t* __restrict__ bv, const uint32_t* __restrict__ ee,
@@ -526,7 +530,10 @@ __global__ void __launch_bounds__(HB) hbv_flood_kernel(const uint32_t* __restric
                                                        int32_t* v_right, int32_t* src, uint8_t* isrc, hbv_big* big, uint32_t big_cap,
                                                        uint32_t* n_big, uint32_t nruns, uint32_t* errflag) {
     const uint64_t n = (uint64_t)blockIdx.x * HB + threadIdx.x;
-    if (n >= 2ull * U || par[n] != (uint32_t)n || (n >= U && palr[n - U])) return;
+    const bool root = n < 2ull * U && par[n] == (uint32_t)n && !(n >= U && palr[n - U]);
+    const unsigned long long roots = __ballot(root);
+    if (roots && (int)__lane_id() == __ffsll((long long)roots) - 1) atomicAdd(n_big + 2, (uint32_t)__popcll(roots));
+    if (!root) return;
     const uint32_t size = ce[n], e_base = be[n], v_base = bv[n];
     if (size > big_limit) {
         const uint32_t q = atomicAdd(n_big, 1u);
@@ -572,6 +579,8 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
                            float* device_ms, void* stream, char* err, size_t errcap) {
     if (!ctx || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_hbv: NULL argument");
     memset(out, 0, sizeof *out);
+    ctx->last_hbv_flood = 0;             // (snk_ctx_last_hbv_flood: a call that fails, or has no unitigs, leaves 0 and no components)
+    ctx->last_hbv_dev_components = ctx->last_hbv_host_components = 0;
     if (device_ms) *device_ms = 0.f;
     if (K != 48 && K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", K);
     if (U == 0) return SNK_OK;
@@ -587,7 +596,9 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
     huge_vec<uint8_t> h_pal(huge);
     huge_vec<uint64_t> h_run(huge);
     std::vector<hbv_big> h_big;
-    uint32_t h_flags[4] = {0, 0, 0, 0}, h_nb[2] = {0, 0}, nruns = 0;
+    uint32_t h_flags[4] = {0, 0, 0, 0}, h_nb[4] = {0, 0, 0, 0}, nruns = 0;
+    uint32_t which = 0;                  // what snk_ctx_last_hbv_flood will say: set on the way, stored when the call has succeeded
+    uint64_t comp_dev = 0, comp_host = 0;
     uint64_t h_nee = 0;
     const int rc = snk_call_guarded(ctx, stream, "snk_dev_hbv", err, errcap, [&](snk_call& c) -> int {
         const hipStream_t st = c.st;
@@ -664,7 +675,7 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
             SNK_HIP_TRY(hipMemcpyAsync(h_order.data(), order, U * 4, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(snk_sync(st));
             if (device_ms) *device_ms = c.ms(0, 1);
-            rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap);
+            rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap, &comp_host);
             if (rc) return rc;
         } else {
             // the sort buffers are dead: node arrays live in `keys` (64 U bytes), the outputs in `keys2`, the vertex ids in `flag`
@@ -678,14 +689,14 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
             const uint32_t big_limit = snk_opt_u32(ctx, SNK_OPT_hbv_big);
             const uint32_t big_cap = (uint32_t)(n2 / ((uint64_t)big_limit + 1) + 1);
             hbv_big* d_big;
-            uint32_t* d_nbig;                      // [0] components for the host, [1] error flag
+            uint32_t* d_nbig;                      // [0] components for the host, [1] error flag, [2] components in all
             if ((rc = c.alloc(big_cap, &d_big)) || (rc = c.alloc(4, &d_nbig))) return rc;
             h_nee = n_ee;
             SNK_HIP_TRY(hipMemcpyAsync(run_beg + nruns, &h_nee, 8, hipMemcpyHostToDevice, st));
             SNK_HIP_TRY(hipMemsetAsync(ce, 0, n2 * 8, st));                       // ce, cv
             SNK_HIP_TRY(hipMemsetAsync(d_fwd, 0xFF, U * 8, st));                  // fwd, rev
             SNK_HIP_TRY(hipMemsetAsync(d_vid, 0xFF, (size_t)nruns * 4, st));
-            SNK_HIP_TRY(hipMemsetAsync(d_nbig, 0, 8, st));
+            SNK_HIP_TRY(hipMemsetAsync(d_nbig, 0, 16, st));
             const uint64_t g2 = snk_blocks(n2, HB), gr = snk_blocks(nruns, HB);
             SNK_HIP_TRY(snk_launch(hbv_cc_init_kernel, g2, HB, 0, st, par, n2));
             SNK_HIP_TRY(snk_launch(hbv_cc_union_kernel, ge, HB, 0, st, codes2, cls, run_beg, n_ee, (uint32_t)U, par, d_nbig + 1));
@@ -698,7 +709,7 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
             SNK_HIP_TRY(snk_launch(hbv_flood_kernel, g2, HB, 0, st, par, palr, (uint32_t)U, ce, be, bv, codes2, vtx_of, run_beg, big_limit,
                                    d_fwd, d_rev, d_vid, d_vl, d_vr, d_src, d_isrc, d_big, big_cap, d_nbig, nruns, d_nbig + 1));
             SNK_HIP_TRY(c.stamp());
-            SNK_HIP_TRY(hipMemcpyAsync(h_nb, d_nbig, 8, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(hipMemcpyAsync(h_nb, d_nbig, 16, hipMemcpyDeviceToHost, st));
             if ((rc = hbv_alloc_out(U, nruns, huge, out, err, errcap))) return rc;
             SNK_HIP_TRY(hipMemcpyAsync(out->fwd_xlat, d_fwd, U * 4, hipMemcpyDeviceToHost, st));
             SNK_HIP_TRY(hipMemcpyAsync(out->rev_xlat, d_rev, U * 4, hipMemcpyDeviceToHost, st));
@@ -715,9 +726,13 @@ extern "C" int snk_dev_hbv(snk_ctx* ctx, uint32_t K, uint64_t U, const void* d_u
                 if (snk_opt_u32(ctx, SNK_OPT_hbv_strict)) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: the device flood gave up (flag %u)", h_nb[1]);
                 SNK_HIP_TRY(fetch_tables());
                 SNK_HIP_TRY(snk_sync(st));
-                if ((rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap))) return rc;
+                if ((rc = hbv_flood(ctx, U, h_pal.data(), h_ee.data(), n_ee, h_vtx.data(), h_run.data(), nruns, out, err, errcap, &comp_host))) return rc;
+                which = 2;
                 goto flooded;
             }
+            which = 1;
+            comp_host = n_big;
+            comp_dev = h_nb[2] - std::min(n_big, h_nb[2]);
             out->n_edges = (int32_t)(n2 - h_flags[1]);
             if (n_big) {               // the connected bulk: flooded here into the blocks the scans gave it
                 if (n_big > big_cap) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_hbv: component list overflow");
@@ -765,7 +780,11 @@ flooded:
         out->bvcomp_order = (int32_t*)malloc(U * 4);
         if (!out->bvcomp_order) return snk_fail(SNK_E_NOMEM, err, errcap, "snk_dev_hbv: host allocation failed");
         for (uint64_t i = 0; i < U; ++i) out->bvcomp_order[i] = (int32_t)h_order[i];
-        return c.end(SNK_OK);
+        if ((rc = c.end(SNK_OK))) return rc;
+        ctx->last_hbv_flood = which;
+        ctx->last_hbv_dev_components = comp_dev;
+        ctx->last_hbv_host_components = comp_host;
+        return SNK_OK;
     });
     if (rc) {                    // (after the frame's wait: no copy into these arrays is still running)
         snk_hbv_free(out);

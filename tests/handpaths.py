@@ -4,13 +4,15 @@ tests/test_gpu_paths_index_handmade.py, tests/test_handpaths_host.py).
 Two things: thin ctypes callers of snk_dev_mark_dups and snk_dev_paths_index on host arrays uploaded as they are (DupsCall, PidxCall, in
 the style of Call in test_gpu_ebcx.py: *out comes in full of 0xA5; EbcxCall is that Call for the fuzz tool), and a generator of read pairs with paths for MarkDups whose first
 edges and offsets come from small palettes, so that the width of the sort key (snk_dups.hip: bits(max edge) + bits(max offset - min
-offset) + 10) is chosen by the test and not by a pather.  Nothing here needs a GPU until a caller is made."""
+offset) + 10) is chosen by the test and not by a pather.  Nothing here needs a GPU until a caller is made.  (The upload and download helpers are tests/devcall.py's.)"""
 from __future__ import annotations
 
 import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
+
+from devcall import _dev, _zeroed, download
 
 INT32_MIN, INT32_MAX = -(2**31), 2**31 - 1
 HEADS = np.array([[0, 1, 2, 3, 0], [3, 3, 1, 0, 2], [0, 1, 2, 3, 1]], np.uint8)       # the first five bases of every read
@@ -201,11 +203,6 @@ def dups_case(name):
 
 # ---- the callers
 
-def _dev(a, dtype):
-    import torch
-    return torch.from_numpy(np.array(a, dtype=dtype)).to(torch.device("cuda", 0))
-
-
 def dev_shifted(a, shift):
     """int32 values on the device, the first one `shift` words behind a 16-byte boundary"""
     import torch
@@ -215,17 +212,6 @@ def dev_shifted(a, shift):
     view.copy_(torch.from_numpy(np.asarray(a, np.int32)))
     assert len(a) == 0 or view.data_ptr() % 16 == 4 * shift            # (an empty view has no address)
     return view
-
-
-def download(engine, ptr, count, dtype):
-    host = np.zeros(max(count, 1), dtype)
-    if count:
-        engine._download(ptr, host.ctypes.data, count * host.itemsize)
-    return host[:count].copy()
-
-
-def _zeroed(out):
-    return C.string_at(C.addressof(out), C.sizeof(out)) == bytes(C.sizeof(out))
 
 
 class _Paths:

@@ -20,6 +20,14 @@ def test_exports_match_header(snk):
     assert declared == bound, (declared ^ bound)
 
 
+def test_last_hbv_flood_without_a_context(snk):
+    """snk_ctx_last_hbv_flood (which id flood the last snk_dev_hbv ran, and the components each side flooded) answers 0 and no components
+    for a NULL context and takes NULL for either counter; with a context it is tests/test_gpu_hbv_handmade.py's witness of every leg."""
+    dev, host = C.c_uint64(7), C.c_uint64(7)
+    assert snk.snk_ctx_last_hbv_flood(None, C.byref(dev), C.byref(host)) == 0 and (dev.value, host.value) == (0, 0)
+    assert snk.snk_ctx_last_hbv_flood(None, None, None) == 0
+
+
 def test_no_cpu_fallback(snk):
     import torch
     if torch.cuda.is_available():

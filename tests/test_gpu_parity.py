@@ -1077,10 +1077,11 @@ def test_circle_pool_retry(engine, monkeypatch, tune):
     _check_against(res, c.exp_keys, c.exp_counts, c.exp_ctx, c.exp_unitigs, c.exp_goodlens, c.exp_hist)
 
 
+# (SNK_HBV_STRICT: a device flood that gives up fails the call instead of handing the graph to the host's flood, which would pass)
 HBV_FLOODS = {"host": {"SNK_HBV_DEV_MIN": "1000000000"},            # the sequential flood over the downloaded classes
-              "device": {"SNK_HBV_DEV_MIN": "0"},                    # components on the device, one thread floods one component
-              "device_big4": {"SNK_HBV_DEV_MIN": "0", "SNK_HBV_BIG": "4"},   # components above 4 nodes go to the host's flood
-              "device_big0": {"SNK_HBV_DEV_MIN": "0", "SNK_HBV_BIG": "0"}}   # every component does
+              "device": {"SNK_HBV_DEV_MIN": "0", "SNK_HBV_STRICT": "1"},                    # components on the device, one thread floods one component
+              "device_big4": {"SNK_HBV_DEV_MIN": "0", "SNK_HBV_BIG": "4", "SNK_HBV_STRICT": "1"},   # components above 4 nodes go to the host's flood
+              "device_big0": {"SNK_HBV_DEV_MIN": "0", "SNK_HBV_BIG": "0", "SNK_HBV_STRICT": "1"}}   # every component does
 
 
 @pytest.mark.parametrize("flood", list(HBV_FLOODS))
