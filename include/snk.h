@@ -455,7 +455,7 @@ int snk_hbv_from_unitigs(uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_
  * call that failed or had no unitigs: 0 and no components. */
 uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components, uint64_t* host_components);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -628,6 +628,53 @@ int snk_write_pathsx(const char* path, uint64_t n_reads, const int64_t* index, u
 int snk_read_pathsx(const char* path, uint64_t* n_reads, uint64_t* n_index, int64_t** index, uint64_t* n_bytes, uint8_t** data, char* err, size_t errcap);
 int snk_write_hbx(const char* path, uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const uint8_t* unitig_bases, const snk_hbv* h, char* err,
                   size_t errcap);
+
+/* ---- path extension: StageExtension ---------------------------------------------------------------------------------
+ * ExtendPathsNew, lib/assembly/src/10X/Extend.cc:14-177 (StageExtension, 10X/runstages/RunStages.cc:159-174, called at 10X/DF.cc:676; DF
+ * writes its second paths index from the result, DF.cc:690), with the HyperBasevectorX overload of ExtendPath
+ * (paths/long/large/GapToyTools4.cc:477-555; min_gain 5, mode 1).  A function of (graph, reads, paths): the graph may be the one the
+ * paths were made on or one a host has patched since.  Three legs per read, in this order, each on the result of the one before:
+ *   1 backward, only with SNK_EXT_BACK (Extend.cc:25-61): while offset < 0 and To(ToLeft(p[0])) is not empty, the first in-edge e, in
+ *     To-list order, whose bases agree with the read at every position l with l - offset - Kmers(e) >= 0 is put in front and Kmers(e)
+ *     added to the offset; it stops when none agrees
+ *   2 quality-aware (:63-95): the path is cut to its first edge, then ExtendPath runs.  It changes nothing when the offset is negative,
+ *     the read does not reach beyond the first edge, or From(ToRight) is empty.  Otherwise it lists the continuations breadth-first in
+ *     From-list order (GapToyTools4.cc:495-515): entries of len >= ext are not expanded but count, and reaching list index 101 fails
+ *     (expanding entries 0..100 left more than 101).  Only entries with len >= ext are kept (:517-523); qsum = the read's raw quality
+ *     summed over the mismatches against the edges' bases from K-1 on (:527-538); the best is taken iff it is the only one or beats
+ *     the runner-up by at least 5 (:539-543) -- ties never decide, so the order among equals does not matter.  A read that is declined
+ *     keeps the one-edge path
+ *   3 exact (Extend.cc:97-177): the path is walked against the read; only if the walk runs off the path's last edge without a mismatch
+ *     and before the read ends does it go on, base by base, stepping at an edge's end to the out-edge whose base K-1 equals the read's
+ *     base.  The reference's loop has no break: several matching out-edges are all pushed.  That is refused here (below)
+ * Arguments: the graph as for snk_dev_path_reads (bvcomp_order, NULL = the arrays are in BVComp order); of `in` the rows, lens (NULL =
+ * read_len) and quals; the From / To lists are the ones a.hbv has.  paths stays valid and unchanged, as do the count result and earlier
+ * stage results.  out->paths: offset / n_edges / start / edges as from snk_dev_path_reads (context memory, valid until the context's next
+ * top-level call; path_ms = time of this call, the other fields 0).  The result depends on no tuning option and is bit-identical from
+ * call to call.
+ * SNK_E_ARG -- the reference would read outside a read or an edge: offset <= -len(read), offset >= Bases(p[0]), a path on a read of length
+ * 0, and with SNK_EXT_BACK a read that ends inside the K-1 bases its first edge shares with its in-edges while leg 1 would run; further
+ * an edge id outside the graph, start / n_edges that do not add up to n_edges_total, quals == NULL, read_len above 256, unknown flags.
+ * SNK_E_UNSUPPORTED: an offset outside +-32767, given or made by leg 1 (the reference keeps the paths in a ReadPathVecX, on entry and
+ * between its legs: an in-edge of more than 32767 k-mers put in front would wrap the offset), a path of more than 255 edges (given or made), a
+ * vertex with more than four out-edges (the list of continuations is sized 1 + 101 x 4 = 405 entries; a.pathsX has two bits per branch),
+ * two out-edges of one vertex with the same base at K-1 met by leg 3. */
+typedef struct snk_dev_extend {
+    snk_dev_paths paths;
+    uint64_t n_back_extended;     /* reads whose path gained an edge in front (SNK_EXT_BACK) */
+    uint64_t n_cut_to_first;      /* reads whose path of two or more edges left leg 2 as its first edge alone: ExtendPath did not re-extend it */
+    uint64_t n_quality_extended;  /* reads ExtendPath extended (leg 2) */
+    uint64_t n_ambiguous;         /* ... declined: runner-up within MIN_GAIN */
+    uint64_t n_too_many;          /* ... declined: more than max_exts extensions */
+    uint64_t n_exact_extended;    /* reads the exact-match leg (leg 3) extended */
+    float ms;                     /* HIP events around the call's device work (graph tables included) */
+    uint32_t reserved0;
+    uint64_t n_enumerated;        /* reads that reached ExtendPath's enumeration (the listed, slow pass) */
+    uint64_t reserved[5];
+} snk_dev_extend;
+#define SNK_EXT_BACK 1u
+int snk_dev_extend_paths(snk_ctx* ctx, uint32_t K, const snk_dev_reads* in, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
+                         const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags, snk_dev_extend* out, void* stream, char* err, size_t errcap);
 
 /* ---- the edge -> barcode lists: a.ebcx ------------------------------------------------------------------------------
  * computeEdgeToBarcodeX, lib/assembly/src/10X/PathsIndex.cc:297-358 (StageEBC, 10X/runstages/RunStages.cc:31-38): per HBV edge the

@@ -27,7 +27,9 @@
 
 #include "snk_call.h"
 #include "snk_common.h"
+#include "snk_hbvadj.h"
 #include "snk_kernels.h"
+#include "snk_pathgraph.h"
 
 namespace {
 
@@ -46,39 +48,6 @@ constexpr int PCAP1 = 20;
 constexpr int PMAX1 = 16;
 constexpr int GPARTS = 4;      // parts per read that travel to the finishing kernel
 constexpr int PMT = 8;         // edges per read there
-
-struct path_graph {            // device arrays
-    const uint64_t* uoff;      // [U+1] unitig offsets into ubases (device order)
-    const uint8_t* ubases;     // 1 byte per base
-    const uint32_t* upack;     // the same bases, 2 bits each, 16 per word, first base in the top bits (one word of slack at either end): what the
-                               //     seed check and the exact-match extension read (a read's whole window is 40 bytes instead of 150 byte loads)
-    const uint4* uinfo;        // [U] x 2: {offset lo, offset hi, bases, flags}, {fwd edge, rev edge, 0, 0}; flags bit 0 / 1: a seed on the
-                               //     forward / reverse-complement copy is dropped (hanging edge rule, BuildReadQGraph48.cc:1240-1247)
-    const int32_t *fwd, *rev;  // [U] HBV edge of the unitig read forward / reverse-complemented
-    const int32_t *vleft, *vright;         // [E]
-    const int32_t *e_unitig;               // [E] device index of the unitig the edge is a copy of
-    const uint8_t* e_rc;                   // [E]
-    const int32_t *to_off, *to_v, *to_e;   // [N+1], [E], [E]: in-edges of a vertex, AddEdge order (graph/DigraphTemplate.h:2572-2582)
-    const int32_t *from_off, *from_v, *from_e;
-    const unsigned long long* dslot;   // dictionary, 8 bytes per slot: fingerprint (30 bits) | strand (1) | position (33 bits: first base of
-                               //   the k-mer in the concatenated unitigs); all ones: empty.  strand: the unitig holds the reverse complement
-                               //   of the canonical form.  A probe is one 8-byte access, a claim ONE 64-bit compare-and-swap; a fingerprint
-                               //   match is VERIFIED against the unitig's bases, so look-ups stay exact (2^-30 false candidates per probe of
-                               //   an occupied slot: a few reads per 10^8 take the verified path).  24 bytes per unitig k-mer.
-    const uint32_t* ublk;      // unitig that holds base 256 b of the concatenation (position -> unitig: this entry, then a step or two along uoff)
-    uint64_t dcap;             // slots: 3 per k-mer, not a power of two
-    unsigned long long fp_mask; // 30 ones; SNK_PATH_FP_MASK (tests) narrows the fingerprint so that false matches happen and the verified path runs
-    // Minimiser index (round 4; ment != NULL: the look-ups go through it and dslot is not built).  A k-mer lies on the graph iff its
-    // minimiser -- the 16-mer with the smallest ordering key among its K-15, the leftmost on ties -- occurs in a unitig at the matching
-    // place and the K bases around it agree.  The index lists the places a unitig k-mer's window picks (its leftmost AND its rightmost
-    // minimum: a read may run against the unitig's strand), ~2 / (K-14) of the unitig bases: 8 bytes each, sorted by key behind a
-    // directory over the key's top bits -- 0.14 GB for the bench graph's 0.27 G k-mers where the k-mer dictionary takes 6.4 GB, small
-    // enough to live in the 256 MB Infinity Cache together with the packed unitigs the candidates are verified against.
-    const unsigned long long* ment;    // [n_ment] key low 30 bits << 34 | the unitig's 16-mer is the reverse complement of the canonical one << 33 | position
-    const uint32_t* mdir;      // [(1 << mdir_bits) + 1] first entry of every key prefix
-    uint32_t mdir_bits;
-    uint32_t idx_dbg;          // SNK_PATH_IDX_DBG (timing aid, results invalid): 1 = window minimum only, 2 = + directory and entries, 3 = + base comparison (no unitig-bounds check)
-};
 
 template <int K>
 __device__ __forceinline__ snk_kmer kmer_at(const uint32_t* words, uint32_t nwords, uint32_t pos) {
@@ -153,7 +122,6 @@ __global__ void __launch_bounds__(256) ublk_kernel(const uint64_t* __restrict__ 
     while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (uoff[mid] <= p) lo = mid; else hi = mid; }
     ublk[b] = (uint32_t)lo;
 }
-constexpr uint64_t UPAD = 512;      // bases of slack in front of (and behind) the packed unitigs: a window may start 270 bases before a hit or run 270 past it
 // 16 bases starting at base p of a packed array (two words, one funnel shift)
 __device__ __forceinline__ uint32_t packed16(const uint32_t* P, uint64_t p) {
     const uint64_t wi = p >> 4;
@@ -885,22 +853,10 @@ int up(snk_call& c, const std::vector<T>& h, const T** out, char* err, size_t er
     *out = d;
     return SNK_OK;
 }
+
+
 int scan64(snk_call& c, const uint64_t* in, uint64_t* out, size_t count) {
     return c.with_temp([&](void* tmp, size_t& tb) { return rocprim::exclusive_scan(tmp, tb, in, out, (uint64_t)0, count, rocprim::plus<uint64_t>(), c.st); });
-}
-
-// adjacency in AddEdge order: a vertex's edges ascending by the vertex at their other end, equal ones in edge-id order
-void adjacency(int32_t N, int32_t E, const int32_t* key_v, const int32_t* other_v, std::vector<int32_t>& off, std::vector<int32_t>& vv, std::vector<int32_t>& ee) {
-    off.assign((size_t)N + 2, 0);
-    for (int32_t e = 0; e < E; ++e) off[key_v[e] + 1]++;
-    for (int32_t v = 0; v < N; ++v) off[v + 1] += off[v];
-    std::vector<int32_t> cur(off.begin(), off.end() - 1);
-    std::vector<std::pair<int32_t, int32_t>> tmp((size_t)E);
-    for (int32_t e = 0; e < E; ++e) tmp[cur[key_v[e]]++] = {other_v[e], e};
-    for (int32_t v = 0; v < N; ++v) std::sort(tmp.begin() + off[v], tmp.begin() + off[v + 1]);
-    vv.resize((size_t)E);
-    ee.resize((size_t)E);
-    for (int32_t i = 0; i < E; ++i) { vv[i] = tmp[i].first; ee[i] = tmp[i].second; }
 }
 
 // sorted (unitig << 32 | barcode) keys -> the first of every run of equal keys (the all-ones filler excluded)
@@ -973,24 +929,15 @@ __global__ void __launch_bounds__(64) ubc_cut_copy_kernel(const uint64_t* __rest
     for (uint64_t i = threadIdx.x; i < n; i += 64) out[noff[u] + i] = in[off[u] + i];
 }
 
-// the graph tables on the host: what the asynchronous uploads read.  The entry point declares them in front of the frame, which waits
-// for the stream before they are let go of, whichever way the call ends.
-struct path_host {
-    std::vector<int32_t> fwd, rev, eu, off_to, v_to, e_to, off_from, v_from, e_from, vl, vr;
-    std::vector<uint8_t> erc, drop;
-};
+}  // namespace
 
-// stamps: 0 start, 1 dictionary built, 2 paths done, 3 / 4 around the barcode lists
-template <int K>
-int path_impl(snk_call& c, path_host& H, const snk_dev_reads* in, uint64_t U, const uint64_t* d_uoff, const uint8_t* d_ubases, const snk_hbv* h, uint32_t flags,
-              snk_dev_paths* out, char* err, size_t errcap) {
-    snk_ctx* const ctx = c.ctx;
+// the graph tables (host: O(U + E)), in the device's unitig numbering, the per-unitig records and the packed unitigs (snk_pathgraph.h)
+int snk_path_graph_tables(snk_call& c, path_host& H, uint32_t K, uint64_t U, const uint64_t* d_uoff, const uint8_t* d_ubases, const snk_hbv* h, path_graph* Gp,
+                          uint64_t* total_bases_out, const char* who, char* err, size_t errcap) {
     const hipStream_t st = c.st;
     int rc;
-    const uint64_t n = in->n_reads;
-    SNK_HIP_TRY(c.stamp());
-    // ---- graph tables (host: O(U + E)), in the device's unitig numbering
-    const int32_t N = h->n_vertices, E = h->n_edges;
+    path_graph& G = *Gp;
+    const int32_t E = h->n_edges;
     std::vector<int32_t> &fwd = H.fwd, &rev = H.rev, &eu = H.eu, &off_to = H.off_to, &v_to = H.v_to, &e_to = H.e_to, &off_from = H.off_from, &v_from = H.v_from, &e_from = H.e_from;
     std::vector<uint8_t> &erc = H.erc, &drop = H.drop;
     fwd.resize(U); rev.resize(U); eu.resize((size_t)E); erc.resize((size_t)E);
@@ -1004,13 +951,16 @@ int path_impl(snk_call& c, path_host& H, const snk_dev_reads* in, uint64_t U, co
         eu[e] = (int32_t)(h->bvcomp_order ? h->bvcomp_order[r] : (int32_t)r);
         erc[e] = h->is_rc[e];
     }
-    adjacency(N, E, h->v_right, h->v_left, off_to, v_to, e_to);
-    adjacency(N, E, h->v_left, h->v_right, off_from, v_from, e_from);
+    {
+        // the From / To lists in a.hbv's order (snk_hbvadj.h), offsets narrowed to the 32 bits an edge count has
+        snk_hbv_lists ls;
+        if ((rc = snk_hbv_lists_build(h, &ls, who, err, errcap))) return rc;
+        off_to.assign(ls.to_off.begin(), ls.to_off.end()); off_to.push_back(E);
+        off_from.assign(ls.from_off.begin(), ls.from_off.end()); off_from.push_back(E);
+        v_to.swap(ls.to_v); e_to.swap(ls.to_e); v_from.swap(ls.from_v); e_from.swap(ls.from_e);
+    }
     std::vector<int32_t> &vl = H.vl, &vr = H.vr;
     vl.assign(h->v_left, h->v_left + E); vr.assign(h->v_right, h->v_right + E);
-    path_args a;
-    memset(&a, 0, sizeof a);
-    path_graph& G = a.G;
     G.uoff = d_uoff; G.ubases = d_ubases;
     if ((rc = up(c, fwd, &G.fwd, err, errcap)) || (rc = up(c, rev, &G.rev, err, errcap)) || (rc = up(c, vl, &G.vleft, err, errcap)) ||
         (rc = up(c, vr, &G.vright, err, errcap)) || (rc = up(c, eu, &G.e_unitig, err, errcap)) || (rc = up(c, erc, &G.e_rc, err, errcap)) ||
@@ -1039,6 +989,7 @@ int path_impl(snk_call& c, path_host& H, const snk_dev_reads* in, uint64_t U, co
     SNK_HIP_TRY(snk_launch(uinfo_kernel, snk_blocks(U, 256), 256, 0, st, d_uoff, U, G.fwd, G.rev, d_drop, uinfo));
     G.uinfo = uinfo;
     const uint64_t total_bases = h_off_last;
+    *total_bases_out = total_bases;
     {
         // the unitigs once more, 2 bits per base (a quarter of the byte array), UPAD bases of slack at either end
         const uint64_t n_words = (total_bases + 15) / 16 + 1;
@@ -1049,6 +1000,25 @@ int path_impl(snk_call& c, path_host& H, const snk_dev_reads* in, uint64_t U, co
         SNK_HIP_TRY(snk_launch(upack_kernel, snk_blocks(n_words, 256), 256, 0, st, d_ubases, total_bases, upack + UPAD / 16, n_words));
         G.upack = upack;
     }
+    return SNK_OK;
+}
+
+namespace {
+
+// stamps: 0 start, 1 dictionary built, 2 paths done, 3 / 4 around the barcode lists
+template <int K>
+int path_impl(snk_call& c, path_host& H, const snk_dev_reads* in, uint64_t U, const uint64_t* d_uoff, const uint8_t* d_ubases, const snk_hbv* h, uint32_t flags,
+              snk_dev_paths* out, char* err, size_t errcap) {
+    snk_ctx* const ctx = c.ctx;
+    const hipStream_t st = c.st;
+    int rc;
+    const uint64_t n = in->n_reads;
+    SNK_HIP_TRY(c.stamp());
+    path_args a;
+    memset(&a, 0, sizeof a);
+    path_graph& G = a.G;
+    uint64_t total_bases = 0;
+    if ((rc = snk_path_graph_tables(c, H, K, U, d_uoff, d_ubases, h, &G, &total_bases, "snk_dev_path_reads", err, errcap))) return rc;
     const uint64_t nk = total_bases >= U * (uint64_t)(K - 1) ? total_bases - U * (uint64_t)(K - 1) : 0;
     if (total_bases >= (1ull << 33) - 1) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_path_reads: more than 2^33 unitig bases (the dictionary keeps 33-bit positions)");
     // Look-ups: the k-mer dictionary (a slot per unitig k-mer: 24 bytes each, one probe or two per look-up) or the minimiser index

@@ -133,7 +133,7 @@ class Result:
         return out
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
-                   paths_index=False, pathsx=False, ebcx=False):
+                   paths_index=False, pathsx=False, ebcx=False, extend=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -152,7 +152,11 @@ class Result:
         ebcx (needs bc): the edge -> barcode lists of computeEdgeToBarcodeX (10X/PathsIndex.cc:297-358; snk_dev_edge_barcodes) ->
         info['ebcx'] = (off u64[E+1], bcs i32[...]): the ascending distinct barcodes > 0 of the reads whose path holds HBV edge e or its
         reverse complement are bcs[off[e]:off[e+1]]; info['ebcx_stats'] = sizes, which sort ran and time; ebcx="general" asks for the full-key
-        sort even when bc is sorted (SNK_EBC_GENERAL_SORT).  download=False: the stats only."""
+        sort even when bc is sorted (SNK_EBC_GENERAL_SORT).  download=False: the stats only.
+        extend (True, or "back" for SNK_EXT_BACK): StageExtension over these paths (10X/DF.cc:676; ExtendPathsNew, 10X/Extend.cc:14-177;
+        snk_dev_extend_paths) -> info['extended'] = (offset i32[n], n_edges u32[n], edges i32[sum]), info['extend_stats'] = the counters and
+        time; with pathsx also info['extended_pathsx'] = (index, data), the ReadPathVecX of the extended paths, and
+        info['extended_pathsx_stats'].  It runs last: every other result is of the paths as pathed.  download=False: the stats only."""
         if ebcx and bc is None:
             raise ValueError("path_reads(ebcx=...) needs bc: the barcode of every read, on the device")
         e = self._e
@@ -226,6 +230,28 @@ class Result:
                 px_stats = _pathsx_stats(zx)
                 if download:
                     px_arrays = (self._dl(zx.index, int(zx.n_index) * 8, np.int64, (int(zx.n_index),)), self._dl(zx.data, int(zx.n_bytes), np.uint8, (int(zx.n_bytes),)))
+            ext_stats = None
+            if extend:
+                xo = _lib.SnkDevExtend()
+                rc = e.lib.snk_dev_extend_paths(e._ctx, int(self.K), C.byref(r), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases, C.byref(h),
+                                                C.byref(out), _lib.EXT_BACK if extend == "back" else 0, C.byref(xo), e._stream(), err, 512)
+                if rc:
+                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+                ext_stats = _extend_stats(xo)
+                xp = xo.paths
+                if download:
+                    xn, xt = int(xp.n_reads), int(xp.n_edges_total)
+                    ext_arrays = (self._dl(xp.offset, xn * 4, np.int32, (xn,)), self._dl(xp.n_edges, xn * 4, np.uint32, (xn,)), self._dl(xp.edges, xt * 4, np.int32, (xt,)))
+                ext_px_stats = None
+                if pathsx:
+                    zx2 = _lib.SnkDevPathsx()
+                    rc = e.lib.snk_dev_paths_zip(e._ctx, C.byref(xp), C.byref(h), C.byref(zx2), e._stream(), err, 512)
+                    if rc:
+                        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+                    ext_px_stats = _pathsx_stats(zx2)
+                    if download:
+                        ext_px_arrays = (self._dl(zx2.index, int(zx2.n_index) * 8, np.int64, (int(zx2.n_index),)),
+                                         self._dl(zx2.data, int(zx2.n_bytes), np.uint8, (int(zx2.n_bytes),)))
         finally:
             e.lib.snk_hbv_free(C.byref(h))
         n, tot = int(out.n_reads), int(out.n_edges_total)
@@ -241,6 +267,10 @@ class Result:
                 info["pathsx_stats"], info["pathsx_dev"] = px_stats, zx     # (zx: device memory of the context, for Engine.unzip_paths)
             if eb_stats is not None:
                 info["ebcx_stats"] = eb_stats
+            if ext_stats is not None:
+                info["extend_stats"] = ext_stats
+                if ext_px_stats is not None:
+                    info["extended_pathsx_stats"] = ext_px_stats
             return None, None, None, info
         off = self._dl(out.offset, n * 4, np.int32, (n,))
         ne = self._dl(out.n_edges, n * 4, np.uint32, (n,))
@@ -255,6 +285,10 @@ class Result:
             info["pathsx"], info["pathsx_stats"] = px_arrays, px_stats
         if eb_stats is not None:
             info["ebcx"], info["ebcx_stats"] = eb_arrays, eb_stats
+        if ext_stats is not None:
+            info["extended"], info["extend_stats"] = ext_arrays, ext_stats
+            if ext_px_stats is not None:
+                info["extended_pathsx"], info["extended_pathsx_stats"] = ext_px_arrays, ext_px_stats
         if unitig_bcs and out.unitig_bc_off:
             nb = int(out.n_unitig_bcs)
             info["unitig_bcs"] = (self._dl(out.unitig_bc_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,)),
@@ -285,6 +319,12 @@ class Result:
 def _ebcx_stats(eb: "_lib.SnkDevEbcx") -> dict:
     return dict(n_hbv_edges=int(eb.n_hbv_edges), n_ebc=int(eb.n_ebc), n_keys=int(eb.n_keys), n_empty_edges=int(eb.n_empty_edges), max_list=int(eb.max_list),
                 bc_sorted=int(eb.bc_sorted), general_sort=int(eb.general_sort), key_bits=int(eb.key_bits), ms=float(eb.ms))
+
+
+def _extend_stats(x: "_lib.SnkDevExtend") -> dict:
+    return dict(n_reads=int(x.paths.n_reads), n_edges_total=int(x.paths.n_edges_total), n_back_extended=int(x.n_back_extended),
+                n_cut_to_first=int(x.n_cut_to_first), n_quality_extended=int(x.n_quality_extended), n_ambiguous=int(x.n_ambiguous),
+                n_too_many=int(x.n_too_many), n_exact_extended=int(x.n_exact_extended), n_enumerated=int(x.n_enumerated), ms=float(x.ms))
 
 
 def _pathsx_stats(zx: "_lib.SnkDevPathsx") -> dict:
@@ -453,6 +493,43 @@ class Engine:
             if a.size:
                 self._download(ptr, a.ctypes.data, a.nbytes)
         return off, ne, edges, float(out.path_ms)
+
+    # ---- path extension (StageExtension) over device-resident reads, unitigs and paths
+    def extend_paths(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, rows: torch.Tensor, read_len: int,
+                     quals: torch.Tensor, lens: torch.Tensor | None, offset: torch.Tensor, n_edges: torch.Tensor, edges: torch.Tensor,
+                     start: torch.Tensor | None = None, back: bool = False, download: bool = True):
+        """snk_dev_extend_paths -- ExtendPathsNew (10X/Extend.cc:14-177) -- over tensors on this engine's device: the unitigs of the graph h
+        (graphio.hbv_handle: unitig_off i64[U + 1], unitig_bases u8[], in the order h numbers them), the reads (packed rows i32[n, words],
+        quals u8[n, stride], lens i16[n] or None) and their paths (offset i32[n], n_edges i32[n] read as u32, edges i32[sum], start i64[n + 1]
+        or None: the paths follow each other).  back: SNK_EXT_BACK.  -> (offset i32[n], n_edges u32[n], edges i32[sum], stats) on the host;
+        download=False: (SnkDevExtend, stats), device memory of the context, valid until its next top-level call."""
+        n = int(n_edges.shape[0])
+        if start is None:
+            start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
+            start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
+        r = _lib.SnkDevReads()
+        r.n_reads, r.rows, r.row_words, r.read_len = int(rows.shape[0]), rows.data_ptr(), (int(rows.shape[1]) if rows.dim() > 1 else 0), int(read_len)
+        r.quals, r.qstride = (quals.data_ptr(), int(quals.shape[1])) if quals is not None else (None, 0)
+        if lens is not None:
+            r.lens = lens.data_ptr()
+        p = _lib.SnkDevPaths()
+        p.n_reads, p.n_edges_total = n, int(edges.shape[0])
+        p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
+        x = _lib.SnkDevExtend()
+        err = C.create_string_buffer(512)
+        rc = self.lib.snk_dev_extend_paths(self._ctx, int(K), C.byref(r), int(unitig_off.shape[0]) - 1, unitig_off.data_ptr(), unitig_bases.data_ptr(),
+                                           C.byref(h), C.byref(p), _lib.EXT_BACK if back else 0, C.byref(x), self._stream(), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        stats = _extend_stats(x)
+        if not download:
+            return x, stats
+        m, tot = int(x.paths.n_reads), int(x.paths.n_edges_total)
+        off, ne, ed = np.empty(m, np.int32), np.empty(m, np.uint32), np.empty(tot, np.int32)
+        for a, ptr in ((off, x.paths.offset), (ne, x.paths.n_edges), (ed, x.paths.edges)):
+            if a.size:
+                self._download(ptr, a.ctypes.data, a.nbytes)
+        return off, ne, ed, stats
 
     # ---- synthetic reads straight into HBM
     def synth(self, sp: _lib.SnkSynthParams, first: int = 0, n: int | None = None, qstride: int | None = None):

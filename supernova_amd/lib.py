@@ -108,6 +108,15 @@ class SnkDevPathsx(C.Structure):
                 ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 6)]
 
 
+class SnkDevExtend(C.Structure):
+    _fields_ = [("paths", SnkDevPaths), ("n_back_extended", C.c_uint64), ("n_cut_to_first", C.c_uint64), ("n_quality_extended", C.c_uint64),
+                ("n_ambiguous", C.c_uint64), ("n_too_many", C.c_uint64), ("n_exact_extended", C.c_uint64), ("ms", C.c_float),
+                ("reserved0", C.c_uint32), ("n_enumerated", C.c_uint64), ("reserved", C.c_uint64 * 5)]
+
+
+EXT_BACK = 1                     # SNK_EXT_BACK
+
+
 class SnkFasthBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("first_pair", C.c_uint64), ("file", C.c_uint32), ("max_len", C.c_uint32),
                 ("ascii", C.c_void_p), ("quals", C.c_void_p), ("lens", C.c_void_p), ("bc_fields", C.c_void_p),
@@ -272,6 +281,7 @@ def _declare(lib: C.CDLL) -> None:
         "snk_read_ebcx": (C.c_int, [cp, P(u64), P(P(u64)), P(P(i32)), cp, sz]),
         "snk_dev_paths_zip": (C.c_int, [vp, P(SnkDevPaths), P(SnkHbv), P(SnkDevPathsx), vp, cp, sz]),
         "snk_dev_paths_unzip": (C.c_int, [vp, P(SnkDevPathsx), P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
+        "snk_dev_extend_paths": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevExtend), vp, cp, sz]),
         "snk_write_pathsx": (C.c_int, [cp, u64, vp, u64, vp, u64, cp, sz]),
         "snk_read_pathsx": (C.c_int, [cp, P(u64), P(u64), P(P(C.c_int64)), P(u64), P(P(C.c_uint8)), cp, sz]),
         "snk_write_hbx": (C.c_int, [cp, u32, u64, vp, vp, P(SnkHbv), cp, sz]),
