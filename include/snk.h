@@ -454,6 +454,12 @@ int snk_hbv_from_unitigs(uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_
  * flooded (one thread each: those of at most hbv_big nodes) and those that host threads flooded (all of them after 0 and 2).  After a
  * call that failed or had no unitigs: 0 and no components. */
 uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components, uint64_t* host_components);
+/* What the bucket-local graph stage did in the context's last count-and-graph call (snk_dev_count_graph, the streamed and the sharded
+ * forms): returns the attempts of its fragment pass -- 1, or 2 when the circles closed inside single chunks needed more fragment slots than
+ * the pool held (bl_pool + F/256 for F open paths) and the pass ran again with the exact number -- or 0 when the stage did not run
+ * (global_graph, SNK_F_NO_GRAPH, an empty table, a failed call).  *in_chunk_circles: those circles; *big_chunks: the chunks that went to
+ * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
+uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
  * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has

@@ -419,6 +419,11 @@ extern "C" uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_
     if (host_components) *host_components = ctx ? ctx->last_hbv_host_components : 0;
     return ctx ? ctx->last_hbv_flood : 0u;
 }
+extern "C" uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks) {
+    if (in_chunk_circles) *in_chunk_circles = ctx ? ctx->last_bl_circles : 0;
+    if (big_chunks) *big_chunks = ctx ? ctx->last_bl_big_chunks : 0u;
+    return ctx ? ctx->last_bl_attempts : 0u;
+}
 extern "C" uint32_t snk_ctx_last_count_limit(const snk_ctx* ctx) { return ctx ? ctx->last_count_limit : 0u; }
 extern "C" int snk_ctx_reserve(snk_ctx* ctx, uint64_t bytes, char* err, size_t errcap) {
     if (!ctx) return snk_fail(SNK_E_ARG, err, errcap, "snk_ctx_reserve: NULL context");

@@ -70,7 +70,9 @@ struct snk_ctx {
     uint32_t last_partition_passes = 1;                // bucket-range passes of the last resident call (snk_ctx_last_partition_passes)
     uint32_t last_hbv_flood = 0;                       // which id flood the last snk_dev_hbv ran: 0 host, 1 device, 2 device gave up and the host redid it (snk_ctx_last_hbv_flood)
     uint64_t last_hbv_dev_components = 0, last_hbv_host_components = 0;   // ... and the components flooded by device threads / by host threads
-    std::vector<unsigned long long> h_region_off;      // host copy of the count regions' dense offsets (source of an async upload)
+    uint32_t last_bl_attempts = 0, last_bl_big_chunks = 0;   // the bucket-local graph stage of the last count-and-graph call: fragment-pass attempts (0: it did not run), big chunks launched
+    uint64_t last_bl_circles = 0;                             // ... and the circles it closed inside one chunk (snk_ctx_last_local_graph)
+    std::vector<unsigned long long> h_region_off;     // host copy of the count regions' dense offsets (source of an async upload)
     snk_opts opts;              // what the host pinned (snk_ctx_set_tuning / snk_ctx_set_option / SNK_TUNING at creation); all clear = the library's own choices
     void* shard = nullptr;      // snk_shard_state (snk_dist.hip)
     void* host_io = nullptr;    // pinned staging + device input buffers of the host-pointer entry point (snk_host.hip)

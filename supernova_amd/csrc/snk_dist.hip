@@ -39,6 +39,7 @@ int snk_shard_begin(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, 
     S->params = *p;
     S->rank = rank; S->world = world; S->NB_total = NB_total; S->NBl = NB_total / world;
     S->circ_all = nullptr; S->join_circles = 0;
+    ctx->last_bl_attempts = ctx->last_bl_big_chunks = 0; ctx->last_bl_circles = 0;
     const uint16_t* good_len = (const uint16_t*)in->good_len;
     int rc;
     const bool fused = in->n_reads && snk_fused_trim_ok(ctx, in);      // the trim inside the partition kernel (snk_msp.hip)
@@ -86,6 +87,7 @@ int snk_shard_job_open(snk_ctx* ctx, const snk_params* p, uint32_t rank, uint32_
     S->params = *p;
     S->rank = rank; S->world = world; S->NB_total = NB_total; S->NBl = NB_total / world;
     S->circ_all = nullptr; S->join_circles = 0;
+    ctx->last_bl_attempts = ctx->last_bl_big_chunks = 0; ctx->last_bl_circles = 0;
     S->job_open = false; S->job_read_len = read_len; S->job_has_bc = has_bc; S->job_reads_ub = reads_ub; S->job_total_reads = total_reads;
     void* q;
     int rc;

@@ -1057,6 +1057,7 @@ static int bl_fragments_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, cons
     uint64_t xf_cap = pool0 ? pool0 + h_F / 256 : 0, xb_cap = xf_cap * (K + 63);
     unsigned long long h_x[2] = {0, 0};
     for (int attempt = 0; attempt < 2; ++attempt) {
+        ctx->last_bl_attempts = (uint32_t)attempt + 1;      // (snk_ctx_last_local_graph)
         G_ALLOC(out->nk, uint32_t, (uint64_t)h_F + xf_cap + 1);
         G_ALLOC(out->hl_self, unsigned long long, 2ull * (h_F + xf_cap) + 2);
         G_ALLOC(out->hl_nb, unsigned long long, 2ull * (h_F + xf_cap) + 2);
@@ -1088,6 +1089,8 @@ static int bl_fragments_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, cons
     out->n_frags = h_F + h_x[0];
     out->total_bases = h_B + h_x[1];
     out->n_local_circles = (uint32_t)h_x[0];
+    ctx->last_bl_circles = h_x[0];
+    ctx->last_bl_big_chunks = h_nbig;
     return SNK_OK;
 }
 

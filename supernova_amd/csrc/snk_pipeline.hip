@@ -80,6 +80,8 @@ static int graph_tail(snk_ctx* ctx, hipStream_t st, const snk_params* p, uint32_
 
     // ---- prune + unitigs
     snk_graph_out go;
+    ctx->last_bl_attempts = ctx->last_bl_big_chunks = 0;       // (snk_ctx_last_local_graph: the bucket-local stage writes them when it runs)
+    ctx->last_bl_circles = 0;
     if (local_graph) {
         snk_u128* keys_final = nullptr;
         rc = snk_local_graph(ctx, st, K, &tab, p->min_freq > 1 ? 1u : 0u, !(p->flags & SNK_F_NO_GRAPH),

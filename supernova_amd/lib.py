@@ -306,6 +306,7 @@ def _declare(lib: C.CDLL) -> None:
         "snk_ctx_last_partition_passes": (u32, [vp]),
         "snk_ctx_last_count_limit": (u32, [vp]),
         "snk_ctx_last_hbv_flood": (u32, [vp, P(u64), P(u64)]),
+        "snk_ctx_last_local_graph": (u32, [vp, P(u64), P(u32)]),
         "snk_fasth_open": (C.c_int, [P(cp), u32, u32, u32, u32, u32, P(vp), cp, sz]),
         "snk_fasth_next": (C.c_int, [vp, P(SnkFasthBatch), cp, sz]),
         "snk_fasth_release": (None, [vp, P(SnkFasthBatch)]),

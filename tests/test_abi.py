@@ -28,6 +28,15 @@ def test_last_hbv_flood_without_a_context(snk):
     assert snk.snk_ctx_last_hbv_flood(None, None, None) == 0
 
 
+def test_last_local_graph_without_a_context(snk):
+    """snk_ctx_last_local_graph (fragment-pass attempts, in-chunk circles and big chunks of the last count-and-graph call) answers 0
+    everywhere for a NULL context and takes NULL for either counter; with a context it is tests/test_gpu_handreads.py's witness of the
+    circle pool's re-run."""
+    circles, big = C.c_uint64(7), C.c_uint32(7)
+    assert snk.snk_ctx_last_local_graph(None, C.byref(circles), C.byref(big)) == 0 and (circles.value, big.value) == (0, 0)
+    assert snk.snk_ctx_last_local_graph(None, None, None) == 0
+
+
 def test_no_cpu_fallback(snk):
     import torch
     if torch.cuda.is_available():
