@@ -461,7 +461,7 @@ uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components,
  * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
 uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -681,6 +681,91 @@ typedef struct snk_dev_extend {
 #define SNK_EXT_BACK 1u
 int snk_dev_extend_paths(snk_ctx* ctx, uint32_t K, const snk_dev_reads* in, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
                          const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags, snk_dev_extend* out, void* stream, char* err, size_t errcap);
+
+/* ---- gap patches into the graph: StageInsertPatch ---------------------------------------------------------------------
+ * StageInsertPatch, lib/assembly/src/10X/runstages/RunStages.cc:176-230 (10X/DF.cc:656): the graph is rebuilt from its own edges, the
+ * junction (K+1)-mers and the closure sequences that StageFindPatch found (BuildAll, paths/long/large/GapToyTools4.cc:187-214;
+ * readsToHBV_Sleek, kmers/BigKPather.cc:1528-1647: every k-mer, no frequency, barcode or quality rule, no prune), every old edge is
+ * pathed over the new graph (Pather_sleek, :594-630 -> to3, left3, RunStages.cc:207-214) and every read path moved onto it
+ * (TranslatePaths, GapToyTools4.cc:220-266).  The result is the graph StageExtension (snk_dev_extend_paths) and the second paths index
+ * work on.  The graph itself is built by snk_dev_count_graph and snk_dev_hbv; the calls here stand around them:
+ *
+ *   snk_patch_plan_sizes   host only: the rows snk_dev_patch_pieces will write.
+ *   snk_dev_patch_pieces   the sequences as rows for the count stage (row_words 16, read_len 256, lens = good_len = the piece's length, no
+ *                          quality rows, no barcodes): the old unitigs (an edge and its reverse complement hold the same k-mers), one
+ *                          (K+1)-mer per pair e1 in To(v), e2 in From(v) -- the last K bases of e1 and base K-1 of e2 --, the closures.  A
+ *                          sequence of more than K bases becomes pieces of at most 256 bases, consecutive ones overlapping by K: each of
+ *                          its (K+1)-mers lies in one piece and every piece has K+1 bases at least.  A sequence of fewer than K bases is
+ *                          skipped.  One of exactly K bases has no piece; its canonical k-mer is listed in d_lonely (ascending, distinct,
+ *                          16 bytes each as snk_dev_result.keys).
+ *   snk_dev_count_graph    on the rows with min_freq = 1, min_bc = 0, bc = NULL, flags 0.
+ *   snk_dev_patch_merge    a listed k-mer that the new table does not hold is a one-k-mer unitig (an isolated old edge of K bases, a
+ *                          closure of K bases that is new): merged into the count result's unitigs in their order (by first K bases).
+ *                          Without such a k-mer the result IS the count result's arrays.
+ *   snk_dev_hbv            on those unitigs: the new edge numbering is the library's own.
+ *   snk_dev_patch_paths    to3 / left3 per OLD edge and the translated paths.  TranslatePaths per read: an empty path stays empty;
+ *                          start = offset + left3[p[0]]; to3[p[0]] empty: cleared; start < Bases(to3[p[0]][0]): that edge at start (a
+ *                          negative start lands here); else q = OverlapAppend over the to3[p[j]] up to the first empty one (the LONGEST
+ *                          suffix / prefix overlap is not repeated, Vec.h:604-619), and while start >= Bases(q[trim]) start -= Kmers(q[trim]),
+ *                          ++trim: q[trim] at start, or cleared when trim runs off q.  A translated path has at most ONE edge.
+ *
+ * MEMORY.  snk_dev_count_graph is a top-level call: at its start everything the context handed out before is free again.  So the rows, the
+ * lengths and the k-mer list are written into buffers the CALLER owns, and whatever a later step reads -- the old unitig arrays, the
+ * closures, the paths -- must by then live in caller-owned memory too (a copy of the earlier count result's unitigs, not the result).
+ * The results of snk_dev_patch_merge and snk_dev_patch_paths are context memory, valid until the context's next top-level call; they,
+ * the count result and the caller's arrays stay valid and unchanged across the calls here.
+ *
+ * Arguments.  unitig_off / closure_off are HOST arrays (u64[n + 1], from 0): the sizes come from them without a device round trip;
+ * d_unitig_bases / d_closure_bases the base codes on the device.  h: HOST, the graph of the old unitigs (bvcomp_order maps its unitig
+ * numbering to the arrays, NULL = they are in BVComp order; the From / To lists are those of the function snk_write_hbv uses).
+ * piece_capacity / lonely_capacity: what d_rows (u32[16 x pieces]), d_lens (u16[pieces]) and d_lonely hold; less than the plan: SNK_E_ARG.
+ * paths: on the OLD graph, offset as int32.  out->paths.offset is int32 (snk_dev_paths_zip does the int16 wrap, as pathsX.append does).
+ * SNK_E_ARG: a closure base code above 3 (pieces); an edge id outside the old graph, start / n_edges that do not add up to n_edges_total,
+ * an old edge whose k-mers are not on the new graph (paths).  The result rule and the call frame of the stages after the graph apply:
+ * after any non-zero return *out is all zero.  Results are bit-identical from call to call and depend on no tuning option. */
+typedef struct snk_patch_plan {
+    uint64_t n_pieces;            /* rows: n_unitig_pieces + n_junctions + n_closure_pieces, in this order */
+    uint64_t n_unitig_pieces, n_junctions, n_closure_pieces;
+    uint64_t n_lonely_max;        /* sequences of exactly K bases: the most k-mers d_lonely can get */
+    uint64_t reserved[3];
+} snk_patch_plan;
+int snk_patch_plan_sizes(uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const snk_hbv* h, uint64_t n_closures, const uint64_t* closure_off,
+                         snk_patch_plan* out, char* err, size_t errcap);
+typedef struct snk_dev_pieces {
+    uint64_t n_pieces, n_lonely;
+    float ms;                     /* HIP events around the call's device work */
+    uint32_t reserved0;
+    uint64_t reserved[5];
+} snk_dev_pieces;
+int snk_dev_patch_pieces(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const uint64_t* unitig_off, const void* d_unitig_bases, const snk_hbv* h, uint64_t n_closures,
+                         const uint64_t* closure_off, const void* d_closure_bases, uint64_t piece_capacity, void* d_rows, void* d_lens, uint64_t lonely_capacity,
+                         void* d_lonely, snk_dev_pieces* out, void* stream, char* err, size_t errcap);
+typedef struct snk_dev_patch_unitigs {
+    uint64_t n_unitigs, unitig_total_bases;
+    const void* unitig_off;       /* u64[n_unitigs + 1] */
+    const void* unitig_bases;     /* as snk_dev_result's: canonical, ordered by their first K bases */
+    uint64_t n_added;             /* one-k-mer unitigs merged in */
+    float ms;
+    uint32_t reserved0;
+    uint64_t reserved[4];
+} snk_dev_patch_unitigs;
+int snk_dev_patch_merge(snk_ctx* ctx, uint32_t K, const snk_dev_result* res, const void* d_lonely, uint64_t n_lonely, snk_dev_patch_unitigs* out, void* stream,
+                        char* err, size_t errcap);
+typedef struct snk_dev_patched {
+    snk_dev_paths paths;          /* translated: n_edges is 0 or 1; path_ms = the translation */
+    uint64_t n_old_edges, n_to3;
+    const void* to3_off;          /* u64[n_old_edges + 1] */
+    const void* to3;              /* i32[n_to3] new edge ids */
+    const void* left3;            /* i32[n_old_edges] */
+    uint64_t n_first;             /* reads kept on the first new edge of their first old edge */
+    uint64_t n_later;             /* reads moved to a later edge of q */
+    uint64_t n_cleared;           /* reads whose path was cleared */
+    float ms, map_ms;             /* HIP events: the whole call; the graph tables, the look-ups and to3 / left3 */
+    uint64_t reserved[4];
+} snk_dev_patched;
+int snk_dev_patch_paths(snk_ctx* ctx, uint32_t K, uint64_t n_old_unitigs, const void* d_old_unitig_off, const void* d_old_unitig_bases, const snk_hbv* h_old,
+                        uint64_t n_new_unitigs, const void* d_new_unitig_off, const void* d_new_unitig_bases, const snk_hbv* h_new, const snk_dev_paths* paths,
+                        snk_dev_patched* out, void* stream, char* err, size_t errcap);
 
 /* ---- the edge -> barcode lists: a.ebcx ------------------------------------------------------------------------------
  * computeEdgeToBarcodeX, lib/assembly/src/10X/PathsIndex.cc:297-358 (StageEBC, 10X/runstages/RunStages.cc:31-38): per HBV edge the

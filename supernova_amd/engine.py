@@ -316,6 +316,59 @@ class Result:
         return us
 
 
+class _DevBytes:
+    """Device memory of the library seen by torch without a copy (__cuda_array_interface__ over the raw pointer)."""
+
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+
+
+class PatchResult:
+    """What Engine.insert_patch leaves: the patched graph and the read paths on it, in tensors and arrays this object owns (they outlive
+    the engine's later calls).  h: the lib.SnkHbv of the new unitigs (bvcomp_order maps its unitig numbering to unitig_off /
+    unitig_bases), freed by close(); unitig_off i64[U + 1], unitig_bases u8[], offset / n_edges / start / edges: tensors on the device
+    as Engine.extend_paths and Engine.zip_paths take them; inv, to3_off, to3, left3: numpy; stats: sizes, counters and times."""
+
+    def __init__(self, engine: "Engine", K: int, h: "_lib.SnkHbv"):
+        self._e, self.K, self.h = engine, K, h
+
+    def close(self):
+        if self.h is not None:
+            self._e.lib.snk_hbv_free(C.byref(self.h))
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def unitigs_bvcomp(self):
+        """-> (off u64[U + 1], bases u8[]) on the host in BVComp order: the numbering of h, what snk_write_hbv / snk_write_hbx take"""
+        off = self.unitig_off.cpu().numpy().view(np.uint64)
+        bases = self.unitig_bases.cpu().numpy()
+        U = len(off) - 1
+        order = np.ctypeslib.as_array(self.h.bvcomp_order, shape=(U,)).astype(np.int64) if U and self.h.bvcomp_order else np.arange(U)
+        lens = np.diff(off.astype(np.int64))[order]
+        noff = np.zeros(U + 1, np.uint64)
+        noff[1:] = np.cumsum(lens, dtype=np.uint64)
+        idx = np.repeat(off[:-1].astype(np.int64)[order] - noff[:-1].astype(np.int64), lens) + np.arange(int(noff[-1]))
+        return noff, np.ascontiguousarray(bases[idx])
+
+    def write(self, path_hbv, path_inv=None, path_hbx=None):
+        """a.hbv (+ a.inv, a.hbx) of the patched graph, as DF writes them"""
+        off, bases = self.unitigs_bvcomp()
+        err = C.create_string_buffer(512)
+        h = _lib.SnkHbv.from_buffer_copy(self.h)
+        h.bvcomp_order = None
+        rc = self._e.lib.snk_write_hbv(str(path_hbv).encode(), str(path_inv).encode() if path_inv else None, self.K, len(off) - 1, off.ctypes.data, bases.ctypes.data,
+                                       C.byref(h), err, 512)
+        if not rc and path_hbx:
+            rc = self._e.lib.snk_write_hbx(str(path_hbx).encode(), self.K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+
+
 def _ebcx_stats(eb: "_lib.SnkDevEbcx") -> dict:
     return dict(n_hbv_edges=int(eb.n_hbv_edges), n_ebc=int(eb.n_ebc), n_keys=int(eb.n_keys), n_empty_edges=int(eb.n_empty_edges), max_list=int(eb.max_list),
                 bc_sorted=int(eb.bc_sorted), general_sort=int(eb.general_sort), key_bits=int(eb.key_bits), ms=float(eb.ms))
@@ -530,6 +583,98 @@ class Engine:
             if a.size:
                 self._download(ptr, a.ctypes.data, a.nbytes)
         return off, ne, ed, stats
+
+    # ---- gap patches into the graph (StageInsertPatch)
+    def insert_patch(self, graph, closures, paths) -> "PatchResult":
+        """StageInsertPatch (10X/runstages/RunStages.cc:176-230) on this engine's device: pieces -> count -> merge -> hbv -> to3 / left3 ->
+        translate (snk_dev_patch_pieces, snk_dev_count_graph with min_freq 1 and no barcode rule, snk_dev_patch_merge, snk_dev_hbv,
+        snk_dev_patch_paths).
+          graph     (K, h, unitig_off, unitig_bases): h a lib.SnkHbv of the OLD unitigs (of snk_dev_hbv, or graphio.hbv_handle), unitig_off
+                    u64 / i64[U + 1] (numpy or tensor), unitig_bases u8[] (tensor on the device, or numpy), in the order h's bvcomp_order names
+          closures  (off u64[n + 1] numpy, base codes u8[]: numpy or tensor on the device)
+          paths     (offset i32[n], n_edges i32[n] read as u32, edges i32[sum], start i64[n + 1] or None) tensors on the device, on the old graph
+        The count in the middle is a top-level call that frees everything the context handed out before, so the engine first copies what
+        it was given into tensors of its own and works on those; the caller's tensors are only read.  -> PatchResult: everything in
+        tensors / arrays the result owns, ready for extend_paths, zip_paths and the writers."""
+        K, h_old, uoff_in, ub_in = graph
+        dev = torch.device("cuda", self.device)
+        own = lambda a, dt: (a.detach().to(dev, dt, copy=True) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)).contiguous()
+        uoff_h = np.ascontiguousarray(uoff_in.detach().cpu().numpy() if isinstance(uoff_in, torch.Tensor) else uoff_in).astype(np.uint64)
+        U_old = len(uoff_h) - 1
+        ub_old = own(ub_in, torch.uint8)
+        uoff_old = torch.from_numpy(uoff_h.view(np.int64)).to(dev)
+        coff_h = np.ascontiguousarray(closures[0]).astype(np.uint64)
+        n_cl = len(coff_h) - 1
+        cb = own(closures[1], torch.uint8)
+        p_off, p_n, p_edges = own(paths[0], torch.int32), own(paths[1], torch.int32), own(paths[2], torch.int32)
+        n = int(p_n.shape[0])
+        if len(paths) > 3 and paths[3] is not None:
+            p_start = own(paths[3], torch.int64)
+        else:
+            p_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            p_start[1:] = torch.cumsum(p_n.to(torch.int64) & 0xFFFFFFFF, 0)
+        err = C.create_string_buffer(512)
+
+        def call(fn, *args):
+            rc = fn(*args, self._stream(), err, 512)
+            if rc:
+                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+
+        # ---- pieces, into tensors of the engine
+        plan = _lib.SnkPatchPlan()
+        rc = self.lib.snk_patch_plan_sizes(int(K), U_old, uoff_h.ctypes.data, C.byref(h_old), n_cl, coff_h.ctypes.data, C.byref(plan), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        n_pieces, n_lmax = int(plan.n_pieces), int(plan.n_lonely_max)
+        rows = torch.empty((n_pieces, 16), dtype=torch.int32, device=dev)
+        lens = torch.empty((n_pieces,), dtype=torch.int16, device=dev)
+        lonely = torch.empty((max(n_lmax, 1), 2), dtype=torch.int64, device=dev)
+        pc = _lib.SnkDevPieces()
+        call(self.lib.snk_dev_patch_pieces, self._ctx, int(K), U_old, uoff_h.ctypes.data, ub_old.data_ptr(), C.byref(h_old), n_cl, coff_h.ctypes.data, cb.data_ptr(),
+             n_pieces, rows.data_ptr(), lens.data_ptr(), n_lmax, lonely.data_ptr(), C.byref(pc))
+        # ---- the graph: the count stage on the pieces, the K-base sequences it leaves out, the ids
+        if n_pieces:
+            res = self.count_graph(rows, 256, lens=lens, good_len=lens, params=Params(K=int(K), min_freq=1, min_bc=0))
+            raw, count_ms = res.raw, res.phase_ms["total"]
+        else:
+            raw, count_ms = _lib.SnkDevResult(), 0.0
+        mu = _lib.SnkDevPatchUnitigs()
+        call(self.lib.snk_dev_patch_merge, self._ctx, int(K), C.byref(raw), lonely.data_ptr(), int(pc.n_lonely), C.byref(mu))
+        U_new, tot_new = int(mu.n_unitigs), int(mu.unitig_total_bases)
+        h_new = _lib.SnkHbv()
+        hbv_ms = C.c_float(0)
+        call(self.lib.snk_dev_hbv, self._ctx, int(K), U_new, mu.unitig_off, mu.unitig_bases, C.byref(h_new), C.byref(hbv_ms))
+        try:
+            ip = _lib.SnkDevPaths()
+            ip.n_reads, ip.n_edges_total = n, int(p_edges.shape[0])
+            ip.offset, ip.n_edges, ip.start, ip.edges = p_off.data_ptr(), p_n.data_ptr(), p_start.data_ptr(), p_edges.data_ptr()
+            px = _lib.SnkDevPatched()
+            call(self.lib.snk_dev_patch_paths, self._ctx, int(K), U_old, uoff_old.data_ptr(), ub_old.data_ptr(), C.byref(h_old), U_new, mu.unitig_off, mu.unitig_bases,
+                 C.byref(h_new), C.byref(ip), C.byref(px))
+            # ---- everything into memory the result owns
+            def take(ptr, count, dt):
+                nbytes = count * torch.empty((), dtype=dt).element_size()
+                return torch.as_tensor(_DevBytes(ptr, nbytes), device=dev).clone().view(dt) if count else torch.empty((0,), dtype=dt, device=dev)
+            E_old, n_to3, tot = int(px.n_old_edges), int(px.n_to3), int(px.paths.n_edges_total)
+            out = PatchResult(self, int(K), h_new)
+            out.unitig_off, out.unitig_bases = take(mu.unitig_off, U_new + 1, torch.int64), take(mu.unitig_bases, tot_new, torch.uint8)
+            out.offset, out.n_edges, out.start, out.edges = take(px.paths.offset, n, torch.int32), take(px.paths.n_edges, n, torch.int32), \
+                take(px.paths.start, n + 1, torch.int64), take(px.paths.edges, tot, torch.int32)
+            out.to3_off = take(px.to3_off, E_old + 1, torch.int64).cpu().numpy().view(np.uint64)
+            out.to3, out.left3 = take(px.to3, n_to3, torch.int32).cpu().numpy(), take(px.left3, E_old, torch.int32).cpu().numpy()
+            inv = np.zeros(max(int(h_new.n_edges), 1), np.int32)
+            rc = self.lib.snk_hbv_involution(C.byref(h_new), U_new, inv.ctypes.data, err, 512)
+            if rc:
+                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+            out.inv = inv[:int(h_new.n_edges)]
+            out.stats = dict(n_pieces=n_pieces, n_unitig_pieces=int(plan.n_unitig_pieces), n_junctions=int(plan.n_junctions), n_closure_pieces=int(plan.n_closure_pieces),
+                             n_lonely=int(pc.n_lonely), n_added=int(mu.n_added), n_first=int(px.n_first), n_later=int(px.n_later), n_cleared=int(px.n_cleared),
+                             n_kmers=int(raw.n_kmers), pieces_ms=float(pc.ms), count_ms=float(count_ms), merge_ms=float(mu.ms), hbv_ms=float(hbv_ms.value),
+                             map_ms=float(px.map_ms), translate_ms=float(px.paths.path_ms))
+            return out
+        except BaseException:
+            self.lib.snk_hbv_free(C.byref(h_new))
+            raise
 
     # ---- synthetic reads straight into HBM
     def synth(self, sp: _lib.SnkSynthParams, first: int = 0, n: int | None = None, qstride: int | None = None):

@@ -117,6 +117,26 @@ class SnkDevExtend(C.Structure):
 EXT_BACK = 1                     # SNK_EXT_BACK
 
 
+class SnkPatchPlan(C.Structure):
+    _fields_ = [("n_pieces", C.c_uint64), ("n_unitig_pieces", C.c_uint64), ("n_junctions", C.c_uint64), ("n_closure_pieces", C.c_uint64),
+                ("n_lonely_max", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
+class SnkDevPieces(C.Structure):
+    _fields_ = [("n_pieces", C.c_uint64), ("n_lonely", C.c_uint64), ("ms", C.c_float), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 5)]
+
+
+class SnkDevPatchUnitigs(C.Structure):
+    _fields_ = [("n_unitigs", C.c_uint64), ("unitig_total_bases", C.c_uint64), ("unitig_off", C.c_void_p), ("unitig_bases", C.c_void_p),
+                ("n_added", C.c_uint64), ("ms", C.c_float), ("reserved0", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+
+class SnkDevPatched(C.Structure):
+    _fields_ = [("paths", SnkDevPaths), ("n_old_edges", C.c_uint64), ("n_to3", C.c_uint64), ("to3_off", C.c_void_p), ("to3", C.c_void_p),
+                ("left3", C.c_void_p), ("n_first", C.c_uint64), ("n_later", C.c_uint64), ("n_cleared", C.c_uint64), ("ms", C.c_float),
+                ("map_ms", C.c_float), ("reserved", C.c_uint64 * 4)]
+
+
 class SnkFasthBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("first_pair", C.c_uint64), ("file", C.c_uint32), ("max_len", C.c_uint32),
                 ("ascii", C.c_void_p), ("quals", C.c_void_p), ("lens", C.c_void_p), ("bc_fields", C.c_void_p),
@@ -282,6 +302,10 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_paths_zip": (C.c_int, [vp, P(SnkDevPaths), P(SnkHbv), P(SnkDevPathsx), vp, cp, sz]),
         "snk_dev_paths_unzip": (C.c_int, [vp, P(SnkDevPathsx), P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_extend_paths": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevExtend), vp, cp, sz]),
+        "snk_patch_plan_sizes": (C.c_int, [u32, u64, vp, P(SnkHbv), u64, vp, P(SnkPatchPlan), cp, sz]),
+        "snk_dev_patch_pieces": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), u64, vp, vp, u64, vp, vp, u64, vp, P(SnkDevPieces), vp, cp, sz]),
+        "snk_dev_patch_merge": (C.c_int, [vp, u32, P(SnkDevResult), vp, u64, P(SnkDevPatchUnitigs), vp, cp, sz]),
+        "snk_dev_patch_paths": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), P(SnkDevPatched), vp, cp, sz]),
         "snk_write_pathsx": (C.c_int, [cp, u64, vp, u64, vp, u64, cp, sz]),
         "snk_read_pathsx": (C.c_int, [cp, P(u64), P(u64), P(P(C.c_int64)), P(u64), P(P(C.c_uint8)), cp, sz]),
         "snk_write_hbx": (C.c_int, [cp, u32, u64, vp, vp, P(SnkHbv), cp, sz]),

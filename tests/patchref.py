@@ -1,0 +1,444 @@
+"""A plain Python restatement of the reference's gap-patch insertion -- StageInsertPatch (10X/runstages/RunStages.cc:176-230) -- its
+hand-made cases, and the fixtures under tests/golden/patch/ (what the reference's own functions made of the cases, renumbered by edge
+sequence onto the BVComp-ordered graph: see tests/golden/patch_driver.cc and make_patch_golden.py).
+
+  1 BuildAll (paths/long/large/GapToyTools4.cc:187-214)      allx = every HBV edge, the junction (K+1)-mers (last K bases of e1 + base
+      K-1 of e2 for e1 in To(v), e2 in From(v)), then the closures
+  2 readsToHBV_Sleek (kmers/BigKPather.cc:1528-1647)         the de Bruijn graph of every k-mer of allx -- no frequency, barcode or
+      quality rule, no prune; a sequence below K bases is skipped, one of exactly K bases enters its k-mer without a context -- and
+      Pather_sleek (:594-630): the first k-mer of a sequence is looked up as (edge, offset), then the walk steps to the out-edge, in
+      From order, whose first K-mer is the sequence's
+  3 to3 / left3 (RunStages.cc:207-214)                        per OLD edge the new edges of its path and its offset on the first
+  4 TranslatePaths (GapToyTools4.cc:220-266)                  per read at most ONE edge (see translate)
+
+The graph of step 2 is made the way the library makes it: allx chopped into pieces of at most 256 bases, consecutive pieces of a
+sequence overlapping by K, counted by the C oracle with min_freq 1 and no barcode rule; the K-base sequences whose k-mer no piece
+holds are added as one-k-mer unitigs; the unitigs go through the library's host graph builder in BVComp order.  That this equals the
+reference's graph -- chopping included -- is what tests/test_patch_host.py shows against the fixtures.
+"""
+from __future__ import annotations
+
+import tempfile
+import zlib
+from pathlib import Path
+from types import SimpleNamespace
+
+import numpy as np
+
+import a48xref
+import extref
+import handunitigs as hu
+
+PATCH = Path(__file__).resolve().parent / "golden" / "patch"
+PIECE = 256
+_CODE = hu._CODE
+COUNTERS = ("n_first", "n_later", "n_cleared")
+
+
+def codes(s: str) -> np.ndarray:
+    return _CODE[np.frombuffer(s.encode(), np.uint8)] if s else np.zeros(0, np.uint8)
+
+
+def text(c) -> str:
+    return np.frombuffer(b"ACGT", np.uint8)[np.asarray(c, np.uint8)].tobytes().decode()
+
+
+# ---- step 1 and the pieces
+
+def build_all(g: a48xref.Graph, edges: list[str], closures: list[str]) -> list[str]:
+    K = g.K
+    allx = list(edges)
+    for v in range(g.N):
+        for e1 in g.to_e[g.to_off[v]:g.to_off[v + 1]]:
+            for e2 in g.from_e[g.from_off[v]:g.from_off[v + 1]]:
+                allx.append(edges[e1][-K:] + edges[e2][K - 1])
+    return allx + list(closures)
+
+
+def piece_spans(L: int, K: int):
+    """the pieces of a sequence of L > K bases: (start, length), at most PIECE bases, consecutive ones overlapping by K"""
+    out, p = [], 0
+    while True:
+        n = min(PIECE, L - p)
+        out.append((p, n))
+        if p + n == L:
+            return out
+        p += PIECE - K
+
+
+def n_pieces(L: int, K: int) -> int:
+    return 0 if L <= K else (L - K + PIECE - K - 1) // (PIECE - K)
+
+
+def pieces(seqs: list[str], K: int):
+    """-> (codes u8[n, 256], lens u16[n], the K-base sequences)"""
+    rows, lens, lonely = [], [], []
+    for s in seqs:
+        if len(s) == K:
+            lonely.append(s)
+        for p, n in (piece_spans(len(s), K) if len(s) > K else ()):
+            r = np.zeros(PIECE, np.uint8)
+            r[:n] = codes(s[p:p + n])
+            rows.append(r)
+            lens.append(n)
+    return (np.stack(rows) if rows else np.zeros((0, PIECE), np.uint8)), np.asarray(lens, np.uint16), lonely
+
+
+def canon(s: str) -> str:
+    r = hu.rc(s)
+    return s if s <= r else r
+
+
+# ---- step 2: the graph
+
+def new_unitigs(allx: list[str], K: int) -> list[str]:
+    """the unitigs of the patched graph in BVComp order"""
+    import oracle_lib
+    rows, lens, lonely = pieces(allx, K)
+    us = []
+    if len(rows):
+        us = list(oracle_lib.OracleResult(rows, lens.astype(np.uint32), None, K=K, min_freq=1, min_bc=0, hbv=False).unitigs)
+    have = set()
+    for s in us:
+        for p in range(len(s) - K + 1):
+            have.add(canon(s[p:p + K]))
+    for s in sorted(set(canon(x) for x in lonely)):
+        if s not in have:
+            us.append(s)
+    return hu.bvcomp_sorted(us)
+
+
+def graph_files(unitigs: list[str], K: int):
+    """unitigs in BVComp order -> (a.hbv bytes, a.inv bytes) as the library's host writer makes them"""
+    from supernova_amd import graphio
+    off, bases = hu.to_arrays(unitigs)
+    with tempfile.TemporaryDirectory() as td:
+        graphio.write_hbv(Path(td) / "a.hbv", Path(td) / "a.inv", K, off, bases)
+        return (Path(td) / "a.hbv").read_bytes(), (Path(td) / "a.inv").read_bytes()
+
+
+def edge_strings(g: a48xref.Graph) -> list[str]:
+    return [text(b) for b in extref.edge_bases(g)]
+
+
+# ---- steps 2 (pathing) and 3
+
+def path_old_edges(old_edges: list[str], g3: a48xref.Graph, e3: list[str]):
+    """Pather_sleek over the old edges -> (to3: list of lists, left3)"""
+    K = g3.K
+    where = {}
+    for e, s in enumerate(e3):
+        for p in range(len(s) - K + 1):
+            where.setdefault(s[p:p + K], (e, p))
+    to3, left3 = [], []
+    for read in old_edges:
+        if len(read) < K:
+            to3.append([])
+            left3.append(0)
+            continue
+        e, offset = where[read[:K]]
+        path = [e]
+        read_rem, edge_rem = len(read), len(e3[e]) - offset
+        while read_rem > edge_rem:
+            read_rem = read_rem - edge_rem + K - 1
+            ro = len(read) - read_rem
+            v = g3.v_right[e]
+            for f in g3.from_e[g3.from_off[v]:g3.from_off[v + 1]]:
+                if e3[f][:K] == read[ro:ro + K]:
+                    e = int(f)
+                    break
+            else:
+                raise AssertionError("Pather_sleek: no out-edge carries the sequence")
+            path.append(e)
+            edge_rem = len(e3[e])
+        to3.append(path)
+        left3.append(offset)
+    return to3, np.asarray(left3, np.int32)
+
+
+# ---- step 4
+
+def overlap_append(q: list, v: list):
+    """Vec.h:604-619: the LONGEST suffix of q that is a prefix of v is not repeated"""
+    best = 0
+    for o in range(min(len(q), len(v)), 0, -1):
+        if q[len(q) - o:] == v[:o]:
+            best = o
+            break
+    q.extend(v[best:])
+
+
+def translate_paths(K, offset, n_edges, edges, to3, left3, len3):
+    """TranslatePaths -> (edge i32[n] or -1, offset i32[n], counters).  len3: Bases per new edge; Kmers = Bases - K + 1."""
+    n = len(n_edges)
+    out_e, out_o = np.full(n, -1, np.int32), np.zeros(n, np.int32)
+    cnt = dict.fromkeys(COUNTERS, 0)
+    at = 0
+    for r in range(n):
+        p = [int(x) for x in edges[at:at + int(n_edges[r])]]
+        at += int(n_edges[r])
+        if not p:
+            continue
+        e = p[0]
+        start = int(offset[r]) + int(left3[e])
+        if not to3[e]:
+            cnt["n_cleared"] += 1
+            continue
+        if start < len3[to3[e][0]]:
+            out_e[r], out_o[r] = to3[e][0], start
+            cnt["n_first"] += 1
+            continue
+        q = []
+        for x in p:
+            if not to3[x]:
+                break
+            overlap_append(q, to3[x])
+        trim = 0
+        while start >= len3[q[trim]]:
+            start -= len3[q[trim]] - K + 1
+            trim += 1
+            if trim == len(q):
+                break
+        if trim == len(q):
+            cnt["n_cleared"] += 1
+            continue
+        out_e[r], out_o[r] = q[trim], start
+        cnt["n_later"] += 1
+    return out_e, out_o, cnt
+
+
+def one_edge_paths(out_e, out_o):
+    """-> (offset, n_edges, edges) of the translated paths"""
+    has = out_e >= 0
+    return np.where(has, out_o, 0).astype(np.int32), has.astype(np.uint32), out_e[has].astype(np.int32)
+
+
+def insert_patch(K, a_hbv: bytes, closures: list[str], offset, n_edges, edges):
+    """All four steps -> namespace(unitigs, a_hbv, a_inv, g3, to3, left3, edge, offset, counters, pathsx)"""
+    g = a48xref.parse_hbv(a_hbv)
+    assert g.K == K
+    old = edge_strings(g)
+    us = new_unitigs(build_all(g, old, closures), K)
+    hbv3, inv3 = graph_files(us, K)
+    g3 = a48xref.parse_hbv(hbv3)
+    e3 = edge_strings(g3)
+    to3, left3 = path_old_edges(old, g3, e3)
+    len3 = np.asarray([len(s) for s in e3], np.int64)
+    out_e, out_o, cnt = translate_paths(K, offset, n_edges, edges, to3, left3, len3)
+    idx, data, _ = a48xref.zip_paths(*one_edge_paths(out_e, out_o), g3)
+    return SimpleNamespace(unitigs=us, a_hbv=hbv3, a_inv=inv3, g3=g3, to3=to3, left3=left3, edge=out_e, offset=out_o, counters=cnt,
+                           pathsx=a48xref.pathsx_bytes(idx, data, len(n_edges)))
+
+
+def flat(to3):
+    off = np.zeros(len(to3) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in to3], dtype=np.uint64)
+    return off, np.asarray([x for l in to3 for x in l], np.int32)
+
+
+# ---- the cases.  An old graph (a tests/handunitigs.py generator: random strings, never equal by chance at K >= 48), closures, and
+# paths placed by rule on every old edge (place_paths): every kind of offset on one-, two- and three-edge paths.
+
+def _two(g, la=37, lb=29):
+    K = g.K
+    return g.add(g.rand(K + la)), g.add(g.rand(K + lb))
+
+
+def _bridge(a, b, gap, K):
+    return a[-K:] + gap + b[:K]
+
+
+def _c_none(g):
+    hu._bubble(g)
+    hu._hairpin_flanks(g)
+    return []
+
+
+def _c_bridge(g):
+    a, b = _two(g)
+    hu._bubble(g)
+    return [_bridge(a, b, g.rand(11), g.K)]
+
+
+def _c_bridge_rc(g):
+    return [hu.rc(x) for x in _c_bridge(g)]
+
+
+def _c_mid_split(g):
+    K = g.K
+    a, b = g.add(g.rand(K + 90)), g.add(g.rand(K + 120))
+    c = g.add(g.rand(K + 30))
+    return [a[31:31 + K] + g.rand(7) + b[40:40 + K], c[-K:] + g.rand(3) + b[85:85 + K]]
+
+
+def _c_inside(g):
+    K = g.K
+    a, b = g.junction(), g.junction()
+    x = g.edge(a, 0, b, 0, 7)
+    g.edge(a, 0, b, 0, 7)
+    g.edge(g.junction(), 0, a, 0, 25)
+    y = g.edge(b, 0, g.junction(), 0, 23)
+    return [x[-(K + 9):] + y[K - 1:K + 12]]
+
+
+def _c_twice(g):
+    K = g.K
+    a, b = _two(g)
+    gap = g.rand(40)
+    full = a[-(K + 5):] + gap + b[:K + 6]
+    return [full, _bridge(a, b, gap, K), full, full[:K + 25], full[12:], hu.rc(full)]
+
+
+def _c_short(g):
+    K = g.K
+    a, b = _two(g)
+    return [g.rand(K - 1), a[3:3 + K], g.rand(K), hu.rc(b[5:5 + K]), g.rand(K + 1), g.pal(K), g.rand(K)]
+
+
+def _c_lonely_edge(g):
+    K = g.K
+    a, b = _two(g)
+    g.add(g.rand(K))
+    g.add(g.pal(K))
+    return [_bridge(a, b, g.rand(5), K)]
+
+
+def _c_palindrome(g):
+    K = g.K
+    a, b = _two(g)
+    return [a[-K:] + g.rand(6) + g.pal(K) + g.rand(9) + b[:K]]
+
+
+def _c_circle(g):
+    K = g.K
+    a = g.add(g.rand(K + 44))
+    g.ring(1, 37, 37)
+    g.ring(2)
+    return [_bridge(a, a, g.rand(8), K)]
+
+
+def _c_new_branch(g):
+    K = g.K
+    j = g.junction()
+    i1 = g.edge(g.junction(), 0, j, 0, 9)
+    o1 = g.edge(j, 0, g.junction(), 0, 12)
+    o2 = g.edge(j, 0, g.junction(), 0, 6)
+    free = [b for b in "ACGT" if b not in (o1[K - 1], o2[K - 1])]
+    return [i1[-K:] + free[0] + g.rand(K + 5), i1[-K:] + free[1] + g.rand(K + 2)]
+
+
+def _c_long_edge(g):
+    K = g.K
+    a, b = g.add(g.rand(3 * PIECE + 17)), g.add(g.rand(PIECE + K + 1))
+    p = PIECE - K                                # the second piece of a starts here: the closure's first k-mer is that piece's first
+    return [a[p:p + K] + g.rand(4) + b[:K], b[-K:] + g.rand(300) + a[2 * p:2 * p + K]]
+
+
+_MAKERS = {"none": _c_none, "bridge": _c_bridge, "bridge_rc": _c_bridge_rc, "mid_split": _c_mid_split, "inside": _c_inside, "twice": _c_twice,
+           "short": _c_short, "lonely_edge": _c_lonely_edge, "palindrome": _c_palindrome, "circle": _c_circle, "new_branch": _c_new_branch,
+           "negative": _c_mid_split, "long_edge": _c_long_edge}
+_SEED = {"bridge_rc": "bridge", "negative": "mid_split"}        # cases on the random strings of another case
+HAND = tuple(_MAKERS)
+KS = (48, 60)
+SYNTH = "synth_2k_err"
+ALL = tuple(f"{n}_k{K}" for n in HAND for K in KS) + (SYNTH,)
+
+
+def place_paths(name, g: a48xref.Graph, lens, negative_only=False):
+    """Paths by rule on every old edge -> (offset i32[n], n_edges u32[n], edges i32[]).  Per edge: one-edge paths at offsets -7, 0, 1, the
+    middle, the last k-mer, the last base and past the end; per two- and three-edge walk along the From lists the same with offsets up to
+    the sum of the walk's k-mers (so that `start` lands on every part of a split edge, and beyond all of them); the same edge twice
+    ([e, e]: what a read round a circle has); an empty path every 16 reads."""
+    K = g.K
+    rng = np.random.default_rng(zlib.crc32(f"paths/{name}/{K}".encode()))
+    out = []
+
+    def offs(walk):
+        L0 = int(lens[walk[0]])
+        span = sum(int(lens[e]) - K + 1 for e in walk)
+        o = {-7, -1, 0, 1, L0 // 2, L0 - K, L0 - K + 1, L0 - 1, L0, span - 1, span, span + K, span + 3 * K}
+        o |= {int(x) for x in rng.integers(-20, span + K, 6)}
+        return sorted(x for x in o if x < 0) if negative_only else sorted(o)
+
+    for e in range(g.E):
+        walks = [[e], [e, e]]
+        v = g.v_right[e]
+        for f in g.from_e[g.from_off[v]:g.from_off[v + 1]]:
+            walks.append([e, int(f)])
+            w = g.v_right[f]
+            for h in g.from_e[g.from_off[w]:g.from_off[w + 1]]:
+                walks.append([e, int(f), int(h)])
+        for w in walks:
+            for o in offs(w):
+                out.append((o, w))
+                if len(out) % 16 == 7:
+                    out.append((0, []))
+    offset = np.asarray([o for o, _ in out], np.int32)
+    n_edges = np.asarray([len(w) for _, w in out], np.uint32)
+    edges = np.asarray([x for _, w in out for x in w], np.int32)
+    return offset, n_edges, edges
+
+
+_made: dict = {}
+
+
+def case(key: str):
+    """-> namespace(key, K, a_hbv, a_inv (the old graph's files), old_unitigs (BVComp order), closures: strings, offset, n_edges, edges)"""
+    if key in _made:
+        return _made[key]
+    if key == SYNTH:
+        import a48ref
+        import goldens
+        c = goldens.load(SYNTH)
+        K = 48
+        g = a48xref.parse_hbv(c.exp_ahbv)
+        es = edge_strings(g)
+        rng = np.random.default_rng(0x9A7C4)
+        cl = []
+        for _ in range(20):
+            a, b = (es[int(i)] for i in rng.integers(0, g.E, 2))
+            pa, pb = int(rng.integers(K, len(a) + 1)), int(rng.integers(0, len(b) - K + 1))
+            gap = text(rng.integers(0, 4, int(rng.integers(0, 60))))
+            cl.append(a[pa - K:pa] + gap + b[pb:pb + K])
+        offset, n_edges, edges = a48xref.parse_paths(a48ref.load(SYNTH)["tmp.paths"])
+        us = hu.bvcomp_sorted(sorted({canon(s) for s in es}))
+        _made[key] = SimpleNamespace(key=key, K=K, a_hbv=c.exp_ahbv, a_inv=c.exp_ainv, old_unitigs=us, closures=cl, offset=offset, n_edges=n_edges, edges=edges)
+        return _made[key]
+    name, K = key.rsplit("_k", 1)
+    K = int(K)
+    gen = hu._Gen(f"patch/{_SEED.get(name, name)}", K)
+    closures = _MAKERS[name](gen)
+    hu.check_valid(hu.bvcomp_sorted(gen.unitigs), K)
+    us = new_unitigs(gen.unitigs, K)             # the generator's unitigs as the graph stage leaves them: canonical, circles rotated
+    assert sorted(len(s) for s in us) == sorted(len(s) for s in gen.unitigs)
+    a_hbv, a_inv = graph_files(us, K)
+    g = a48xref.parse_hbv(a_hbv)
+    lens = [len(s) for s in edge_strings(g)]
+    offset, n_edges, edges = place_paths(name, g, lens, negative_only=name == "negative")
+    _made[key] = SimpleNamespace(key=key, K=K, a_hbv=a_hbv, a_inv=a_inv, old_unitigs=us, closures=closures, offset=offset, n_edges=n_edges, edges=edges)
+    return _made[key]
+
+
+def closures_arrays(closures):
+    off = np.zeros(len(closures) + 1, np.uint64)
+    if closures:
+        off[1:] = np.cumsum([len(s) for s in closures], dtype=np.uint64)
+    return off, np.ascontiguousarray(codes("".join(closures)))
+
+
+_gold: dict = {}
+
+
+def golden(key: str):
+    """the reference's result -> namespace(a_hbv, a_inv, to3_off, to3, left3, edge, offset, pathsx, ref_summary); the case is made again
+    from its seed and compared with what the fixture was made from first"""
+    if key not in _gold:
+        z = np.load(PATCH / f"{key}.npz")
+        c = case(key)
+        off, cb = closures_arrays(c.closures)
+        assert bytes(z["in_hbv_crc"]) == str(zlib.crc32(c.a_hbv)).encode() and np.array_equal(z["closure_off"], off) and np.array_equal(z["closure_codes2"], hu.pack2(cb)) \
+            and bytes(z["in_paths_crc"]) == str(zlib.crc32(c.offset.tobytes() + c.n_edges.tobytes() + c.edges.tobytes())).encode(), \
+            f"{key}: the generator no longer makes the input of the fixture"
+        _gold[key] = SimpleNamespace(a_hbv=bytes(z["a_hbv"]), a_inv=bytes(z["a_inv"]), to3_off=z["to3_off"], to3=z["to3"], left3=z["left3"], edge=z["edge"],
+                                     offset=z["offset"], pathsx=bytes(z["pathsx"]), ref_summary=bytes(z["ref_summary"]).decode())
+    return _gold[key]
