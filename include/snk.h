@@ -461,7 +461,7 @@ uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components,
  * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
 uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -681,6 +681,57 @@ typedef struct snk_dev_extend {
 #define SNK_EXT_BACK 1u
 int snk_dev_extend_paths(snk_ctx* ctx, uint32_t K, const snk_dev_reads* in, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
                          const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags, snk_dev_extend* out, void* stream, char* err, size_t errcap);
+
+/* ---- pairs that disagree with the graph: MarkBads, a.bad ----------------------------------------------------------------
+ * MarkBads, lib/assembly/src/10X/SecretOps.cc:70-107 (ReadPath) and :22-59 (ReadPathVecX): the first step of StageFindPatch
+ * (10X/runstages/RunStages.cc:261; also :52).  DF keeps the result as a.bad (10X/DF.cc:644) and FindEdgePairs drops such pairs from its
+ * "rights" (10X/Closomatic.cc:293,316).  For every read with a path p on the graph:
+ *   m      = hb.Cat(p) (paths/HyperBasevector.cc:631-635), a chain of TrimCat (feudal/BaseVec.h:550-558): every edge but the last gives its
+ *            first Kmers(e) bases, the last all of its own.  The edges need not be adjacent: where two disagree inside the K-1 bases
+ *            they would share, m shows the LATER edge's
+ *   badsum = the raw quality q[l] summed over the read positions l with 0 <= offset + l < |m| and read[l] != m[offset + l]; positions in
+ *            front of m or behind it are skipped, not counted
+ *   bad[i] = badsum > 150 for read 2i or read 2i + 1 (a read without a path contributes nothing; MAX_BAD and MIN_HQ of the source are unused)
+ * flags = 0: offset is the path's int (the ReadPath overload).  SNK_BADS_X: the ReadPathVecX overload, which is what DF runs and what the
+ * a.bad of a stock run holds -- the path has been through zip / unzip, so the offset is static_cast<int16_t>(offset): beyond +-32767 it
+ * wraps and the read is compared where it does not lie.  That is reproduced (every position is range-checked: nothing is read out of
+ * bounds); n_offsets_wrapped counts such reads in either mode.  With SNK_BADS_X the paths must be what snk_dev_paths_zip accepts and
+ * snk_dev_paths_unzip gives back unchanged: at most 255 edges and no vertex with more than four out-edges (SNK_E_UNSUPPORTED), every
+ * step e -> e' with e' in From(ToRight(e)) (SNK_E_ARG).
+ * Arguments as for snk_dev_extend_paths: of `in` the rows, lens (NULL = read_len) and quals.  bad: u8[n_reads / 2], context memory,
+ * valid until the context's next top-level call.  in, paths, the count result and earlier stage results stay valid and unchanged.  The
+ * result is bit-identical from call to call and depends on no tuning option.
+ * SNK_E_ARG: an odd n_reads (the reference asserts dup.size( ) * 2 == bases.size( )), paths->n_reads != n_reads, an edge id outside the
+ * graph, an edge of fewer than K bases, start / n_edges that do not add up to n_edges_total, quals == NULL, read_len above 256, unknown
+ * flags.  After any failure *out is all zero. */
+#define SNK_BADS_X 1u     /* offsets as a ReadPathVecX holds them (int16): what DF's a.bad has */
+typedef struct snk_dev_bads {
+    uint64_t n_pairs;
+    const void* bad;              /* u8[n_pairs] */
+    uint64_t n_placed;            /* reads with a path */
+    uint64_t n_mismatch_reads;    /* ... with at least one mismatch inside m, whatever its quality */
+    uint64_t n_bad_reads;         /* ... with badsum > 150 */
+    uint64_t n_bad_pairs;         /* pairs flagged */
+    uint64_t n_offsets_wrapped;   /* reads with a path whose offset does not fit an int16 */
+    float ms;                     /* HIP events around the device work, graph tables included (_df: the whole call, host clock) */
+    uint32_t n_slabs;             /* launches of the comparison kernel: 1, or the slabs of the _df form */
+    float tables_ms, kernel_ms;   /* the resident form's two parts: graph tables + the checks of the paths; the comparison kernel.  They take
+                                     one of the reserved slots; the _df form leaves them 0 (its kernels run between the slabs' copies) */
+    uint64_t reserved[5];
+} snk_dev_bads;
+int snk_dev_mark_bads(snk_ctx* ctx, uint32_t K, const snk_dev_reads* in, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
+                      const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags, snk_dev_bads* out, void* stream, char* err, size_t errcap);
+/* The same over reads [first, first + n) of an opened reads.fastb / reads.qualp (snk_df_open), for a job whose quality rows are not
+ * resident (the ASSEMBLER_DF ingest keeps 46 bytes per read): the files are decoded again slab by slab, the kernel runs on every slab
+ * as it is decoded, and no more than the ring's slabs of quality rows ever exist.  paths: of reads [first, first + n), on the device.
+ * first and slab_reads (0 = 262144; the ring takes 16 at least) must be even, so that mates never straddle slabs (SNK_E_ARG);
+ * read_len, threads as for snk_dev_ingest_df.  The graph tables are built once per call.  The result is byte for byte the resident
+ * form's; file errors as snk_dev_ingest_df's.  A slab whose quality bytes do not fit its slot is decoded in pieces cut where the bytes
+ * say; a cut inside a pair is refused (SNK_E_UNSUPPORTED: more than 192 quality bytes per read on average over a slab). */
+struct snk_df_files;      /* (snk_df_open, below) */
+int snk_dev_mark_bads_df(snk_ctx* ctx, uint32_t K, struct snk_df_files* f, uint64_t first, uint64_t n, uint32_t read_len, uint32_t threads, uint64_t slab_reads,
+                         uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags,
+                         snk_dev_bads* out, char* err, size_t errcap);
 
 /* ---- gap patches into the graph: StageInsertPatch ---------------------------------------------------------------------
  * StageInsertPatch, lib/assembly/src/10X/runstages/RunStages.cc:176-230 (10X/DF.cc:656): the graph is rebuilt from its own edges, the

@@ -33,6 +33,7 @@
 #include <thread>
 #include <vector>
 
+#include "snk_bads.h"
 #include "snk_common.h"
 #include "snk_ctx.h"
 #include "snk_synth.h"
@@ -799,6 +800,56 @@ extern "C" int snk_dev_ingest_df_count_graph(snk_ctx* ctx, snk_df_files* f, uint
     }
     fill_ingest(out, n, max_len, st, streamed ? 3 : 4, t0, t_ready);
     return SNK_OK;
+}
+
+// MarkBads (snk_bads.hip) over reads [first, first + n) of the triple: the ingest above keeps no quality rows, so they are decoded again,
+// slab by slab, into the frame's per-slot buffers and the comparison kernel runs on every slab right behind its decode kernels, on the
+// ring's stream.  The graph tables and the checks of the paths are made once (snk_bads_begin).  paths and the unitigs must be complete
+// when this is called: it works on the ring's own stream.
+extern "C" int snk_dev_mark_bads_df(snk_ctx* ctx, uint32_t K, snk_df_files* f, uint64_t first, uint64_t n, uint32_t read_len, uint32_t threads, uint64_t slab_reads,
+                                    uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags,
+                                    snk_dev_bads* out, char* err, size_t errcap) {
+    static const char who[] = "snk_dev_mark_bads_df";
+    if (!ctx || !f || !h || !paths || !out) return snk_fail(SNK_E_ARG, err, errcap, "%s: NULL argument", who);
+    memset(out, 0, sizeof *out);
+    const double t0 = now_s();
+    int rc = snk_bads_check_args(who, K, n, read_len, true, n_unitigs, d_unitig_off, d_unitig_bases, h, paths, flags, err, errcap);
+    if (rc) return rc;
+    if ((first & 1) || (slab_reads & 1))
+        return snk_fail(SNK_E_ARG, err, errcap, "%s: first = %llu and slab_reads = %llu must be even (mates must not straddle slabs)", who, (unsigned long long)first,
+                        (unsigned long long)slab_reads);
+    df_io* io;
+    uint32_t max_len;
+    if ((rc = prepare(ctx, f, first, n, read_len, threads, &slab_reads, &io, &max_len, err, errcap))) return rc;
+    const uint32_t row_words = (max_len + 15) / 16, qstride = row_words * 16;
+    df_stats st;
+    path_host H;           // (the uploads of the graph tables read it: declared in front of the frame)
+    rc = snk_call_run(ctx, io->cs, who, out, err, errcap, [&](snk_call& c) -> int {
+        int r2;
+        bads_job job;
+        if ((r2 = snk_bads_begin(c, H, who, K, n, n_unitigs, d_unitig_off, d_unitig_bases, h, paths, flags, &job, err, errcap))) return r2;
+        struct obuf { uint32_t* rows; uint8_t* quals; uint16_t* lens; } O[NSLOT];          // what a slot's slab is decoded into: all the quality rows there ever are
+        for (auto& o : O)
+            if ((r2 = c.alloc((slab_reads + 1) * row_words, &o.rows)) || (r2 = c.alloc((slab_reads + 16) * (uint64_t)qstride, &o.quals)) || (r2 = c.alloc(slab_reads + 8, &o.lens)))
+                return r2;
+        r2 = run_slabs(ctx, io, f, first, n, slab_reads, max_len, row_words, qstride,
+                       [&](int s, uint64_t, uint64_t, slab_dev* sd) { sd->rows = O[s].rows; sd->quals = O[s].quals; sd->lens = O[s].lens; sd->bc = nullptr; return SNK_OK; },
+                       [&](int, const slab_dev& sd) {
+                           if (((sd.first - first) & 1) || (sd.n & 1))        // (a slab whose bytes do not fit its slot is decoded in pieces, cut where the bytes say)
+                               return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "%s: the slab at read %llu had to be split inside a pair (its quality bytes do not fit a slot)", who,
+                                               (unsigned long long)sd.first);
+                           SNK_HIP_TRY(snk_bads_slab(job, sd.first - first, sd.n, sd.rows, row_words, max_len, sd.quals, qstride, sd.lens, io->cs));
+                           return SNK_OK;
+                       },
+                       &st, err, errcap);
+        if (!r2) r2 = check_errs(io, f, qstride, err, errcap);
+        if (r2) return r2;
+        if ((r2 = snk_bads_finish(c, job, out, err, errcap))) return r2;
+        out->n_slabs = st.n_slabs;
+        return c.end(SNK_OK, {job.bad});
+    });
+    if (!rc) out->ms = (float)((now_s() - t0) * 1e3);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------

@@ -133,7 +133,7 @@ class Result:
         return out
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
-                   paths_index=False, pathsx=False, ebcx=False, extend=False):
+                   paths_index=False, pathsx=False, ebcx=False, extend=False, mark_bads=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -156,7 +156,11 @@ class Result:
         extend (True, or "back" for SNK_EXT_BACK): StageExtension over these paths (10X/DF.cc:676; ExtendPathsNew, 10X/Extend.cc:14-177;
         snk_dev_extend_paths) -> info['extended'] = (offset i32[n], n_edges u32[n], edges i32[sum]), info['extend_stats'] = the counters and
         time; with pathsx also info['extended_pathsx'] = (index, data), the ReadPathVecX of the extended paths, and
-        info['extended_pathsx_stats'].  It runs last: every other result is of the paths as pathed.  download=False: the stats only."""
+        info['extended_pathsx_stats'].  It runs last: every other result is of the paths as pathed.  download=False: the stats only.
+        mark_bads (True, or "x" for SNK_BADS_X: offsets as the ReadPathVecX of a stock DF holds them): MarkBads over these paths
+        (10X/SecretOps.cc:22-59,70-107; snk_dev_mark_bads) -> info['bads'] = dict(bad u8[n/2], n_bad_pairs, n_bad_reads, n_mismatch_reads,
+        n_placed, n_offsets_wrapped, ms): what graphio.write_bad / write_a48 make a.bad of.  download=False: the counters, and
+        info['bads_dev'] = the SnkDevBads itself (device memory of the context, valid until the engine's next count_graph or path_reads)."""
         if ebcx and bc is None:
             raise ValueError("path_reads(ebcx=...) needs bc: the barcode of every read, on the device")
         e = self._e
@@ -192,6 +196,16 @@ class Result:
                 dups = dict(dup=self._dl(dd.dup, npairs, np.uint8, (npairs,)) if download else None, interdup_rate=float(dd.interdup_rate),
                             n_dup_pairs=int(dd.n_dup_pairs), n_dup_reads=int(dd.n_dup_reads), n_interdup_reads=int(dd.n_interdup_reads),
                             n_art_pairs=int(dd.n_art_pairs), n_placed=int(dd.n_placed), ms=float(dd.ms))
+            bads = None
+            if mark_bads:
+                bd = _lib.SnkDevBads()
+                rc = e.lib.snk_dev_mark_bads(e._ctx, int(self.K), C.byref(r), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases, C.byref(h), C.byref(out),
+                                             _lib.BADS_X if mark_bads == "x" else 0, C.byref(bd), e._stream(), err, 512)
+                if rc:
+                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+                bads = _bads_stats(bd)
+                if download:
+                    bads["bad"] = self._dl(bd.bad, int(bd.n_pairs), np.uint8, (int(bd.n_pairs),))
             pidx = None
             if paths_index:
                 ne_hbv = int(h.n_edges)
@@ -261,6 +275,8 @@ class Result:
                         lookup=("index" if out.lookup_index else "kmer_dictionary"), retries=int(out.retries))
             if dups is not None:
                 info["dups"] = {k: v for k, v in dups.items() if k != "dup"}
+            if bads is not None:
+                info["bads"], info["bads_dev"] = bads, bd
             if pidx is not None:
                 info["pidx"] = pidx
             if px_stats is not None:
@@ -279,6 +295,8 @@ class Result:
                     n_slow=int(out.n_slow), retries=int(out.retries))
         if dups is not None:
             info["dups"] = dups
+        if bads is not None:
+            info["bads"] = bads
         if pidx is not None:
             info["pidx"], info["paths_index"], info["countsb"], info["inv"] = pidx, pidx_arrays[:2], pidx_arrays[2], pidx_arrays[3]
         if px_stats is not None:
@@ -378,6 +396,11 @@ def _extend_stats(x: "_lib.SnkDevExtend") -> dict:
     return dict(n_reads=int(x.paths.n_reads), n_edges_total=int(x.paths.n_edges_total), n_back_extended=int(x.n_back_extended),
                 n_cut_to_first=int(x.n_cut_to_first), n_quality_extended=int(x.n_quality_extended), n_ambiguous=int(x.n_ambiguous),
                 n_too_many=int(x.n_too_many), n_exact_extended=int(x.n_exact_extended), n_enumerated=int(x.n_enumerated), ms=float(x.ms))
+
+
+def _bads_stats(b: "_lib.SnkDevBads") -> dict:
+    return dict(n_pairs=int(b.n_pairs), n_placed=int(b.n_placed), n_mismatch_reads=int(b.n_mismatch_reads), n_bad_reads=int(b.n_bad_reads),
+                n_bad_pairs=int(b.n_bad_pairs), n_offsets_wrapped=int(b.n_offsets_wrapped), n_slabs=int(b.n_slabs), ms=float(b.ms), tables_ms=float(b.tables_ms), kernel_ms=float(b.kernel_ms))
 
 
 def _pathsx_stats(zx: "_lib.SnkDevPathsx") -> dict:
@@ -583,6 +606,62 @@ class Engine:
             if a.size:
                 self._download(ptr, a.ctypes.data, a.nbytes)
         return off, ne, ed, stats
+
+    # ---- MarkBads (the first step of StageFindPatch) over device-resident unitigs and paths, and reads that are resident or in the stage's files
+    def _paths_struct(self, offset, n_edges, edges, start):
+        n = int(n_edges.shape[0])
+        if start is None:
+            start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
+            start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
+        p = _lib.SnkDevPaths()
+        p.n_reads, p.n_edges_total = n, int(edges.shape[0])
+        p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
+        return p, start
+
+    def _bads_result(self, b: "_lib.SnkDevBads", download: bool):
+        stats = _bads_stats(b)
+        if not download:
+            return b, stats
+        bad = np.empty(int(b.n_pairs), np.uint8)
+        if bad.size:
+            self._download(b.bad, bad.ctypes.data, bad.nbytes)
+        return bad, stats
+
+    def mark_bads(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, rows: torch.Tensor, read_len: int,
+                  quals: torch.Tensor, lens: torch.Tensor | None, offset: torch.Tensor, n_edges: torch.Tensor, edges: torch.Tensor,
+                  start: torch.Tensor | None = None, x: bool = False, download: bool = True):
+        """snk_dev_mark_bads -- MarkBads (10X/SecretOps.cc:70-107; x=True: the ReadPathVecX overload, :22-59, int16 offsets: what a stock DF
+        writes as a.bad) -- over tensors on this engine's device, the arguments of extend_paths.  -> (bad u8[n / 2], stats) on the host;
+        download=False: (SnkDevBads, stats), device memory of the context, valid until its next top-level call."""
+        r = _lib.SnkDevReads()
+        r.n_reads, r.rows, r.row_words, r.read_len = int(rows.shape[0]), rows.data_ptr(), (int(rows.shape[1]) if rows.dim() > 1 else 0), int(read_len)
+        r.quals, r.qstride = (quals.data_ptr(), int(quals.shape[1])) if quals is not None else (None, 0)
+        if lens is not None:
+            r.lens = lens.data_ptr()
+        p, start = self._paths_struct(offset, n_edges, edges, start)
+        b = _lib.SnkDevBads()
+        err = C.create_string_buffer(512)
+        rc = self.lib.snk_dev_mark_bads(self._ctx, int(K), C.byref(r), int(unitig_off.shape[0]) - 1, unitig_off.data_ptr(), unitig_bases.data_ptr(),
+                                        C.byref(h), C.byref(p), _lib.BADS_X if x else 0, C.byref(b), self._stream(), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        return self._bads_result(b, download)
+
+    def mark_bads_df(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, files, offset: torch.Tensor,
+                     n_edges: torch.Tensor, edges: torch.Tensor, start: torch.Tensor | None = None, first: int = 0, n: int | None = None, read_len: int = 0,
+                     threads: int = 0, slab_reads: int = 0, x: bool = False, download: bool = True):
+        """snk_dev_mark_bads_df: the same over reads [first, first + n) of an opened triple (dfin.DfFiles), decoded again slab by slab -- for
+        a job that kept no quality rows.  The paths are those of these reads.  first and slab_reads must be even.  Results as mark_bads."""
+        n = int(n_edges.shape[0]) if n is None else int(n)
+        p, start = self._paths_struct(offset, n_edges, edges, start)
+        torch.cuda.current_stream(self.device).synchronize()          # (the call works on the ring's own stream: its inputs must be complete)
+        b = _lib.SnkDevBads()
+        err = C.create_string_buffer(512)
+        rc = self.lib.snk_dev_mark_bads_df(self._ctx, int(K), files._h, int(first), n, int(read_len), int(threads), int(slab_reads), int(unitig_off.shape[0]) - 1,
+                                           unitig_off.data_ptr(), unitig_bases.data_ptr(), C.byref(h), C.byref(p), _lib.BADS_X if x else 0, C.byref(b), err, 512)
+        if rc:
+            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        return self._bads_result(b, download)
 
     # ---- gap patches into the graph (StageInsertPatch)
     def insert_patch(self, graph, closures, paths) -> "PatchResult":

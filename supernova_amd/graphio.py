@@ -6,6 +6,7 @@
   write_hbv            a.hbv / a.inv as DF keeps the graph (paths/HyperBasevector.cc:121-125)
   write_paths, write_paths_index, write_dup, write_a48
                        the rest of a.48/: a.paths, a.paths.inv, a.countsb, a.dup (10X/DF.cc:584-600, 10X/PathsIndex.cc:23-145)
+  write_bad            a.bad, the pair flags of MarkBads that StageFindPatch leaves (10X/DF.cc:644); write_a48 adds it when the result holds 'bads'
   write_pathsx / read_pathsx, write_hbx
                        the compressed forms DF goes on working from: a.pathsX (10X/paths/ReadPathVecX.cc:976-996) and a.hbx
                        (paths/HyperBasevector.cc:133-137); write_a48 adds them when the result holds 'pathsx'
@@ -164,6 +165,12 @@ def write_dup(path, dup: np.ndarray) -> None:
     _call(_lib.load().snk_write_dup, str(path).encode(), len(dup), dup.ctypes.data)
 
 
+def write_bad(path, bad: np.ndarray) -> None:
+    """a.bad (vec<Bool> of MarkBads, 10X/DF.cc:644): one flag per read pair.  BinaryWriter::writeFile(vec<Bool>), the container of a.dup."""
+    bad = np.ascontiguousarray(bad, dtype=np.uint8)
+    _call(_lib.load().snk_write_dup, str(path).encode(), len(bad), bad.ctypes.data)
+
+
 def write_pathsx(path, index: np.ndarray, data: np.ndarray, n_reads: int) -> None:
     """a.pathsX (ReadPathVecX::writeBinary, 10X/paths/ReadPathVecX.cc:976-996) from what snk_dev_paths_zip made: index i64[ceil(n_reads / 10)] =
     the byte offset of every 10th read's record, data u8[...] = the records."""
@@ -233,7 +240,8 @@ def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.n
     order: graphio.unitigs_to_arrays(res.unitigs())), a.paths (what res.path_reads returned), a.paths.inv, a.countsb (info['paths_index'],
     info['countsb']: path_reads(..., paths_index=True)) and a.dup (info['dups']['dup']: mark_dups=True).  With info['pathsx']
     (path_reads(..., pathsx=True)) also a.hbx and a.pathsX, the two other files a DF entered at START=patch opens (10X/DF.cc:612-630).
-    Returns the involution."""
+    With info['bads'] (path_reads(..., mark_bads="x"), or dict(bad=...) of Engine.mark_bads) also a.bad, which StageFindPatch leaves
+    (10X/DF.cc:644).  Returns the involution."""
     from pathlib import Path
     d = Path(dir)
     d.mkdir(parents=True, exist_ok=True)
@@ -250,6 +258,8 @@ def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.n
     if "pathsx" in info:
         write_hbx(d / "a.hbx", K, off, bases)
         write_pathsx(d / "a.pathsX", info["pathsx"][0], info["pathsx"][1], len(path_n_edges))
+    if "bads" in info:
+        write_bad(d / "a.bad", info["bads"]["bad"])
     return inv
 
 

@@ -117,6 +117,15 @@ class SnkDevExtend(C.Structure):
 EXT_BACK = 1                     # SNK_EXT_BACK
 
 
+class SnkDevBads(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("bad", C.c_void_p), ("n_placed", C.c_uint64), ("n_mismatch_reads", C.c_uint64), ("n_bad_reads", C.c_uint64),
+                ("n_bad_pairs", C.c_uint64), ("n_offsets_wrapped", C.c_uint64), ("ms", C.c_float), ("n_slabs", C.c_uint32), ("tables_ms", C.c_float), ("kernel_ms", C.c_float),
+                ("reserved", C.c_uint64 * 5)]
+
+
+BADS_X = 1                       # SNK_BADS_X
+
+
 class SnkPatchPlan(C.Structure):
     _fields_ = [("n_pieces", C.c_uint64), ("n_unitig_pieces", C.c_uint64), ("n_junctions", C.c_uint64), ("n_closure_pieces", C.c_uint64),
                 ("n_lonely_max", C.c_uint64), ("reserved", C.c_uint64 * 3)]
@@ -302,6 +311,8 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_paths_zip": (C.c_int, [vp, P(SnkDevPaths), P(SnkHbv), P(SnkDevPathsx), vp, cp, sz]),
         "snk_dev_paths_unzip": (C.c_int, [vp, P(SnkDevPathsx), P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_extend_paths": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevExtend), vp, cp, sz]),
+        "snk_dev_mark_bads": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevBads), vp, cp, sz]),
+        "snk_dev_mark_bads_df": (C.c_int, [vp, u32, vp, u64, u64, u32, u32, u64, u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevBads), cp, sz]),
         "snk_patch_plan_sizes": (C.c_int, [u32, u64, vp, P(SnkHbv), u64, vp, P(SnkPatchPlan), cp, sz]),
         "snk_dev_patch_pieces": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), u64, vp, vp, u64, vp, vp, u64, vp, P(SnkDevPieces), vp, cp, sz]),
         "snk_dev_patch_merge": (C.c_int, [vp, u32, P(SnkDevResult), vp, u64, P(SnkDevPatchUnitigs), vp, cp, sz]),
