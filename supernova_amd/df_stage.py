@@ -280,26 +280,20 @@ def compute_mspedges(args, out_dir: str, device: int = 0, bc_start: int | None =
         bc_start = bc_start_of(reads[:-len(".fastb")])
     gp = graph_params_of(args)
     lib = _lib.load()
-    err = C.create_string_buffer(512)
-
-    def ok(rc):
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-
     h, files = C.c_void_p(), C.c_void_p()
-    ok(lib.snk_ctx_create(device, C.byref(h), err, 512))
+    _lib.call(lib.snk_ctx_create, device, C.byref(h))
     try:
         info = _lib.SnkDfInfo()
-        ok(lib.snk_df_open(reads.encode(), _get(args, "quals").encode(), _get(args, "bci").encode(), C.byref(files), C.byref(info), err, 512))
+        _lib.call(lib.snk_df_open, reads.encode(), _get(args, "quals").encode(), _get(args, "bci").encode(), C.byref(files), C.byref(info))
         p = _lib.SnkParams()
         p.K, p.min_qual, p.min_freq, p.min_bc = gp["K"], gp["MIN_QUAL"], gp["MIN_FREQ"], gp["MIN_BC"]
         p.flags = 2                                    # SNK_F_UNSORTED_TABLE: the hand-off is the unitigs
         res, st = _lib.SnkDevResult(), _lib.SnkDevIngest()
         threads = int(_get(args, "__threads") or 0)
         # "barcoded datatypes start at" (RunStages.cc:398, DF.cc:358-363) = ign_bc_below
-        ok(lib.snk_dev_ingest_df_count_graph(h, files, 0, info.n_reads, 0, min(threads, 64), 0, C.byref(p), bc_start, C.byref(res), C.byref(st), err, 512))
+        _lib.call(lib.snk_dev_ingest_df_count_graph, h, files, 0, info.n_reads, 0, min(threads, 64), 0, C.byref(p), bc_start, C.byref(res), C.byref(st))
         d_img, nb = C.c_void_p(0), C.c_uint64(0)
-        ok(lib.snk_dev_bv_image(h, gp["K"], res.n_unitigs, res.unitig_off, res.unitig_bases, 1, C.byref(d_img), C.byref(nb), None, err, 512))
+        _lib.call(lib.snk_dev_bv_image, h, gp["K"], res.n_unitigs, res.unitig_off, res.unitig_bases, 1, C.byref(d_img), C.byref(nb), None)
         image = np.empty(int(nb.value), dtype=np.uint8)
         _lib.check(lib.snk_dev_download(h, d_img, image.ctypes.data, image.nbytes, None))
         if stats is not None:

@@ -13,15 +13,6 @@ from . import lib as _lib
 from .ingest import DeviceReads
 
 
-def _err():
-    return C.create_string_buffer(512)
-
-
-def _check(rc, err):
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-
-
 class DfFiles:
     def __init__(self, head, with_bci: bool = True):
         head = str(head)
@@ -31,9 +22,8 @@ class DfFiles:
         self.head = head
         self._h = C.c_void_p()
         info = _lib.SnkDfInfo()
-        err = _err()
         bci = (head + ".bci").encode() if with_bci else None
-        _check(self.lib.snk_df_open((head + ".fastb").encode(), (head + ".qualp").encode(), bci, C.byref(self._h), C.byref(info), err, 512), err)
+        _lib.call(self.lib.snk_df_open, (head + ".fastb").encode(), (head + ".qualp").encode(), bci, C.byref(self._h), C.byref(info))
         self.n_reads, self.n_barcodes = int(info.n_reads), int(info.n_barcodes)
         self.file_bytes = int(info.fastb_bytes) + int(info.qualp_bytes) + int(info.bci_bytes)
 
@@ -56,22 +46,22 @@ class DfFiles:
 
     def max_len(self, engine, first: int = 0, n: int | None = None) -> int:
         n = self.n_reads - first if n is None else n
-        out, err = C.c_uint32(0), _err()
-        _check(self.lib.snk_df_max_len(engine._ctx, self._h, first, n, C.byref(out), err, 512), err)
+        out = C.c_uint32(0)
+        _lib.call(self.lib.snk_df_max_len, engine._ctx, self._h, first, n, C.byref(out))
         return int(out.value)
 
     def ingest(self, engine, first: int = 0, n: int | None = None, read_len: int = 0, threads: int = 0, slab_reads: int = 0) -> DeviceReads:
         n = self.n_reads - first if n is None else n
-        raw, err = _lib.SnkDevIngest(), _err()
-        _check(self.lib.snk_dev_ingest_df(engine._ctx, self._h, first, n, read_len, threads, slab_reads, C.byref(raw), err, 512), err)
+        raw = _lib.SnkDevIngest()
+        _lib.call(self.lib.snk_dev_ingest_df, engine._ctx, self._h, first, n, read_len, threads, slab_reads, C.byref(raw))
         return DeviceReads(self.lib, raw)
 
     def ingest_trimmed(self, engine, K: int = 48, min_qual: int = 7, first: int = 0, n: int | None = None, read_len: int = 0, threads: int = 0,
                        slab_reads: int = 0) -> DeviceReads:
         """The compact form (snk_dev_ingest_df_trimmed): packed rows, good lengths, barcode ids -- no quality rows, no lengths."""
         n = self.n_reads - first if n is None else n
-        raw, err = _lib.SnkDevIngest(), _err()
-        _check(self.lib.snk_dev_ingest_df_trimmed(engine._ctx, self._h, first, n, read_len, threads, slab_reads, K, min_qual, C.byref(raw), err, 512), err)
+        raw = _lib.SnkDevIngest()
+        _lib.call(self.lib.snk_dev_ingest_df_trimmed, engine._ctx, self._h, first, n, read_len, threads, slab_reads, K, min_qual, C.byref(raw))
         return DeviceReads(self.lib, raw)
 
     def count_graph(self, engine, params=None, first: int = 0, n: int | None = None, read_len: int = 0, threads: int = 0, slab_reads: int = 0,
@@ -82,9 +72,9 @@ class DfFiles:
         from .engine import Params, Result
         params = params or Params()
         n = self.n_reads - first if n is None else n
-        raw, res, p, err = _lib.SnkDevIngest(), _lib.SnkDevResult(), params.to_c(), _err()
-        _check(self.lib.snk_dev_ingest_df_count_graph(engine._ctx, self._h, first, n, read_len, threads, slab_reads, C.byref(p), ign_bc_below,
-                                                      C.byref(res), C.byref(raw), err, 512), err)
+        raw, res, p = _lib.SnkDevIngest(), _lib.SnkDevResult(), params.to_c()
+        _lib.call(self.lib.snk_dev_ingest_df_count_graph, engine._ctx, self._h, first, n, read_len, threads, slab_reads, C.byref(p), ign_bc_below,
+                  C.byref(res), C.byref(raw))
         stats = dict(n_reads=int(raw.n_reads), file_bytes=int(raw.text_bytes), seconds=float(raw.seconds), io_wait_seconds=float(raw.decode_wait_seconds),
                      n_slabs=int(raw.n_batches), max_len=int(raw.max_len), setup_seconds=float(raw.setup_seconds),
                      mode="streamed" if int(raw.n_files) == 3 else "compact")
@@ -101,14 +91,12 @@ def write_df(head, rows: np.ndarray, quals: np.ndarray, bc: np.ndarray | None = 
     read_len = int(read_len if read_len is not None else quals.shape[1])
     lp = np.ascontiguousarray(lens, dtype=np.uint16) if lens is not None else None
     bp = np.ascontiguousarray(bc, dtype=np.int32) if bc is not None else None
-    err = _err()
-    _check(lib.snk_write_df(str(head).encode(), n, rows.ctypes.data, rows.shape[1], lp.ctypes.data if lp is not None else None, read_len, quals.ctypes.data,
-                            quals.shape[1], bp.ctypes.data if bp is not None else None, threads, adversarial, err, 512), err)
+    _lib.call(lib.snk_write_df, str(head).encode(), n, rows.ctypes.data, rows.shape[1], lp.ctypes.data if lp is not None else None, read_len, quals.ctypes.data,
+              quals.shape[1], bp.ctypes.data if bp is not None else None, threads, adversarial)
 
 
 def write_synth_df(head, sp: _lib.SnkSynthParams, first: int = 0, n: int | None = None, qual_jitter: int = 0, threads: int = 0) -> None:
     lib = _lib.load()
     n = int(sp.n_reads) - first if n is None else n
     Path(str(head)).parent.mkdir(parents=True, exist_ok=True)
-    err = _err()
-    _check(lib.snk_synth_df_write(str(head).encode(), C.byref(sp), first, n, qual_jitter, threads, err, 512), err)
+    _lib.call(lib.snk_synth_df_write, str(head).encode(), C.byref(sp), first, n, qual_jitter, threads)

@@ -15,8 +15,50 @@ import numpy as np
 import torch
 
 from . import lib as _lib
+from .graphio import hbv_arrays
 
 PHASES = ("trim", "plan", "partition", "count", "sort", "graph", "-", "total")
+
+
+# ---- the two input structs of the device stages, from tensors (the one place each is filled)
+class DevArray:
+    """A device array the library allocated itself, known by pointer and shape only, where the builders take a tensor."""
+
+    def __init__(self, ptr, *shape):
+        self._ptr, self.shape = ptr, shape
+
+    def data_ptr(self):
+        return self._ptr
+
+
+def _ptr(a):
+    return a.data_ptr() if hasattr(a, "data_ptr") else a      # (a tensor, or a plain pointer / None)
+
+
+def dev_reads(rows, read_len, quals=None, lens=None, good_len=None, bc=None, group=None, ign_bc_below=0, read_index_base=0) -> "_lib.SnkDevReads":
+    """snk_dev_reads over tensors: rows i32[n, words] (1-D rows: row_words 0), quals u8[n, stride] or None (null, qstride 0); every other
+    pointer is null when None.  It checks nothing: the struct only points into the tensors, which the caller keeps alive over the call."""
+    r = _lib.SnkDevReads()
+    r.n_reads, r.rows, r.row_words, r.read_len = int(rows.shape[0]), rows.data_ptr(), (int(rows.shape[1]) if len(rows.shape) > 1 else 0), int(read_len)
+    if quals is not None:
+        r.quals, r.qstride = quals.data_ptr(), int(quals.shape[1])
+    r.lens, r.good_len, r.bc, r.group = _ptr(lens), _ptr(good_len), _ptr(bc), _ptr(group)
+    r.ign_bc_below, r.read_index_base = ign_bc_below, read_index_base
+    return r
+
+
+def dev_paths(offset, n_edges, edges, start=None):
+    """snk_dev_paths as a stage's input, over tensors: offset i32[n], n_edges i32[n] (read as u32), edges i32[sum], start i64[n + 1] (None:
+    the paths follow each other, start = the exclusive prefix sum of n_edges, made here on n_edges.device).  -> (SnkDevPaths, start): the
+    struct points into start, so the caller holds it until the call has returned."""
+    n = int(n_edges.shape[0])
+    if start is None:
+        start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
+        start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
+    p = _lib.SnkDevPaths()
+    p.n_reads, p.n_edges_total = n, int(edges.shape[0])
+    p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
+    return p, start
 
 
 @dataclass
@@ -60,17 +102,14 @@ class Result:
         self.graph_ms = {names[i]: float(raw.graph_ms[i]) for i in range(5) if names[i] != "-"}
 
     def _dl(self, ptr, nbytes, dtype, shape):
-        out = np.empty(shape, dtype=dtype)
-        if nbytes:
-            self._e._download(ptr, out.ctypes.data, nbytes)
-        return out
+        return self._e._fetch(ptr, nbytes // np.dtype(dtype).itemsize, dtype).reshape(shape)
 
     def good_len(self) -> np.ndarray:
-        return self._dl(self.raw.good_len, self.n_reads * 2, np.uint16, (self.n_reads,))
+        return self._e._fetch(self.raw.good_len, self.n_reads, np.uint16)
 
     def keys(self) -> np.ndarray:
         """[n_kmers, 4] u32 words MSB-first (include/snk.h key convention), ascending."""
-        lohi = self._dl(self.raw.keys, self.n_kmers * 16, np.uint64, (self.n_kmers, 2))
+        lohi = self._e._fetch(self.raw.keys, self.n_kmers * 2, np.uint64).reshape(self.n_kmers, 2)
         lo, hi = lohi[:, 0], lohi[:, 1]
         w = np.empty((self.n_kmers, 4), dtype=np.uint32)
         w[:, 0] = hi >> np.uint64(32)
@@ -80,57 +119,45 @@ class Result:
         return w
 
     def counts(self) -> np.ndarray:
-        return self._dl(self.raw.counts, self.n_kmers * 4, np.uint32, (self.n_kmers,))
+        return self._e._fetch(self.raw.counts, self.n_kmers, np.uint32)
 
     def ctx(self) -> np.ndarray:
-        return self._dl(self.raw.ctx, self.n_kmers, np.uint8, (self.n_kmers,))
+        return self._e._fetch(self.raw.ctx, self.n_kmers, np.uint8)
 
     def spectrum(self) -> np.ndarray:
-        nb = int(self.raw.spectrum_bins)
-        return self._dl(self.raw.spectrum, nb * 8, np.uint64, (nb,))
+        return self._e._fetch(self.raw.spectrum, self.raw.spectrum_bins, np.uint64)
 
     def unitig_arrays(self):
-        off = self._dl(self.raw.unitig_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,))
-        bases = self._dl(self.raw.unitig_bases, self.unitig_total_bases, np.uint8, (self.unitig_total_bases,))
-        return off, bases
+        return self._e._fetch(self.raw.unitig_off, self.n_unitigs + 1, np.uint64), self._e._fetch(self.raw.unitig_bases, self.unitig_total_bases, np.uint8)
 
     def unitig_groups(self) -> np.ndarray:
         """Grouped runs: group id of every unitig (same order as unitig_arrays())."""
-        return self._dl(self.raw.unitig_group, self.n_unitigs * 4, np.uint32, (self.n_unitigs,))
+        return self._e._fetch(self.raw.unitig_group, self.n_unitigs, np.uint32)
 
     def bv_image_device(self):
         """a13 on the device: (device pointer, bytes) of the .bv hand-off file -- "BINWRITE", count, per unitig u32 length + 2-bit bases in
         BVComp order (snk_dev_bv_image).  Context memory: valid until the engine's next top-level call."""
         ptr, nb = C.c_void_p(0), C.c_uint64(0)
-        err = C.create_string_buffer(512)
-        rc = self._e.lib.snk_dev_bv_image(self._e._ctx, int(self.K), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases, 1,
-                                          C.byref(ptr), C.byref(nb), self._e._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        self._e._call(self._e.lib.snk_dev_bv_image, int(self.K), *self._unitigs(), 1, C.byref(ptr), C.byref(nb))
         return ptr.value, int(nb.value)
 
     def bv_image(self) -> bytes:
-        ptr, nb = self.bv_image_device()
-        return self._dl(ptr, nb, np.uint8, (nb,)).tobytes()
+        return self._e._fetch(*self.bv_image_device(), np.uint8).tobytes()
+
+    def _unitigs(self):
+        """(n_unitigs, unitig_off, unitig_bases): the unitig arguments of the device stages"""
+        return self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases
 
     def hbv(self) -> dict:
         """The graph from the device-resident unitigs (buildHBVFromEdges, HBVFromEdges.cc:244-296; snk_dev_hbv):
         vertex ids per HBV edge, fwd/rev translation per unitig, numbered in BVComp order; 'order'[r] = index of the
         rank-r unitig in unitig_arrays().  Must be called before the engine's next count_graph."""
-        h = _lib.SnkHbv()
-        ms = C.c_float(0)
-        err = C.create_string_buffer(512)
-        rc = self._e.lib.snk_dev_hbv(self._e._ctx, int(self.K), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases,
-                                     C.byref(h), C.byref(ms), self._e._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        ne, nu = h.n_edges, self.n_unitigs
-        arr = lambda p, m, dt: (np.array(np.ctypeslib.as_array(p, shape=(m,)), dtype=dt, copy=True) if m else np.zeros(0, dt))      # (one copy: the C arrays are freed below)
-        out = dict(n_vertices=h.n_vertices, n_edges=ne, v_left=arr(h.v_left, ne, np.int32), v_right=arr(h.v_right, ne, np.int32),
-                   src=arr(h.src_unitig, ne, np.int32), is_rc=arr(h.is_rc, ne, np.uint8), fwd=arr(h.fwd_xlat, nu, np.int32),
-                   rev=arr(h.rev_xlat, nu, np.int32), order=arr(h.bvcomp_order, nu, np.int32), device_ms=float(ms.value))
-        self._e.lib.snk_hbv_free(C.byref(h))
-        return out
+        h, ms = _lib.SnkHbv(), C.c_float(0)
+        self._e._call(self._e.lib.snk_dev_hbv, int(self.K), *self._unitigs(), C.byref(h), C.byref(ms))
+        try:
+            return dict(hbv_arrays(h, self.n_unitigs, order=True), device_ms=float(ms.value))
+        finally:
+            self._e.lib.snk_hbv_free(C.byref(h))
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
                    paths_index=False, pathsx=False, ebcx=False, extend=False, mark_bads=False):
@@ -142,7 +169,9 @@ class Result:
         unitig_bcs: the rest of f4 -- per unitig (numbering of unitig_arrays()) the sorted distinct barcodes > 0 of the reads with a
         k-mer on it (tada's edge -> barcode sets) -> info['unitig_bcs'] = (off u64[U+1], bcs u32[...]); unitig_bcs="exhaustive" derives them
         the slow, literal way (every k-mer of every barcoded read looked up); bcs_nocut: without the 20 000-entry cut.
-        info['retries']: the lists that overflowed and were regrown (snk_dev_paths.retries: 1 redo list, 2 path edges, 4 barcode keys).
+        info['retries']: the lists that overflowed and were regrown (snk_dev_paths.retries: 1 redo list, 2 path edges, 4 barcode keys);
+        next to it, in both modes: dict_ms, path_ms, bcs_ms, hbv_device_ms, dict_slots, lookup ('index' or 'kmer_dictionary'), n_slow,
+        n_edges_total, n_unitig_bcs.  download=False: (None, None, None, info) -- nothing but counters and times comes to the host.
         paths_index: writePathsIndex over these paths (10X/PathsIndex.cc:23-145; snk_dev_paths_index) -> info['paths_index'] = (off u64[E+1],
         ids u64[...]): the reads of HBV edge e are ids[off[e]:off[e+1]], ascending, a read as often as its path holds e; info['countsb'] =
         i32[E] read support, an edge and its reverse complement summed; info['inv'] = the involution; info['pidx'] = counters and time.
@@ -163,155 +192,48 @@ class Result:
         info['bads_dev'] = the SnkDevBads itself (device memory of the context, valid until the engine's next count_graph or path_reads)."""
         if ebcx and bc is None:
             raise ValueError("path_reads(ebcx=...) needs bc: the barcode of every read, on the device")
-        e = self._e
-        h = _lib.SnkHbv()
-        ms = C.c_float(0)
-        err = C.create_string_buffer(512)
-        rc = e.lib.snk_dev_hbv(e._ctx, int(self.K), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases, C.byref(h), C.byref(ms),
-                               e._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        e, K = self._e, int(self.K)
+        h, ms = _lib.SnkHbv(), C.c_float(0)
+        e._call(e.lib.snk_dev_hbv, K, *self._unitigs(), C.byref(h), C.byref(ms))
+        graph = (*self._unitigs(), C.byref(h))
+        stages = {}
         try:
-            r = _lib.SnkDevReads()
-            r.n_reads, r.rows, r.row_words, r.read_len = rows.shape[0], rows.data_ptr(), rows.shape[1], read_len
-            r.quals, r.qstride = quals.data_ptr(), quals.shape[1]
-            if lens is not None:
-                r.lens = lens.data_ptr()
+            r = dev_reads(rows, read_len, quals, lens, bc=bc if unitig_bcs else None)
             out = _lib.SnkDevPaths()
-            if unitig_bcs and bc is not None:
-                r.bc = bc.data_ptr()
-            rc = e.lib.snk_dev_path_reads2(e._ctx, int(self.K), C.byref(r), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases,
-                                           C.byref(h), (0 if not unitig_bcs else 1 | (2 if unitig_bcs == "exhaustive" else 0) | (4 if bcs_nocut else 0)), C.byref(out), e._stream(), err, 512)
-            if rc:
-                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-            dups = None
+            e._call(e.lib.snk_dev_path_reads2, K, C.byref(r), *graph,
+                    (0 if not unitig_bcs else 1 | (2 if unitig_bcs == "exhaustive" else 0) | (4 if bcs_nocut else 0)), C.byref(out))
             if mark_dups:
                 if bc is not None:
                     r.bc = bc.data_ptr()
-                dd = _lib.SnkDevDups()
-                rc = e.lib.snk_dev_mark_dups(e._ctx, C.byref(r), C.byref(out), C.byref(dd), e._stream(), err, 512)
-                if rc:
-                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                npairs = int(dd.n_pairs)
-                dups = dict(dup=self._dl(dd.dup, npairs, np.uint8, (npairs,)) if download else None, interdup_rate=float(dd.interdup_rate),
-                            n_dup_pairs=int(dd.n_dup_pairs), n_dup_reads=int(dd.n_dup_reads), n_interdup_reads=int(dd.n_interdup_reads),
-                            n_art_pairs=int(dd.n_art_pairs), n_placed=int(dd.n_placed), ms=float(dd.ms))
-            bads = None
+                stages.update(e._dups_info(e._dups(r, out), download))
             if mark_bads:
-                bd = _lib.SnkDevBads()
-                rc = e.lib.snk_dev_mark_bads(e._ctx, int(self.K), C.byref(r), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases, C.byref(h), C.byref(out),
-                                             _lib.BADS_X if mark_bads == "x" else 0, C.byref(bd), e._stream(), err, 512)
-                if rc:
-                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                bads = _bads_stats(bd)
-                if download:
-                    bads["bad"] = self._dl(bd.bad, int(bd.n_pairs), np.uint8, (int(bd.n_pairs),))
-            pidx = None
+                stages.update(e._bads_info(e._bads(K, r, graph, out, mark_bads == "x"), download))
+            if paths_index or ebcx:
+                n_hbv = int(h.n_edges)
+                inv = np.zeros(max(n_hbv, 1), dtype=np.int32)
+                _lib.call(e.lib.snk_hbv_involution, C.byref(h), self.n_unitigs, inv.ctypes.data)
             if paths_index:
-                ne_hbv = int(h.n_edges)
-                inv = np.zeros(max(ne_hbv, 1), dtype=np.int32)
-                rc = e.lib.snk_hbv_involution(C.byref(h), self.n_unitigs, inv.ctypes.data, err, 512)
-                px = _lib.SnkDevPidx()
-                if not rc:
-                    rc = e.lib.snk_dev_paths_index(e._ctx, C.byref(out), ne_hbv, inv.ctypes.data, C.byref(px), e._stream(), err, 512)
-                if rc:
-                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                nent = int(px.n_entries)
-                pidx = dict(n_hbv_edges=ne_hbv, n_entries=nent, n_empty_edges=int(px.n_empty_edges), key_bits=int(px.key_bits), ms=float(px.ms))
-                if download:
-                    pidx_arrays = (self._dl(px.index_off, (ne_hbv + 1) * 8, np.uint64, (ne_hbv + 1,)), self._dl(px.index_ids, nent * 8, np.uint64, (nent,)),
-                                   self._dl(px.counts, ne_hbv * 4, np.int32, (ne_hbv,)), inv[:ne_hbv].copy())
-            eb_stats = None
+                stages.update(e._pidx_info(e._pidx(out, n_hbv, inv), n_hbv, inv, download))
             if ebcx:
-                ne_hbv = int(h.n_edges)
-                inv = np.zeros(max(ne_hbv, 1), dtype=np.int32)
-                rc = e.lib.snk_hbv_involution(C.byref(h), self.n_unitigs, inv.ctypes.data, err, 512)
-                eb = _lib.SnkDevEbcx()
-                if not rc:
-                    rc = e.lib.snk_dev_edge_barcodes(e._ctx, C.byref(out), bc.data_ptr(), ne_hbv, inv.ctypes.data,
-                                                     _lib.EBC_GENERAL_SORT if ebcx == "general" else 0, C.byref(eb), e._stream(), err, 512)
-                if rc:
-                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                eb_stats = _ebcx_stats(eb)
-                if download:
-                    eb_arrays = (self._dl(eb.ebc_off, (ne_hbv + 1) * 8, np.uint64, (ne_hbv + 1,)), self._dl(eb.ebc, int(eb.n_ebc) * 4, np.int32, (int(eb.n_ebc),)))
-            px_stats = None
+                stages.update(e._ebcx_info(e._ebcx(out, bc, n_hbv, inv, ebcx == "general"), n_hbv, download))
             if pathsx:
-                zx = _lib.SnkDevPathsx()
-                rc = e.lib.snk_dev_paths_zip(e._ctx, C.byref(out), C.byref(h), C.byref(zx), e._stream(), err, 512)
-                if rc:
-                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                px_stats = _pathsx_stats(zx)
-                if download:
-                    px_arrays = (self._dl(zx.index, int(zx.n_index) * 8, np.int64, (int(zx.n_index),)), self._dl(zx.data, int(zx.n_bytes), np.uint8, (int(zx.n_bytes),)))
-            ext_stats = None
+                stages.update(e._pathsx_info(e._zip(out, graph[3]), download, dev_key="pathsx_dev"))
             if extend:
-                xo = _lib.SnkDevExtend()
-                rc = e.lib.snk_dev_extend_paths(e._ctx, int(self.K), C.byref(r), self.n_unitigs, self.raw.unitig_off, self.raw.unitig_bases, C.byref(h),
-                                                C.byref(out), _lib.EXT_BACK if extend == "back" else 0, C.byref(xo), e._stream(), err, 512)
-                if rc:
-                    raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                ext_stats = _extend_stats(xo)
-                xp = xo.paths
-                if download:
-                    xn, xt = int(xp.n_reads), int(xp.n_edges_total)
-                    ext_arrays = (self._dl(xp.offset, xn * 4, np.int32, (xn,)), self._dl(xp.n_edges, xn * 4, np.uint32, (xn,)), self._dl(xp.edges, xt * 4, np.int32, (xt,)))
-                ext_px_stats = None
+                xo = e._extend(K, r, graph, out, extend == "back")
+                stages.update(e._extend_info(xo, download))
                 if pathsx:
-                    zx2 = _lib.SnkDevPathsx()
-                    rc = e.lib.snk_dev_paths_zip(e._ctx, C.byref(xp), C.byref(h), C.byref(zx2), e._stream(), err, 512)
-                    if rc:
-                        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-                    ext_px_stats = _pathsx_stats(zx2)
-                    if download:
-                        ext_px_arrays = (self._dl(zx2.index, int(zx2.n_index) * 8, np.int64, (int(zx2.n_index),)),
-                                         self._dl(zx2.data, int(zx2.n_bytes), np.uint8, (int(zx2.n_bytes),)))
+                    stages.update(e._pathsx_info(e._zip(xo.paths, graph[3]), download, prefix="extended_"))
         finally:
             e.lib.snk_hbv_free(C.byref(h))
-        n, tot = int(out.n_reads), int(out.n_edges_total)
+        info = dict(dict_ms=float(out.dict_ms), path_ms=float(out.path_ms), bcs_ms=float(out.bcs_ms), hbv_device_ms=float(ms.value),
+                    dict_slots=int(out.dict_slots), lookup=("index" if out.lookup_index else "kmer_dictionary"), n_slow=int(out.n_slow),
+                    retries=int(out.retries), n_edges_total=int(out.n_edges_total), n_unitig_bcs=int(out.n_unitig_bcs))
+        info.update(stages)
         if not download:          # timings only (bench.py: the results stay on the device)
-            info = dict(dict_ms=float(out.dict_ms), path_ms=float(out.path_ms), bcs_ms=float(out.bcs_ms), hbv_device_ms=float(ms.value),
-                        dict_slots=int(out.dict_slots), n_edges_total=tot, n_unitig_bcs=int(out.n_unitig_bcs), n_slow=int(out.n_slow),
-                        lookup=("index" if out.lookup_index else "kmer_dictionary"), retries=int(out.retries))
-            if dups is not None:
-                info["dups"] = {k: v for k, v in dups.items() if k != "dup"}
-            if bads is not None:
-                info["bads"], info["bads_dev"] = bads, bd
-            if pidx is not None:
-                info["pidx"] = pidx
-            if px_stats is not None:
-                info["pathsx_stats"], info["pathsx_dev"] = px_stats, zx     # (zx: device memory of the context, for Engine.unzip_paths)
-            if eb_stats is not None:
-                info["ebcx_stats"] = eb_stats
-            if ext_stats is not None:
-                info["extend_stats"] = ext_stats
-                if ext_px_stats is not None:
-                    info["extended_pathsx_stats"] = ext_px_stats
             return None, None, None, info
-        off = self._dl(out.offset, n * 4, np.int32, (n,))
-        ne = self._dl(out.n_edges, n * 4, np.uint32, (n,))
-        edges = self._dl(out.edges, tot * 4, np.int32, (tot,))
-        info = dict(dict_ms=float(out.dict_ms), path_ms=float(out.path_ms), bcs_ms=float(out.bcs_ms), hbv_device_ms=float(ms.value), dict_slots=int(out.dict_slots), lookup=("index" if out.lookup_index else "kmer_dictionary"),
-                    n_slow=int(out.n_slow), retries=int(out.retries))
-        if dups is not None:
-            info["dups"] = dups
-        if bads is not None:
-            info["bads"] = bads
-        if pidx is not None:
-            info["pidx"], info["paths_index"], info["countsb"], info["inv"] = pidx, pidx_arrays[:2], pidx_arrays[2], pidx_arrays[3]
-        if px_stats is not None:
-            info["pathsx"], info["pathsx_stats"] = px_arrays, px_stats
-        if eb_stats is not None:
-            info["ebcx"], info["ebcx_stats"] = eb_arrays, eb_stats
-        if ext_stats is not None:
-            info["extended"], info["extend_stats"] = ext_arrays, ext_stats
-            if ext_px_stats is not None:
-                info["extended_pathsx"], info["extended_pathsx_stats"] = ext_px_arrays, ext_px_stats
         if unitig_bcs and out.unitig_bc_off:
-            nb = int(out.n_unitig_bcs)
-            info["unitig_bcs"] = (self._dl(out.unitig_bc_off, (self.n_unitigs + 1) * 8, np.uint64, (self.n_unitigs + 1,)),
-                                  self._dl(out.unitig_bcs, nb * 4, np.uint32, (nb,)))
-        return off, ne, edges, info
+            info["unitig_bcs"] = (e._fetch(out.unitig_bc_off, self.n_unitigs + 1, np.uint64), e._fetch(out.unitig_bcs, out.n_unitig_bcs, np.uint32))
+        return (*e._fetch_paths(out), info)
 
     def check(self, reads: "_lib.SnkDevReads | None" = None, ordered: bool = True) -> dict:
         """snk_dev_check_graph over this result's own arrays (include/snk.h, "the graph verifier"): the reassembly invariants of the
@@ -376,15 +298,17 @@ class PatchResult:
     def write(self, path_hbv, path_inv=None, path_hbx=None):
         """a.hbv (+ a.inv, a.hbx) of the patched graph, as DF writes them"""
         off, bases = self.unitigs_bvcomp()
-        err = C.create_string_buffer(512)
         h = _lib.SnkHbv.from_buffer_copy(self.h)
         h.bvcomp_order = None
-        rc = self._e.lib.snk_write_hbv(str(path_hbv).encode(), str(path_inv).encode() if path_inv else None, self.K, len(off) - 1, off.ctypes.data, bases.ctypes.data,
-                                       C.byref(h), err, 512)
-        if not rc and path_hbx:
-            rc = self._e.lib.snk_write_hbx(str(path_hbx).encode(), self.K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        unitigs = (self.K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h))
+        _lib.call(self._e.lib.snk_write_hbv, str(path_hbv).encode(), str(path_inv).encode() if path_inv else None, *unitigs)
+        if path_hbx:
+            _lib.call(self._e.lib.snk_write_hbx, str(path_hbx).encode(), *unitigs)
+
+
+def _graph(h: "_lib.SnkHbv", unitig_off, unitig_bases):
+    """(n_unitigs, unitig_off, unitig_bases, byref(h)): the graph arguments of the device stages, from tensors"""
+    return int(unitig_off.shape[0]) - 1, unitig_off.data_ptr(), unitig_bases.data_ptr(), C.byref(h)
 
 
 def _ebcx_stats(eb: "_lib.SnkDevEbcx") -> dict:
@@ -425,10 +349,7 @@ class Engine:
         self.lib = _lib.load()
         self.device = torch.cuda.current_device() if device is None else device
         h = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_ctx_create(self.device, C.byref(h), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(self.lib.snk_ctx_create, self.device, C.byref(h))
         self._ctx = h
         _LIVE.add(self)
 
@@ -442,10 +363,7 @@ class Engine:
 
     # ---- tuning (include/snk.h "tuning"): options live in the context, not in the environment
     def set_option(self, name: str, value: int):
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_ctx_set_option(self._ctx, name.encode(), int(value), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(self.lib.snk_ctx_set_option, self._ctx, name.encode(), int(value))
 
     def clear_option(self, name: str | None = None):
         """Back to the library's own choice (None: every option)."""
@@ -477,10 +395,7 @@ class Engine:
             if not hasattr(t, k) or k.startswith("last_") or k == "reserved":
                 raise AttributeError(k)
             setattr(t, k, int(v))
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_ctx_set_tuning(self._ctx, C.byref(t), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(self.lib.snk_ctx_set_tuning, self._ctx, C.byref(t))
 
     def get_tuning(self) -> dict:
         """What is pinned (0 = the library chooses) and, in last_*, what the context's last call ran with."""
@@ -491,10 +406,7 @@ class Engine:
     def reserve(self, n_bytes: int):
         """Map n_bytes of device memory into the context's scratch arena now and keep them mapped between calls (snk_ctx_reserve): a call
         that outgrows the arena otherwise pays the driver ~25-30 ms per new GB inside the call."""
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_ctx_reserve(self._ctx, int(n_bytes), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(self.lib.snk_ctx_reserve, self._ctx, int(n_bytes))
 
     def release_cache(self):
         """Hand the context's cached, unused device memory back (snk_ctx_trim): for callers that change problem size and share the GPU."""
@@ -517,34 +429,100 @@ class Engine:
     def _download(self, dptr, hptr, nbytes):
         _lib.check(self.lib.snk_dev_download(self._ctx, dptr, hptr, nbytes, self._stream()))
 
+    def _call(self, fn, *args):
+        """fn(ctx, *args, stream, err, errcap): the shape of nearly every device entry point"""
+        _lib.call(fn, self._ctx, *args, self._stream())
+
+    def _fetch(self, ptr, count, dtype) -> np.ndarray:
+        """count elements of device memory as a numpy array of its own (no copy is issued for none)"""
+        out = np.empty(int(count), dtype=dtype)
+        if out.size:
+            self._download(ptr, out.ctypes.data, out.nbytes)
+        return out
+
+    def _fetch_paths(self, p: "_lib.SnkDevPaths"):
+        """-> (offset i32[n], n_edges u32[n], edges i32[sum])"""
+        return self._fetch(p.offset, p.n_reads, np.int32), self._fetch(p.n_edges, p.n_reads, np.uint32), self._fetch(p.edges, p.n_edges_total, np.int32)
+
+    def _fetch_pathsx(self, zx: "_lib.SnkDevPathsx"):
+        """-> (index i64[], data u8[])"""
+        return self._fetch(zx.index, zx.n_index, np.int64), self._fetch(zx.data, zx.n_bytes, np.uint8)
+
+    # ---- the stages after the graph.  The Python face of a stage is builder, core, fetch: dev_reads / dev_paths make the input structs,
+    # one core per stage takes ctypes structs (graph = n_unitigs, unitig_off, unitig_bases, byref(h)) and returns the stage's out-struct,
+    # and _fetch brings down what the caller asked for.  Result.path_reads runs the same cores over the paths it has just made and adds
+    # each stage's *_info to its info dict.
+    def _stage(self, fn, out, *args):
+        self._call(fn, *args, C.byref(out))
+        return out
+
+    def _dups(self, r, p):
+        return self._stage(self.lib.snk_dev_mark_dups, _lib.SnkDevDups(), C.byref(r), C.byref(p))
+
+    def _bads(self, K, r, graph, p, x):
+        return self._stage(self.lib.snk_dev_mark_bads, _lib.SnkDevBads(), int(K), C.byref(r), *graph, C.byref(p), _lib.BADS_X if x else 0)
+
+    def _pidx(self, p, n_hbv, inv):
+        return self._stage(self.lib.snk_dev_paths_index, _lib.SnkDevPidx(), C.byref(p), n_hbv, inv.ctypes.data)
+
+    def _ebcx(self, p, bc, n_hbv, inv, general):
+        return self._stage(self.lib.snk_dev_edge_barcodes, _lib.SnkDevEbcx(), C.byref(p), bc.data_ptr(), n_hbv, inv.ctypes.data,
+                           _lib.EBC_GENERAL_SORT if general else 0)
+
+    def _zip(self, p, h_ref):
+        return self._stage(self.lib.snk_dev_paths_zip, _lib.SnkDevPathsx(), C.byref(p), h_ref)
+
+    def _extend(self, K, r, graph, p, back):
+        return self._stage(self.lib.snk_dev_extend_paths, _lib.SnkDevExtend(), int(K), C.byref(r), *graph, C.byref(p), _lib.EXT_BACK if back else 0)
+
+    def _dups_info(self, dd, download):
+        d = dict(interdup_rate=float(dd.interdup_rate), n_dup_pairs=int(dd.n_dup_pairs), n_dup_reads=int(dd.n_dup_reads),
+                 n_interdup_reads=int(dd.n_interdup_reads), n_art_pairs=int(dd.n_art_pairs), n_placed=int(dd.n_placed), ms=float(dd.ms))
+        if download:
+            d["dup"] = self._fetch(dd.dup, dd.n_pairs, np.uint8)
+        return {"dups": d}
+
+    def _bads_info(self, bd, download):
+        got, stats = self._bads_result(bd, download)
+        return {"bads": dict(stats, bad=got)} if download else {"bads": stats, "bads_dev": got}
+
+    def _pidx_info(self, px, n_hbv, inv, download):
+        d = {"pidx": dict(n_hbv_edges=n_hbv, n_entries=int(px.n_entries), n_empty_edges=int(px.n_empty_edges), key_bits=int(px.key_bits), ms=float(px.ms))}
+        if download:
+            d.update(paths_index=(self._fetch(px.index_off, n_hbv + 1, np.uint64), self._fetch(px.index_ids, px.n_entries, np.uint64)),
+                     countsb=self._fetch(px.counts, n_hbv, np.int32), inv=inv[:n_hbv].copy())
+        return d
+
+    def _ebcx_info(self, eb, n_hbv, download):
+        d = {"ebcx_stats": _ebcx_stats(eb)}
+        if download:
+            d["ebcx"] = (self._fetch(eb.ebc_off, n_hbv + 1, np.uint64), self._fetch(eb.ebc, eb.n_ebc, np.int32))
+        return d
+
+    def _pathsx_info(self, zx, download, prefix="", dev_key=None):
+        d = {prefix + "pathsx_stats": _pathsx_stats(zx)}
+        if download:
+            d[prefix + "pathsx"] = self._fetch_pathsx(zx)
+        elif dev_key:
+            d[dev_key] = zx         # (device memory of the context, for Engine.unzip_paths)
+        return d
+
+    def _extend_info(self, xo, download):
+        d = {"extend_stats": _extend_stats(xo)}
+        if download:
+            d["extended"] = self._fetch_paths(xo.paths)
+        return d
+
     # ---- compressed read paths (ReadPathVecX) from and to device-resident paths
     def zip_paths(self, h: "_lib.SnkHbv", offset: torch.Tensor, n_edges: torch.Tensor, edges: torch.Tensor, start: torch.Tensor | None = None,
                   download: bool = True):
         """snk_dev_paths_zip over paths held in torch tensors on this engine's device: offset i32[n], n_edges i32[n] (read as u32), edges
         i32[sum], start i64[n + 1] (None: the paths follow each other), on the graph h (graphio.hbv_handle).  -> (index i64[], data u8[],
         stats) on the host, or with download=False (SnkDevPathsx, stats): device memory of the context, valid until its next top-level call."""
-        n = int(n_edges.shape[0])
-        if start is None:
-            start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
-            start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
-        p = _lib.SnkDevPaths()
-        p.n_reads, p.n_edges_total = n, int(edges.shape[0])
-        p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
-        zx = _lib.SnkDevPathsx()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_paths_zip(self._ctx, C.byref(p), C.byref(h), C.byref(zx), self._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        p, start = dev_paths(offset, n_edges, edges, start)
+        zx = self._zip(p, C.byref(h))
         stats = _pathsx_stats(zx)
-        if not download:
-            return zx, stats
-        index = np.empty(int(zx.n_index), np.int64)
-        data = np.empty(int(zx.n_bytes), np.uint8)
-        if index.size:
-            self._download(zx.index, index.ctypes.data, index.nbytes)
-        if data.size:
-            self._download(zx.data, data.ctypes.data, data.nbytes)
-        return index, data, stats
+        return (*self._fetch_pathsx(zx), stats) if download else (zx, stats)
 
     def unzip_paths(self, h: "_lib.SnkHbv", index, data=None, n_reads: int | None = None, download: bool = True):
         """snk_dev_paths_unzip: a ReadPathVecX on the device -- index i64[] and data u8[] as torch tensors with n_reads, or the SnkDevPathsx
@@ -556,19 +534,8 @@ class Engine:
             zx = _lib.SnkDevPathsx()
             zx.n_reads, zx.n_bytes, zx.n_index = int(n_reads), int(data.shape[0]), int(index.shape[0])
             zx.data, zx.index = data.data_ptr(), index.data_ptr()
-        out = _lib.SnkDevPaths()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_paths_unzip(self._ctx, C.byref(zx), C.byref(h), C.byref(out), self._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        if not download:
-            return out, float(out.path_ms)
-        n, tot = int(out.n_reads), int(out.n_edges_total)
-        off, ne, edges = np.empty(n, np.int32), np.empty(n, np.uint32), np.empty(tot, np.int32)
-        for a, ptr in ((off, out.offset), (ne, out.n_edges), (edges, out.edges)):
-            if a.size:
-                self._download(ptr, a.ctypes.data, a.nbytes)
-        return off, ne, edges, float(out.path_ms)
+        out = self._stage(self.lib.snk_dev_paths_unzip, _lib.SnkDevPaths(), C.byref(zx), C.byref(h))
+        return (*self._fetch_paths(out), float(out.path_ms)) if download else (out, float(out.path_ms))
 
     # ---- path extension (StageExtension) over device-resident reads, unitigs and paths
     def extend_paths(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, rows: torch.Tensor, read_len: int,
@@ -579,53 +546,17 @@ class Engine:
         quals u8[n, stride], lens i16[n] or None) and their paths (offset i32[n], n_edges i32[n] read as u32, edges i32[sum], start i64[n + 1]
         or None: the paths follow each other).  back: SNK_EXT_BACK.  -> (offset i32[n], n_edges u32[n], edges i32[sum], stats) on the host;
         download=False: (SnkDevExtend, stats), device memory of the context, valid until its next top-level call."""
-        n = int(n_edges.shape[0])
-        if start is None:
-            start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
-            start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
-        r = _lib.SnkDevReads()
-        r.n_reads, r.rows, r.row_words, r.read_len = int(rows.shape[0]), rows.data_ptr(), (int(rows.shape[1]) if rows.dim() > 1 else 0), int(read_len)
-        r.quals, r.qstride = (quals.data_ptr(), int(quals.shape[1])) if quals is not None else (None, 0)
-        if lens is not None:
-            r.lens = lens.data_ptr()
-        p = _lib.SnkDevPaths()
-        p.n_reads, p.n_edges_total = n, int(edges.shape[0])
-        p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
-        x = _lib.SnkDevExtend()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_extend_paths(self._ctx, int(K), C.byref(r), int(unitig_off.shape[0]) - 1, unitig_off.data_ptr(), unitig_bases.data_ptr(),
-                                           C.byref(h), C.byref(p), _lib.EXT_BACK if back else 0, C.byref(x), self._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        p, start = dev_paths(offset, n_edges, edges, start)
+        x = self._extend(K, dev_reads(rows, read_len, quals, lens), _graph(h, unitig_off, unitig_bases), p, back)
         stats = _extend_stats(x)
-        if not download:
-            return x, stats
-        m, tot = int(x.paths.n_reads), int(x.paths.n_edges_total)
-        off, ne, ed = np.empty(m, np.int32), np.empty(m, np.uint32), np.empty(tot, np.int32)
-        for a, ptr in ((off, x.paths.offset), (ne, x.paths.n_edges), (ed, x.paths.edges)):
-            if a.size:
-                self._download(ptr, a.ctypes.data, a.nbytes)
-        return off, ne, ed, stats
+        return (*self._fetch_paths(x.paths), stats) if download else (x, stats)
 
     # ---- MarkBads (the first step of StageFindPatch) over device-resident unitigs and paths, and reads that are resident or in the stage's files
     def _paths_struct(self, offset, n_edges, edges, start):
-        n = int(n_edges.shape[0])
-        if start is None:
-            start = torch.zeros(n + 1, dtype=torch.int64, device=n_edges.device)
-            start[1:] = torch.cumsum(n_edges.to(torch.int64) & 0xFFFFFFFF, 0)
-        p = _lib.SnkDevPaths()
-        p.n_reads, p.n_edges_total = n, int(edges.shape[0])
-        p.offset, p.n_edges, p.start, p.edges = offset.data_ptr(), n_edges.data_ptr(), start.data_ptr(), edges.data_ptr()
-        return p, start
+        return dev_paths(offset, n_edges, edges, start)
 
     def _bads_result(self, b: "_lib.SnkDevBads", download: bool):
-        stats = _bads_stats(b)
-        if not download:
-            return b, stats
-        bad = np.empty(int(b.n_pairs), np.uint8)
-        if bad.size:
-            self._download(b.bad, bad.ctypes.data, bad.nbytes)
-        return bad, stats
+        return (self._fetch(b.bad, b.n_pairs, np.uint8) if download else b), _bads_stats(b)
 
     def mark_bads(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, rows: torch.Tensor, read_len: int,
                   quals: torch.Tensor, lens: torch.Tensor | None, offset: torch.Tensor, n_edges: torch.Tensor, edges: torch.Tensor,
@@ -633,19 +564,8 @@ class Engine:
         """snk_dev_mark_bads -- MarkBads (10X/SecretOps.cc:70-107; x=True: the ReadPathVecX overload, :22-59, int16 offsets: what a stock DF
         writes as a.bad) -- over tensors on this engine's device, the arguments of extend_paths.  -> (bad u8[n / 2], stats) on the host;
         download=False: (SnkDevBads, stats), device memory of the context, valid until its next top-level call."""
-        r = _lib.SnkDevReads()
-        r.n_reads, r.rows, r.row_words, r.read_len = int(rows.shape[0]), rows.data_ptr(), (int(rows.shape[1]) if rows.dim() > 1 else 0), int(read_len)
-        r.quals, r.qstride = (quals.data_ptr(), int(quals.shape[1])) if quals is not None else (None, 0)
-        if lens is not None:
-            r.lens = lens.data_ptr()
-        p, start = self._paths_struct(offset, n_edges, edges, start)
-        b = _lib.SnkDevBads()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_mark_bads(self._ctx, int(K), C.byref(r), int(unitig_off.shape[0]) - 1, unitig_off.data_ptr(), unitig_bases.data_ptr(),
-                                        C.byref(h), C.byref(p), _lib.BADS_X if x else 0, C.byref(b), self._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        return self._bads_result(b, download)
+        p, start = dev_paths(offset, n_edges, edges, start)
+        return self._bads_result(self._bads(K, dev_reads(rows, read_len, quals, lens), _graph(h, unitig_off, unitig_bases), p, x), download)
 
     def mark_bads_df(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, files, offset: torch.Tensor,
                      n_edges: torch.Tensor, edges: torch.Tensor, start: torch.Tensor | None = None, first: int = 0, n: int | None = None, read_len: int = 0,
@@ -653,14 +573,11 @@ class Engine:
         """snk_dev_mark_bads_df: the same over reads [first, first + n) of an opened triple (dfin.DfFiles), decoded again slab by slab -- for
         a job that kept no quality rows.  The paths are those of these reads.  first and slab_reads must be even.  Results as mark_bads."""
         n = int(n_edges.shape[0]) if n is None else int(n)
-        p, start = self._paths_struct(offset, n_edges, edges, start)
+        p, start = dev_paths(offset, n_edges, edges, start)
         torch.cuda.current_stream(self.device).synchronize()          # (the call works on the ring's own stream: its inputs must be complete)
         b = _lib.SnkDevBads()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_mark_bads_df(self._ctx, int(K), files._h, int(first), n, int(read_len), int(threads), int(slab_reads), int(unitig_off.shape[0]) - 1,
-                                           unitig_off.data_ptr(), unitig_bases.data_ptr(), C.byref(h), C.byref(p), _lib.BADS_X if x else 0, C.byref(b), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(self.lib.snk_dev_mark_bads_df, self._ctx, int(K), files._h, int(first), n, int(read_len), int(threads), int(slab_reads),
+                  *_graph(h, unitig_off, unitig_bases), C.byref(p), _lib.BADS_X if x else 0, C.byref(b))
         return self._bads_result(b, download)
 
     # ---- gap patches into the graph (StageInsertPatch)
@@ -687,30 +604,17 @@ class Engine:
         cb = own(closures[1], torch.uint8)
         p_off, p_n, p_edges = own(paths[0], torch.int32), own(paths[1], torch.int32), own(paths[2], torch.int32)
         n = int(p_n.shape[0])
-        if len(paths) > 3 and paths[3] is not None:
-            p_start = own(paths[3], torch.int64)
-        else:
-            p_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-            p_start[1:] = torch.cumsum(p_n.to(torch.int64) & 0xFFFFFFFF, 0)
-        err = C.create_string_buffer(512)
-
-        def call(fn, *args):
-            rc = fn(*args, self._stream(), err, 512)
-            if rc:
-                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-
+        ip, p_start = dev_paths(p_off, p_n, p_edges, own(paths[3], torch.int64) if len(paths) > 3 and paths[3] is not None else None)
         # ---- pieces, into tensors of the engine
         plan = _lib.SnkPatchPlan()
-        rc = self.lib.snk_patch_plan_sizes(int(K), U_old, uoff_h.ctypes.data, C.byref(h_old), n_cl, coff_h.ctypes.data, C.byref(plan), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(self.lib.snk_patch_plan_sizes, int(K), U_old, uoff_h.ctypes.data, C.byref(h_old), n_cl, coff_h.ctypes.data, C.byref(plan))
         n_pieces, n_lmax = int(plan.n_pieces), int(plan.n_lonely_max)
         rows = torch.empty((n_pieces, 16), dtype=torch.int32, device=dev)
         lens = torch.empty((n_pieces,), dtype=torch.int16, device=dev)
         lonely = torch.empty((max(n_lmax, 1), 2), dtype=torch.int64, device=dev)
         pc = _lib.SnkDevPieces()
-        call(self.lib.snk_dev_patch_pieces, self._ctx, int(K), U_old, uoff_h.ctypes.data, ub_old.data_ptr(), C.byref(h_old), n_cl, coff_h.ctypes.data, cb.data_ptr(),
-             n_pieces, rows.data_ptr(), lens.data_ptr(), n_lmax, lonely.data_ptr(), C.byref(pc))
+        self._call(self.lib.snk_dev_patch_pieces, int(K), U_old, uoff_h.ctypes.data, ub_old.data_ptr(), C.byref(h_old), n_cl, coff_h.ctypes.data, cb.data_ptr(),
+                   n_pieces, rows.data_ptr(), lens.data_ptr(), n_lmax, lonely.data_ptr(), C.byref(pc))
         # ---- the graph: the count stage on the pieces, the K-base sequences it leaves out, the ids
         if n_pieces:
             res = self.count_graph(rows, 256, lens=lens, good_len=lens, params=Params(K=int(K), min_freq=1, min_bc=0))
@@ -718,18 +622,15 @@ class Engine:
         else:
             raw, count_ms = _lib.SnkDevResult(), 0.0
         mu = _lib.SnkDevPatchUnitigs()
-        call(self.lib.snk_dev_patch_merge, self._ctx, int(K), C.byref(raw), lonely.data_ptr(), int(pc.n_lonely), C.byref(mu))
+        self._call(self.lib.snk_dev_patch_merge, int(K), C.byref(raw), lonely.data_ptr(), int(pc.n_lonely), C.byref(mu))
         U_new, tot_new = int(mu.n_unitigs), int(mu.unitig_total_bases)
         h_new = _lib.SnkHbv()
         hbv_ms = C.c_float(0)
-        call(self.lib.snk_dev_hbv, self._ctx, int(K), U_new, mu.unitig_off, mu.unitig_bases, C.byref(h_new), C.byref(hbv_ms))
+        self._call(self.lib.snk_dev_hbv, int(K), U_new, mu.unitig_off, mu.unitig_bases, C.byref(h_new), C.byref(hbv_ms))
         try:
-            ip = _lib.SnkDevPaths()
-            ip.n_reads, ip.n_edges_total = n, int(p_edges.shape[0])
-            ip.offset, ip.n_edges, ip.start, ip.edges = p_off.data_ptr(), p_n.data_ptr(), p_start.data_ptr(), p_edges.data_ptr()
             px = _lib.SnkDevPatched()
-            call(self.lib.snk_dev_patch_paths, self._ctx, int(K), U_old, uoff_old.data_ptr(), ub_old.data_ptr(), C.byref(h_old), U_new, mu.unitig_off, mu.unitig_bases,
-                 C.byref(h_new), C.byref(ip), C.byref(px))
+            self._call(self.lib.snk_dev_patch_paths, int(K), U_old, uoff_old.data_ptr(), ub_old.data_ptr(), C.byref(h_old), U_new, mu.unitig_off, mu.unitig_bases,
+                       C.byref(h_new), C.byref(ip), C.byref(px))
             # ---- everything into memory the result owns
             def take(ptr, count, dt):
                 nbytes = count * torch.empty((), dtype=dt).element_size()
@@ -739,12 +640,9 @@ class Engine:
             out.unitig_off, out.unitig_bases = take(mu.unitig_off, U_new + 1, torch.int64), take(mu.unitig_bases, tot_new, torch.uint8)
             out.offset, out.n_edges, out.start, out.edges = take(px.paths.offset, n, torch.int32), take(px.paths.n_edges, n, torch.int32), \
                 take(px.paths.start, n + 1, torch.int64), take(px.paths.edges, tot, torch.int32)
-            out.to3_off = take(px.to3_off, E_old + 1, torch.int64).cpu().numpy().view(np.uint64)
-            out.to3, out.left3 = take(px.to3, n_to3, torch.int32).cpu().numpy(), take(px.left3, E_old, torch.int32).cpu().numpy()
+            out.to3_off, out.to3, out.left3 = self._fetch(px.to3_off, E_old + 1, np.uint64), self._fetch(px.to3, n_to3, np.int32), self._fetch(px.left3, E_old, np.int32)
             inv = np.zeros(max(int(h_new.n_edges), 1), np.int32)
-            rc = self.lib.snk_hbv_involution(C.byref(h_new), U_new, inv.ctypes.data, err, 512)
-            if rc:
-                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+            _lib.call(self.lib.snk_hbv_involution, C.byref(h_new), U_new, inv.ctypes.data)
             out.inv = inv[:int(h_new.n_edges)]
             out.stats = dict(n_pieces=n_pieces, n_unitig_pieces=int(plan.n_unitig_pieces), n_junctions=int(plan.n_junctions), n_closure_pieces=int(plan.n_closure_pieces),
                              n_lonely=int(pc.n_lonely), n_added=int(mu.n_added), n_first=int(px.n_first), n_later=int(px.n_later), n_cleared=int(px.n_cleared),
@@ -789,70 +687,38 @@ class Engine:
                     read_index_base: int = 0, group: torch.Tensor | None = None) -> Result:
         params = params or Params()
         assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous()
-        r = _lib.SnkDevReads()
-        r.n_reads = rows.shape[0]
-        r.rows = rows.data_ptr()
-        r.row_words = rows.shape[1]
-        r.read_len = read_len
         if lens is not None:
             assert lens.dtype == torch.int16 and lens.is_cuda
-            r.lens = lens.data_ptr()
         if quals is not None:
             assert quals.dtype == torch.uint8 and quals.is_cuda and quals.is_contiguous()
-            r.quals = quals.data_ptr()
-            r.qstride = quals.shape[1]
         if good_len is not None:
             assert good_len.dtype == torch.int16 and good_len.is_cuda
-            r.good_len = good_len.data_ptr()
         if bc is not None:
             assert bc.dtype == torch.int32 and bc.is_cuda
-            r.bc = bc.data_ptr()
-        r.ign_bc_below = ign_bc_below
-        r.read_index_base = read_index_base
         if group is not None:
             assert group.dtype == torch.int32 and group.is_cuda and group.is_contiguous()
-            r.group = group.data_ptr()
-        return self.count_graph_reads(r, params)
+        return self.count_graph_reads(dev_reads(rows, read_len, quals, lens, good_len, bc, group, ign_bc_below, read_index_base), params)
 
     # ---- streamed input: the job's reads arrive slab by slab (snk_dev_stream_begin / _append / _finish)
     def stream_begin(self, read_len: int, total_reads_ub: int, has_bc: bool = True, params: Params | None = None):
         self._stream_params = params or Params()
         p = self._stream_params.to_c()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_stream_begin(self._ctx, C.byref(p), int(read_len), int(total_reads_ub), 1 if has_bc else 0, self._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        self._call(self.lib.snk_dev_stream_begin, C.byref(p), int(read_len), int(total_reads_ub), 1 if has_bc else 0)
 
     def stream_append(self, rows: torch.Tensor, read_len: int, quals: torch.Tensor | None = None, bc: torch.Tensor | None = None,
                       lens: torch.Tensor | None = None, good_len: torch.Tensor | None = None, ign_bc_below: int = 0, read_index_base: int = 0):
         """One slab (asynchronous: its tensors must stay alive until the engine's stream has passed the call)."""
         assert rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous()
-        r = _lib.SnkDevReads()
-        r.n_reads, r.rows, r.row_words, r.read_len = rows.shape[0], rows.data_ptr(), rows.shape[1], read_len
-        if lens is not None:
-            r.lens = lens.data_ptr()
         if quals is not None:
             assert quals.dtype == torch.uint8 and quals.is_cuda and quals.is_contiguous()
-            r.quals, r.qstride = quals.data_ptr(), quals.shape[1]
-        if good_len is not None:
-            r.good_len = good_len.data_ptr()
-        if bc is not None:
-            r.bc = bc.data_ptr()
-        r.ign_bc_below, r.read_index_base = ign_bc_below, read_index_base
-        self.stream_append_reads(r)
+        self.stream_append_reads(dev_reads(rows, read_len, quals, lens, good_len, bc, None, ign_bc_below, read_index_base))
 
     def stream_append_reads(self, r: "_lib.SnkDevReads"):
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_stream_append(self._ctx, C.byref(r), self._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        self._call(self.lib.snk_dev_stream_append, C.byref(r))
 
     def stream_finish(self) -> Result:
         raw = _lib.SnkDevResult()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_stream_finish(self._ctx, C.byref(raw), self._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        self._call(self.lib.snk_dev_stream_finish, C.byref(raw))
         return Result(self, raw, self._stream_params.K, self._stream_params)
 
     def count_graph_reads(self, r: "_lib.SnkDevReads", params: Params | None = None) -> Result:
@@ -860,10 +726,7 @@ class Engine:
         params = params or Params()
         p = params.to_c()
         raw = _lib.SnkDevResult()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_count_graph(self._ctx, C.byref(r), C.byref(p), C.byref(raw), self._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        self._call(self.lib.snk_dev_count_graph, C.byref(r), C.byref(p), C.byref(raw))
         return Result(self, raw, params.K, params)
 
     # ---- the graph verifier (snk_dev_check_graph)
@@ -876,11 +739,7 @@ class Engine:
         ci.n_unitigs, ci.unitig_off, ci.unitig_bases, ci.unitig_group = n_unitigs, unitig_off, unitig_bases, unitig_group
         rep = _lib.SnkCheckReport()
         rep.struct_size = C.sizeof(_lib.SnkCheckReport)
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_check_graph(self._ctx, C.byref(ci), C.byref(reads) if reads is not None else None, C.byref(rep), self._stream(),
-                                          err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        self._call(self.lib.snk_dev_check_graph, C.byref(ci), C.byref(reads) if reads is not None else None, C.byref(rep))
         return rep.to_dict()
 
     def check_graph(self, keys: torch.Tensor, counts: torch.Tensor, ctx: torch.Tensor, unitig_off: torch.Tensor, unitig_bases: torch.Tensor,

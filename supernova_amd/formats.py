@@ -19,10 +19,7 @@ def read_fastb(path):
     lib = _lib.load()
     n, mx = C.c_uint64(0), C.c_uint32(0)
     pl, pr = C.POINTER(C.c_uint16)(), C.POINTER(C.c_uint32)()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_read_fastb(str(path).encode(), C.byref(n), C.byref(mx), C.byref(pl), C.byref(pr), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_read_fastb, str(path).encode(), C.byref(n), C.byref(mx), C.byref(pl), C.byref(pr))
     rw = max(1, (mx.value + 15) // 16)
     lens = np.ctypeslib.as_array(pl, shape=(max(n.value, 1),))[: n.value].copy()
     rows = np.ctypeslib.as_array(pr, shape=(max(n.value * rw, 1),))[: n.value * rw].copy().reshape(n.value, rw)
@@ -34,10 +31,7 @@ def read_fastb(path):
 def read_qualp(path, n_reads: int, qstride: int) -> np.ndarray:
     lib = _lib.load()
     q = np.zeros((n_reads, qstride), dtype=np.uint8)
-    err = C.create_string_buffer(512)
-    rc = lib.snk_read_qualp(str(path).encode(), n_reads, qstride, q.ctypes.data, err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_read_qualp, str(path).encode(), n_reads, qstride, q.ctypes.data)
     return q
 
 
@@ -46,8 +40,5 @@ def read_bci(path, n_reads: int):
     lib = _lib.load()
     bc = np.zeros(n_reads, dtype=np.int32)
     nb = C.c_uint64(0)
-    err = C.create_string_buffer(512)
-    rc = lib.snk_read_bci(str(path).encode(), n_reads, bc.ctypes.data, C.byref(nb), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_read_bci, str(path).encode(), n_reads, bc.ctypes.data, C.byref(nb))
     return bc, int(nb.value)

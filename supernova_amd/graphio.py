@@ -43,10 +43,7 @@ def write_bv(path: str, off: np.ndarray, bases: np.ndarray) -> None:
     lib = _lib.load()
     off = np.ascontiguousarray(off, dtype=np.uint64)
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    err = C.create_string_buffer(512)
-    rc = lib.snk_write_bv(str(path).encode(), len(off) - 1, off.ctypes.data, bases.ctypes.data, err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_write_bv, str(path).encode(), len(off) - 1, off.ctypes.data, bases.ctypes.data)
 
 
 def read_bv(path: str):
@@ -54,10 +51,7 @@ def read_bv(path: str):
     n = C.c_uint64(0)
     po = C.POINTER(C.c_uint64)()
     pb = C.POINTER(C.c_uint8)()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_read_bv(str(path).encode(), C.byref(n), C.byref(po), C.byref(pb), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_read_bv, str(path).encode(), C.byref(n), C.byref(po), C.byref(pb))
     off = np.ctypeslib.as_array(po, shape=(n.value + 1,)).copy()
     tot = int(off[-1])
     bases = np.ctypeslib.as_array(pb, shape=(max(tot, 1),))[:tot].copy()
@@ -68,23 +62,22 @@ def read_bv(path: str):
     return off, bases
 
 
-def hbv_from_unitigs(K: int, off: np.ndarray, bases: np.ndarray) -> dict:
-    """Unitigs in BVComp order -> HBV description (vertex ids per edge, fwd/rev translation)."""
-    lib = _lib.load()
-    off = np.ascontiguousarray(off, dtype=np.uint64)
-    bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    h = _lib.SnkHbv()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_hbv_from_unitigs(K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-    ne, nu = h.n_edges, len(off) - 1
-    arr = lambda p, m, dt: (np.ctypeslib.as_array(p, shape=(m,)).astype(dt).copy() if m else np.zeros(0, dt))
+def hbv_arrays(h: "_lib.SnkHbv", n_unitigs: int, order: bool = False) -> dict:
+    """A lib.SnkHbv as a dict of numpy copies (the C arrays stay the caller's to free); order: with 'order' = bvcomp_order."""
+    ne, nu = h.n_edges, n_unitigs
+    arr = lambda p, m, dt: (np.array(np.ctypeslib.as_array(p, shape=(m,)), dtype=dt, copy=True) if m else np.zeros(0, dt))
     out = dict(n_vertices=h.n_vertices, n_edges=ne, v_left=arr(h.v_left, ne, np.int32), v_right=arr(h.v_right, ne, np.int32),
                src=arr(h.src_unitig, ne, np.int32), is_rc=arr(h.is_rc, ne, np.uint8), fwd=arr(h.fwd_xlat, nu, np.int32),
                rev=arr(h.rev_xlat, nu, np.int32))
-    lib.snk_hbv_free(C.byref(h))
+    if order:
+        out["order"] = arr(h.bvcomp_order, nu, np.int32)
     return out
+
+
+def hbv_from_unitigs(K: int, off: np.ndarray, bases: np.ndarray) -> dict:
+    """Unitigs in BVComp order -> HBV description (vertex ids per edge, fwd/rev translation)."""
+    with hbv_handle(K, off, bases) as h:
+        return hbv_arrays(h, len(off) - 1)
 
 
 @contextlib.contextmanager
@@ -95,7 +88,7 @@ def hbv_handle(K: int, off: np.ndarray, bases: np.ndarray):
     off = np.ascontiguousarray(off, dtype=np.uint64)
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
     h = _lib.SnkHbv()
-    _call(lib.snk_hbv_from_unitigs, K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h))
+    _lib.call(lib.snk_hbv_from_unitigs, K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h))
     try:
         yield h
     finally:
@@ -107,30 +100,13 @@ def write_hbv(path_hbv, path_inv, K: int, off: np.ndarray, bases: np.ndarray) ->
     lib = _lib.load()
     off = np.ascontiguousarray(off, dtype=np.uint64)
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    h = _lib.SnkHbv()
-    err = C.create_string_buffer(512)
     nu = len(off) - 1
-    rc = lib.snk_hbv_from_unitigs(K, nu, off.ctypes.data, bases.ctypes.data, C.byref(h), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-    try:
+    with hbv_handle(K, off, bases) as h:
         inv = np.zeros(max(h.n_edges, 1), dtype=np.int32)
-        rc = lib.snk_hbv_involution(C.byref(h), nu, inv.ctypes.data, err, 512)
-        if not rc:
-            rc = lib.snk_write_hbv(str(path_hbv).encode(), str(path_inv).encode() if path_inv else None, K, nu, off.ctypes.data,
-                                   bases.ctypes.data, C.byref(h), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(lib.snk_hbv_involution, C.byref(h), nu, inv.ctypes.data)
+        _lib.call(lib.snk_write_hbv, str(path_hbv).encode(), str(path_inv).encode() if path_inv else None, K, nu, off.ctypes.data,
+                  bases.ctypes.data, C.byref(h))
         return inv[:h.n_edges].copy()
-    finally:
-        lib.snk_hbv_free(C.byref(h))
-
-
-def _call(fn, *args):
-    err = C.create_string_buffer(512)
-    rc = fn(*args, err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
 
 
 def write_paths(path, offset: np.ndarray, n_edges: np.ndarray, edges: np.ndarray, start: np.ndarray | None = None) -> None:
@@ -143,8 +119,8 @@ def write_paths(path, offset: np.ndarray, n_edges: np.ndarray, edges: np.ndarray
     if start is not None:
         start = np.ascontiguousarray(start, dtype=np.uint64)
         assert len(start) >= len(n_edges)
-    _call(_lib.load().snk_write_paths, str(path).encode(), len(n_edges), offset.ctypes.data, n_edges.ctypes.data,
-          start.ctypes.data if start is not None else None, edges.ctypes.data)
+    _lib.call(_lib.load().snk_write_paths, str(path).encode(), len(n_edges), offset.ctypes.data, n_edges.ctypes.data,
+              start.ctypes.data if start is not None else None, edges.ctypes.data)
 
 
 def write_paths_index(path_inv, path_countsb, off: np.ndarray, ids: np.ndarray, counts: np.ndarray) -> None:
@@ -155,20 +131,20 @@ def write_paths_index(path_inv, path_countsb, off: np.ndarray, ids: np.ndarray, 
     counts = np.ascontiguousarray(counts, dtype=np.int32)
     E = len(off) - 1
     assert E >= 0 and len(counts) == E and len(ids) == int(off[-1])
-    _call(_lib.load().snk_write_paths_index, str(path_inv).encode() if path_inv else None, str(path_countsb).encode() if path_countsb else None, E,
-          off.ctypes.data, ids.ctypes.data, counts.ctypes.data)
+    _lib.call(_lib.load().snk_write_paths_index, str(path_inv).encode() if path_inv else None, str(path_countsb).encode() if path_countsb else None, E,
+              off.ctypes.data, ids.ctypes.data, counts.ctypes.data)
 
 
 def write_dup(path, dup: np.ndarray) -> None:
     """a.dup (vec<Bool> of MarkDups, 10X/DF.cc:599-600): one flag per read pair."""
     dup = np.ascontiguousarray(dup, dtype=np.uint8)
-    _call(_lib.load().snk_write_dup, str(path).encode(), len(dup), dup.ctypes.data)
+    _lib.call(_lib.load().snk_write_dup, str(path).encode(), len(dup), dup.ctypes.data)
 
 
 def write_bad(path, bad: np.ndarray) -> None:
     """a.bad (vec<Bool> of MarkBads, 10X/DF.cc:644): one flag per read pair.  BinaryWriter::writeFile(vec<Bool>), the container of a.dup."""
     bad = np.ascontiguousarray(bad, dtype=np.uint8)
-    _call(_lib.load().snk_write_dup, str(path).encode(), len(bad), bad.ctypes.data)
+    _lib.call(_lib.load().snk_write_dup, str(path).encode(), len(bad), bad.ctypes.data)
 
 
 def write_pathsx(path, index: np.ndarray, data: np.ndarray, n_reads: int) -> None:
@@ -176,7 +152,7 @@ def write_pathsx(path, index: np.ndarray, data: np.ndarray, n_reads: int) -> Non
     the byte offset of every 10th read's record, data u8[...] = the records."""
     index = np.ascontiguousarray(index, dtype=np.int64)
     data = np.ascontiguousarray(data, dtype=np.uint8)
-    _call(_lib.load().snk_write_pathsx, str(path).encode(), int(n_reads), index.ctypes.data, len(index), data.ctypes.data, len(data))
+    _lib.call(_lib.load().snk_write_pathsx, str(path).encode(), int(n_reads), index.ctypes.data, len(index), data.ctypes.data, len(data))
 
 
 def read_pathsx(path):
@@ -185,7 +161,7 @@ def read_pathsx(path):
     n, ni, nb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     pi = C.POINTER(C.c_int64)()
     pd = C.POINTER(C.c_uint8)()
-    _call(lib.snk_read_pathsx, str(path).encode(), C.byref(n), C.byref(ni), C.byref(pi), C.byref(nb), C.byref(pd))
+    _lib.call(lib.snk_read_pathsx, str(path).encode(), C.byref(n), C.byref(ni), C.byref(pi), C.byref(nb), C.byref(pd))
     try:
         index = np.ctypeslib.as_array(pi, shape=(ni.value,)).copy() if ni.value else np.zeros(0, np.int64)
         data = np.ctypeslib.as_array(pd, shape=(nb.value,)).copy() if nb.value else np.zeros(0, np.uint8)
@@ -202,7 +178,7 @@ def write_ebcx(path, off: np.ndarray, bcs: np.ndarray) -> None:
     bcs = np.ascontiguousarray(bcs, dtype=np.int32)
     E = len(off) - 1
     assert E >= 0 and len(bcs) == int(off[-1])
-    _call(_lib.load().snk_write_ebcx, str(path).encode(), E, off.ctypes.data, bcs.ctypes.data)
+    _lib.call(_lib.load().snk_write_ebcx, str(path).encode(), E, off.ctypes.data, bcs.ctypes.data)
 
 
 def read_ebcx(path):
@@ -211,7 +187,7 @@ def read_ebcx(path):
     E = C.c_uint64(0)
     po = C.POINTER(C.c_uint64)()
     pb = C.POINTER(C.c_int32)()
-    _call(lib.snk_read_ebcx, str(path).encode(), C.byref(E), C.byref(po), C.byref(pb))
+    _lib.call(lib.snk_read_ebcx, str(path).encode(), C.byref(E), C.byref(po), C.byref(pb))
     try:
         off = np.ctypeslib.as_array(po, shape=(E.value + 1,)).copy()
         bcs = np.ctypeslib.as_array(pb, shape=(int(off[-1]),)).copy() if off[-1] else np.zeros(0, np.int32)
@@ -226,13 +202,8 @@ def write_hbx(path, K: int, off: np.ndarray, bases: np.ndarray) -> None:
     lib = _lib.load()
     off = np.ascontiguousarray(off, dtype=np.uint64)
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    h = _lib.SnkHbv()
-    nu = len(off) - 1
-    _call(lib.snk_hbv_from_unitigs, K, nu, off.ctypes.data, bases.ctypes.data, C.byref(h))
-    try:
-        _call(lib.snk_write_hbx, str(path).encode(), K, nu, off.ctypes.data, bases.ctypes.data, C.byref(h))
-    finally:
-        lib.snk_hbv_free(C.byref(h))
+    with hbv_handle(K, off, bases) as h:
+        _lib.call(lib.snk_write_hbx, str(path).encode(), K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(h))
 
 
 def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.ndarray, path_n_edges: np.ndarray, path_edges: np.ndarray, info: dict) -> np.ndarray:

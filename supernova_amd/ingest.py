@@ -7,6 +7,7 @@ synthetic read model.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -24,11 +25,8 @@ def write_synth_fasth(directory, sp: _lib.SnkSynthParams, n_files: int, pairs_pe
     paths = [str(directory / f"chunk{i:04d}.fasth.gz") for i in range(n_files)]
 
     def mk(i):
-        err = C.create_string_buffer(512)
         tb = C.c_uint64(0)
-        rc = lib.snk_synth_fasth_write(paths[i].encode(), C.byref(sp), i * pairs_per_file, pairs_per_file, level, C.byref(tb), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(lib.snk_synth_fasth_write, paths[i].encode(), C.byref(sp), i * pairs_per_file, pairs_per_file, level, C.byref(tb))
         return int(tb.value)
 
     with ThreadPoolExecutor(max(1, min(workers, n_files))) as ex:      # (the C call releases the GIL)
@@ -58,14 +56,10 @@ class DeviceReads:
                           n_batches=int(raw.n_batches), max_len=int(raw.max_len), setup_seconds=float(raw.setup_seconds))
 
     def dev_reads(self, with_bc: bool = True) -> _lib.SnkDevReads:
-        r = _lib.SnkDevReads()
-        r.n_reads, r.rows, r.row_words, r.read_len = self.n_reads, self.raw.rows, self.raw.row_words, self.read_len
-        r.lens, r.quals, r.qstride = self.raw.lens, self.raw.quals, self.raw.qstride
-        if self.raw.good_len:                       # the compact form of snk_dev_ingest_df_trimmed: no quality rows, the trim is done
-            r.good_len = self.raw.good_len
-        if with_bc and self.raw.bc:
-            r.bc = self.raw.bc
-        return r
+        from .engine import DevArray, dev_reads
+        raw = self.raw         # (good_len: the compact form of snk_dev_ingest_df_trimmed -- no quality rows, the trim is done)
+        return dev_reads(DevArray(raw.rows, self.n_reads, raw.row_words), self.read_len, quals=DevArray(raw.quals, self.n_reads, raw.qstride),
+                         lens=raw.lens, good_len=raw.good_len, bc=raw.bc if with_bc else None)
 
     def close(self):
         if self.raw is not None:
@@ -79,23 +73,25 @@ class DeviceReads:
             pass
 
 
-def ingest_fasth(engine, paths, read_len: int, whitelist: bytes | None = None, threads: int = 0, batch_pairs: int = 0) -> DeviceReads:
-    lib = engine.lib
-    err = C.create_string_buffer(512)
+@contextlib.contextmanager
+def _bc_index(engine, whitelist: bytes | None):
+    """The whitelist in HBM for the length of one ingest call (a null handle without one)."""
     ix = C.c_void_p()
     if whitelist is not None:
-        rc = lib.snk_bc_index_create(engine._ctx, whitelist, len(whitelist), C.byref(ix), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(engine.lib.snk_bc_index_create, engine._ctx, whitelist, len(whitelist), C.byref(ix))
     try:
-        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
-        raw = _lib.SnkDevIngest()
-        rc = lib.snk_dev_ingest_fasth(engine._ctx, arr, len(paths), read_len, ix, threads, batch_pairs, C.byref(raw), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        yield ix
     finally:
         if ix:
-            lib.snk_bc_index_destroy(ix)
+            engine.lib.snk_bc_index_destroy(ix)
+
+
+def ingest_fasth(engine, paths, read_len: int, whitelist: bytes | None = None, threads: int = 0, batch_pairs: int = 0) -> DeviceReads:
+    lib = engine.lib
+    with _bc_index(engine, whitelist) as ix:
+        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        raw = _lib.SnkDevIngest()
+        _lib.call(lib.snk_dev_ingest_fasth, engine._ctx, arr, len(paths), read_len, ix, threads, batch_pairs, C.byref(raw))
     return DeviceReads(lib, raw)
 
 
@@ -106,22 +102,11 @@ def ingest_count_graph(engine, paths, read_len: int, whitelist: bytes | None = N
     from .engine import Params, Result
     lib = engine.lib
     params = params or Params()
-    err = C.create_string_buffer(512)
-    ix = C.c_void_p()
-    if whitelist is not None:
-        rc = lib.snk_bc_index_create(engine._ctx, whitelist, len(whitelist), C.byref(ix), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-    try:
+    with _bc_index(engine, whitelist) as ix:
         arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
         raw, res, p = _lib.SnkDevIngest(), _lib.SnkDevResult(), params.to_c()
-        rc = lib.snk_dev_ingest_count_graph(engine._ctx, arr, len(paths), read_len, ix, threads, batch_pairs, int(total_reads_hint), C.byref(p), C.byref(res),
-                                            C.byref(raw), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-    finally:
-        if ix:
-            lib.snk_bc_index_destroy(ix)
+        _lib.call(lib.snk_dev_ingest_count_graph, engine._ctx, arr, len(paths), read_len, ix, threads, batch_pairs, int(total_reads_hint), C.byref(p), C.byref(res),
+                  C.byref(raw))
     stats = dict(n_reads=int(raw.n_reads), text_bytes=int(raw.text_bytes), compressed_bytes=int(raw.compressed_bytes), seconds=float(raw.seconds),
                  decode_wait_seconds=float(raw.decode_wait_seconds), n_files=int(raw.n_files), n_batches=int(raw.n_batches), max_len=int(raw.max_len),
                  setup_seconds=float(raw.setup_seconds))

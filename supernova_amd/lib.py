@@ -386,7 +386,20 @@ def _declare(lib: C.CDLL) -> None:
     lib._snk_declared = tuple(sig)
 
 
+ERRCAP = 512
+
+
+def call(fn, *args) -> None:
+    """fn(*args, err, ERRCAP) for an ABI function whose C signature ends in (char* err, size_t errcap): a non-zero return raises
+    SnkError with the code and the text the function left in err."""
+    err = C.create_string_buffer(ERRCAP)
+    rc = fn(*args, err, ERRCAP)
+    if rc:
+        raise SnkError(rc, err.value.decode(errors="replace"))
+
+
 def check(code: int) -> None:
+    """The same for the functions that report through snk_last_error."""
     if code != 0:
         raise SnkError(code, load().snk_last_error().decode(errors="replace"))
 

@@ -77,14 +77,12 @@ class DeviceBcIndexer:
         self.device = device
         self._ctx = C.c_void_p()
         self._ix = C.c_void_p()
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_ctx_create(device, C.byref(self._ctx), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        rc = self.lib.snk_bc_index_create(self._ctx, whitelist_bytes, len(whitelist_bytes), C.byref(self._ix), err, 512)
-        if rc:
+        _lib.call(self.lib.snk_ctx_create, device, C.byref(self._ctx))
+        try:
+            _lib.call(self.lib.snk_bc_index_create, self._ctx, whitelist_bytes, len(whitelist_bytes), C.byref(self._ix))
+        except _lib.SnkError:
             self.lib.snk_ctx_destroy(self._ctx)
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+            raise
         self.num_bcs = int(self.lib.snk_bc_index_lines(self._ix))
 
     @classmethod
@@ -102,10 +100,7 @@ class DeviceBcIndexer:
         d_f = torch.from_numpy(fields).to(dev)
         d_ids = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
-        err = C.create_string_buffer(512)
-        rc = self.lib.snk_dev_bc_ids(self._ctx, self._ix, d_f.data_ptr(), stride, n, d_ids.data_ptr(), None, err, 512)
-        if rc:
-            raise self._lib_mod.SnkError(rc, err.value.decode(errors="replace"))
+        self._lib_mod.call(self.lib.snk_dev_bc_ids, self._ctx, self._ix, d_f.data_ptr(), stride, n, d_ids.data_ptr(), None)
         return d_ids[:n].cpu().numpy()
 
     def close(self):
@@ -128,10 +123,7 @@ def read_fasth_native(paths):
         n, mx = C.c_uint64(0), C.c_uint32(0)
         pa, pq, pf = C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint8)(), C.POINTER(C.c_uint8)()
         pl = C.POINTER(C.c_uint16)()
-        err = C.create_string_buffer(512)
-        rc = lib.snk_read_fasth(str(p).encode(), STRIDE, C.byref(n), C.byref(mx), C.byref(pa), C.byref(pq), C.byref(pl), C.byref(pf), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(lib.snk_read_fasth, str(p).encode(), STRIDE, C.byref(n), C.byref(mx), C.byref(pa), C.byref(pq), C.byref(pl), C.byref(pf))
         nr = int(n.value)
         take = lambda ptr, shape, dt: (np.ctypeslib.as_array(ptr, shape=shape).astype(dt).copy() if nr else np.zeros(shape, dt))
         parts.append((take(pa, (nr, STRIDE), np.uint8), take(pq, (nr, STRIDE), np.uint8), take(pl, (nr,), np.uint16),
@@ -151,17 +143,12 @@ def read_fasth_stream(paths, threads=0, batch_pairs=0, stride=256):
     lib = _lib.load()
     arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
     h = C.c_void_p()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_fasth_open(arr, len(paths), stride, batch_pairs, threads, 0, C.byref(h), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_fasth_open, arr, len(paths), stride, batch_pairs, threads, 0, C.byref(h))
     got, text, nb = [], 0, 0
     try:
         while True:
             b = _lib.SnkFasthBatch()
-            rc = lib.snk_fasth_next(h, C.byref(b), err, 512)
-            if rc:
-                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+            _lib.call(lib.snk_fasth_next, h, C.byref(b))
             if b.n_pairs == 0:
                 break
             npair = int(b.n_pairs)
@@ -233,10 +220,7 @@ def count_graph_host(asc, quals, lens, bc, K=48, min_qual=7, min_freq=3, min_bc=
     from . import lib as _lib
     lib = _lib.load()
     h = C.c_void_p()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_ctx_create(device, C.byref(h), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_ctx_create, device, C.byref(h))
     try:
         asc = np.ascontiguousarray(asc, dtype=np.uint8)
         quals = np.ascontiguousarray(quals, dtype=np.uint8)
@@ -248,9 +232,7 @@ def count_graph_host(asc, quals, lens, bc, K=48, min_qual=7, min_freq=3, min_bc=
         p = _lib.SnkParams()
         p.K, p.min_qual, p.min_freq, p.min_bc = K, min_qual, min_freq, min_bc
         out = _lib.SnkResult()
-        rc = lib.snk_count_graph(h, C.byref(r), C.byref(p), C.byref(out), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(lib.snk_count_graph, h, C.byref(r), C.byref(p), C.byref(out))
         U = out.n_unitigs
         off = np.ctypeslib.as_array(out.unitig_off, shape=(U + 1,)).copy()
         tot = int(off[-1])

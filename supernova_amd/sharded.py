@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import lib as _lib
-from .engine import Engine, Params
+from .engine import Engine, Params, Result, dev_reads
 
 
 # ------------------------------------------------------------------------------------------------ communicators
@@ -280,11 +280,7 @@ class ShardedResult:
         # the most this rank sent to ONE other rank per exchange (xGMI is point to point: an exchange takes as long as its fullest pair)
         self.pair_max_bytes = {EXCH_NAMES[i]: int(raw.pair_max_bytes[i]) for i in range(7)}
 
-    def _dl(self, ptr, nbytes, dtype, shape):
-        out = np.empty(shape, dtype=dtype)
-        if nbytes:
-            self._e._download(ptr, out.ctypes.data, nbytes)
-        return out
+    _dl = Result._dl
 
     def keys(self):
         lohi = self._dl(self.raw.keys, self.n_kmers * 16, np.uint64, (self.n_kmers, 2))
@@ -329,10 +325,7 @@ def local_world(world: int) -> list[int]:
     """`world` in-process ranks on one device: handles for ShardedEngine(engine, handle), one per rank / host thread."""
     lib = _lib.load()
     arr = (C.c_void_p * world)()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_comm_create_local(world, arr, err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_comm_create_local, world, arr)
     return [int(arr[r]) for r in range(world)]
 
 
@@ -363,7 +356,6 @@ def rccl_comm(engine: Engine, dist) -> int:
     """An RCCL communicator for libsnk on the engine's device: rank 0 makes the 128-byte unique id, torch.distributed carries
     it to the other ranks (a broadcast of 128 bytes -- everything else of the step runs behind the C ABI)."""
     lib = engine.lib
-    err = C.create_string_buffer(512)
     rank, world = dist.get_rank(), dist.get_world_size()
     from pathlib import Path
     cand = Path(torch.__file__).parent / "lib" / "librccl.so"      # the RCCL of this process: the one torch ships
@@ -371,9 +363,7 @@ def rccl_comm(engine: Engine, dist) -> int:
         lib.snk_comm_set_rccl_path(str(cand).encode())
     idb = (C.c_uint8 * 128)()
     if rank == 0:
-        rc = lib.snk_comm_unique_id(idb, err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        _lib.call(lib.snk_comm_unique_id, idb)
     if world > 1:
         dev = torch.device("cuda", engine.device) if dist.get_backend() == "nccl" else torch.device("cpu")
         t = torch.tensor(list(idb), dtype=torch.uint8, device=dev)
@@ -381,9 +371,7 @@ def rccl_comm(engine: Engine, dist) -> int:
         for i, v in enumerate(t.cpu().tolist()):
             idb[i] = v
     h = C.c_void_p()
-    rc = lib.snk_comm_create_rccl(engine._ctx, idb, rank, world, C.byref(h), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_comm_create_rccl, engine._ctx, idb, rank, world, C.byref(h))
     return int(h.value)
 
 
@@ -453,10 +441,7 @@ def gloo_comm(engine: Engine, dist):
 
     cb_a, cb_g = _lib.COMM_A2A(a2a), _lib.COMM_GATHER(gather)
     h = C.c_void_p()
-    err = C.create_string_buffer(512)
-    rc = lib.snk_comm_create_callbacks(rank, world, cb_a, cb_g, None, C.byref(h), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    _lib.call(lib.snk_comm_create_callbacks, rank, world, cb_a, cb_g, None, C.byref(h))
     return int(h.value), (cb_a, cb_g)
 
 
@@ -494,38 +479,16 @@ class ShardedEngine:
 
     def count_graph(self, rows, read_len, quals=None, bc=None, lens=None, good_len=None, params: Params | None = None,
                     ign_bc_below: int = 0, read_index_base: int = 0, total_reads: int = 0) -> ShardedResult:
-        e, lib = self.eng, self.lib
-        params = params or Params()
-        err = C.create_string_buffer(512)
-        r = _lib.SnkDevReads()
-        r.n_reads, r.rows, r.row_words, r.read_len = rows.shape[0], rows.data_ptr(), rows.shape[1], read_len
-        if lens is not None:
-            r.lens = lens.data_ptr()
-        if quals is not None:
-            r.quals, r.qstride = quals.data_ptr(), quals.shape[1]
-        if good_len is not None:
-            r.good_len = good_len.data_ptr()
-        if bc is not None:
-            r.bc = bc.data_ptr()
-        r.ign_bc_below, r.read_index_base = ign_bc_below, read_index_base
-        p = params.to_c()
-        raw = _lib.SnkShardResult()
-        rc = lib.snk_shard_step(e._ctx, self.comm, C.byref(r), C.byref(p), int(total_reads), 0, C.byref(raw), e._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
-        return ShardedResult(e, params.K, raw)
+        return self.count_graph_reads(dev_reads(rows, read_len, quals, lens, good_len, bc, None, ign_bc_below, read_index_base), params, total_reads)
 
     def count_graph_reads(self, r: "_lib.SnkDevReads", params: Params | None = None, total_reads: int = 0) -> ShardedResult:
         """The same step for reads described by plain device pointers (e.g. a rank's share of the ASSEMBLER_DF stage inputs in the compact
         form of snk_dev_ingest_df_trimmed: rows, good lengths, barcode ids; r.read_index_base = global index of the rank's first read)."""
-        e, lib = self.eng, self.lib
+        e = self.eng
         params = params or Params()
-        err = C.create_string_buffer(512)
         p = params.to_c()
         raw = _lib.SnkShardResult()
-        rc = lib.snk_shard_step(e._ctx, self.comm, C.byref(r), C.byref(p), int(total_reads), 0, C.byref(raw), e._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        e._call(self.lib.snk_shard_step, self.comm, C.byref(r), C.byref(p), int(total_reads), 0, C.byref(raw))
         return ShardedResult(e, params.K, raw)
 
     def count_graph_streamed(self, slabs, read_len, total_reads: int, rank_reads_ub: int, params: Params | None = None, ign_bc_below: int = 0) -> ShardedResult:
@@ -534,35 +497,18 @@ class ShardedEngine:
         passes the same figure), rank_reads_ub = an upper bound of what this rank appends."""
         e, lib = self.eng, self.lib
         params = params or Params()
-        err = C.create_string_buffer(512)
         p = params.to_c()
         it = iter(slabs)
         first = next(it)
         has_bc = 1 if first.get("bc") is not None else 0
-        rc = lib.snk_shard_stream_begin(e._ctx, self.comm, C.byref(p), int(read_len), int(rank_reads_ub), int(total_reads), has_bc, e._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        e._call(lib.snk_shard_stream_begin, self.comm, C.byref(p), int(read_len), int(rank_reads_ub), int(total_reads), has_bc)
         import itertools
         keep = []
         for sl in itertools.chain([first], it):
-            r = _lib.SnkDevReads()
-            rows = sl["rows"]
-            r.n_reads, r.rows, r.row_words, r.read_len = rows.shape[0], rows.data_ptr(), rows.shape[1], read_len
-            if sl.get("lens") is not None:
-                r.lens = sl["lens"].data_ptr()
-            if sl.get("quals") is not None:
-                r.quals, r.qstride = sl["quals"].data_ptr(), sl["quals"].shape[1]
-            if sl.get("good_len") is not None:
-                r.good_len = sl["good_len"].data_ptr()
-            if sl.get("bc") is not None:
-                r.bc = sl["bc"].data_ptr()
-            r.ign_bc_below, r.read_index_base = ign_bc_below, int(sl.get("read_index_base", 0))
-            rc = lib.snk_shard_stream_append(e._ctx, C.byref(r), e._stream(), err, 512)
-            if rc != 0:
-                raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+            r = dev_reads(sl["rows"], read_len, sl.get("quals"), sl.get("lens"), sl.get("good_len"), sl.get("bc"), None, ign_bc_below,
+                          int(sl.get("read_index_base", 0)))
+            e._call(lib.snk_shard_stream_append, C.byref(r))
             keep.append(sl)          # (the launches read the slab's tensors: they stay alive until the step is through)
         raw = _lib.SnkShardResult()
-        rc = lib.snk_shard_stream_finish(e._ctx, self.comm, 0, C.byref(raw), e._stream(), err, 512)
-        if rc != 0:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        e._call(lib.snk_shard_stream_finish, self.comm, 0, C.byref(raw))
         return ShardedResult(e, params.K, raw)

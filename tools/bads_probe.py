@@ -24,17 +24,14 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from supernova_amd import dfin, lib as _lib, synth  # noqa: E402
-from supernova_amd.engine import Engine, Params, _bads_stats  # noqa: E402
+from supernova_amd.engine import Engine, Params, _bads_stats, dev_paths, dev_reads  # noqa: E402
 
 
 def twice(call):
     """the second of two calls -> stats"""
     for _ in range(2):
         b = _lib.SnkDevBads()
-        err = C.create_string_buffer(512)
-        rc = call(b, err)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        call(b)
     return _bads_stats(b)
 
 
@@ -48,32 +45,23 @@ def run(eng, name, sp, scratch):
     dev = rows.device
     off_t, ne_t, edges_t = (torch.from_numpy(a.view(np.int32)).to(dev) for a in (off, ne, edges))
     del off, ne, edges
-    start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    start[1:] = torch.cumsum(ne_t.to(torch.int64), 0)
-    r = _lib.SnkDevReads()
-    r.n_reads, r.rows, r.row_words, r.read_len = n, rows.data_ptr(), rows.shape[1], sp.read_len
-    r.quals, r.qstride = quals.data_ptr(), quals.shape[1]
-    p = _lib.SnkDevPaths()
-    p.n_reads, p.n_edges_total = n, int(edges_t.shape[0])
-    p.offset, p.n_edges, p.start, p.edges = off_t.data_ptr(), ne_t.data_ptr(), start.data_ptr(), edges_t.data_ptr()
+    r = dev_reads(rows, sp.read_len, quals)
+    p, start = dev_paths(off_t, ne_t, edges_t)          # (start: the struct points into it)
     h = _lib.SnkHbv()
     ms = C.c_float(0)
-    err = C.create_string_buffer(512)
-    rc = eng.lib.snk_dev_hbv(eng._ctx, int(res.K), res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(ms), eng._stream(), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    eng._call(eng.lib.snk_dev_hbv, int(res.K), res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(ms))
     graph = (res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(p))
     try:
         torch.cuda.synchronize()
         got = {}
         for tag, flags in (("plain", 0), ("x", _lib.BADS_X)):
-            got[tag] = twice(lambda b, e: eng.lib.snk_dev_mark_bads(eng._ctx, int(res.K), C.byref(r), *graph, flags, C.byref(b), eng._stream(), e, 512))
+            got[tag] = twice(lambda b: eng._call(eng.lib.snk_dev_mark_bads, int(res.K), C.byref(r), *graph, flags, C.byref(b)))
         t0 = time.time()
         dfin.write_synth_df(Path(scratch) / "reads", sp)
         write_s = time.time() - t0
         with dfin.DfFiles(Path(scratch) / "reads") as files:
             for tag, flags in (("df_plain", 0), ("df_x", _lib.BADS_X)):
-                got[tag] = twice(lambda b, e: eng.lib.snk_dev_mark_bads_df(eng._ctx, int(res.K), files._h, 0, n, 0, 0, 0, *graph, flags, C.byref(b), e, 512))
+                got[tag] = twice(lambda b: _lib.call(eng.lib.snk_dev_mark_bads_df, eng._ctx, int(res.K), files._h, 0, n, 0, 0, 0, *graph, flags, C.byref(b)))
             file_bytes = files.file_bytes
     finally:
         eng.lib.snk_hbv_free(C.byref(h))

@@ -19,18 +19,14 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from supernova_amd import lib as _lib, synth  # noqa: E402
-from supernova_amd.engine import Engine, Params, _extend_stats  # noqa: E402
+from supernova_amd.engine import Engine, Params, _extend_stats, dev_paths, dev_reads  # noqa: E402
 
 
 def extend(eng, res, h, r, p, flags):
     """snk_dev_extend_paths on the result's own unitig arrays, the second of two calls -> stats"""
     for _ in range(2):
         x = _lib.SnkDevExtend()
-        err = C.create_string_buffer(512)
-        rc = eng.lib.snk_dev_extend_paths(eng._ctx, int(res.K), C.byref(r), res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(p), flags,
-                                          C.byref(x), eng._stream(), err, 512)
-        if rc:
-            raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+        eng._call(eng.lib.snk_dev_extend_paths, int(res.K), C.byref(r), res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(p), flags, C.byref(x))
     return _extend_stats(x)
 
 
@@ -51,22 +47,13 @@ def run(eng, name, sp):
     edges_t = edges_t[~torch.repeat_interleave(far, ne64)].contiguous()
     zero = torch.zeros((), dtype=torch.int32, device=dev)
     off_t, ne_t = torch.where(far, zero, off_t), torch.where(far, zero, ne_t)
-    start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    start[1:] = torch.cumsum(ne_t.to(torch.int64), 0)
     n_far = int(far.sum())
     del far, ne64
-    r = _lib.SnkDevReads()
-    r.n_reads, r.rows, r.row_words, r.read_len = n, rows.data_ptr(), rows.shape[1], sp.read_len
-    r.quals, r.qstride = quals.data_ptr(), quals.shape[1]
-    p = _lib.SnkDevPaths()
-    p.n_reads, p.n_edges_total = n, int(edges_t.shape[0])
-    p.offset, p.n_edges, p.start, p.edges = off_t.data_ptr(), ne_t.data_ptr(), start.data_ptr(), edges_t.data_ptr()
+    r = dev_reads(rows, sp.read_len, quals)
+    p, start = dev_paths(off_t, ne_t, edges_t)
     h = _lib.SnkHbv()
     ms = C.c_float(0)
-    err = C.create_string_buffer(512)
-    rc = eng.lib.snk_dev_hbv(eng._ctx, int(res.K), res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(ms), eng._stream(), err, 512)
-    if rc:
-        raise _lib.SnkError(rc, err.value.decode(errors="replace"))
+    eng._call(eng.lib.snk_dev_hbv, int(res.K), res.n_unitigs, res.raw.unitig_off, res.raw.unitig_bases, C.byref(h), C.byref(ms))
     n_hbv = int(h.n_edges)
     # ... and so does an offset that the backward leg would move there: a path at a negative offset whose first edge has an in-edge of more
     # than 32767 k-mers goes in without its path too (whether or not that in-edge would agree with the read: the call itself refuses what
@@ -85,10 +72,8 @@ def run(eng, name, sp):
     n_far_back = int(far.sum())
     edges_t = edges_t[~torch.repeat_interleave(far, ne_t.to(torch.int64))].contiguous()
     off_t, ne_t = torch.where(far, zero, off_t), torch.where(far, zero, ne_t)
-    start[1:] = torch.cumsum(ne_t.to(torch.int64), 0)
     del far, first
-    p.n_edges_total = int(edges_t.shape[0])
-    p.offset, p.n_edges, p.start, p.edges = off_t.data_ptr(), ne_t.data_ptr(), start.data_ptr(), edges_t.data_ptr()
+    p, start = dev_paths(off_t, ne_t, edges_t)
     try:
         torch.cuda.synchronize()
         plain = extend(eng, res, h, r, p, 0)
