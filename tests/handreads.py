@@ -23,8 +23,14 @@ twice each (below MIN_FREQ) -- the base next to a junction, the last base of a r
 barcodes=True (K=48: the reference's K=60 build has no barcode rule) four reads of ONE barcode that fork off for 20 bases (enough
 instances, one barcode); a few copies with barcode 0.  This too is asserted over strings.
 
+noise="paths" is the variant for the stages behind the graph (read pathing, MarkDups: tests/test_handreads_paths_host.py,
+tests/test_gpu_handreads_paths.py, tests/golden/make_handreads_paths_golden.py): the clean reads at random qualities of 8..40 and, among
+them, a layer of reads with substituted bases and of chimeras whose new k-mers occur once each (_make_paths) -- again the graph of the
+clean reads by construction, and asserted over strings.
+
     unitig_set(name, K) -> list of strings          reads(name, K, noise=False) -> namespace(codes, quals, lens, bc, rows, read_len, facts, digest)
     load(name, K, noise) -> the reads and the reference's results for them (tests/golden/handreads/); differs() compares a result with them
+    load_paths(name, noise) -> the reads and the reference's paths and duplicate flags for them (K=48; tests/golden/handreads/paths/); paths_differ()
 """
 from __future__ import annotations
 
@@ -395,14 +401,159 @@ def digest(codes, quals, lens, bc) -> str:
     return h.hexdigest()
 
 
+# ---- the third variant, for the pather: the clean reads at random qualities and a layer of reads with errors
+
+KINDS = ("sub1", "first", "last", "sub2near", "sub2far", "chimera")
+LAYER_BC = N_BC + 2          # the layer's own barcode (N_BC + 1 is the noisy variant's one-barcode branch)
+VARIANTS = (False, True, "paths")
+
+
+def vname(noise):
+    return "paths" if noise == "paths" else "noisy" if noise else "clean"
+
+
+def _make_paths(name, K):
+    """The reads of noise="paths".  The clean reads keep their order among themselves, their strands and barcodes, at qualities drawn from
+    8..40 (never below min_qual = 7: the trim and the count see what they saw).  Among them, at drawn places, lie the reads of the error
+    layer: made from the clean reads of at least K + 1 bases, in a barcode of their own, at qualities drawn from 0..40, a quarter with a Q2
+    tail of 0..30 bases.  One layer read per such clean read (five at least), its kind taken in turn from sub1, first, last, sub2near, sub2far (one
+    substituted base anywhere / the first base / the last base / two fewer than 10 apart / two more than K apart: a captured gap between
+    two seeds, where the read has 2K + 10 bases, else sub1); then one chimera per four clean reads, at least 8 (single_k1, whose one read of
+    K + 1 bases has six joints with itself, gets those that are free): a prefix of at least K
+    bases of one clean read joined to a suffix of another, reverse-complemented half the time, cut to L bases.
+    ASSERTED over strings: every k-mer that covers a changed base or a chimera's joint lies outside the case and in no other layer read
+    (one instance: never retained), so the table, the pruned contexts and the unitigs stay those of the clean reads; every kind occurs
+    (sub2far where a clean read has 2K + 10 bases); the number of reads is even, so that MarkDups runs.  A case without a read of K + 1
+    bases (single_k, single_pal_k) has no layer.  rows added to the namespace: kind i8[n] (-1: a clean read, else the index into KINDS),
+    parent i32[n] (the row of the clean read a layer read was made from; a chimera's: its prefix's), clean_rows (the rows of the clean reads)."""
+    c = reads(name, K, False)
+    rng = np.random.default_rng(zlib.crc32(f"handreads/{name}/{K}/paths".encode()))
+    asc = np.frombuffer(b"ACGT", np.uint8)
+    clean = [asc[c.codes[i, :int(c.lens[i])]].tobytes().decode() for i in range(len(c.lens))]
+    case_kmers = _canon_set(unitig_set(name, K), K)
+    usable = [i for i, s in enumerate(clean) if len(s) >= K + 1]
+    long_enough = [i for i in usable if len(clean[i]) >= 2 * K + 10]
+    used: set = set()
+    layer, kinds, parents = [], [], []
+
+    def accept(m, windows):
+        """the k-mers of m inside the windows (those that cover a changed base, or a chimera's joint) are new: outside the case, in no layer read"""
+        touched = _canon_set([m[max(0, a):b] for a, b in windows], K)
+        once = _canon_counts([m], [LAYER_BC], K)          # (a chimera of a read and its own reverse complement, two substitutions a circle's period apart: twice)
+        if not touched or (touched & case_kmers) or (touched & used) or any(once[k][0] != 1 for k in touched):
+            return False
+        used.update(touched)
+        return True
+
+    def substituted(s, spots):
+        m = s
+        for pos in spots:
+            for d in (1, 2, 3):
+                t = m[:pos] + "ACGT"[("ACGT".index(m[pos]) + d) % 4] + m[pos + 1:]
+                w = _canon_set([t[max(0, pos - K + 1):pos + K]], K)
+                if not (w & case_kmers) and not (w & used):
+                    break
+            m = t
+        return m if accept(m, [(pos - K + 1, pos + K) for pos in spots]) else None
+
+    def spots_of(kind, n):
+        if kind == "first":
+            return [0]
+        if kind == "last":
+            return [n - 1]
+        if kind == "sub2near":
+            p = int(rng.integers(0, n - 1))
+            return [p, min(n - 1, p + int(rng.integers(1, 10)))]
+        if kind == "sub2far":
+            p = int(rng.integers(0, n - K - 1))
+            return [p, int(rng.integers(p + K + 1, n))]
+        return [int(rng.integers(0, n))]
+
+    for t in range(max(len(usable), 5) if usable else 0):          # (at least one turn per kind)
+        i, kind = usable[t % len(usable)], KINDS[t % 5]
+        if kind == "sub2far" and len(clean[i]) < 2 * K + 10:
+            if long_enough and not kinds.count(4):
+                i = long_enough[0]          # (the case has few reads of that length: the kind's first turn takes one of them)
+            else:
+                kind = "sub1"
+        for _ in range(4):
+            m = substituted(clean[i], spots_of(kind, len(clean[i])))
+            if m is not None:
+                layer.append(m); kinds.append(KINDS.index(kind)); parents.append(i)
+                break
+            if kind in ("first", "last"):
+                break
+    n_chimeras = max(8, len(clean) // 4) if usable else 0
+    if usable:
+        n_chimeras += (len(clean) + len(layer) + n_chimeras) % 2          # (an even number of reads)
+    for _ in range(n_chimeras):
+        for _ in range(32):
+            i, j = (int(x) for x in rng.choice(usable, 2))
+            a, b = clean[i], rc(clean[j]) if rng.random() < 0.5 else clean[j]
+            cut = int(rng.integers(K, len(a) + 1))
+            m = (a[:cut] + b[len(b) - int(rng.integers(K, len(b) + 1)):])[:L]
+            if len(m) > cut and accept(m, [(cut - K + 1, cut + K - 1)]):
+                layer.append(m); kinds.append(5); parents.append(i)
+                break
+    if (len(clean) + len(layer)) % 2 and layer:          # (a chimera found no free joint)
+        layer.pop(); kinds.pop(); parents.pop()
+    # every k-mer of a layer read is a k-mer of the case or one of the layer's own, and those occur once
+    own = _canon_counts(layer, [LAYER_BC] * len(layer), K)
+    for k, e in own.items():
+        assert k in case_kmers or (k in used and e[0] == 1), f"{name} K={K}: the layer k-mer {k} has {e[0]} instances"
+    n_kind = {k: kinds.count(x) for x, k in enumerate(KINDS)}
+    if usable:
+        assert all(n_kind[k] > 0 for k in KINDS if k != "sub2far") and (n_kind["sub2far"] > 0 or not long_enough), (name, K, n_kind)
+        one_read = len({min(clean[i], rc(clean[i])) for i in usable}) == 1          # (single_k1: one read of K + 1 bases has six joints with itself)
+        assert n_kind["chimera"] >= (1 if one_read else 8), (name, K, n_kind)
+    for m, x, p in zip(layer, kinds, parents):
+        s = clean[p]
+        diff = [q for q in range(min(len(m), len(s))) if m[q] != s[q]]
+        if KINDS[x] == "chimera":
+            assert len(m) <= L and m[:K] == s[:K]
+        else:
+            assert len(m) == len(s) and len(diff) == (2 if x in (3, 4) else 1)
+            assert x != 1 or diff == [0]
+            assert x != 2 or diff == [len(s) - 1]
+            assert x != 3 or diff[1] - diff[0] < 10
+            assert x != 4 or (diff[1] - diff[0] > K and len(s) >= 2 * K + 10)
+    # ---- the rows: the clean reads in their order, the layer's reads at drawn places among them
+    n = len(clean) + len(layer)
+    is_layer = np.zeros(n, bool)
+    is_layer[rng.choice(n, len(layer), replace=False)] = True
+    clean_rows = np.nonzero(~is_layer)[0]
+    codes = np.zeros((n, L), np.uint8)
+    quals = np.zeros((n, L), np.uint8)
+    lens = np.zeros(n, np.uint16)
+    bc = np.zeros(n, np.int32)
+    kind = np.full(n, -1, np.int8)
+    parent = np.full(n, -1, np.int32)
+    codes[clean_rows], lens[clean_rows], bc[clean_rows] = c.codes, c.lens, c.bc
+    for row in clean_rows:
+        quals[row, :lens[row]] = rng.integers(8, 41, int(lens[row]))
+    for t, row in enumerate(np.nonzero(is_layer)[0]):
+        m = layer[t]
+        lens[row], bc[row], kind[row], parent[row] = len(m), LAYER_BC, kinds[t], clean_rows[parents[t]]
+        codes[row, :len(m)] = hu._CODE[np.frombuffer(m.encode(), np.uint8)]
+        quals[row, :len(m)] = rng.integers(0, 41, len(m))
+        if rng.random() < 0.25:
+            quals[row, len(m) - int(rng.integers(0, 31)):len(m)] = 2
+    facts = dict(c.facts, noise=None, n_reads=n, layer=dict(n_layer_reads=len(layer), n_layer_kmers=sum(k not in case_kmers for k in own), kinds=n_kind))
+    assert n % 2 == 0 or not layer
+    return SimpleNamespace(name=name, K=K, noise="paths", codes=codes, quals=quals, lens=lens, bc=bc, read_len=L, facts=facts, kind=kind, parent=parent,
+                           clean_rows=clean_rows, digest=digest(codes, quals, lens, bc))
+
+
 _reads: dict = {}
 
 
 def reads(name, K, noise=False):
-    """Made once per process and left unchanged.  The noisy reads carry the one-barcode branch at K=48 only."""
-    key = (name, K, bool(noise))
+    """Made once per process and left unchanged.  The noisy reads carry the one-barcode branch at K=48 only; noise="paths" is the
+    pather's variant (_make_paths)."""
+    noise = "paths" if noise == "paths" else bool(noise)
+    key = (name, K, noise)
     if key not in _reads:
-        r = _make(name, K, bool(noise), barcodes=K == 48)
+        r = _make_paths(name, K) if noise == "paths" else _make(name, K, noise, barcodes=K == 48)
         r.rows = None
         _reads[key] = r
     return _reads[key]
@@ -472,6 +623,52 @@ def load(name, K, noise=False):
     r, g = reads(name, K, noise), golden(name, K)
     assert r.digest == g.digests[bool(noise)], f"{name} K={K}: the generator no longer makes the reads the fixture was made from"
     return r, SimpleNamespace(hashed=g.hashed, fields=g.noisy if noise else g.clean, unitig_lens=g.unitig_lens, n_kmers=g.n_kmers)
+
+
+# ---- the reference's paths (K=48: it has no K=60 pather), tests/golden/handreads/paths/, written by tests/golden/make_handreads_paths_golden.py
+
+PATHS_GOLD = GOLD / "paths"
+PATH_FIELDS = ("path_off", "path_n", "path_edges")
+DUP_FIELDS = ("dup", "interdup", "art_perc")          # (where the number of reads is even: MarkDups takes pairs)
+_pgold: dict = {}
+
+
+def load_paths(name, noise):
+    """The reads of one variant, regenerated and checked against the digest, and what the reference's pathReads and MarkDups made of them
+    -> (reads, namespace(hashed, fields: per PATH_FIELDS / DUP_FIELDS name an array (a float for the two rates), or its SHA-256 for the
+    HASHED cases, has_dups))"""
+    if name not in _pgold:
+        _pgold[name] = (json.loads((PATHS_GOLD / "big_hashes.json").read_text())[f"{name}_k48"] if name in HASHED
+                        else dict(np.load(PATHS_GOLD / f"{name}_k48.npz")))
+    z, v, r = _pgold[name], vname(noise), reads(name, 48, noise)
+    if name in HASHED:
+        fields, dg = dict(z[v]), z[v]["reads_digest"]
+    else:
+        fields = {f: z[f"{v}_{f}"] for f in PATH_FIELDS + DUP_FIELDS if f"{v}_{f}" in z}
+        dg = bytes(z[f"{v}_reads_digest"]).decode()
+    assert r.digest == dg, f"{name} {v}: the generator no longer makes the reads the fixture was made from"
+    for f in ("interdup", "art_perc"):
+        if f in fields:
+            fields[f] = float(fields[f])
+    return r, SimpleNamespace(hashed=name in HASHED, fields=fields, has_dups="dup" in fields)
+
+
+def paths_differ(exp, got: dict):
+    """None, or the name of the first field of PATH_FIELDS / DUP_FIELDS (those the expectation has) in which a result differs from it;
+    got: path_off, path_n, path_edges, and with duplicate flags dup, interdup and n_art (the number of artifactual pairs)"""
+    for f in PATH_FIELDS + DUP_FIELDS:
+        if f not in exp.fields or (f == "art_perc" and "n_art" not in got):
+            continue
+        if f == "interdup":
+            same = float(got[f]) == exp.fields[f]
+        elif f == "art_perc":          # the reference only logs it, at two significant digits: the count goes through the same rounding
+            same = float(f"{100.0 * got['n_art'] / max(len(got['dup']), 1):.2g}") == float(f"{exp.fields[f]:.2g}")
+        else:
+            a = np.ascontiguousarray(got[f], np.uint8 if f == "dup" else np.int32)
+            same = sha(a) == exp.fields[f] if exp.hashed else np.array_equal(a, exp.fields[f])
+        if not same:
+            return f
+    return None
 
 
 def differs(exp, got: dict, fields=FIELDS):

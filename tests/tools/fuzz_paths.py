@@ -29,10 +29,7 @@ import pathgen
 from supernova_amd import graphio, lib as _lib
 from supernova_amd.engine import Engine, Params
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
-seed = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
-only = int(sys.argv[3]) if len(sys.argv) > 3 else -1      # replay one case of a sweep
-eng = Engine(0)
+eng = None                      # the sweep's engine (main); a test that borrows later_stages passes its own
 PATH_OPTIONS = ("path_index", "path_two_pass", "path_fast_gs", "path_fused", "path_redo_all", "path_slots_x10", "path_fp_mask",
                 "path_edge_cap", "path_redo_cap", "path_ubc_cap", "dups_two_sorts", "unitig_bc_cut")
 BC_LISTS_MAX_READS = 20000      # the barcode lists' restatement is plain Python
@@ -66,9 +63,11 @@ def reads_for(rng, c):
     return codes, quals, lens, bc
 
 
-def later_stages(c, us, off, ne, edges, bc, info):
-    """The paths index, the zip, its unzip and the edge -> barcode lists of one case against their numpy restatements -> mismatch lines."""
+def later_stages(c, us, off, ne, edges, bc, info, engine=None):
+    """The paths index, the zip, its unzip and the edge -> barcode lists of one case against their numpy restatements -> mismatch lines.
+    c: the case's K and use_bc; info: of a path_reads call with paths_index, pathsx and ebcx; engine: the sweep's unless given."""
     import torch
+    eng = engine or globals()["eng"]
     bad = []
     K, inv = c["K"], info["inv"]
     u = graphio.unitigs_to_arrays(us)
@@ -159,28 +158,38 @@ def run_case(case, c, v, codes, quals, lens, bc):
     return bad, info, res.n_unitigs, int(o_n.max()) if len(o_n) else 0
 
 
-rng = np.random.default_rng(seed)
-bad_cases = 0
-for case in range(n_cases):
-    c, v = draw_case(rng)
-    data = reads_for(rng, c)
-    if only >= 0 and case != only:
-        continue
-    n = data[0].shape[0]
-    vtxt = " ".join(f"{k}={x}" for k, x in v.items())
-    tag = f"case {case}: K={c['K']} L={c['L']} G={c['G']} n={n} err={c['err']} nbc={c['nbc']} dups={c['dup_frac']} min_freq={c['min_freq']} " \
-          f"min_bc={c['min_bc']} nb={c['nb']} bc={c['use_bc']} pad={c['pad']} | {vtxt}"
-    try:
-        bad, info, nu, longest = run_case(case, c, v, *data)
-    except _lib.SnkError as ex:
-        bad, info, nu, longest = [f"library error: {ex}"], {}, -1, -1
-    if bad:
-        bad_cases += 1
-        print("FAIL " + tag, flush=True)
-        for b in bad:
-            print("     " + b, flush=True)
-    else:
-        print(f"ok   {tag} -> {nu} unitigs, longest path {longest} edges, {info['n_slow']} slow, retries {info['retries']}, "
-              f"{info['dups']['n_dup_pairs']} dup pairs", flush=True)
-print(f"{n_cases - bad_cases} of {n_cases} cases bit-exact")
-sys.exit(1 if bad_cases else 0)
+def main():
+    global eng
+    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 30
+    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 12345
+    only = int(sys.argv[3]) if len(sys.argv) > 3 else -1      # replay one case of a sweep
+    eng = Engine(0)
+    rng = np.random.default_rng(seed)
+    bad_cases = 0
+    for case in range(n_cases):
+        c, v = draw_case(rng)
+        data = reads_for(rng, c)
+        if only >= 0 and case != only:
+            continue
+        n = data[0].shape[0]
+        vtxt = " ".join(f"{k}={x}" for k, x in v.items())
+        tag = f"case {case}: K={c['K']} L={c['L']} G={c['G']} n={n} err={c['err']} nbc={c['nbc']} dups={c['dup_frac']} min_freq={c['min_freq']} " \
+              f"min_bc={c['min_bc']} nb={c['nb']} bc={c['use_bc']} pad={c['pad']} | {vtxt}"
+        try:
+            bad, info, nu, longest = run_case(case, c, v, *data)
+        except _lib.SnkError as ex:
+            bad, info, nu, longest = [f"library error: {ex}"], {}, -1, -1
+        if bad:
+            bad_cases += 1
+            print("FAIL " + tag, flush=True)
+            for b in bad:
+                print("     " + b, flush=True)
+        else:
+            print(f"ok   {tag} -> {nu} unitigs, longest path {longest} edges, {info['n_slow']} slow, retries {info['retries']}, "
+                  f"{info['dups']['n_dup_pairs']} dup pairs", flush=True)
+    print(f"{n_cases - bad_cases} of {n_cases} cases bit-exact")
+    return 1 if bad_cases else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
