@@ -461,7 +461,7 @@ uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components,
  * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
 uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -732,6 +732,61 @@ struct snk_df_files;      /* (snk_df_open, below) */
 int snk_dev_mark_bads_df(snk_ctx* ctx, uint32_t K, struct snk_df_files* f, uint64_t first, uint64_t n, uint32_t read_len, uint32_t threads, uint64_t slab_reads,
                          uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags,
                          snk_dev_bads* out, char* err, size_t errcap);
+
+/* ---- gap-patch candidates: FindEdgePairs, a.hops -------------------------------------------------------------------------
+ * FindEdgePairs, lib/assembly/src/10X/Closomatic.cc:17-354: the second step of StageFindPatch (10X/runstages/RunStages.cc:263-266).
+ * DF keeps the result as a.hops (10X/DF.cc:642-643); the closures that snk_dev_patch_pieces takes are made for these pairs.  The
+ * result is the sorted set of (e1, e2) that three rules give.  Kmers(e) = bases - K + 1; a read's barcode class is its bc value (10x data:
+ * bidc = N + bc, all bc == 0 reads are one class); `entries of e` are the reads of the paths index entry of e.
+ *   sink(e)     every edge leaving ToRight(e) has at most 120 k-mers and ends in a vertex with no out-edge and one in-edge (an e with
+ *               nothing behind it is a sink); source(e) is the mirror image over the edges entering ToLeft(e)
+ *   keys        for every entry r of a sink e1 whose mate has a path: e2 = inv[last edge of the mate's path], e2 != e1, class of r
+ *   part 1      (e1, e2) with keys of two classes or more, and source(e2) unless SNK_HOPS_ONE_GOOD
+ *   part 2      for an e1 that is the first element of no part-1 pair: (e1, e2) with keys of two classes or more,
+ *               Kmers(e2) >= 100 and ToRight(e1) != ToLeft(e2)
+ *   part 3      for every e of K + 1 k-mers or more whose entries, with those of inv[e], are of two classes or more.  X = the path suffixes
+ *               from every occurrence of e, the mates' paths reversed and inverted, the reversed and inverted prefixes up to every
+ *               occurrence of inv[e].  From the members that begin with e, a sequence x grows by a member y that holds x's last edge
+ *               at a place that is not its last and agrees with x wherever the two overlap; e is `extended` when some reachable x has 100
+ *               k-mers or more behind its first edge.  If it is not: over the entries of pairs with bad == 0, too_easy = the edges behind e
+ *               on the same path, can = (edge, class) of the mates' inverted paths and of the inverted prefixes ending in inv[e],
+ *               both only edges of 40 k-mers or more other than e and inv[e]; (e, f) for every f of two classes in can that is
+ *               not in too_easy
+ * The closure of part 3 runs on the device over the set of sequences reached so far, at most ext_budget of them per edge (0 = the
+ * default and the most, 128; a larger value counts as 128) in 4 096 ints; an edge that needs more, or that has more than 65 536 index
+ * entries with a member of two edges or more, is finished by a host routine without a bound (n_ext_host counts them).  No result depends on the budget.  SNK_HOPS_EXT_HOST sends every closure to the host routine (tests).
+ * paths: of snk_dev_path_reads or a later stage, and what snk_dev_paths_zip accepts and gives back unchanged (the reference reads a
+ * ReadPathVecX): the refusals of SNK_BADS_X.  px: the paths index of these paths, or NULL (made inside the call).  d_bc: i32 per read;
+ * d_bad: u8 per pair (snk_dev_mark_bads).  pairs: i32[2 * n_pairs], ascending by (first, second), context memory valid until the
+ * context's next top-level call.  The result is bit-identical from call to call and depends on no tuning option.
+ * SNK_E_ARG: an odd read count, an edge id outside the graph, an inv that is not an involution, a px whose n_hbv_edges or n_entries
+ * do not match, unknown flags, NULL d_bc / d_bad with reads.  After any failure *out is all zero. */
+#define SNK_HOPS_ONE_GOOD 1u   /* DF's ONE_GOOD=True; DF's default is False */
+#define SNK_HOPS_EXT_HOST 2u   /* tests: every closure of part 3 on the host leg */
+typedef struct snk_dev_hops {
+    uint64_t n_pairs;
+    const void* pairs;                         /* i32[2 * n_pairs], ascending (first, second) */
+    uint64_t n_part1, n_part2, n_part3;        /* distinct pairs each part contributed, before the final unique */
+    uint64_t n_sink_edges;                     /* edges with sink(e) */
+    uint64_t n_long_edges;                     /* edges of K + 1 k-mers or more */
+    uint64_t n_two_class;                      /* ... whose entries are of two classes or more = the next three */
+    uint64_t n_ext_round0;                     /* ... extended by a member of X as it stands */
+    uint64_t n_ext_closure;                    /* ... extended by the closure */
+    uint64_t n_ext_host;                       /* closures the host routine finished (extended or not) */
+    uint64_t n_not_extended;
+    float ms, tables_ms;                       /* HIP events: the whole call; graph tables, checks of the paths and the index */
+    uint32_t ext_budget;                       /* the budget the call ran with */
+    float part12_ms, part3_ms;
+    uint64_t reserved[4];
+} snk_dev_hops;
+int snk_dev_edge_pairs(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h,
+                       const int32_t* inv /* host */, const snk_dev_paths* paths, const snk_dev_pidx* px /* NULL: made inside */,
+                       const void* d_bc /* i32 per read */, const void* d_bad /* u8 per pair */, uint32_t flags, uint32_t ext_budget /* 0 = default */,
+                       snk_dev_hops* out, void* stream, char* err, size_t errcap);
+/* a.hops = BinaryWriter::writeFile(vec<pair<int,int>>) (10X/DF.cc:642-643): "BINWRITE", u64 count, two i32 per pair.  snk_read_hops:
+ * *pairs is malloc'ed (snk_host_free). */
+int snk_write_hops(const char* path, uint64_t n_pairs, const int32_t* pairs, char* err, size_t errcap);
+int snk_read_hops(const char* path, uint64_t* n_pairs, int32_t** pairs, char* err, size_t errcap);
 
 /* ---- gap patches into the graph: StageInsertPatch ---------------------------------------------------------------------
  * StageInsertPatch, lib/assembly/src/10X/runstages/RunStages.cc:176-230 (10X/DF.cc:656): the graph is rebuilt from its own edges, the

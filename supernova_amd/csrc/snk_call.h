@@ -1,5 +1,5 @@
 // snk_call.h -- the call frame of the device stages that run after the graph (snk_dev_hbv, snk_dev_check_graph, snk_dev_path_reads2,
-// snk_dev_mark_dups, snk_dev_paths_index, snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df).
+// snk_dev_mark_dups, snk_dev_paths_index, snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs).
 //
 // One protocol, one owner.  Such an entry point checks the arguments that need no device, zeroes *out and hands its body to
 // snk_call_run.  The frame makes the context's device current, picks the stream, remembers where the call's scratch begins, and on
@@ -127,3 +127,8 @@ int snk_call_run(snk_ctx* ctx, void* stream, const char* who, Out* out, char* er
 // the caller; the result is their maximum).  Any 4-byte-aligned pointer.  Shared by the paths index and the compressed paths
 // (snk_pidx.hip), which refuse an id outside the graph before they index with it.
 hipError_t snk_max_edge_id(const uint32_t* edges, uint64_t n, uint32_t* range, hipStream_t st);
+// The lists of the paths index inside a frame (snk_pidx.hip): off[E + 1], ids[n_edges_total] and, with_counts, room for counts[E] (the
+// caller fills it), all scratch of c.  Refuses, as `who`, a path table that does not add up and an edge id outside [0, E).  What
+// snk_dev_paths_index is made of, and what snk_dev_edge_pairs runs when it is given no index.
+int snk_pidx_lists(snk_call& c, const struct snk_dev_paths* paths, uint64_t E, const char* who, bool with_counts, unsigned long long** off, unsigned long long** ids,
+                   int32_t** counts, uint32_t* key_bits, char* err, size_t errcap);

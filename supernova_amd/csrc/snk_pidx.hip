@@ -131,11 +131,46 @@ hipError_t snk_max_edge_id(const uint32_t* edges, uint64_t n, uint32_t* range, h
     return snk_launch(max_edge_id_kernel, snk_blocks_capped(n / 4 + 1, PB, PIDX_GRID_CAP), PB, 0, st, edges, n, range);
 }
 
+int snk_pidx_lists(snk_call& c, const snk_dev_paths* paths, uint64_t E, const char* who, bool with_counts, unsigned long long** p_off, unsigned long long** p_ids,
+                   int32_t** p_counts, uint32_t* p_key_bits, char* err, size_t errcap) {
+    const hipStream_t st = c.st;
+    const uint64_t n = paths->n_edges_total, n_reads = paths->n_reads;
+    int rc;
+    unsigned long long *off, *ids, *rid;
+    uint32_t *skey, *range;
+    *p_counts = nullptr;
+    // (results first: what is handed back behind them coalesces)
+    if ((rc = c.alloc(E + 1, &off)) || (rc = c.alloc(n, &ids)) || (with_counts && (rc = c.alloc(E, p_counts))) || (rc = c.alloc(n, &rid)) || (rc = c.alloc(n + 4, &skey)) ||
+        (rc = c.alloc(256 + 1, &range)))
+        return rc;
+    SNK_HIP_TRY(hipMemsetAsync(range, 0, 257 * 4, st));
+    uint32_t key_bits = 0;
+    while (key_bits < 32 && (1ull << key_bits) < E) ++key_bits;
+    if (n) {
+        SNK_HIP_TRY(snk_launch(pidx_fill_kernel, snk_blocks_capped(n_reads, PB, PIDX_GRID_CAP), PB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges, n_reads, n,
+                               rid, range + 256));
+        SNK_HIP_TRY(snk_max_edge_id((const uint32_t*)paths->edges, n, range, st));
+        uint32_t h_range[257];
+        SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(snk_sync(st));
+        uint32_t emax = 0;
+        for (int q = 0; q < 256; ++q) emax = std::max(emax, h_range[q]);
+        if (h_range[256]) return snk_fail(SNK_E_ARG, err, errcap, "%s: start / n_edges do not add up to n_edges_total = %llu", who, (unsigned long long)n);
+        if (emax >= E) return snk_fail(SNK_E_ARG, err, errcap, "%s: a path holds edge id %lld, the graph has %llu edges", who, (long long)(int32_t)emax, (unsigned long long)E);
+        const uint32_t bits = std::max(1u, key_bits);
+        if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)paths->edges, skey, rid, ids, (size_t)n, 0u, bits, st); })))
+            return rc;
+    }
+    SNK_HIP_TRY(snk_launch(pidx_offsets_kernel, snk_blocks_capped(n ? (n + 3) / 4 : E + 1, PB, PIDX_GRID_CAP), PB, 0, st, skey, n, E, off));
+    *p_off = off; *p_ids = ids; *p_key_bits = key_bits;
+    return SNK_OK;
+}
+
 extern "C" int snk_dev_paths_index(snk_ctx* ctx, const snk_dev_paths* paths, uint64_t E, const int32_t* inv, snk_dev_pidx* out, void* stream, char* err,
                                    size_t errcap) {
     if (!ctx || !paths || !out || (E && !inv)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: NULL argument");
     memset(out, 0, sizeof *out);
-    const uint64_t n = paths->n_edges_total, n_reads = paths->n_reads;
+    const uint64_t n = paths->n_edges_total;
     if (E > 0x7FFFFFFFull) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: %llu HBV edges (edge ids are int32)", (unsigned long long)E);
     if (n && (!paths->start || !paths->n_edges || !paths->edges)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: paths without their device arrays");
     if ((uintptr_t)paths->edges & 15u) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: paths->edges is not 16-byte aligned");
@@ -152,35 +187,13 @@ extern "C" int snk_dev_paths_index(snk_ctx* ctx, const snk_dev_paths* paths, uin
         const hipStream_t st = c.st;
         SNK_HIP_TRY(c.stamp());
         int rc;
-        unsigned long long *off, *ids, *rid, *stat;
+        unsigned long long *off, *ids, *stat;
         int32_t *counts, *d_inv;
-        uint32_t *skey, *range;
-        // (results first: what is handed back behind them coalesces)
-        if ((rc = c.alloc(E + 1, &off)) || (rc = c.alloc(n, &ids)) || (rc = c.alloc(E, &counts)) || (rc = c.alloc(n, &rid)) || (rc = c.alloc(n + 4, &skey)) ||
-            (rc = c.alloc(E, &d_inv)) || (rc = c.alloc(512, &stat)) || (rc = c.alloc(256 + 1, &range)))
-            return rc;
+        uint32_t key_bits;
+        if ((rc = snk_pidx_lists(c, paths, E, "snk_dev_paths_index", true, &off, &ids, &counts, &key_bits, err, errcap))) return rc;
+        if ((rc = c.alloc(E, &d_inv)) || (rc = c.alloc(512, &stat))) return rc;
         SNK_HIP_TRY(hipMemsetAsync(stat, 0, 512 * 8, st));
-        SNK_HIP_TRY(hipMemsetAsync(range, 0, 257 * 4, st));
         if (E) SNK_HIP_TRY(hipMemcpyAsync(d_inv, inv, E * 4, hipMemcpyHostToDevice, st));
-        uint32_t key_bits = 0;
-        while (key_bits < 32 && (1ull << key_bits) < E) ++key_bits;
-        if (n) {
-            SNK_HIP_TRY(snk_launch(pidx_fill_kernel, snk_blocks_capped(n_reads, PB, PIDX_GRID_CAP), PB, 0, st, (const unsigned long long*)paths->start, (const uint32_t*)paths->n_edges, n_reads, n,
-                                   rid, range + 256));
-            SNK_HIP_TRY(snk_max_edge_id((const uint32_t*)paths->edges, n, range, st));
-            uint32_t h_range[257];
-            SNK_HIP_TRY(hipMemcpyAsync(h_range, range, sizeof h_range, hipMemcpyDeviceToHost, st));
-            SNK_HIP_TRY(snk_sync(st));
-            uint32_t emax = 0;
-            for (int q = 0; q < 256; ++q) emax = std::max(emax, h_range[q]);
-            if (h_range[256]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: start / n_edges do not add up to n_edges_total = %llu", (unsigned long long)n);
-            if (emax >= E)
-                return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_paths_index: a path holds edge id %lld, the graph has %llu edges", (long long)(int32_t)emax, (unsigned long long)E);
-            const uint32_t bits = std::max(1u, key_bits);
-            if ((rc = c.with_temp([&](void* tmp, size_t& tb) { return rocprim::radix_sort_pairs(tmp, tb, (const uint32_t*)paths->edges, skey, rid, ids, (size_t)n, 0u, bits, st); })))
-                return rc;
-        }
-        SNK_HIP_TRY(snk_launch(pidx_offsets_kernel, snk_blocks_capped(n ? (n + 3) / 4 : E + 1, PB, PIDX_GRID_CAP), PB, 0, st, skey, n, E, off));
         if (E) SNK_HIP_TRY(snk_launch(pidx_counts_kernel, snk_blocks_capped(E, PB, PIDX_GRID_CAP), PB, 0, st, off, d_inv, E, counts, stat));
         unsigned long long h_stat[512];
         SNK_HIP_TRY(hipMemcpyAsync(h_stat, stat, sizeof h_stat, hipMemcpyDeviceToHost, st));

@@ -160,7 +160,7 @@ class Result:
             self._e.lib.snk_hbv_free(C.byref(h))
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
-                   paths_index=False, pathsx=False, ebcx=False, extend=False, mark_bads=False):
+                   paths_index=False, pathsx=False, ebcx=False, extend=False, mark_bads=False, hops=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -189,9 +189,16 @@ class Result:
         mark_bads (True, or "x" for SNK_BADS_X: offsets as the ReadPathVecX of a stock DF holds them): MarkBads over these paths
         (10X/SecretOps.cc:22-59,70-107; snk_dev_mark_bads) -> info['bads'] = dict(bad u8[n/2], n_bad_pairs, n_bad_reads, n_mismatch_reads,
         n_placed, n_offsets_wrapped, ms): what graphio.write_bad / write_a48 make a.bad of.  download=False: the counters, and
-        info['bads_dev'] = the SnkDevBads itself (device memory of the context, valid until the engine's next count_graph or path_reads)."""
+        info['bads_dev'] = the SnkDevBads itself (device memory of the context, valid until the engine's next count_graph or path_reads).
+        hops (True, or "one_good" for SNK_HOPS_ONE_GOOD; needs bc, implies paths_index): FindEdgePairs over these paths (10X/Closomatic.cc:17-354;
+        snk_dev_edge_pairs), the second step of StageFindPatch, with the flags of mark_bads when that is given and all-false flags
+        otherwise -> info['hops'] = i32[n, 2], the pairs ascending: what graphio.write_hops / write_a48 make a.hops of;
+        info['hops_stats'] = the counters and times.  download=False: the stats only."""
         if ebcx and bc is None:
             raise ValueError("path_reads(ebcx=...) needs bc: the barcode of every read, on the device")
+        if hops and bc is None:
+            raise ValueError("path_reads(hops=...) needs bc: the barcode of every read, on the device")
+        paths_index = paths_index or bool(hops)
         e, K = self._e, int(self.K)
         h, ms = _lib.SnkHbv(), C.c_float(0)
         e._call(e.lib.snk_dev_hbv, K, *self._unitigs(), C.byref(h), C.byref(ms))
@@ -206,14 +213,21 @@ class Result:
                 if bc is not None:
                     r.bc = bc.data_ptr()
                 stages.update(e._dups_info(e._dups(r, out), download))
+            bd = None
             if mark_bads:
-                stages.update(e._bads_info(e._bads(K, r, graph, out, mark_bads == "x"), download))
+                bd = e._bads(K, r, graph, out, mark_bads == "x")
+                stages.update(e._bads_info(bd, download))
             if paths_index or ebcx:
                 n_hbv = int(h.n_edges)
                 inv = np.zeros(max(n_hbv, 1), dtype=np.int32)
                 _lib.call(e.lib.snk_hbv_involution, C.byref(h), self.n_unitigs, inv.ctypes.data)
             if paths_index:
-                stages.update(e._pidx_info(e._pidx(out, n_hbv, inv), n_hbv, inv, download))
+                px = e._pidx(out, n_hbv, inv)
+                stages.update(e._pidx_info(px, n_hbv, inv, download))
+            if hops:
+                bad = torch.zeros(max(int(out.n_reads) // 2, 1), dtype=torch.uint8, device=bc.device) if bd is None else None
+                hp = e._hops(K, graph, inv, out, px, bc.data_ptr(), bad.data_ptr() if bd is None else bd.bad, hops == "one_good")
+                stages.update(e._hops_info(hp, download))
             if ebcx:
                 stages.update(e._ebcx_info(e._ebcx(out, bc, n_hbv, inv, ebcx == "general"), n_hbv, download))
             if pathsx:
@@ -325,6 +339,13 @@ def _extend_stats(x: "_lib.SnkDevExtend") -> dict:
 def _bads_stats(b: "_lib.SnkDevBads") -> dict:
     return dict(n_pairs=int(b.n_pairs), n_placed=int(b.n_placed), n_mismatch_reads=int(b.n_mismatch_reads), n_bad_reads=int(b.n_bad_reads),
                 n_bad_pairs=int(b.n_bad_pairs), n_offsets_wrapped=int(b.n_offsets_wrapped), n_slabs=int(b.n_slabs), ms=float(b.ms), tables_ms=float(b.tables_ms), kernel_ms=float(b.kernel_ms))
+
+
+def _hops_stats(hp: "_lib.SnkDevHops") -> dict:
+    d = {k: int(getattr(hp, k)) for k in ("n_pairs", "n_part1", "n_part2", "n_part3", "n_sink_edges", "n_long_edges", "n_two_class", "n_ext_round0", "n_ext_closure",
+                                          "n_ext_host", "n_not_extended", "ext_budget")}
+    d.update({k: float(getattr(hp, k)) for k in ("ms", "tables_ms", "part12_ms", "part3_ms")})
+    return d
 
 
 def _pathsx_stats(zx: "_lib.SnkDevPathsx") -> dict:
@@ -462,6 +483,16 @@ class Engine:
     def _bads(self, K, r, graph, p, x):
         return self._stage(self.lib.snk_dev_mark_bads, _lib.SnkDevBads(), int(K), C.byref(r), *graph, C.byref(p), _lib.BADS_X if x else 0)
 
+    def _hops(self, K, graph, inv, p, px, bc_ptr, bad_ptr, one_good, ext_host=False, ext_budget=0):
+        return self._stage(self.lib.snk_dev_edge_pairs, _lib.SnkDevHops(), int(K), *graph, inv.ctypes.data, C.byref(p), C.byref(px) if px is not None else None,
+                           bc_ptr, bad_ptr, (_lib.HOPS_ONE_GOOD if one_good else 0) | (_lib.HOPS_EXT_HOST if ext_host else 0), int(ext_budget))
+
+    def _hops_info(self, hp, download):
+        d = {"hops_stats": _hops_stats(hp)}
+        if download:
+            d["hops"] = self._fetch(hp.pairs, 2 * hp.n_pairs, np.int32).reshape(-1, 2)
+        return d
+
     def _pidx(self, p, n_hbv, inv):
         return self._stage(self.lib.snk_dev_paths_index, _lib.SnkDevPidx(), C.byref(p), n_hbv, inv.ctypes.data)
 
@@ -579,6 +610,20 @@ class Engine:
         _lib.call(self.lib.snk_dev_mark_bads_df, self._ctx, int(K), files._h, int(first), n, int(read_len), int(threads), int(slab_reads),
                   *_graph(h, unitig_off, unitig_bases), C.byref(p), _lib.BADS_X if x else 0, C.byref(b))
         return self._bads_result(b, download)
+
+    # ---- FindEdgePairs (the second step of StageFindPatch): the edge pairs gap closing tries, a.hops
+    def edge_pairs(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, inv: np.ndarray, offset: torch.Tensor,
+                   n_edges: torch.Tensor, edges: torch.Tensor, bc: torch.Tensor, bad: torch.Tensor, start: torch.Tensor | None = None, pidx=None,
+                   one_good: bool = False, ext_host: bool = False, ext_budget: int = 0, download: bool = True):
+        """snk_dev_edge_pairs -- FindEdgePairs (10X/Closomatic.cc:17-354) -- over tensors on this engine's device: the unitigs of the graph h
+        (graphio.hbv_handle) and its involution inv (numpy i32[E]), the paths as for extend_paths, bc i32[n] and bad u8[n / 2] (mark_bads).
+        pidx: a SnkDevPidx of these paths (the context's last paths index), or None: the index is made inside the call.  one_good:
+        SNK_HOPS_ONE_GOOD; ext_host / ext_budget: where part 3's closures run (no result depends on either).  -> (pairs i32[n, 2], stats) on
+        the host; download=False: (SnkDevHops, stats), device memory of the context, valid until its next top-level call."""
+        p, start = dev_paths(offset, n_edges, edges, start)
+        inv = np.ascontiguousarray(inv, dtype=np.int32)
+        hp = self._hops(K, _graph(h, unitig_off, unitig_bases), inv, p, pidx, bc.data_ptr(), bad.data_ptr(), one_good, ext_host, ext_budget)
+        return (self._hops_info(hp, True)["hops"] if download else hp), _hops_stats(hp)
 
     # ---- gap patches into the graph (StageInsertPatch)
     def insert_patch(self, graph, closures, paths) -> "PatchResult":

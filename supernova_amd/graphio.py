@@ -6,6 +6,7 @@
   write_hbv            a.hbv / a.inv as DF keeps the graph (paths/HyperBasevector.cc:121-125)
   write_paths, write_paths_index, write_dup, write_a48
                        the rest of a.48/: a.paths, a.paths.inv, a.countsb, a.dup (10X/DF.cc:584-600, 10X/PathsIndex.cc:23-145)
+  write_hops / read_hops  a.hops, the edge pairs of FindEdgePairs that StageFindPatch leaves (10X/DF.cc:642-643); write_a48 adds it when the result holds 'hops'
   write_bad            a.bad, the pair flags of MarkBads that StageFindPatch leaves (10X/DF.cc:644); write_a48 adds it when the result holds 'bads'
   write_pathsx / read_pathsx, write_hbx
                        the compressed forms DF goes on working from: a.pathsX (10X/paths/ReadPathVecX.cc:976-996) and a.hbx
@@ -147,6 +148,24 @@ def write_bad(path, bad: np.ndarray) -> None:
     _lib.call(_lib.load().snk_write_dup, str(path).encode(), len(bad), bad.ctypes.data)
 
 
+def write_hops(path, pairs: np.ndarray) -> None:
+    """a.hops (vec<pair<int,int>> of FindEdgePairs, 10X/DF.cc:642-643): pairs i32[n, 2], as snk_dev_edge_pairs gives them."""
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    _lib.call(_lib.load().snk_write_hops, str(path).encode(), len(pairs), pairs.ctypes.data)
+
+
+def read_hops(path) -> np.ndarray:
+    """a.hops -> pairs i32[n, 2]."""
+    lib = _lib.load()
+    n = C.c_uint64(0)
+    pp = C.POINTER(C.c_int32)()
+    _lib.call(lib.snk_read_hops, str(path).encode(), C.byref(n), C.byref(pp))
+    try:
+        return np.ctypeslib.as_array(pp, shape=(n.value, 2)).copy() if n.value else np.zeros((0, 2), np.int32)
+    finally:
+        lib.snk_host_free(pp)
+
+
 def write_pathsx(path, index: np.ndarray, data: np.ndarray, n_reads: int) -> None:
     """a.pathsX (ReadPathVecX::writeBinary, 10X/paths/ReadPathVecX.cc:976-996) from what snk_dev_paths_zip made: index i64[ceil(n_reads / 10)] =
     the byte offset of every 10th read's record, data u8[...] = the records."""
@@ -212,7 +231,8 @@ def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.n
     info['countsb']: path_reads(..., paths_index=True)) and a.dup (info['dups']['dup']: mark_dups=True).  With info['pathsx']
     (path_reads(..., pathsx=True)) also a.hbx and a.pathsX, the two other files a DF entered at START=patch opens (10X/DF.cc:612-630).
     With info['bads'] (path_reads(..., mark_bads="x"), or dict(bad=...) of Engine.mark_bads) also a.bad, which StageFindPatch leaves
-    (10X/DF.cc:644).  Returns the involution."""
+    (10X/DF.cc:644); with info['hops'] (path_reads(..., hops=True), or the pairs of Engine.edge_pairs) also a.hops, the other file of that
+    step (10X/DF.cc:642-643).  Returns the involution."""
     from pathlib import Path
     d = Path(dir)
     d.mkdir(parents=True, exist_ok=True)
@@ -231,6 +251,8 @@ def write_a48(dir, K: int, off: np.ndarray, bases: np.ndarray, path_offset: np.n
         write_pathsx(d / "a.pathsX", info["pathsx"][0], info["pathsx"][1], len(path_n_edges))
     if "bads" in info:
         write_bad(d / "a.bad", info["bads"]["bad"])
+    if "hops" in info:
+        write_hops(d / "a.hops", info["hops"])
     return inv
 
 

@@ -126,6 +126,17 @@ class SnkDevBads(C.Structure):
 BADS_X = 1                       # SNK_BADS_X
 
 
+class SnkDevHops(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("pairs", C.c_void_p), ("n_part1", C.c_uint64), ("n_part2", C.c_uint64), ("n_part3", C.c_uint64),
+                ("n_sink_edges", C.c_uint64), ("n_long_edges", C.c_uint64), ("n_two_class", C.c_uint64), ("n_ext_round0", C.c_uint64),
+                ("n_ext_closure", C.c_uint64), ("n_ext_host", C.c_uint64), ("n_not_extended", C.c_uint64), ("ms", C.c_float), ("tables_ms", C.c_float),
+                ("ext_budget", C.c_uint32), ("part12_ms", C.c_float), ("part3_ms", C.c_float), ("reserved", C.c_uint64 * 4)]
+
+
+HOPS_ONE_GOOD = 1                # SNK_HOPS_ONE_GOOD
+HOPS_EXT_HOST = 2                # SNK_HOPS_EXT_HOST
+
+
 class SnkPatchPlan(C.Structure):
     _fields_ = [("n_pieces", C.c_uint64), ("n_unitig_pieces", C.c_uint64), ("n_junctions", C.c_uint64), ("n_closure_pieces", C.c_uint64),
                 ("n_lonely_max", C.c_uint64), ("reserved", C.c_uint64 * 3)]
@@ -312,6 +323,9 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_paths_unzip": (C.c_int, [vp, P(SnkDevPathsx), P(SnkHbv), P(SnkDevPaths), vp, cp, sz]),
         "snk_dev_extend_paths": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevExtend), vp, cp, sz]),
         "snk_dev_mark_bads": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevBads), vp, cp, sz]),
+        "snk_dev_edge_pairs": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevPaths), P(SnkDevPidx), vp, vp, u32, u32, P(SnkDevHops), vp, cp, sz]),
+        "snk_write_hops": (C.c_int, [cp, u64, vp, cp, sz]),
+        "snk_read_hops": (C.c_int, [cp, P(u64), P(P(i32)), cp, sz]),
         "snk_dev_mark_bads_df": (C.c_int, [vp, u32, vp, u64, u64, u32, u32, u64, u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevBads), cp, sz]),
         "snk_patch_plan_sizes": (C.c_int, [u32, u64, vp, P(SnkHbv), u64, vp, P(SnkPatchPlan), cp, sz]),
         "snk_dev_patch_pieces": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), u64, vp, vp, u64, vp, vp, u64, vp, P(SnkDevPieces), vp, cp, sz]),
