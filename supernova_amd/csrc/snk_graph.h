@@ -123,6 +123,10 @@ struct snk_bl_state {          // device arrays of the bucket-local stage (index
     unsigned long long* index; // boundary k-mers only
     uint64_t index_mask, n_boundary;
     unsigned long long *qcount, *qcursor;
+    // one-GPU stage, unsorted table: the k-mer spectrum accumulated by the prune kernels as they write counts[] (want_spec: asked for by
+    // the caller; spec: 65536 bins, null = not accumulated; spec_over: a count beyond that range was seen, snk_spectrum has to run)
+    unsigned long long* spec;
+    uint32_t want_spec, spec_over;
 };
 int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, unsigned long long* h_qcount, char* err, size_t errcap);
 int snk_bl_dist_fill(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, const unsigned long long* d_qoff, void* d_qbuf, char* err, size_t errcap);

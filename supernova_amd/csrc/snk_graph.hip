@@ -393,6 +393,7 @@ static int rank_lists_wyllie(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint6
     for (int b = 0; b < 2; ++b) { G_ALLOC(nxt[b], uint32_t, ns); G_ALLOC(dst[b], uint32_t, ns); G_ALLOC(tl[b], uint32_t, ns); }
     uint32_t* flags;   // [0] changed, [1] circles cut
     G_ALLOC(flags, uint32_t, 4);
+    SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));      // (flags[1] is read back as n_circles also when nothing was cut)
     uint32_t* h_flags = nullptr;
     SNK_HIP_TRY(hipHostMalloc((void**)&h_flags, 16, hipHostMallocDefault));
     int max_rounds = 2;
@@ -495,28 +496,93 @@ __global__ void __launch_bounds__(TB) spl_walk1_kernel(const unsigned long long*
     rdist[k] = d;
     rtail[k] = cur;        // the terminal state when nx == NONE (overwritten by the jumping otherwise)
 }
-__global__ void __launch_bounds__(TB) spl_walk2_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
-                                                       const uint32_t* __restrict__ w, const uint32_t* __restrict__ rdist,
-                                                       const uint32_t* __restrict__ rtail, uint64_t m, uint2* __restrict__ rk) {
-    uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (k >= m) return;
-    uint32_t cur = spl_state[k];
-    unsigned long long rec = wrec[cur];
-    uint32_t d = rdist[k];
-    const uint32_t t = rtail[k];
-    for (;;) {
-        rk[cur] = make_uint2(d, t);
-        uint32_t l = (uint32_t)rec;
-        if (l == NONE) break;
-        cur = l ^ 1u;
-        rec = wrec[cur];
-        if (rec >> 63) break;
-        d -= w ? w[cur >> 1] : 1u;
-    }
-}
 __global__ void __launch_bounds__(TB) unranked_check_kernel(const uint2* __restrict__ rk, uint64_t ns, uint32_t* __restrict__ flag) {
     uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
     if (s < ns && rk[s].y == NONE) *flag = 1u;
+}
+
+// ---- the one-GPU ranking's own set-up and second walk (rank_lists; the sharded ranking keeps the kernels above).
+// The splitter predicate is cheap to recompute from link[] and the hash, so no per-state mark array is kept: the scan reads
+// the predicate through an iterator, and one pass writes the compacted splitter list and the walk records.
+struct spl_flag_fn {
+    const uint32_t* link;
+    uint64_t ns;
+    uint32_t split_mask;
+    __device__ uint32_t operator()(uint64_t s) const {
+        if (s >= ns) return 0u;                       // the scan's closing element: sid[ns] = number of splitters
+        return (link[s ^ 1ull] == NONE || sampled_state((uint32_t)s, split_mask)) ? 1u : 0u;
+    }
+};
+__global__ void __launch_bounds__(TB) spl_setup_kernel(const uint32_t* __restrict__ link, const uint32_t* __restrict__ sid, uint64_t ns, uint32_t split_mask,
+                                                       uint32_t* __restrict__ spl_state, unsigned long long* __restrict__ wrec) {
+    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    if (s >= ns) return;
+    unsigned long long r = link[s];
+    if (link[s ^ 1ull] == NONE || sampled_state((uint32_t)s, split_mask)) {
+        const uint32_t id = sid[s];
+        r |= ((unsigned long long)id << 32) | (1ull << 63);
+        spl_state[id] = (uint32_t)s;
+    }
+    wrec[s] = r;
+}
+// The links are an involution: a list e_0 -> ... -> e_n also exists as its mirror e_n^1 -> ... -> e_0^1, and with
+// rk[e_i] = (d_i, e_n), d_i = sum of w_j over j > i, the mirror's rank is rk[e_i ^ 1] = (W - d_i - w_i, e_0 ^ 1) with
+// W = d_0 + w_0.  So only one list of each pair is walked a second time, and each visited state writes both ranks.
+// After the jumping has converged every head splitter knows its terminal t; t ^ 1 is the mirror's head, a splitter, and its
+// splitter id keys the pair (e_0, W): every entry that is read was written, so the table needs no clear.  (Before
+// convergence the entries read may be stale: that walk's result is thrown away.)
+__global__ void __launch_bounds__(TB) spl_head_info_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
+                                                           const uint32_t* __restrict__ w, const uint32_t* __restrict__ rdist,
+                                                           const uint32_t* __restrict__ rtail, uint64_t m, uint2* __restrict__ info) {
+    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    if (k >= m) return;
+    const uint32_t h = spl_state[k];
+    if ((uint32_t)wrec[h ^ 1u] != NONE) return;       // not a head
+    const uint32_t t = rtail[k];
+    const uint32_t id = (uint32_t)(wrec[t ^ 1u] >> 32) & 0x7FFFFFFFu;
+    info[id] = make_uint2(h, rdist[k] + (w ? w[h >> 1] : 1u));
+}
+// The list whose terminal is the smaller of (t, e_0 ^ 1) is the one walked.  t == e_0 ^ 1: the list is its own mirror (it
+// holds both states of every fragment on it), is walked as before and writes one rank per state.  *ranked counts the ranks
+// written: a state no walk reaches (a circle without a splitter) shows as *ranked != ns.
+__global__ void __launch_bounds__(TB) spl_walk2m_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
+                                                        const uint32_t* __restrict__ w, const uint32_t* __restrict__ rdist,
+                                                        const uint32_t* __restrict__ rtail, const uint2* __restrict__ info, uint64_t m,
+                                                        uint2* __restrict__ rk, uint32_t* __restrict__ ranked) {
+    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
+    uint32_t cnt = 0;
+    if (k < m) {
+        uint32_t cur = spl_state[k];
+        unsigned long long rec = wrec[cur];
+        uint32_t d = rdist[k];
+        const uint32_t t = rtail[k];
+        const uint2 hw = info[(uint32_t)(wrec[t ^ 1u] >> 32) & 0x7FFFFFFFu];
+        const uint32_t mt = hw.x ^ 1u;                // the mirror's terminal
+        if (t <= mt) {
+            const bool self = t == mt;
+            uint32_t wc = w ? w[cur >> 1] : 1u;
+            for (;;) {
+                if (self) {
+                    rk[cur] = make_uint2(d, t);
+                    cnt += 1;
+                } else {
+                    const uint32_t dm = hw.y - d - wc;
+                    // the two states of a fragment are neighbours in rk[]: one 16-byte store
+                    ((uint4*)rk)[cur >> 1] = (cur & 1u) ? make_uint4(dm, mt, d, t) : make_uint4(d, t, dm, mt);
+                    cnt += 2;
+                }
+                const uint32_t l = (uint32_t)rec;
+                if (l == NONE) break;
+                cur = l ^ 1u;
+                rec = wrec[cur];
+                if (rec >> 63) break;
+                wc = w ? w[cur >> 1] : 1u;
+                d -= wc;
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(ranked, cnt);
 }
 
 // ---- circles, cut without the general algorithm.  The ruling-set ranking sees a circle in one of two ways: its splitters form a
@@ -641,39 +707,34 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
         return rank_lists_wyllie(ctx, st, link, n, weights, circ, rk_out, n_circles, rounds, err, errcap);
     uint32_t cut_total = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-    uint8_t* spl;
-    uint32_t *flag32, *sid;
-    G_ALLOC(spl, uint8_t, ns + 1);
-    G_ALLOC(flag32, uint32_t, ns + 1);
+    uint32_t* sid;
     G_ALLOC(sid, uint32_t, ns + 1);
-    SNK_HIP_TRY(hipMemsetAsync(flag32 + ns, 0, 4, st));
     const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
-    SNK_HIP_TRY(snk_launch(spl_mark_kernel, snk_blocks(ns, TB), TB, 0, st, link, ns, split_mask, spl, flag32));
     {
+        auto flag_it = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), spl_flag_fn{link, ns, split_mask});
         size_t tb = 0;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, flag32, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
+        SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, flag_it, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
         void* tmp;
         int rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap);
         if (rc) return rc;
-        SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, flag32, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
+        SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, flag_it, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
     }
     uint32_t m32 = 0;
     SNK_HIP_TRY(hipMemcpyAsync(&m32, sid + ns, 4, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
     const uint64_t m = m32;
-    uint32_t* spl_state = flag32;      // flag32 is dead after the scan: reuse it for the compacted splitter list
-    if (m) SNK_HIP_TRY(snk_launch(spl_collect_kernel, snk_blocks(ns, TB), TB, 0, st, spl, sid, ns, spl_state));
+    uint32_t* spl_state;
+    G_ALLOC(spl_state, uint32_t, m + 1);
     uint32_t *rn[2], *rd[2], *rt[2];
     for (int b = 0; b < 2; ++b) { G_ALLOC(rn[b], uint32_t, m + 1); G_ALLOC(rd[b], uint32_t, m + 1); G_ALLOC(rt[b], uint32_t, m + 1); }
     unsigned long long* wrec;
     G_ALLOC(wrec, unsigned long long, ns);
-    SNK_HIP_TRY(snk_launch(spl_pack_kernel, snk_blocks(ns, TB), TB, 0, st, link, spl, sid, ns, wrec));
+    SNK_HIP_TRY(snk_launch(spl_setup_kernel, snk_blocks(ns, TB), TB, 0, st, (const uint32_t*)link, (const uint32_t*)sid, ns, split_mask, spl_state, wrec));
     SNK_HIP_TRY(snk_launch(spl_walk1_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, m, rn[0], rd[0], rt[0]));
-    uint32_t* rn_orig;
-    G_ALLOC(rn_orig, uint32_t, m + 1);
-    if (m) SNK_HIP_TRY(hipMemcpyAsync(rn_orig, rn[0], m * 4, hipMemcpyDeviceToDevice, st));
+    uint2* info;                       // (head state, list weight) of every list, keyed by the splitter id of its mirror's head
+    G_ALLOC(info, uint2, m + 1);
     // pointer jumping on the splitter list
-    uint32_t* flags;
+    uint32_t* flags;                   // [0] the batch's last round changed something, [1] ranks the second walk wrote
     G_ALLOC(flags, uint32_t, 4);
     int max_rounds = 2;
     while ((1ull << (max_rounds - 1)) < m + 1) ++max_rounds;
@@ -696,14 +757,14 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
             ++r_done;
         }
         // optimistic: rank the states from what the rounds left (harmless if they had not converged: it is redone)
-        SNK_HIP_TRY(hipMemsetAsync(rk, 0xFF, ns * 8, st));
-        SNK_HIP_TRY(snk_launch(spl_walk2_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, rd[cur], rt[cur], m, rk));
-        SNK_HIP_TRY(snk_launch(unranked_check_kernel, snk_blocks(ns, TB), TB, 0, st, rk, ns, flags + 1));
+        // (flags[1] was cleared with flags[0] above: a redone walk counts from zero)
+        SNK_HIP_TRY(snk_launch(spl_head_info_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, rd[cur], rt[cur], m, info));
+        SNK_HIP_TRY(snk_launch(spl_walk2m_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, rd[cur], rt[cur], (const uint2*)info, m, rk, flags + 1));
         uint32_t h2[2] = {0, 0};
         SNK_HIP_TRY(hipMemcpyAsync(h2, flags, 8, hipMemcpyDeviceToHost, st));
         SNK_HIP_TRY(snk_sync(st));
         converged = h2[0] == 0;
-        unranked = h2[1] != 0;          // states no walk reached: a circle without a splitter
+        unranked = h2[1] != ns;         // states no walk reached: a circle without a splitter
     }
     if (converged && !unranked) {
         *rk_out = rk;
@@ -714,6 +775,13 @@ static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, 
     // circles.  In the join (circ given) they are cut here and the lists ranked once more; the k-mer level ranking of the global
     // graph stage needs the cut AT the minimum k-mer (it is the reference's cut there): the general algorithm does that.
     if (!circ || attempt == 1) break;
+    // the cut wants every splitter's next splitter as the first walk left it; the jumping has overwritten that, and only this
+    // rare path needs it: walk again (wrec[] is unchanged) instead of keeping a copy on every call
+    uint32_t *rn_orig, *rd_spare, *rt_spare;
+    G_ALLOC(rn_orig, uint32_t, m + 1);
+    G_ALLOC(rd_spare, uint32_t, m + 1);
+    G_ALLOC(rt_spare, uint32_t, m + 1);
+    SNK_HIP_TRY(snk_launch(spl_walk1_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, m, rn_orig, rd_spare, rt_spare));
     uint32_t n_cut = 0, bad = 0;
     int rcc = cut_circles_sparse(ctx, st, link, ns, m, spl_state, wrec, rn_orig, rn[cur], converged, circ, &n_cut, &bad, err, errcap);
     if (rcc) return rcc;

@@ -137,6 +137,23 @@ __device__ __forceinline__ uint32_t oriented_base(snk_kmer k, bool rc, int idx) 
 }
 
 // ---------------------------------------------------------------------------------------------- L1: local prune
+// The k-mer spectrum rides on the prune: it writes counts[] for every retained k-mer exactly once, so the two later passes over
+// counts[] (the maximum, then the histogram: 2 x 1.07 GB on the benchmark) are not needed while the largest count stays below
+// BL_SPEC_BINS -- snk_spectrum's minimum bin count, so the array handed out is the same.  Counts below BL_SPEC_LDS (all but repeats)
+// go to a per-workgroup LDS histogram, flushed once per workgroup into one of BL_SPEC_REPL copies (a third of a million workgroups
+// adding to the same few dozen addresses would queue up on them; each copy is four lines of its own); larger counts go straight to the bins.
+// layout of B->spec (64-bit words): [BL_SPEC_BINS bins][BL_SPEC_REPL x BL_SPEC_LDS / 2 words of 32-bit copies][16 words: the overflow flag's line]
+constexpr int BL_SPEC_LDS = 128;
+constexpr int BL_SPEC_REPL = 64;
+constexpr uint32_t BL_SPEC_BINS = 65536u;
+constexpr uint32_t BL_SPEC_OVER = BL_SPEC_BINS + BL_SPEC_REPL * BL_SPEC_LDS / 2;
+constexpr uint32_t BL_SPEC_WORDS = BL_SPEC_OVER + 16;
+__global__ void __launch_bounds__(BL_SPEC_LDS) bl_spec_fold_kernel(unsigned long long* __restrict__ spec) {
+    const uint32_t* rep = reinterpret_cast<const uint32_t*>(spec + BL_SPEC_BINS);
+    unsigned long long s = 0;
+    for (int r = 0; r < BL_SPEC_REPL; ++r) s += rep[r * BL_SPEC_LDS + threadIdx.x];
+    spec[threadIdx.x] += s;
+}
 template <int K, int CAP, int T, bool BIG, bool GR, int MM>
 __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __restrict__ desc, uint32_t NB, bl_shard sh, const bl_regions& rg,
                                                      const snk_u128* __restrict__ keys, const uint64_t* __restrict__ vals,
@@ -144,7 +161,8 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
                                                      uint32_t* __restrict__ count_out, uint8_t* __restrict__ pend_out,
                                                      uint32_t* __restrict__ nbr_out, uint32_t* __restrict__ nbnd,
                                                      uint32_t* __restrict__ biglist, uint32_t* __restrict__ nbig,
-                                                     unsigned long long* __restrict__ gindex, uint64_t gmask) {
+                                                     unsigned long long* __restrict__ gindex, uint64_t gmask,
+                                                     unsigned long long* __restrict__ spec, uint32_t* __restrict__ shist) {
     constexpr int HT = CAP <= 256 ? 512 : 4096;
     // at K=48 without groups only the top 32 bits of the low key word are sequence (LDS per chunk = waves per CU)
     typedef typename std::conditional<(K <= 48 && !GR), uint32_t, uint64_t>::type klo_w;
@@ -324,7 +342,15 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
         ctx_out[gi] = (uint8_t)keep;
         pend_out[gi] = (uint8_t)pm;
         if (sh.premote) sh.premote[gi] = (uint8_t)(res >> 16);
-        count_out[gi] = (uint32_t)(v >> 8);
+        const uint32_t cnt = (uint32_t)(v >> 8);
+        count_out[gi] = cnt;
+        if (spec) {
+            // the spectrum, here where the count is in a register (spectrum_kernel's rule: saturated at 2^24-1, one bin per count)
+            const uint32_t sc = cnt > 0xFFFFFFu ? 0xFFFFFFu : cnt;
+            if (sc < (uint32_t)BL_SPEC_LDS) atomicAdd(&shist[sc], 1u);
+            else if (sc < BL_SPEC_BINS) atomicAdd(&spec[sc], 1ull);
+            else spec[BL_SPEC_OVER] = 1ull;          // more bins are needed than were laid out: the host takes snk_spectrum
+        }
         // (chunk-local index << 1 | rev fits 12 bits -- a chunk holds at most 1280 k-mers --: one word per k-mer for both sides, 0xFFF = none;
         // bit 15: the k-mer is its own reverse complement -- the fragment kernel's sizing pass then needs no keys at all)
         nbr_out[gi] = (nb0 == NONE ? 0x0FFFu : nb0) | (snk_kmer_eq(k, kr) ? 0x8000u : 0u) | ((nb1 == NONE ? 0x0FFFu : nb1) << 16);
@@ -368,19 +394,31 @@ __global__ void __launch_bounds__(T) bl_prune_kernel(const uint4* __restrict__ d
                                                      uint32_t* __restrict__ count_out, uint8_t* __restrict__ pend_out,
                                                      uint32_t* __restrict__ nbr_out, uint32_t* __restrict__ nbnd,
                                                      uint32_t* __restrict__ biglist, uint32_t* __restrict__ nbig, const uint32_t* __restrict__ n_dev,
-                                                     unsigned long long* __restrict__ gindex, uint64_t gmask) {
+                                                     unsigned long long* __restrict__ gindex, uint64_t gmask, unsigned long long* __restrict__ spec) {
+    __shared__ uint32_t shist[BL_SPEC_LDS];
+    if (spec) {
+        for (int j = threadIdx.x; j < BL_SPEC_LDS; j += T) shist[j] = 0;
+        __syncthreads();
+    }
     if (BIG && n_dev) {
         // the list's length is still on the device (no read-back between the two prune launches): a fixed grid strides over it
         const uint32_t nb = *n_dev;
         for (uint32_t w = blockIdx.x; w < nb; w += gridDim.x)
-            bl_prune_chunk<K, CAP, T, BIG, GR, MM>(biglist_in[w], desc, NB, sh, rg, keys, vals, do_prune, ctx_out, count_out, pend_out, nbr_out, nbnd, biglist, nbig, gindex, gmask);
-        return;
+            bl_prune_chunk<K, CAP, T, BIG, GR, MM>(biglist_in[w], desc, NB, sh, rg, keys, vals, do_prune, ctx_out, count_out, pend_out, nbr_out, nbnd, biglist, nbig, gindex, gmask,
+                                                   spec, shist);
+    } else {
+        for (uint32_t r = 0; r < cpw; ++r) {
+            const uint32_t w = blockIdx.x * cpw + r;
+            if (w >= nchunks) break;
+            bl_prune_chunk<K, CAP, T, BIG, GR, MM>(BIG ? biglist_in[w] : w, desc, NB, sh, rg, keys, vals, do_prune, ctx_out, count_out, pend_out, nbr_out,
+                                           nbnd, biglist, nbig, gindex, gmask, spec, shist);
+        }
     }
-    for (uint32_t r = 0; r < cpw; ++r) {
-        const uint32_t w = blockIdx.x * cpw + r;
-        if (w >= nchunks) return;
-        bl_prune_chunk<K, CAP, T, BIG, GR, MM>(BIG ? biglist_in[w] : w, desc, NB, sh, rg, keys, vals, do_prune, ctx_out, count_out, pend_out, nbr_out,
-                                       nbnd, biglist, nbig, gindex, gmask);
+    if (spec) {
+        __syncthreads();
+        uint32_t* rep = reinterpret_cast<uint32_t*>(spec + BL_SPEC_BINS) + (blockIdx.x % BL_SPEC_REPL) * BL_SPEC_LDS;
+        for (int j = threadIdx.x; j < BL_SPEC_LDS; j += T)
+            if (shist[j]) atomicAdd(&rep[j], shist[j]);
     }
 }
 
@@ -961,20 +999,26 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
         G_ALLOC(index0, unsigned long long, tg0 + 1);
         SNK_HIP_TRY(hipMemsetAsync(index0, 0, (tg0 + 1) * 8, st));
     }
+    unsigned long long* spec = nullptr;
+    if (B->want_spec) {
+        G_ALLOC(spec, unsigned long long, BL_SPEC_WORDS);
+        SNK_HIP_TRY(hipMemsetAsync(spec, 0, (size_t)BL_SPEC_WORDS * 8, st));
+    }
     bl_regions rg;
     rg.keys_r = tab->keys_r; rg.vals_r = tab->vals_r; rg.desc_src = desc_src;
     rg.keys_dense = const_cast<snk_u128*>(tab->keys);
     const bool long_m = ctx->mlen == (uint32_t)SNK_M_LONG;
     SNK_HIP_TRY(snk_launch(long_m ? bl_prune_kernel<K, SCAP, ST, false, GR, SNK_M_LONG> : bl_prune_kernel<K, SCAP, ST, false, GR, SNK_M_OF(K)>, snk_blocks(nchunks, cpw), ST, 0, st, (const uint4*)B->desc, NBh, sh, rg,
                            (const uint32_t*)nullptr, nchunks, cpw, tab->keys, tab->vals, B->do_prune | (snk_opt_u32(ctx, SNK_OPT_bl_noclassify) ? 2u : 0u), B->ctx, B->counts, B->pend, B->nbr, nbnd,
-                           B->biglist, ctr, (const uint32_t*)nullptr, index0, tg0 - 1));
+                           B->biglist, ctr, (const uint32_t*)nullptr, index0, tg0 - 1, spec));
     // the chunks that did not fit the one-wave variant (split sub-passes near the table's capacity): their number stays on the
     // device until the read-back below -- the big variant runs a fixed grid that strides over the list
     uint32_t h_nbig = 0;
     SNK_HIP_TRY(hipMemcpyAsync(ctr + 1, ctr, 4, hipMemcpyDeviceToDevice, st));       // (ctr[0] is the small kernel's list cursor)
     SNK_HIP_TRY(snk_launch(long_m ? bl_prune_kernel<K, BCAP, BT, true, GR, SNK_M_LONG> : bl_prune_kernel<K, BCAP, BT, true, GR, SNK_M_OF(K)>, 2048, BT, 0, st, (const uint4*)B->desc, NBh, sh, rg,
                            (const uint32_t*)B->biglist, 0u, 1u, tab->keys, tab->vals, B->do_prune | (snk_opt_u32(ctx, SNK_OPT_bl_noclassify) ? 2u : 0u), B->ctx, B->counts, B->pend, B->nbr,
-                           nbnd, B->biglist, ctr + 2, (const uint32_t*)(ctr + 1), index0, tg0 - 1));
+                           nbnd, B->biglist, ctr + 2, (const uint32_t*)(ctr + 1), index0, tg0 - 1, spec));
+    if (spec) SNK_HIP_TRY(snk_launch(bl_spec_fold_kernel, 1, BL_SPEC_LDS, 0, st, spec));
     if (tab->keys_r) {       // the region-partitioned copy is dead (stream order): later stages may reuse it
         snk_ctx_release_block(ctx, tab->keys_r);
         snk_ctx_release_block(ctx, tab->vals_r);
@@ -990,12 +1034,15 @@ static int bl_prune_impl(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* er
         if (rc) return rc;
         SNK_HIP_TRY(rocprim::reduce(tmp, tb, in, d_sum, 0ull, (size_t)nchunks, rocprim::plus<unsigned long long>(), st));
     }
-    unsigned long long h_bnd = 0, h_gaveup = 0;
+    unsigned long long h_bnd = 0, h_gaveup = 0, h_spec_over = 0;
     if (index0) SNK_HIP_TRY(hipMemcpyAsync(&h_gaveup, index0 + tg0, 8, hipMemcpyDeviceToHost, st));
+    if (spec) SNK_HIP_TRY(hipMemcpyAsync(&h_spec_over, spec + BL_SPEC_OVER, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(hipMemcpyAsync(&h_bnd, d_sum, 8, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(hipMemcpyAsync(&h_nbig, ctr + 1, 4, hipMemcpyDeviceToHost, st));
     SNK_HIP_TRY(snk_sync(st));
     B->nbig = h_nbig;
+    B->spec = spec;
+    B->spec_over = h_spec_over != 0;
     B->n_boundary = h_bnd;
     ctx->last_bnd = h_bnd; ctx->last_bnd_n = n;
     uint64_t tg = 1024;
@@ -1125,6 +1172,7 @@ static int local_graph_impl(snk_ctx* ctx, hipStream_t st, const snk_table* tab, 
     B.K = K;
     B.world = 1;
     B.do_prune = do_prune;
+    B.want_spec = sort_table ? 0u : 1u;
     int rc = bl_prune_impl<K, GR>(ctx, st, &B, err, errcap);
     if (rc) return rc;
     tm.mark();  // 1
@@ -1170,7 +1218,10 @@ static int local_graph_impl(snk_ctx* ctx, hipStream_t st, const snk_table* tab, 
         SNK_HIP_TRY(snk_launch(bl_unpack_vals_kernel, snk_blocks(n, TB), TB, 0, st, v_out, n, B.counts, B.ctx));
         *keys_final = k_out;
     }
-    if ((rc = snk_spectrum(ctx, st, B.counts, n, &out->spectrum, &out->spectrum_bins, err, errcap))) return rc;
+    if (B.spec && !B.spec_over) {       // the prune has it already (every count below the fixed bin range)
+        out->spectrum = B.spec;
+        out->spectrum_bins = BL_SPEC_BINS;
+    } else if ((rc = snk_spectrum(ctx, st, B.counts, n, &out->spectrum, &out->spectrum_bins, err, errcap))) return rc;
     tm.mark();  // 5
     if (ms) { ms[0] = tm.ms(0, 1); ms[1] = tm.ms(1, 2); ms[2] = tm.ms(2, 3); ms[3] = tm.ms(3, 4); ms[4] = tm.ms(4, 5); }
     return SNK_OK;
