@@ -461,7 +461,7 @@ uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components,
  * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
 uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -787,6 +787,62 @@ int snk_dev_edge_pairs(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void*
  * *pairs is malloc'ed (snk_host_free). */
 int snk_write_hops(const char* path, uint64_t n_pairs, const int32_t* pairs, char* err, size_t errcap);
 int snk_read_hops(const char* path, uint64_t* n_pairs, int32_t** pairs, char* err, size_t errcap);
+
+/* ---- gap closures: CloseGap and CloseGap2, closures.fastb ---------------------------------------------------------------------
+ * CloseGap2 / CloseGap, lib/assembly/src/10X/Closomatic.cc:480-657 / :356-459: the third step of StageFindPatch
+ * (10X/runstages/RunStages.cc:334-384), run for every pair of a.hops.  The result is EXACTLY what DF writes as closures.fastb
+ * (10X/DF.cc:645) with STACKSTER=False: Stackster, which adds more closures for the same pairs with DF's default STACKSTER=True, is not
+ * part of this library.  Per pair (e1, e2), sides es = { e1, inv[e2] }:
+ *   rows        of side e: for every index entry of e, in index order, every place j with p[j] == e -- pos = offset - sum Kmers(p[l < j]),
+ *               forward; then the same over inv[e], the row reverse-complemented.  A read that visits the edge twice, or that the index
+ *               lists twice, gives its rows as often.  Forward cells in front of the edge are dropped; nothing is cut at its end.
+ *               M = the largest column over all rows; the stack keeps its last max_width columns and loses the rows without a cell
+ *               there; the stack of inv[e2] is reversed (both are when e1 == inv[e2])
+ *   CloseGap2   in front of that: followers = the (edge, distance) behind e along the paths (those on inv[e] through inv); a group of 5
+ *               or more identical ones gives every 32-mer of that edge with its position; the partner of a forward read of side ei that is
+ *               no forward row of side 1 - ei, and whose 32-mers are found there at exactly one distinct position - place, becomes a
+ *               forward row at the END of side 1 - ei (ei = 0 first, ids ascending; the ids are taken before any partner is added)
+ *   offsets     GetOffsets1 (paths/long/ReadStack.cc:1192-1512) on the two seed consensuses (quality sums as doubles in row order, Q0
+ *               counts 0.1, Q1 and Q2 0.2; the LOWEST base on a tie): none if either has 1000 columns or more; 8-mer seeds; per offset
+ *               bits = -10/6 x the minimum of log10(BinomialSum(n, k, 0.75)) over its windows, bad windows as written; bits >= 25; the
+ *               invalidation with its flank of 10; big near small.  The table of log binomial sums is made once per context ON THE HOST with
+ *               the reference's arithmetic (long double, pow, log10); the device only reads it
+ *   closures    for at most two surviving offsets (more: none): stack 1's rows, then stack 2's shifted by the offset; per column the
+ *               HIGHEST base on a tie (an empty column: T)
+ * The result is in pair order, then offset order -- the order closures.fastb has.  Qualities are phred values of at most 63 (what the reference's PQVec holds).
+ * in: packed rows, quality rows, lengths.  paths: plain ReadPaths (the reference reads a.paths here, RunStages.cc:326): offsets are ints,
+ * nothing wraps, the refusals of SNK_BADS_X do not apply.  px: the paths index of these paths, or NULL (made inside the call).  d_pairs:
+ * device i32[2 * n_pairs], the pairs of snk_dev_hops.  max_width: 0 = 400, DF's constant.
+ * CloseGap2's 32-mers live in a hash table of device scratch per pair, sized by what the pair needs: bod_budget of them per side at most (0 = the default and the most, 262 144); a pair with a side over the budget
+ * is finished by a host routine without a bound (n_place_host counts them).  No result depends on the budget.  SNK_CLOSE_PLACE_HOST sends
+ * every pair's placement to the host routine (tests).
+ * closure_off / bases are what snk_dev_patch_pieces and snk_patch_plan_sizes take (closure_off after a download).  Context memory valid
+ * until the context's next top-level call.  The result is bit-identical from call to call and depends on no tuning option.
+ * SNK_E_ARG: an odd read count, a pair id outside the graph, an inv that is not an involution, a px whose n_hbv_edges or n_entries do
+ * not match, unknown flags, NULL reads with n_pairs > 0.  After any failure *out is all zero. */
+#define SNK_CLOSE_CG1 1u          /* CloseGap (DF's CG2=False); without it CloseGap2, DF's default */
+#define SNK_CLOSE_PLACE_HOST 2u   /* tests: every partner placement on the host leg */
+typedef struct snk_dev_closures {
+    uint64_t n_closures, n_bases, n_pairs;
+    const void* closure_off;                   /* u64[n_closures + 1] */
+    const void* bases;                         /* u8[n_bases]: base codes 0 .. 3 */
+    const void* pair_first;                    /* u64[n_pairs + 1]: the closures of pair p are pair_first[p] .. pair_first[p + 1] */
+    uint64_t n_pairs_0, n_pairs_1, n_pairs_2, n_pairs_many;   /* pairs by surviving offsets; more than two gives no closure (Closomatic.cc:647) */
+    uint64_t n_rows;                           /* stack rows kept, both sides of every pair */
+    uint64_t n_partners_tried, n_partners_placed;
+    uint64_t n_followers;                      /* (edge, distance) groups of 5 or more */
+    uint64_t n_cons_too_long;                  /* pairs with a consensus of 1000 columns or more */
+    uint64_t n_place_host;                     /* pairs whose placement the host routine did */
+    float ms, tables_ms;                       /* HIP events: the whole call; graph tables, checks, the index */
+    float gather_ms, close_ms;                 /* rows and placement; offsets and closures */
+    uint32_t max_width, bod_budget;            /* what the call ran with */
+    uint64_t reserved[4];
+} snk_dev_closures;
+int snk_dev_close_gaps(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h,
+                       const int32_t* inv /* host */, const snk_dev_reads* in, const snk_dev_paths* paths, const snk_dev_pidx* px /* NULL: made inside */,
+                       uint64_t n_pairs, const void* d_pairs /* i32[2 * n_pairs] */, uint32_t max_width /* 0 = 400 */, uint32_t flags,
+                       uint32_t bod_budget /* 0 = default */, snk_dev_closures* out, void* stream, char* err, size_t errcap);
+/* closures.fastb = BinaryWriter::writeFile(vec<basevector>) (10X/DF.cc:645) is the layout snk_write_bv writes and snk_read_bv reads. */
 
 /* ---- gap patches into the graph: StageInsertPatch ---------------------------------------------------------------------
  * StageInsertPatch, lib/assembly/src/10X/runstages/RunStages.cc:176-230 (10X/DF.cc:656): the graph is rebuilt from its own edges, the

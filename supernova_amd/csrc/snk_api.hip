@@ -481,6 +481,7 @@ extern "C" void snk_ctx_destroy(snk_ctx* ctx) {
     if (ctx->host_io && ctx->host_io_free) ctx->host_io_free(ctx->host_io);
     if (ctx->df_io && ctx->df_io_free) ctx->df_io_free(ctx->df_io);
     if (ctx->shard_host && ctx->shard_host_free) ctx->shard_host_free(ctx->shard_host);
+    if (ctx->close_table && ctx->close_table_free) ctx->close_table_free(ctx->close_table);
     if (ctx->stream_job && ctx->stream_job_free) ctx->stream_job_free(ctx->stream_job);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;

@@ -84,6 +84,8 @@ struct snk_ctx {
     void (*stream_job_invalidate)(void*) = nullptr;   // the arena the open job lives in is being recycled: append / finish must fail from now on
     void* shard_host = nullptr; // pinned staging, exchange stream and events of snk_shard_step (snk_shard_step.hip)
     void (*shard_host_free)(void*) = nullptr;
+    void* close_table = nullptr; // device copy of GetOffsets1's table of log binomial sums, made by the first snk_dev_close_gaps (snk_close.hip); plain hipMalloc
+    void (*close_table_free)(void*) = nullptr;
 };
 
 // every top-level entry point: the context's device is current

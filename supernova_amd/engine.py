@@ -160,7 +160,7 @@ class Result:
             self._e.lib.snk_hbv_free(C.byref(h))
 
     def path_reads(self, rows, read_len: int, quals, lens=None, mark_dups=False, bc=None, unitig_bcs=False, download=True, bcs_nocut=False,
-                   paths_index=False, pathsx=False, ebcx=False, extend=False, mark_bads=False, hops=False):
+                   paths_index=False, pathsx=False, ebcx=False, extend=False, mark_bads=False, hops=False, closures=False):
         """f1: the reads (untrimmed packed rows + quality rows on the device) onto the graph of this result's unitigs --
         pathReads with the new aligner (BuildReadQGraph48.cc:1441-1469).  Returns (offset i32[n], n_edges u32[n], edges i32[sum],
         info) on the host, HBV edge ids as numbered by buildHBVFromEdges.  Must be called before the engine's next count_graph.
@@ -193,7 +193,13 @@ class Result:
         hops (True, or "one_good" for SNK_HOPS_ONE_GOOD; needs bc, implies paths_index): FindEdgePairs over these paths (10X/Closomatic.cc:17-354;
         snk_dev_edge_pairs), the second step of StageFindPatch, with the flags of mark_bads when that is given and all-false flags
         otherwise -> info['hops'] = i32[n, 2], the pairs ascending: what graphio.write_hops / write_a48 make a.hops of;
-        info['hops_stats'] = the counters and times.  download=False: the stats only."""
+        info['hops_stats'] = the counters and times.  download=False: the stats only.
+        closures (True, or "cg1" for SNK_CLOSE_CG1; needs hops): CloseGap2 / CloseGap for those pairs (10X/Closomatic.cc:356-657;
+        snk_dev_close_gaps), the third step of StageFindPatch with STACKSTER=False -> info['closures'] = (closure_off u64[n + 1], bases u8[],
+        pair_first u64[n_pairs + 1]): what graphio.write_closures makes closures.fastb of and Engine.insert_patch takes;
+        info['closures_stats'] = the counters and times.  download=False: the stats only."""
+        if closures and not hops:
+            raise ValueError("path_reads(closures=...) needs hops: the pairs to close")
         if ebcx and bc is None:
             raise ValueError("path_reads(ebcx=...) needs bc: the barcode of every read, on the device")
         if hops and bc is None:
@@ -228,6 +234,8 @@ class Result:
                 bad = torch.zeros(max(int(out.n_reads) // 2, 1), dtype=torch.uint8, device=bc.device) if bd is None else None
                 hp = e._hops(K, graph, inv, out, px, bc.data_ptr(), bad.data_ptr() if bd is None else bd.bad, hops == "one_good")
                 stages.update(e._hops_info(hp, download))
+                if closures:
+                    stages.update(e._close_info(e._close(K, graph, inv, r, out, px, hp.n_pairs, hp.pairs, closures == "cg1"), download))
             if ebcx:
                 stages.update(e._ebcx_info(e._ebcx(out, bc, n_hbv, inv, ebcx == "general"), n_hbv, download))
             if pathsx:
@@ -345,6 +353,13 @@ def _hops_stats(hp: "_lib.SnkDevHops") -> dict:
     d = {k: int(getattr(hp, k)) for k in ("n_pairs", "n_part1", "n_part2", "n_part3", "n_sink_edges", "n_long_edges", "n_two_class", "n_ext_round0", "n_ext_closure",
                                           "n_ext_host", "n_not_extended", "ext_budget")}
     d.update({k: float(getattr(hp, k)) for k in ("ms", "tables_ms", "part12_ms", "part3_ms")})
+    return d
+
+
+def _close_stats(cl: "_lib.SnkDevClosures") -> dict:
+    d = {k: int(getattr(cl, k)) for k in ("n_closures", "n_bases", "n_pairs", "n_pairs_0", "n_pairs_1", "n_pairs_2", "n_pairs_many", "n_rows", "n_partners_tried",
+                                          "n_partners_placed", "n_followers", "n_cons_too_long", "n_place_host", "max_width", "bod_budget")}
+    d.update({k: float(getattr(cl, k)) for k in ("ms", "tables_ms", "gather_ms", "close_ms")})
     return d
 
 
@@ -493,6 +508,20 @@ class Engine:
             d["hops"] = self._fetch(hp.pairs, 2 * hp.n_pairs, np.int32).reshape(-1, 2)
         return d
 
+    def _close(self, K, graph, inv, r, p, px, n_pairs, pairs_ptr, cg1=False, max_width=0, place_host=False, bod_budget=0):
+        return self._stage(self.lib.snk_dev_close_gaps, _lib.SnkDevClosures(), int(K), *graph, inv.ctypes.data, C.byref(r), C.byref(p), C.byref(px) if px is not None else None,
+                           int(n_pairs), pairs_ptr, int(max_width), (_lib.CLOSE_CG1 if cg1 else 0) | (_lib.CLOSE_PLACE_HOST if place_host else 0), int(bod_budget))
+
+    def _close_fetch(self, cl):
+        """-> (closure_off u64[n + 1], bases u8[], pair_first u64[n_pairs + 1]) on the host"""
+        return (self._fetch(cl.closure_off, cl.n_closures + 1, np.uint64), self._fetch(cl.bases, cl.n_bases, np.uint8), self._fetch(cl.pair_first, cl.n_pairs + 1, np.uint64))
+
+    def _close_info(self, cl, download):
+        d = {"closures_stats": _close_stats(cl)}
+        if download:
+            d["closures"] = self._close_fetch(cl)
+        return d
+
     def _pidx(self, p, n_hbv, inv):
         return self._stage(self.lib.snk_dev_paths_index, _lib.SnkDevPidx(), C.byref(p), n_hbv, inv.ctypes.data)
 
@@ -625,6 +654,24 @@ class Engine:
         hp = self._hops(K, _graph(h, unitig_off, unitig_bases), inv, p, pidx, bc.data_ptr(), bad.data_ptr(), one_good, ext_host, ext_budget)
         return (self._hops_info(hp, True)["hops"] if download else hp), _hops_stats(hp)
 
+    # ---- CloseGap2 / CloseGap (the third step of StageFindPatch): the closures of the pairs, closures.fastb
+    def close_gaps(self, K: int, h: "_lib.SnkHbv", unitig_off: torch.Tensor, unitig_bases: torch.Tensor, inv: np.ndarray, rows: torch.Tensor, read_len: int,
+                   quals: torch.Tensor, lens: torch.Tensor | None, offset: torch.Tensor, n_edges: torch.Tensor, edges: torch.Tensor, pairs: torch.Tensor,
+                   start: torch.Tensor | None = None, pidx=None, cg1: bool = False, max_width: int = 0, place_host: bool = False, bod_budget: int = 0,
+                   download: bool = True):
+        """snk_dev_close_gaps -- CloseGap2 (cg1=True: CloseGap; 10X/Closomatic.cc:356-657) -- over tensors on this engine's device: the graph and
+        inv as for edge_pairs, the reads as for mark_bads, the paths as for extend_paths, pairs i32[n_pairs, 2] (edge_pairs).  What DF writes
+        as closures.fastb with STACKSTER=False.  max_width: 0 = 400.  place_host / bod_budget: where CloseGap2's partner placement runs (no
+        result depends on either).  -> (closure_off u64[n + 1], bases u8[], pair_first u64[n_pairs + 1], stats) on the host: the tuple
+        goes into insert_patch as its closures as it is; download=False: (SnkDevClosures, stats), device memory of the context, valid until its next
+        top-level call."""
+        p, start = dev_paths(offset, n_edges, edges, start)
+        inv = np.ascontiguousarray(inv, dtype=np.int32)
+        n_pairs = int(pairs.shape[0]) if len(pairs.shape) > 1 else int(pairs.shape[0]) // 2
+        cl = self._close(K, _graph(h, unitig_off, unitig_bases), inv, dev_reads(rows, read_len, quals, lens), p, pidx, n_pairs, pairs.data_ptr(), cg1, max_width,
+                         place_host, bod_budget)
+        return (*self._close_fetch(cl), _close_stats(cl)) if download else (cl, _close_stats(cl))
+
     # ---- gap patches into the graph (StageInsertPatch)
     def insert_patch(self, graph, closures, paths) -> "PatchResult":
         """StageInsertPatch (10X/runstages/RunStages.cc:176-230) on this engine's device: pieces -> count -> merge -> hbv -> to3 / left3 ->
@@ -632,7 +679,7 @@ class Engine:
         snk_dev_patch_paths).
           graph     (K, h, unitig_off, unitig_bases): h a lib.SnkHbv of the OLD unitigs (of snk_dev_hbv, or graphio.hbv_handle), unitig_off
                     u64 / i64[U + 1] (numpy or tensor), unitig_bases u8[] (tensor on the device, or numpy), in the order h's bvcomp_order names
-          closures  (off u64[n + 1] numpy, base codes u8[]: numpy or tensor on the device)
+          closures  (off u64[n + 1] numpy, base codes u8[]: numpy or tensor on the device), or the longer tuple close_gaps returns: only these two are read
           paths     (offset i32[n], n_edges i32[n] read as u32, edges i32[sum], start i64[n + 1] or None) tensors on the device, on the old graph
         The count in the middle is a top-level call that frees everything the context handed out before, so the engine first copies what
         it was given into tensors of its own and works on those; the caller's tensors are only read.  -> PatchResult: everything in

@@ -154,6 +154,12 @@ def write_hops(path, pairs: np.ndarray) -> None:
     _lib.call(_lib.load().snk_write_hops, str(path).encode(), len(pairs), pairs.ctypes.data)
 
 
+def write_closures(path, off: np.ndarray, bases: np.ndarray) -> None:
+    """closures.fastb (vec<basevector> of StageFindPatch, 10X/DF.cc:645): closure_off u64[n + 1] and base codes u8[], as snk_dev_close_gaps
+    gives them.  BinaryWriter::writeFile(vec<basevector>) is the layout of the unitig hand-off file: snk_write_bv writes it."""
+    write_bv(path, off, bases)
+
+
 def read_hops(path) -> np.ndarray:
     """a.hops -> pairs i32[n, 2]."""
     lib = _lib.load()

@@ -137,6 +137,18 @@ HOPS_ONE_GOOD = 1                # SNK_HOPS_ONE_GOOD
 HOPS_EXT_HOST = 2                # SNK_HOPS_EXT_HOST
 
 
+class SnkDevClosures(C.Structure):
+    _fields_ = [("n_closures", C.c_uint64), ("n_bases", C.c_uint64), ("n_pairs", C.c_uint64), ("closure_off", C.c_void_p), ("bases", C.c_void_p),
+                ("pair_first", C.c_void_p), ("n_pairs_0", C.c_uint64), ("n_pairs_1", C.c_uint64), ("n_pairs_2", C.c_uint64), ("n_pairs_many", C.c_uint64),
+                ("n_rows", C.c_uint64), ("n_partners_tried", C.c_uint64), ("n_partners_placed", C.c_uint64), ("n_followers", C.c_uint64),
+                ("n_cons_too_long", C.c_uint64), ("n_place_host", C.c_uint64), ("ms", C.c_float), ("tables_ms", C.c_float), ("gather_ms", C.c_float),
+                ("close_ms", C.c_float), ("max_width", C.c_uint32), ("bod_budget", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+
+CLOSE_CG1 = 1                    # SNK_CLOSE_CG1
+CLOSE_PLACE_HOST = 2             # SNK_CLOSE_PLACE_HOST
+
+
 class SnkPatchPlan(C.Structure):
     _fields_ = [("n_pieces", C.c_uint64), ("n_unitig_pieces", C.c_uint64), ("n_junctions", C.c_uint64), ("n_closure_pieces", C.c_uint64),
                 ("n_lonely_max", C.c_uint64), ("reserved", C.c_uint64 * 3)]
@@ -325,6 +337,8 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_mark_bads": (C.c_int, [vp, u32, P(SnkDevReads), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevBads), vp, cp, sz]),
         "snk_dev_edge_pairs": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevPaths), P(SnkDevPidx), vp, vp, u32, u32, P(SnkDevHops), vp, cp, sz]),
         "snk_write_hops": (C.c_int, [cp, u64, vp, cp, sz]),
+        "snk_dev_close_gaps": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevReads), P(SnkDevPaths), P(SnkDevPidx), u64, vp, u32, u32, u32, P(SnkDevClosures),
+                                        vp, cp, sz]),
         "snk_read_hops": (C.c_int, [cp, P(u64), P(P(i32)), cp, sz]),
         "snk_dev_mark_bads_df": (C.c_int, [vp, u32, vp, u64, u64, u32, u32, u64, u64, vp, vp, P(SnkHbv), P(SnkDevPaths), u32, P(SnkDevBads), cp, sz]),
         "snk_patch_plan_sizes": (C.c_int, [u32, u64, vp, P(SnkHbv), u64, vp, P(SnkPatchPlan), cp, sz]),

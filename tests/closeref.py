@@ -1,0 +1,596 @@
+"""A plain numpy / Python restatement of the reference's CloseGap and CloseGap2 -- lib/assembly/src/10X/Closomatic.cc:356-657, the third
+step of StageFindPatch (10X/runstages/RunStages.cc:334-384) with STACKSTER=False, whose result DF keeps as closures.fastb -- with the parts
+of paths/long/ReadStack.cc they call (GetOffsets1 :1192-1512, Merge :355-398, Consensus1 :406-427, ColumnConsensus1 :1841-1861, Trim
+:714-725, Reverse :346-353), and the fixtures under tests/golden/closures/ (closures and file bytes the reference's own functions wrote,
+see tests/golden/make_closures_golden.py, which asserts that this restatement reproduces them before it saves a case).
+
+A stack is kept as its window only: rows x (at most max_width) columns of base codes (-1: blank) and qualities (-1: undefined).  Column
+sums are doubles added in row order, as the reference adds them.  Unlike the reference it counts what the device code counts (COUNTERS)
+and says which filter of GetOffsets1 removed an offset (FILTERS).
+"""
+from __future__ import annotations
+
+from pathlib import Path
+from types import SimpleNamespace
+
+import numpy as np
+
+CLOSURES = Path(__file__).resolve().parent / "golden" / "closures"
+MAX_WIDTH = 400                                        # RunStages.cc: DF's max_width
+MIN_EDGE_COUNT, L32 = 5, 32                            # Closomatic.cc:494-495
+MIN_STRETCH, W, MIN_BITS, MIN_BITS_SAVE, WX, MAX_EWX, MAX_OVERLAP = 8, 20, 25.0, 40.0, 40, 20, 1000        # ReadStack.cc:1205-1213
+FLANK, MIN_SLOPE, MIN_ADD = 10, 2.0, 10.0              # :1434, :1489-1490
+COUNTERS = ("n_pairs_0", "n_pairs_1", "n_pairs_2", "n_pairs_many", "n_rows", "n_partners_tried", "n_partners_placed", "n_followers", "n_cons_too_long")
+FILTERS = ("seeds", "below_bits", "invalidated", "big_near_small", "survive")
+
+_table = None
+
+
+def bits_table() -> np.ndarray:
+    """PrecomputedBinomialSums<1000>(20, 0.75) (ReadStack.cc:47-62): t[n][k] = log10(BinomialSum(n, k, 0.75)) for 20 <= n < 1000, k < n,
+    every other entry 0.0.  BinomialSum (random/Bernoulli.cc:40-50) accumulates in long double from pow(0.25, n), a double that is 0 from
+    n = 538 on: those rows are -inf."""
+    global _table
+    if _table is None:
+        ld = np.longdouble
+        ns = np.arange(W, MAX_OVERLAP)
+        t = np.zeros((MAX_OVERLAP, MAX_OVERLAP), np.float64)
+        s, choose = np.zeros(len(ns), ld), np.ones(len(ns), ld)
+        prod = (np.float64(0.25) ** ns.astype(np.float64)).astype(ld)
+        ratio = ld(np.float64(0.75) / (np.float64(1.0) - np.float64(0.75)))
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            for i in range(MAX_OVERLAP - 1):
+                s = s + choose * prod
+                live = ns > i
+                t[ns[live], i] = np.log10(s[live].astype(np.float64))
+                choose = choose * (ns - i).astype(np.float64).astype(ld)
+                choose = choose / ld(np.float64(i + 1))
+                prod = prod * ratio
+        _table = t
+    return _table
+
+
+def _col_sums(base, qual):
+    """per column the four quality sums, rows added in order: Q0 counts 0.1, Q1 and Q2 0.2"""
+    rows, cols = base.shape
+    s = np.zeros((4, cols), np.float64)
+    ci = np.arange(cols)
+    for r in range(rows):
+        d = qual[r] >= 0
+        if not d.any():
+            continue
+        q = qual[r][d].astype(np.float64)
+        q = np.where(q == 0, 0.1, np.where(q <= 2, 0.2, q))
+        s[base[r][d], ci[d]] += q
+    return s
+
+
+def seed_consensus(base, qual) -> np.ndarray:
+    """readstack::Consensus1( ) = ColumnConsensus1 per column: std::max_element, the LOWEST base on a tie, A for an empty column"""
+    return np.argmax(_col_sums(base, qual), axis=0).astype(np.uint8)
+
+
+def final_consensus(base, qual) -> np.ndarray:
+    """readstack::Consensus1(con, conq): pair<double,int> sorted descending, the HIGHEST base on a tie, T for an empty column"""
+    return (3 - np.argmax(_col_sums(base, qual)[::-1], axis=0)).astype(np.uint8)
+
+
+def get_offsets1(con1, con2, why: dict | None = None):
+    """GetOffsets1 -> the surviving offsets in ascending order, or None when a consensus has 1000 columns or more"""
+    c1, c2 = len(con1), len(con2)
+    if max(c1, c2) >= MAX_OVERLAP:
+        return None
+    why = why if why is not None else {}
+    for k in FILTERS:
+        why.setdefault(k, 0)
+    if c1 < MIN_STRETCH or c2 < MIN_STRETCH:
+        return []
+    code = lambda c: sum(c[i:len(c) - MIN_STRETCH + 1 + i].astype(np.int64) << (2 * (MIN_STRETCH - 1 - i)) for i in range(MIN_STRETCH))
+    k1, k2 = code(con1), code(con2)
+    i, j = np.nonzero(k1[:, None] == k2[None, :])
+    doffsets = np.unique(i - j)
+    why["seeds"] += len(doffsets)
+    t = bits_table()
+    offsets = []                                       # (offset, bits)
+    for o in (int(x) for x in doffsets):
+        lo, hi = max(0, o), min(c1, c2 + o)
+        overlap = hi - lo
+        err = con1[lo:hi] != con2[lo - o:hi - o]
+        se = np.concatenate([[0], np.cumsum(err)]).astype(np.int64)
+        bw = np.zeros(overlap + 1, bool)
+        if overlap - WX >= 0:
+            m = np.arange(0, overlap - WX + 1)
+            errs = se[m + 1] - se[np.maximum(0, m - WX + 1)]
+            bw[np.maximum(0, m - WX)[errs >= MAX_EWX]] = True
+        nextbad = np.full(overlap + 1, 1 << 30, np.int64)
+        for b in range(overlap - 1, -1, -1):
+            nextbad[b] = b if bw[b] else nextbad[b + 1]
+        start = np.arange(overlap)
+        limit = np.minimum(overlap - start, nextbad[:overlap] + (WX - 1) - start)
+        minp = 0.0
+        if overlap >= W:
+            n = np.arange(W, overlap + 1)
+            S, N = start[:, None], n[None, :]
+            mask = N <= limit[:, None]
+            k = se[np.minimum(S + N, overlap)] - se[S]
+            vals = t[np.broadcast_to(N, mask.shape)[mask], k[mask]]
+            if len(vals):
+                minp = min(minp, float(vals.min()))
+        bits = -minp * 10.0 / 6.0
+        if bits >= MIN_BITS:
+            offsets.append((o, bits))
+        else:
+            why["below_bits"] += 1
+    # ---- offsets that invalidate other offsets (:1422-1485)
+    n = len(offsets)
+    val1, val2 = np.zeros((n, c1), bool), np.zeros((n, c2), bool)
+    mism = []
+    for x, (o, _) in enumerate(offsets):
+        lo, hi = max(0, o), min(c1, c2 + o)
+        match = con1[lo:hi] == con2[lo - o:hi - o]
+        mism.append(lo + np.nonzero(~match)[0])
+        edge = np.diff(np.concatenate([[0], match.astype(np.int8), [0]]))
+        for a, b in zip(np.nonzero(edge == 1)[0], np.nonzero(edge == -1)[0]):
+            low1, high1 = lo + a, lo + b
+            if low1 + FLANK < high1 - FLANK:
+                val1[x, low1 + FLANK:high1 - FLANK] = True
+                val2[x, low1 + FLANK - o:high1 - FLANK - o] = True
+    inval = np.zeros((n, n), bool)                     # [j][i]: j invalidates i
+    for x, (o, _) in enumerate(offsets):
+        p1 = mism[x]
+        if len(p1):
+            inval[:, x] = (val1[:, p1] & val2[:, p1 - o]).any(axis=1)
+    to_delete = np.zeros(n, bool)
+    for x in range(n):
+        if not inval[:, x].any():
+            to_delete |= inval[x, :]
+    why["invalidated"] += int(to_delete.sum())
+    offsets = [v for v, d in zip(offsets, to_delete) if not d]
+    if "trace" in why:
+        why["trace"].append(list(offsets))             # (offset, bits) in front of big near small
+    # ---- big near small: delete small (:1487-1502)
+    n = len(offsets)
+    del2 = [False] * n
+    for i1 in range(n):
+        for i2 in range(n):
+            if del2[i1]:
+                continue
+            if offsets[i2][1] >= MIN_BITS_SAVE:
+                continue
+            delta = offsets[i1][1] - offsets[i2][1]
+            if delta < MIN_ADD:
+                continue
+            if delta / abs(offsets[i1][0] - offsets[i2][0]) < MIN_SLOPE:
+                continue
+            del2[i2] = True
+    why["big_near_small"] += sum(del2)
+    out = [v[0] for v, d in zip(offsets, del2) if not d]
+    why["survive"] += len(out)
+    return out
+
+
+class Input:
+    """what CloseGap reads: the graph's edges, inv, the paths and their index, the reads with their qualities"""
+
+    def __init__(self, K, eb, inv, offset, n_edges, edges, codes, quals, lens, read_ids=None):
+        import hopsref
+        self.K, self.eb, self.inv = K, eb, [int(x) for x in inv]
+        self.ne = [len(b) for b in eb]
+        self.km = [len(b) - K + 1 for b in eb]
+        ne = np.asarray(n_edges, dtype=np.int64)
+        start = np.concatenate([[0], np.cumsum(ne)])
+        edges = np.asarray(edges, dtype=np.int64)
+        self.off = [int(x) for x in offset]
+        self.P = [tuple(int(e) for e in edges[start[r]:start[r + 1]]) for r in range(len(ne))]
+        self.pidx = hopsref.paths_index(ne, edges, len(eb))
+        # the reads: all of them, or (read_ids given) rows for those ids only
+        self.row_of = None if read_ids is None else {int(r): i for i, r in enumerate(read_ids)}
+        self.codes, self.quals, self.lens = codes, quals, lens
+
+    def read(self, rid):
+        i = rid if self.row_of is None else self.row_of[rid]
+        n = int(self.lens[i])
+        return self.codes[i][:n], self.quals[i][:n]
+
+
+def _locs(I: Input, e: int, cg2: bool):
+    """-> (locs [(id, pos, fw)], prec [(edge, distance)]) in the reference's order (Closomatic.cc:381-392, :505-531)"""
+    locs, prec = [], []
+    for pas in (1, 2):
+        f = e if pas == 1 else I.inv[e]
+        for rid in (int(x) for x in I.pidx[f]):
+            p = I.P[rid]
+            n = len(p)
+            for j in range(n):
+                if p[j] != f:
+                    continue
+                if cg2:
+                    add = 0
+                    if pas == 1:
+                        for l in range(j + 1, n):
+                            add += I.km[p[l - 1]]
+                            prec.append((p[l], add))
+                    else:
+                        for l in range(j - 1, -1, -1):
+                            add += I.km[p[l + 1]]
+                            prec.append((I.inv[p[l]], add))
+                locs.append((rid, I.off[rid] - sum(I.km[p[l]] for l in range(j)), pas == 1))
+    return locs, prec
+
+
+def _stack(I: Input, e: int, locs, max_width: int, reverse: bool):
+    """-> (base i8[rows, cols], qual i16[rows, cols]) of the rows that are kept, after Trim and Reverse"""
+    ne = I.ne[e]
+    M = 0
+    for rid, pos, fw in locs:
+        M = max(M, pos + int(I.lens[rid if I.row_of is None else I.row_of[rid]]) if fw else ne - pos)
+    trim = M > max_width
+    T = M - max_width if trim else 0
+    cols = M - T
+    bs, qs = [], []
+    for rid, pos, fw in locs:
+        b, q = I.read(rid)
+        n = len(b)
+        rb, rq = np.full(cols, -1, np.int8), np.full(cols, -1, np.int16)
+        if fw:
+            j0, j1 = max(0, -pos, T - pos), n
+            if j0 < j1:
+                rb[pos + j0 - T:pos + j1 - T] = b[j0:j1]
+                rq[pos + j0 - T:pos + j1 - T] = q[j0:j1]
+        else:
+            j0, j1 = 0, min(n, ne - pos - T)           # column ne - 1 - pos - j >= T
+            if j0 < j1:
+                c = ne - 1 - pos - T - np.arange(j0, j1)
+                rb[c] = 3 - b[j0:j1].astype(np.int8)
+                rq[c] = q[j0:j1]
+        if trim and not (rq >= 0).any():
+            continue                                   # Trim erases a row with no defined cell in the window
+        bs.append(rb)
+        qs.append(rq)
+    base = np.array(bs, np.int8).reshape(len(bs), cols)
+    qual = np.array(qs, np.int16).reshape(len(qs), cols)
+    if reverse:
+        base = np.where(base[:, ::-1] >= 0, 3 - base[:, ::-1], -1).astype(np.int8)
+        qual = qual[:, ::-1]
+    return base, qual
+
+
+def _merge(b1, q1, b2, q2, o):
+    """readstack::Merge: stack 1's rows, then stack 2's, shifted by the offset"""
+    c1, c2 = b1.shape[1], b2.shape[1]
+    l1, r1 = max(0, -o), max(0, o + c2 - c1)
+    l2, r2 = max(0, o), max(0, c1 - (o + c2))
+    pad = lambda a, l, r, v: np.pad(a, ((0, 0), (l, r)), constant_values=v)
+    return np.concatenate([pad(b1, l1, r1, -1), pad(b2, l2, r2, -1)]), np.concatenate([pad(q1, l1, r1, -1), pad(q2, l2, r2, -1)])
+
+
+def close_gap(I: Input, e1: int, e2: int, cg2: bool, max_width: int = MAX_WIDTH, cnt: dict | None = None, why: dict | None = None):
+    """CloseGap (cg2 False) or CloseGap2 for one pair -> its closures, a list of u8 code arrays"""
+    cnt = cnt if cnt is not None else dict.fromkeys(COUNTERS, 0)
+    es = [e1, I.inv[e2]]
+    locs, bod, n_bod = [None, None], [None, None], [0, 0]
+    for ei in range(2):
+        locs[ei], prec = _locs(I, es[ei], cg2)
+        if cg2:
+            prec.sort()
+            bod[ei] = {}
+            i = 0
+            while i < len(prec):
+                j = i
+                while j < len(prec) and prec[j] == prec[i]:
+                    j += 1
+                if j - i >= MIN_EDGE_COUNT:
+                    cnt["n_followers"] += 1
+                    g, add = prec[i]
+                    E = I.eb[g]
+                    for l in range(len(E) - L32 + 1):
+                        bod[ei].setdefault(bytes(E[l:l + L32]), set()).add(add + l)
+                    n_bod[ei] += max(0, len(E) - L32 + 1)
+                i = j
+    if why is not None:
+        why["bod_max"] = max(why.get("bod_max", 0), *n_bod)           # the most 32-mers a side's follower edges have: what bod_budget is about
+    if cg2:                                            # the unplaced partners (:550-581)
+        ids = [sorted({rid for rid, _, fw in locs[ei] if fw}) for ei in range(2)]
+        for ei in range(2):
+            other = set(ids[1 - ei])
+            for id1 in ids[ei]:
+                id2 = id1 ^ 1
+                if id2 in other:
+                    continue
+                cnt["n_partners_tried"] += 1
+                b, _ = I.read(id2)
+                finds = set()
+                for l in range(len(b) - L32 + 1):
+                    for pos in bod[1 - ei].get(bytes(b[l:l + L32]), ()):
+                        finds.add(pos - l)
+                if len(finds) == 1:
+                    cnt["n_partners_placed"] += 1
+                    locs[1 - ei].append((id2, finds.pop(), True))
+    stacks = []
+    for ei in range(2):
+        stacks.append(_stack(I, es[ei], locs[ei], max_width, es[ei] == I.inv[e2]))
+        cnt["n_rows"] += stacks[ei][0].shape[0]
+    con1, con2 = seed_consensus(*stacks[0]), seed_consensus(*stacks[1])
+    o = get_offsets1(con1, con2, why)
+    if o is None:
+        cnt["n_cons_too_long"] += 1
+        o = []
+    cnt["n_pairs_0" if len(o) == 0 else "n_pairs_1" if len(o) == 1 else "n_pairs_2" if len(o) == 2 else "n_pairs_many"] += 1
+    if len(o) > 2:
+        return []
+    return [final_consensus(*_merge(*stacks[0], *stacks[1], off)) for off in o]
+
+
+def close_gaps(I: Input, pairs, cg2: bool, max_width: int = MAX_WIDTH):
+    """every pair in order -> (closure_off u64[n + 1], bases u8[], pair_first u64[n_pairs + 1], counters, filters)"""
+    cnt, why = dict.fromkeys(COUNTERS, 0), dict.fromkeys(FILTERS, 0)
+    cl, first = [], [0]
+    for e1, e2 in pairs:
+        cl += close_gap(I, int(e1), int(e2), cg2, max_width, cnt, why)
+        first.append(len(cl))
+    off = np.concatenate([[0], np.cumsum([len(c) for c in cl])]).astype(np.uint64)
+    bases = np.concatenate(cl).astype(np.uint8) if cl else np.zeros(0, np.uint8)
+    return off, bases, np.array(first, np.uint64), cnt, why
+
+
+def fastb_bytes(off, bases) -> bytes:
+    """closures.fastb = BinaryWriter::writeFile(vec<basevector>): "BINWRITE", u64 count, per entry u32 length + ceil(len / 4) bytes, base j at
+    bits 2 * (j % 4) -- the layout of the unitig hand-off file (snk_write_bv)"""
+    out = [b"BINWRITE", np.uint64(len(off) - 1).tobytes()]
+    for i in range(len(off) - 1):
+        b = np.asarray(bases[int(off[i]):int(off[i + 1])], np.uint8)
+        n = len(b)
+        p = np.zeros((n + 3) // 4 * 4, np.uint8)
+        p[:n] = b
+        p = p.reshape(-1, 4)
+        out += [np.uint32(n).tobytes(), (p[:, 0] | p[:, 1] << 2 | p[:, 2] << 4 | p[:, 3] << 6).astype(np.uint8).tobytes()]
+    return b"".join(out)
+
+
+def parse_fastb(b: bytes):
+    """-> (off u64[n + 1], base codes u8[]) of a BINWRITE vec<basevector>"""
+    assert b[:8] == b"BINWRITE"
+    n = int(np.frombuffer(b, "<u8", 1, 8)[0])
+    at, lens, parts = 16, [], []
+    for _ in range(n):
+        m = int(np.frombuffer(b, "<u4", 1, at)[0])
+        at += 4
+        nb = (m + 3) // 4
+        w = np.frombuffer(b, np.uint8, nb, at)
+        at += nb
+        parts.append(((w[:, None] >> np.array([0, 2, 4, 6], np.uint8)[None, :]) & 3).reshape(-1)[:m].astype(np.uint8))
+        lens.append(m)
+    assert at == len(b), f"{len(b) - at} bytes behind the last basevector"
+    return np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64), (np.concatenate(parts) if parts else np.zeros(0, np.uint8))
+
+
+# ---- the fixtures
+
+GOLDEN = ("synth_2k_err", "synth_6k_clean", "synth_20k_err", "adversarial", "synth_4k_dups")          # = goldens.CASES, on hopsref's inputs
+TANDEM = {"tandem": 48, "tandem_k60": 60}
+HAND = {"hand_k48": 48, "hand_k60": 60}                # tests/handclose.py
+GENERATED = ("gapped",) + tuple(TANDEM) + tuple(HAND)
+ALL = GOLDEN + GENERATED
+FLAGS = ("cg2", "cg1")
+BOD_BUDGET = 1 << 18                                   # the library's default bod_budget (include/snk.h)
+WIDE, WIDE_CASES = 1200, ("tandem", "hand_k48", "hand_k60")                  # a second max_width, for the cases with a stack that wide: keys <key>_wide
+_cases: dict = {}
+
+
+def needed_reads(c) -> np.ndarray:
+    """the reads CloseGap2 can touch for the pairs of c: the index entries of e1, inv[e2] and their inverses, and their mates"""
+    pidx = hopsref_index(c)
+    need = set()
+    for e1, e2 in c.pairs:
+        for e in (int(e1), int(c.inv[e2])):
+            for f in (e, int(c.inv[e])):
+                need.update(int(r) for r in pidx[f])
+    need |= {r ^ 1 for r in need}
+    return np.array(sorted(need), np.int64)
+
+
+def hopsref_index(c):
+    import hopsref
+    return hopsref.paths_index(c.paths[1], c.paths[2], c.g.E)
+
+
+def digest(c, reads) -> str:
+    import hashlib
+    import hopsref
+    h = hashlib.sha256(hopsref.digest(c).encode())
+    for a, dt in ((c.pairs, np.int32), (reads.ids, np.int64), (reads.codes, np.uint8), (reads.quals, np.uint8), (reads.lens, np.uint16)):
+        h.update(np.ascontiguousarray(a, dtype=dt).tobytes())
+    return h.hexdigest()
+
+
+def gapped_reads():
+    """the reads of `gapped` (tests/golden/make_hops_golden.gapped_input), made again from its seed -> (codes, quals, lens, bc)"""
+    rng = np.random.default_rng(20261020)
+    G, n_pairs, L, insert = 24000, 9000, 150, 420
+    genome = rng.integers(0, 4, G, dtype=np.uint8)
+    holes, at = [], 1500
+    while at < G - 1500:
+        w = int(rng.integers(50, 251))
+        holes.append((at, at + w))
+        at += w + int(rng.integers(1200, 2600))
+    comp = lambda s: (3 - s)[::-1]
+    reads, bcs = [], []
+    for _ in range(n_pairs):
+        a = int(rng.integers(0, G - insert))
+        frag = genome[a:a + insert] if rng.random() < 0.5 else comp(genome[a:a + insert])
+        spans = [(a, a + L), (a + insert - L, a + insert)]
+        if any(s < h1 and h0 < e for s, e in spans for h0, h1 in holes):
+            continue
+        reads += [frag[:L], comp(frag)[:L]]
+        b = int(rng.integers(1, 41))
+        bcs += [b, b]
+    order = np.argsort(np.array(bcs[::2]), kind="stable")
+    codes = np.stack(reads).reshape(-1, 2, L)[order].reshape(-1, L)
+    bc = np.array(bcs, np.int32).reshape(-1, 2)[order].reshape(-1)
+    n = len(codes)
+    return codes, np.full((n, L), 35, np.uint8), np.full(n, L, np.uint16), bc
+
+
+def tandem_input(K: int = 48):
+    """`tandem` (K = 48) and `tandem_k60`: made from a seed, for what the golden cases do not reach.  Every locus is a sequence LF + (unit x copies) + RF; edge A is
+    its left end with the first bases of the repeat, edge B its right end with the last ones (isolated edges: fewer than K - 1 bases of the
+    repeat in each), and 150-base reads of either strand are laid over all of it with errors and low qualities -- a read with K bases on A
+    (else on B) gets that edge as its path.  The reads that bridge the repeat see several registers of it: pairs with one, two and more than
+    two surviving offsets, offsets that the bits test, the invalidation and (thin loci) big near small remove.  Also: a locus whose left flank is
+    1 300 bases with reads all along it (rows wholly in front of the kept window), reads whose path visits A twice, a pair (A, rc(A)) --
+    e1 == inv[e2] --, and a pair whose second side no read touches.
+    -> namespace(K, unitigs (BVComp order), codes, quals, lens, paths as strand strings, pairs as strand strings)"""
+    import handunitigs as hu
+    L = 150
+    rng = np.random.default_rng(20261021 + (K - 48))
+    rand = lambda n: "".join("ACGT"[i] for i in rng.integers(0, 4, n))
+    code = lambda t: np.frombuffer(t.encode(), np.uint8).copy()
+    unitigs, reads, paths, pairs = [], [], [], []
+    loci = [(250, int(rng.integers(6, 31)), int(rng.integers(3, 9)), 250, 0) for _ in range(14)]
+    # thin loci: the two stacks share only some 30 to 60 columns around a short-unit repeat, so a shifted register keeps its few mismatches
+    # inside the flank that no offset validates -- what big near small is there for
+    loci += [(250, int(rng.integers(2, 5)), int(rng.integers(8, 14)), 250, int(rng.integers(50, 81))) for _ in range(24)]
+    # crafted thin loci: reads that end exactly 6 columns behind the repeat and begin exactly 6 in front of it, so the true register has all
+    # of its 42 columns (42 bits) and a register shifted by a unit or two keeps the repeat (25 to 28 bits) with its mismatches inside the flank
+    loci += [(250, ul, 30 // ul, 250, -((L - K) - 6 - 30)) for ul in (3, 2, 3, 2)]
+    loci += [(1300, 17, 5, 250, 0), (250, 9, 6, 250, 0)]
+    for li, (nl, ul, copies, nr, pad) in enumerate(loci):
+        rep = rand(ul) * copies
+        crafted, pad = pad < 0, abs(pad)
+        if pad:
+            rep = rand(pad) + rep + rand(pad)
+        S = rand(nl) + rep + rand(nr)
+        keep = 0 if pad else min(40, len(rep) // 2)
+        A, B = S[:nl + keep], S[len(S) - nr - keep:]
+        b0 = len(S) - len(B)
+        unitigs += [A, B]
+        n_reads = 2 * int((len(S) * 12) // L // 2)
+        for q in range(n_reads):
+            s0 = int(rng.integers(0, len(S) - L + 1))
+            if li == len(loci) - 1 and s0 + L > len(A) - 10:          # the last locus: no read reaches the gap or B
+                s0 = int(rng.integers(0, len(A) - 10 - L + 1))
+            r = list(S[s0:s0 + L])
+            for x in np.nonzero(rng.random(L) < 0.01)[0]:
+                r[x] = "ACGT"[(("ACGT".index(r[x])) + 1 + int(rng.integers(0, 3))) % 4]
+            r = "".join(r)
+            if s0 + K <= len(A):
+                edge, off = A, s0
+            elif s0 + L >= b0 + K:
+                edge, off = B, s0 - b0
+            else:
+                edge, off = None, 0
+            fw = rng.random() < 0.5
+            if not fw:
+                r = hu.rc(r)
+                if edge is not None:
+                    off, edge = len(edge) - (off + L), hu.rc(edge)
+            p = [] if edge is None else [edge]
+            if edge is not None and rng.random() < 0.03:
+                p = [edge, edge]                                      # a path that visits the edge twice
+            reads.append(r)
+            paths.append((off, p))
+        if crafted:
+            for s0, edge, off in ((len(A) - K, A, len(A) - K), (b0 + K - L, B, K - L)):
+                reads += [S[s0:s0 + L]] * 4
+                paths += [(off, [edge])] * 4
+        pairs.append((A, B))
+        if li == 0:
+            pairs.append((A, hu.rc(A)))
+    pairs.append((loci and unitigs[0], unitigs[-1]))               # B of the last locus: no rows on the second side
+    n = len(reads)
+    codes = np.stack([np.searchsorted(code("ACGT"), code(r)) for r in reads]).astype(np.uint8)
+    quals = rng.choice(np.array([0, 1, 2, 2, 7, 12, 20, 30, 30, 35, 35, 35], np.uint8), (n, L))
+    us = hu.bvcomp_sorted(sorted({min(u, hu.rc(u)) for u in unitigs}))
+    hu.check_valid(us, K)
+    return SimpleNamespace(K=K, unitigs=us, codes=codes, quals=quals, lens=np.full(n, L, np.uint16), paths=paths, pairs=pairs)
+
+
+def made_input(name: str):
+    """the input of a TANDEM or HAND case, before the graph has numbered its edges"""
+    if name in HAND:
+        import handclose
+        return handclose.case(HAND[name])
+    return tandem_input(TANDEM[name])
+
+
+def made_graph(name: str):
+    """-> (a.hbv, a.inv) of a made case's unitigs, written by this library's writer (the hand-made graph holds an edge too long to store)"""
+    import tempfile
+    from supernova_amd import graphio
+    t = made_input(name)
+    with tempfile.TemporaryDirectory() as td:
+        graphio.write_hbv(Path(td) / "g.hbv", Path(td) / "g.inv", t.K, *graphio.unitigs_to_arrays(t.unitigs))
+        return (Path(td) / "g.hbv").read_bytes(), (Path(td) / "g.inv").read_bytes()
+
+
+def tandem_case(a_hbv: bytes, a_inv: bytes, name: str = "tandem"):
+    """tandem_input on the graph as a.hbv numbers it -> the namespace the golden cases have (hopsref.load) with all reads"""
+    import a48xref
+    import extref
+    import hopsref
+    t = made_input(name)
+    c = SimpleNamespace(name=name, a_hbv=a_hbv, a_inv=a_inv, unitigs=t.unitigs, g=a48xref.parse_hbv(a_hbv))
+    c.eb = extref.edge_bases(c.g)
+    edge_of = {"".join("ACGT"[x] for x in b): e for e, b in enumerate(c.eb)}
+    c.paths = (np.array([o for o, _ in t.paths], np.int32), np.array([len(p) for _, p in t.paths], np.uint32),
+               np.array([edge_of[e] for _, p in t.paths for e in p], np.int32))
+    c.bc, c.bad = np.zeros(len(t.paths), np.int32), np.zeros(len(t.paths) // 2, np.uint8)
+    hopsref._finish(c)
+    c.pairs = np.array(sorted({(edge_of[a], edge_of[b]) for a, b in t.pairs}), np.int32).reshape(-1, 2)
+    c.hops = hopsref.hops_bytes(c.pairs)
+    c.edge_of, c.items = edge_of, getattr(t, "items", None)
+    return c, (t.codes, t.quals, t.lens)
+
+
+def golden_reads(name: str, c):
+    """the reads of a golden case that its pairs need, from tests/golden/<case>.npz"""
+    import goldens
+    gc = goldens.load(name)
+    ids = needed_reads(c)
+    return SimpleNamespace(ids=ids, codes=gc.codes[ids], quals=gc.quals[ids], lens=np.asarray(gc.lens)[ids].astype(np.uint16))
+
+
+def load(name: str):
+    """-> the namespace of hopsref.load(name) with the closures on top: reads (ids, codes, quals, lens: only those the pairs need), I (the
+    restatement's Input), and per flag in FLAGS closure_off_<f>, bases_<f>, pair_first_<f>, fastb_<f> (the reference's file bytes),
+    counts_<f> (dict of COUNTERS, the restatement's), for the WIDE_CASES also <f>_wide = the same at max_width WIDE; ref_summary_closures.  Loaded once per process and left unchanged."""
+    if name in _cases:
+        return _cases[name]
+    import hopsref
+    z = np.load(CLOSURES / f"{name}.npz")
+    if name in TANDEM or name in HAND:
+        a_hbv, a_inv = (bytes(z["a_hbv"]), bytes(z["a_inv"])) if name in TANDEM else made_graph(name)
+        c, (codes, quals, lens) = tandem_case(a_hbv, a_inv, name)
+        ids = needed_reads(c)
+        c.reads = SimpleNamespace(ids=ids, codes=codes[ids], quals=quals[ids], lens=lens[ids])
+    else:
+        c = hopsref.load(name)
+    if name in GOLDEN:
+        c.reads = golden_reads(name, c)
+    elif name == "gapped":
+        codes, quals, lens, bc = gapped_reads()
+        assert np.array_equal(bc, c.bc), "gapped: the reads made again are not those of the hops fixture"
+        ids = needed_reads(c)
+        c.reads = SimpleNamespace(ids=ids, codes=codes[ids], quals=quals[ids], lens=lens[ids])
+    assert bytes(z["input_digest"]).decode() == digest(c, c.reads), f"{name}: the fixture was made from another input"
+    c.I = Input(c.K, c.eb, c.inv, *c.paths, c.reads.codes, c.reads.quals, c.reads.lens, c.reads.ids)
+    for f in FLAGS + (tuple(f + "_wide" for f in FLAGS) if name in WIDE_CASES else ()):
+        setattr(c, f"fastb_{f}", bytes(z[f"fastb_{f}"]))
+        off, bases = parse_fastb(getattr(c, f"fastb_{f}"))
+        setattr(c, f"closure_off_{f}", off)
+        setattr(c, f"bases_{f}", bases)
+        setattr(c, f"pair_first_{f}", z[f"pair_first_{f}"].astype(np.uint64))
+        setattr(c, f"counts_{f}", dict(zip(COUNTERS, (int(v) for v in z[f"counts_{f}"]))))
+    c.ref_summary_closures = bytes(z["ref_summary"]).decode()
+    _cases[name] = c
+    return c
+
+
+def full_reads(c, read_len: int | None = None):
+    """codes u8[n, L], quals u8[n, L], lens u16[n] for ALL reads of the case's paths: the needed ones filled in, every other row zero (no
+    pair's edges index it)"""
+    n = len(c.paths[1])
+    L = int(read_len or c.reads.codes.shape[1])
+    codes, quals, lens = np.zeros((n, L), np.uint8), np.zeros((n, L), np.uint8), np.full(n, L, np.uint16)
+    codes[c.reads.ids], quals[c.reads.ids], lens[c.reads.ids] = c.reads.codes, c.reads.quals, c.reads.lens
+    return codes, quals, lens
