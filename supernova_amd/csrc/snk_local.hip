@@ -533,14 +533,26 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
                                                     unsigned long long* __restrict__ hl_nb, uint64_t* __restrict__ bstart,
                                                     uint8_t* __restrict__ fbases, uint32_t* __restrict__ fgroup, uint32_t* __restrict__ sfrag, bl_extra_pool xp) {
     constexpr int SPT = (2 * CAP + T - 1) / T;        // states per thread
-    // LDS per chunk decides how many chunk waves a CU holds (one wave each): at K=48 without groups only the top 32
-    // bits of the low key word are sequence, and the neighbour list (dead once the links are built) shares its memory
-    // with the fragment offsets (written after the ranking): 10.5 -> 8.3 KB, 15 -> 18 waves per CU
+    constexpr int NPT = (CAP + T - 1) / T;            // nodes per thread
+    // LDS per chunk decides how many chunk waves a CU holds (one wave each), and the waves in flight are what hides the
+    // chain of LDS round trips a chunk is.  The one-wave variant (ONEW) therefore keeps in LDS only what lanes read from
+    // each other all the time: the neighbour list (dead once the links are built, so it shares its memory with the
+    // fragment offsets written after the ranking), links, ranking records, contexts, pending bits, heads.  Its keys stay
+    // in the registers of the lanes that loaded them (kq[]: node tid + q T in slot q).  Where a single lane needs ANOTHER
+    // node's key -- half links, circles -- it loads it again from keys[], which the wave read a moment ago (a cache hit);
+    // the head k-mers, written by the whole wave in step, take it from the owning lane by shuffles.  The palindrome flag
+    // is bit 15 of the node's first neighbour word; the fragment and base counters and "a record moved" are wave-level
+    // values (ballot, DPP scan).  K=48 ungrouped emit: 8464 -> 5120 B of LDS (K=60 / grouped: 9488 -> 5120), 38 -> 56
+    // VGPRs (62 at K=60), no scratch: 19 -> 32 workgroups fit a CU's 160 KB; measured resident 17 -> 27 waves per CU, 6.0 -> 4.8 ms.
+    // The 1280-node / 256-thread variant is not short of waves in the same way: it keeps its keys (at K=48 without
+    // groups the top 32 bits of the low word: the rest is no sequence) and its counters in LDS.
+    constexpr bool ONEW = T == 64;
     typedef typename std::conditional<(K <= 48 && !GR), uint32_t, uint64_t>::type klo_w;
     constexpr int KLS = (K <= 48 && !GR) ? 32 : 0;
-    __shared__ uint64_t khi[CAP];
-    __shared__ klo_w klo[CAP];
-    __shared__ uint16_t nbL[2 * CAP];                  // local neighbour << 1 | rev (chunk-local indices fit 16 bits)
+    __shared__ uint64_t khi[ONEW ? 1 : CAP];
+    __shared__ klo_w klo[ONEW ? 1 : CAP];
+    // local neighbour << 1 | rev (chunk-local indices fit 12 bits, 0x0FFF: none); bit 15 of a node's first word: palindrome
+    __shared__ uint16_t nbL[2 * CAP];
     // ranking record of an exit state: next state | hops << FB | terminal << 2 FB (one LDS word per state)
     typedef typename std::conditional<(CAP <= 256), uint32_t, uint64_t>::type wrec_t;
     constexpr int FB = CAP <= 256 ? 10 : 16;
@@ -553,10 +565,10 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
     // offsets are 32-bit words per fragment
     constexpr bool WIDE = (uint32_t)CAP * (uint32_t)K > 65535u;
     uint16_t* foffL = nbL;
-    __shared__ uint32_t frel[WIDE ? CAP : 1];
+    __shared__ uint32_t frel[WIDE ? CAP : 1];          // (referenced only if WIDE)
     __shared__ uint16_t hnode[CAP];                    // heads: node << 1 | rc
-    __shared__ uint8_t ctxL[CAP], pendL[CAP], palL[CAP];
-    __shared__ uint32_t fcnt, bcnt, changed;
+    __shared__ uint8_t ctxL[CAP], pendL[CAP];
+    __shared__ uint32_t fcnt, bcnt, changed;           // (referenced only if !ONEW)
     const int tid = threadIdx.x;
     const uint32_t c = BIG ? biglist_in[blockIdx.x] : blockIdx.x;
     const chunk_t ch = chunk_get(desc, c);
@@ -565,10 +577,12 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
     const uint32_t n = ch.n;
     const uint32_t c_foff = EMIT ? foff[c] : 0u;       // issued now, needed after the ranking
     const uint64_t c_boff = EMIT ? boff[c] : 0ull;
-    if (tid == 0) { fcnt = 0; bcnt = 0; changed = 0; }
+    if constexpr (!ONEW) {
+        if (tid == 0) { fcnt = 0; bcnt = 0; changed = 0; }
+    }
+    uint32_t w_frags = 0, w_bases = 0;                 // ONEW: the chunk's fragments and bases so far (the same in every lane)
+    snk_kmer kq[NPT] = {};                             // EMIT: the keys of the lane's own nodes (zero beyond the chunk)
     {   // every load of the chunk is issued before the first LDS store (a chunk wave starts with 5 loads per node)
-        constexpr int NPT = (CAP + T - 1) / T;
-        snk_kmer kq[NPT];
         uint32_t cq[NPT], pq[NPT];
         uint32_t nq[NPT];
 #pragma unroll
@@ -586,21 +600,37 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
         for (int q = 0; q < NPT; ++q) {
             const uint32_t i = tid + q * T;
             if (i < n) {
-                if (EMIT) {
+                if constexpr (EMIT && !ONEW) {
                     const snk_kmer k = kq[q];
                     khi[i] = k.hi;
                     klo[i] = (klo_w)(k.lo >> KLS);
                 }
-                palL[i] = (uint8_t)((nq[q] >> 15) & 1u);          // (noted by the prune, which has the reverse complement at hand)
                 ctxL[i] = (uint8_t)cq[q];
                 pendL[i] = (uint8_t)pq[q];
-                const uint32_t a0 = nq[q] & 0x0FFFu, a1 = (nq[q] >> 16) & 0x0FFFu;
-                nbL[2 * i] = a0 == 0x0FFFu ? NONE16 : (uint16_t)a0;
-                nbL[2 * i + 1] = a1 == 0x0FFFu ? NONE16 : (uint16_t)a1;
+                nbL[2 * i] = (uint16_t)(nq[q] & 0x8FFFu);             // (bit 15: palindrome, noted by the prune, which has the reverse complement at hand)
+                nbL[2 * i + 1] = (uint16_t)((nq[q] >> 16) & 0x0FFFu);
             }
         }
     }
     __syncthreads();
+    auto is_pal = [&](uint32_t i) -> bool { return (nbL[2 * i] >> 15) != 0; };
+    // a node's key (ONEW: loaded again, without the bits that are no sequence, as the LDS copy is)
+    auto key_of = [&](uint32_t i) -> snk_kmer {
+        snk_kmer k;
+        if constexpr (ONEW) {
+            k = load_key(keys, ch.base + i);
+            k.lo = (k.lo >> KLS) << KLS;
+        } else {
+            k.hi = khi[i];
+            k.lo = (uint64_t)klo[i] << KLS;
+        }
+        return k;
+    };
+    // the key of the lane's own node i = tid + q T (q is a constant once the loop round it is unrolled: kq[] stays in registers)
+    auto own_key = [&](int q, uint32_t i) -> snk_kmer {
+        if constexpr (ONEW) return kq[q];
+        else return key_of(i);
+    };
     // reciprocal-unique links inside the chunk (BuildReadQGraph48.cc:408-428): state = node << 1 | exit side
     uint32_t myterm = 0;
     for (uint32_t s = tid; s < 2 * n; s += T) {
@@ -611,13 +641,13 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
         if (__popc(bits) == 1) {
             const uint32_t b = __ffs(bits) - 1;
             if (!((pendL[i] >> (4 * side + b)) & 1u)) {
-                const uint32_t nb = nbL[s];
-                if (nb != NONE16) {
+                const uint32_t nb = nbL[s] & 0x0FFFu;
+                if (nb != 0x0FFFu) {
                     const uint32_t j = nb >> 1, rev = nb & 1u;
                     const uint32_t fs = side ^ 1u ^ rev;
                     const uint32_t cj = ctxL[j];
                     const uint32_t deg = fs ? __popc(cj & 0xF0u) : __popc(cj & 0x0Fu);
-                    if (deg == 1 && !palL[i] && !palL[j]) out = (uint16_t)((j << 1) | fs);
+                    if (deg == 1 && !is_pal(i) && !is_pal(j)) out = (uint16_t)((j << 1) | fs);
                 }
             }
         }
@@ -627,9 +657,14 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
         else wr[s] = (wrec_t)(out ^ 1u) | ((wrec_t)1 << FB) | ((wrec_t)(out ^ 1u) << (2 * FB));
     }
     if (!EMIT) {      // sizing pass: a chunk has (terminal states / 2) open paths
-        snk_wave_add(&fcnt, myterm);
-        __syncthreads();
-        if (tid == 0) nfrag[c] = fcnt >> 1;
+        if constexpr (ONEW) {
+            const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)snk_wave_scan_incl(myterm), 63);
+            if (tid == 0) nfrag[c] = total >> 1;
+        } else {
+            snk_wave_add(&fcnt, myterm);
+            __syncthreads();
+            if (tid == 0) nfrag[c] = fcnt >> 1;
+        }
         return;
     }
     __syncthreads();
@@ -655,6 +690,10 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
                 }
             }
         }
+        // one wave: whether a record moved is a vote, and the round that moves none has nothing to write
+        if constexpr (ONEW) {
+            if (!__any(any)) break;
+        }
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < SPT; ++q) {
@@ -662,12 +701,16 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
             const uint32_t s = tid + q * T;
             if (s < 2 * n) wr[s] = rr[q];
         }
-        if (any) changed = 1;
-        __syncthreads();
-        const bool go = changed != 0;
-        __syncthreads();
-        if (tid == 0) changed = 0;
-        if (!go) break;
+        if constexpr (ONEW) {
+            __syncthreads();
+        } else {
+            if (any) changed = 1;
+            __syncthreads();
+            const bool go = changed != 0;
+            __syncthreads();
+            if (tid == 0) changed = 0;
+            if (!go) break;
+        }
     }
     __syncthreads();
     auto w_next = [&](uint32_t st) -> uint32_t { return (uint32_t)wr[st] & FM; };
@@ -679,12 +722,13 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
         const uint32_t i = s >> 1, side = s & 1u;
         const uint32_t cc = ctxL[i];
         const uint32_t bits = side ? (cc >> 4) : (cc & 15u);
-        if (__popc(bits) != 1 || palL[i]) return NONE64;
+        // (the flag lies in the word of state 2 i, and describe() below writes the offset of a fragment over the word of its smaller
+        // terminal state: a state of one of the fragment's own end nodes, written by the lane that asks here, after it has asked)
+        if (__popc(bits) != 1 || is_pal(i)) return NONE64;
         const uint32_t b = __ffs(bits) - 1;
         if (!((pendL[i] >> (4 * side + b)) & 1u)) return NONE64;
-        snk_kmer k;
-        k.hi = khi[i];
-        k.lo = GR ? ((uint64_t)klo[i] & ~0xFFFFFFFFull) : ((uint64_t)klo[i] << KLS);
+        snk_kmer k = key_of(i);
+        if (GR) k.lo &= ~0xFFFFFFFFull;
         const snk_kmer y = side ? snk_kmer_pred<K>(k, b) : snk_kmer_succ<K>(k, b);
         if (snk_kmer_eq(y, snk_kmer_rc<K>(y))) return NONE64;
         const uint64_t gi = ch.base + i;
@@ -700,49 +744,71 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
         const uint32_t rev = a & 1u, fs = side ^ 1u ^ rev;
         return 2ull * ((DIST ? da.my_node_off : 0ull) + (a >> 1)) + fs;
     };
-    // fragment descriptor; returns the offset of its bases
-    auto describe = [&](uint32_t pid, uint32_t other, uint32_t cnt, bool with_half, uint32_t head_node, bool head_rc) {
-        const uint32_t lf = atomicAdd(&fcnt, 1u);
-        const uint32_t rel = atomicAdd(&bcnt, cnt + (uint32_t)K - 1u);
+    // descriptor of the open path that is fragment lf of the chunk, its bases at offset rel
+    auto describe = [&](uint32_t lf, uint32_t rel, uint32_t pid, uint32_t other, uint32_t cnt, uint32_t head_node, bool head_rc, uint32_t group) {
         const uint64_t f = (uint64_t)c_foff + lf;
         nk[f] = cnt;
         hl_self[2 * f] = 2ull * ((DIST ? da.my_node_off : 0ull) + ch.base) + pid;
         hl_self[2 * f + 1] = 2ull * ((DIST ? da.my_node_off : 0ull) + ch.base) + other;
-        hl_nb[2 * f] = with_half ? half_link(pid) : NONE64;
-        hl_nb[2 * f + 1] = with_half ? half_link(other) : NONE64;
+        hl_nb[2 * f] = half_link(pid);
+        hl_nb[2 * f + 1] = half_link(other);
         bstart[f] = c_boff + rel;
         if (sfrag) { sfrag[2 * ch.base + pid] = (uint32_t)(2 * f); sfrag[2 * ch.base + other] = (uint32_t)(2 * f + 1); }
-        if (GR) fgroup[f] = (uint32_t)klo[head_node];
-        if (WIDE) { foffL[pid] = (uint16_t)lf; frel[lf] = rel; }
+        if (GR) fgroup[f] = group;
+        if constexpr (WIDE) { foffL[pid] = (uint16_t)lf; frel[lf] = rel; }
         else foffL[pid] = (uint16_t)rel;
         hnode[lf] = (uint16_t)((head_node << 1) | (head_rc ? 1u : 0u));
-        return rel;
     };
 
-    // nodes on open paths: position and orientation from the two ranks (walking from the smaller terminal)
-    for (uint32_t i = tid; i < n; i += T) {
-        if (w_next(2 * i) != FM) continue;                // on a circle
-        const uint32_t tR = w_tail(2 * i), tL = w_tail(2 * i + 1), dR = w_dist(2 * i), dL = w_dist(2 * i + 1);
-        const bool fwd = tL < tR;
-        const uint32_t pos = fwd ? dL : dR;
-        if (pos == 0) describe(fwd ? tL : tR, fwd ? tR : tL, dR + dL + 1u, true, i, !fwd);
+    // nodes on open paths: position and orientation from the two ranks (walking from the smaller terminal); the head of a path
+    // describes it.  One wave hands out fragment numbers and base offsets by a ballot and a prefix sum over its lanes (node order
+    // within each step of 64 nodes, as the LDS counters gave a single wave); the 256-thread variant keeps two LDS counters.
+#pragma unroll
+    for (int q = 0; q < NPT; ++q) {
+        if ((uint32_t)(q * T) >= n) break;               // uniform
+        const uint32_t i = tid + q * T;
+        bool head = false, fwd = false;
+        uint32_t tR = 0, tL = 0, cnt = 0;
+        if (i < n && w_next(2 * i) == FM) {              // (else: beyond the chunk, or on a circle)
+            tR = w_tail(2 * i); tL = w_tail(2 * i + 1);
+            const uint32_t dR = w_dist(2 * i), dL = w_dist(2 * i + 1);
+            fwd = tL < tR;
+            head = (fwd ? dL : dR) == 0;
+            cnt = dR + dL + 1u;
+        }
+        const uint32_t nb = head ? cnt + (uint32_t)K - 1u : 0u;
+        uint32_t lf = 0, rel = 0;
+        if constexpr (ONEW) {
+            const unsigned long long hm = __ballot(head);
+            if (hm == 0) continue;                       // uniform
+            const uint32_t incl = snk_wave_scan_incl(nb);
+            lf = w_frags + (uint32_t)__popcll(hm & ((1ull << tid) - 1ull));
+            rel = w_bases + incl - nb;
+            w_frags += (uint32_t)__popcll(hm);
+            w_bases += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        } else if (head) {
+            lf = atomicAdd(&fcnt, 1u);
+            rel = atomicAdd(&bcnt, nb);
+        }
+        if (head) describe(lf, rel, fwd ? tL : tR, fwd ? tR : tL, cnt, i, !fwd, GR ? (uint32_t)own_key(q, i).lo : 0u);
     }
     // nodes no terminal is reachable from lie on smooth circles inside the chunk: cut at the left side of the minimum
     // k-mer (canonicalizeCircle, BuildReadQGraph48.cc:375-397); the circle's minimum node describes and writes it
     for (uint32_t i = tid; i < n; i += T) {
         if (w_next(2 * i) == FM) continue;
-        uint32_t cur = i << 1, mn = i, cnt = 1;
+        uint32_t cur = i << 1, cnt = 1;
+        const snk_kmer ki = key_of(i);
         bool closed = false;
         while (cnt <= n) {
             const uint32_t l = lnk[cur];
             if (l == NONE16) break;
             const uint32_t j = l >> 1;
             if (j == i) { closed = true; break; }
-            if (khi[j] < khi[mn] || (khi[j] == khi[mn] && klo[j] < klo[mn])) mn = j;
+            if (snk_kmer_lt(key_of(j), ki)) break;         // not the circle's minimum: another node's to write
             cur = l ^ 1u;
             ++cnt;
         }
-        if (closed && mn == i) {
+        if (closed) {
             // a circle inside the chunk: its slot comes from the pool behind the paths' slots
             const unsigned long long xf = atomicAdd(&xp.cur[0], 1ull);
             const unsigned long long xb = atomicAdd(&xp.cur[1], (unsigned long long)(cnt + K - 1));
@@ -758,16 +824,13 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
                 hl_nb[2 * f + 1] = NONE64;
                 bstart[f] = bo;
                 if (sfrag) { sfrag[2 * ch.base + pid] = (uint32_t)(2 * f); sfrag[2 * ch.base + e] = (uint32_t)(2 * f + 1); }
-                if (GR) fgroup[f] = (uint32_t)klo[i];
-                snk_kmer k;
-                k.hi = khi[i];
-                k.lo = (uint64_t)klo[i] << KLS;
+                if (GR) fgroup[f] = (uint32_t)ki.lo;
+                snk_kmer k = ki;
                 for (int b = 0; b < K; ++b) fbases[bo + b] = (uint8_t)oriented_base<K>(k, false, b);
                 uint32_t curs = i << 1;
                 for (uint32_t pos = 1; pos < cnt; ++pos) {
                     const uint32_t l = lnk[curs];
-                    k.hi = khi[l >> 1];
-                    k.lo = (uint64_t)klo[l >> 1] << KLS;
+                    k = key_of(l >> 1);
                     fbases[bo + (K - 1) + pos] = (uint8_t)oriented_base<K>(k, (l & 1u) == 0, K - 1);
                     curs = l ^ 1u;
                 }
@@ -776,39 +839,59 @@ __global__ void __launch_bounds__(T) bl_frag_kernel(const uint4* __restrict__ de
     }
     __syncthreads();
     // every path node writes its last base at its position
-    for (uint32_t i = tid; i < n; i += T) {
-        if (w_next(2 * i) != FM) continue;
+#pragma unroll
+    for (int q = 0; q < NPT; ++q) {
+        const uint32_t i = tid + q * T;
+        if (i >= n || w_next(2 * i) != FM) continue;
         const uint32_t tR = w_tail(2 * i), tL = w_tail(2 * i + 1), dR = w_dist(2 * i), dL = w_dist(2 * i + 1);
         const bool fwd = tL < tR;
         const uint32_t pos = fwd ? dL : dR;
         if (pos == 0) continue;
-        snk_kmer k;
-        k.hi = khi[i];
-        k.lo = (uint64_t)klo[i] << KLS;
-        const uint32_t fo = foffL[fwd ? tL : tR];
+        const snk_kmer k = own_key(q, i);
+        uint32_t fo = foffL[fwd ? tL : tR];
+        if constexpr (WIDE) fo = frel[fo];
         // (round 4, measured with these stores compiled out: 8.55 -> 8.23 ms -- the one-byte-per-node stores are NOT what the kernel
         // spends its time on, so packing the fragments' bases to 2 bits, DESIGN 8 item 6 of round 3, would not buy the 2 ms hoped for)
-        fbases[c_boff + (WIDE ? frel[fo] : fo) + (K - 1) + pos] = (uint8_t)oriented_base<K>(k, !fwd, K - 1);
+        fbases[c_boff + fo + (K - 1) + pos] = (uint8_t)oriented_base<K>(k, !fwd, K - 1);
     }
     // head k-mers: K / 4 lanes per head, four bases (one dword store at byte alignment) per lane, four heads per wave
     // instruction (K lanes writing a byte each made this the kernel's largest block of memory instructions: one per head)
     struct __attribute__((packed)) u32_any { uint32_t v; };
-    const uint32_t nheads = fcnt;
+    uint32_t nheads = w_frags;
+    if constexpr (!ONEW) nheads = fcnt;
     constexpr int HPI = T / 16;                            // heads per iteration: sixteen lanes each
     static_assert(K % 4 == 0 && K / 4 <= 16, "a head is K / 4 dwords, one per lane of its group");
-    for (uint32_t h0 = 0; h0 < nheads; h0 += HPI) {
+    for (uint32_t h0 = 0; h0 < nheads; h0 += HPI) {        // (uniform: nheads is the same in every lane)
         const uint32_t h = h0 + (tid >> 4);
         const int q = tid & 15;
-        if (h < nheads && q < K / 4) {
-            const uint32_t hn = hnode[h];
-            const uint32_t i = hn >> 1;
-            const bool rc = hn & 1u;
+        const bool act = h < nheads && q < K / 4;
+        const uint32_t hn = act ? hnode[h] : 0u;
+        const uint32_t i = hn >> 1;
+        const bool rc = hn & 1u;
+        snk_kmer k;
+        if constexpr (ONEW) {
+            // the head's key from the lane that holds it: every lane offers the words of slot s, the asker takes those of its
+            // node's slot.  Against loading the key again (profiles/frag_occupancy_ab.log, call 2): -0.23 ms in the fragments
+            // phase in every run, the same kernel time under the profiler.  Legal here, where the whole wave is at the same
+            // place; half links and circles are asked for by single lanes.
+            k.hi = 0; k.lo = 0;
+#pragma unroll
+            for (int s = 0; s < NPT; ++s) {
+                if ((uint32_t)(s * T) >= n) break;               // uniform
+                const int src = (int)(i & 63u);
+                const uint32_t a0 = (uint32_t)__shfl((int)(uint32_t)(kq[s].hi >> 32), src), a1 = (uint32_t)__shfl((int)(uint32_t)kq[s].hi, src);
+                const uint32_t a2 = (uint32_t)__shfl((int)(uint32_t)(kq[s].lo >> 32), src);
+                uint32_t a3 = 0;                                 // (K <= 48: no base in the low half of the low word)
+                if constexpr (K > 48) a3 = (uint32_t)__shfl((int)(uint32_t)kq[s].lo, src);
+                if ((i >> 6) == (uint32_t)s) { k.hi = ((uint64_t)a0 << 32) | a1; k.lo = ((uint64_t)a2 << 32) | a3; }
+            }
+        } else {
+            k = key_of(i);
+        }
+        if (act) {
             uint32_t fo;
-            if (WIDE) fo = frel[h];                               // head h belongs to fragment h of the chunk
+            if constexpr (WIDE) fo = frel[h];                     // head h belongs to fragment h of the chunk
             else { const uint32_t tR = w_tail(2 * i), tL = w_tail(2 * i + 1); fo = foffL[tL < tR ? tL : tR]; }
-            snk_kmer k;
-            k.hi = khi[i];
-            k.lo = (uint64_t)klo[i] << KLS;
             const uint32_t v = oriented_base<K>(k, rc, 4 * q) | (oriented_base<K>(k, rc, 4 * q + 1) << 8) | (oriented_base<K>(k, rc, 4 * q + 2) << 16) |
                                (oriented_base<K>(k, rc, 4 * q + 3) << 24);
             reinterpret_cast<u32_any*>(fbases + c_boff + fo + 4 * q)->v = v;
