@@ -167,10 +167,17 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
     // at K=48 without groups only the top 32 bits of the low key word are sequence (LDS per chunk = waves per CU)
     typedef typename std::conditional<(K <= 48 && !GR), uint32_t, uint64_t>::type klo_w;
     constexpr int KLS = (K <= 48 && !GR) ? 32 : 0;
+    // The one-wave variant is resident by the workgroup, and what decides how many fit a CU is its static LDS (5120 B: 32 per CU) and
+    // its registers: node number + 1 fits 9 bits, so its table entries are 16-bit halves of the words they are claimed in (1 KB, not 2);
+    // the miss list holds ML entries and a batch with more misses is classified in rounds; the miss and boundary counters are a
+    // prefix sum over the wave's lanes (snk_wave_scan_incl) and lane 63's total, not LDS words.  The 1280-node variant keeps 32-bit
+    // entries, a list for every possible miss and its counters.
+    constexpr bool ONE = !BIG && T == 64;
+    constexpr int ML = ONE ? 128 : 8 * T;
     __shared__ uint64_t khi[CAP];
     __shared__ klo_w klo[CAP];
-    __shared__ uint32_t ht[HT];
-    __shared__ uint32_t bcnt;
+    __shared__ uint32_t ht[ONE ? HT / 2 : HT];
+    __shared__ uint32_t bcnt;                // (!ONE only: a variable nothing uses takes no LDS)
     const int tid = threadIdx.x;
     const chunk_t ch = chunk_get(desc, c);
     if (ch.n == 0) return;
@@ -183,48 +190,57 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
     uint64_t src = ch.base;
     if (rg.keys_r) { src = rg.desc_src[c]; keys = rg.keys_r; vals = rg.vals_r; }
     __syncthreads();      // the previous chunk of this workgroup is done with the LDS arrays
-    for (int s = tid; s < HT; s += T) ht[s] = 0;
-    if (tid == 0) bcnt = 0;
+    for (int s = tid; s < (ONE ? HT / 2 : HT); s += T) ht[s] = 0;
+    if constexpr (!ONE) { if (tid == 0) bcnt = 0; }
     constexpr int NPT = (CAP + T - 1) / T;             // nodes per thread
-    uint64_t myv[NPT];
-    snk_kmer kq[NPT];
+    {
+        // the keys are staged in a scope of their own: once they are in LDS (and in their dense place) no register holds them
+        snk_kmer kq[NPT];
 #pragma unroll
-    for (int q = 0; q < NPT; ++q) {          // all loads first, then the LDS stores
-        const uint32_t i = tid + q * T;
-        myv[q] = 0;
-        if (i < n) {
-            kq[q] = load_key(keys, src + i);
-            myv[q] = vals[src + i];
+        for (int q = 0; q < NPT; ++q) {          // all loads first, then the LDS stores
+            const uint32_t i = tid + q * T;
+            if (i < n) kq[q] = load_key(keys, src + i);
+        }
+#pragma unroll
+        for (int q = 0; q < NPT; ++q) {
+            const uint32_t i = tid + q * T;
+            if (i < n) {
+                khi[i] = kq[q].hi;
+                klo[i] = (klo_w)(kq[q].lo >> KLS);
+                if (rg.keys_r) { uint64_t* d = reinterpret_cast<uint64_t*>(rg.keys_dense + ch.base + i); d[0] = kq[q].lo; d[1] = kq[q].hi; }
+            }
         }
     }
-#pragma unroll
-    for (int q = 0; q < NPT; ++q) {
-        const uint32_t i = tid + q * T;
-        if (i < n) {
-            khi[i] = kq[q].hi;
-            klo[i] = (klo_w)(kq[q].lo >> KLS);
-            if (rg.keys_r) { uint64_t* d = reinterpret_cast<uint64_t*>(rg.keys_dense + ch.base + i); d[0] = kq[q].lo; d[1] = kq[q].hi; }
-        }
-    }
+    // (count << 8 | context) of the first batch's node: asked for here, needed behind the table build; every batch asks for the next one's
+    uint64_t vnext = (uint32_t)tid < n ? vals[src + tid] : 0ull;
     __syncthreads();
     for (uint32_t i = tid; i < n; i += T) {
         uint32_t slot = lhash(khi[i], (uint64_t)klo[i] << KLS) & (HT - 1);
-        for (;;) {
-            const uint32_t old = atomicCAS(&ht[slot], 0u, i + 1u);
-            if (old == 0u) break;
-            slot = (slot + 1) & (HT - 1);
+        if constexpr (ONE) {
+            // a 16-bit entry is claimed with a CAS on the word that holds it; the other half may change under the attempt: then again
+            for (;;) {
+                uint32_t* const w = &ht[slot >> 1];
+                const uint32_t s16 = (slot & 1u) << 4;
+                const uint32_t cur = *reinterpret_cast<volatile uint32_t*>(w);
+                if ((cur >> s16) & 0xFFFFu) { slot = (slot + 1) & (HT - 1); continue; }
+                if (atomicCAS(w, cur, cur | ((i + 1u) << s16)) == cur) break;
+            }
+        } else {
+            for (;;) {
+                const uint32_t old = atomicCAS(&ht[slot], 0u, i + 1u);
+                if (old == 0u) break;
+                slot = (slot + 1) & (HT - 1);
+            }
         }
     }
     __syncthreads();
     const uint32_t split_mask = (1u << ch.lg) - 1u;
     uint32_t mybnd = 0;
-    __shared__ uint16_t mlist[8 * T];        // misses of the current batch of T nodes: thread << 3 | bit
+    __shared__ uint16_t mlist[ML];           // misses of the current batch of T nodes (a round of them): thread << 3 | bit
     __shared__ uint32_t resL[T];             // per thread: keep bits | pending bits << 8 decided for its misses
-    __shared__ uint32_t mcnt;
-#pragma unroll
-    for (int q = 0; q < NPT; ++q) {
-        const uint32_t i0 = q * T;
-        if (i0 >= n) break;
+    __shared__ uint32_t mcnt;                // (!ONE only)
+    const uint16_t* const ht16 = reinterpret_cast<const uint16_t*>(ht);      // (ONE: entry `slot` is half slot & 1 of word slot >> 1)
+    for (uint32_t i0 = 0; i0 < n; i0 += T) {
         const uint32_t i = i0 + tid;
         const bool act = i < n;
         snk_kmer k;
@@ -232,7 +248,8 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
         k.lo = act ? ((uint64_t)klo[i] << KLS) : 0ull;
         uint64_t tag = 0;                                    // grouped runs: the group id in the low 32 key bits
         if (GR) { tag = k.lo & 0xFFFFFFFFull; k.lo &= ~0xFFFFFFFFull; }
-        const uint64_t v = myv[q];
+        const uint64_t v = vnext;
+        vnext = i + T < n ? vals[src + i + T] : 0ull;
         const uint32_t c0 = (uint32_t)(v & 0xFFu);
         uint32_t keep = 0, miss = 0, nb0 = NONE, nb1 = NONE;
         // the reverse complement of a neighbour follows from the k-mer's own in one shift: rc(succ(k, b)) =
@@ -248,7 +265,7 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
             int32_t j = -1;
             uint32_t slot = lhash(cy.hi, cy.lo) & (HT - 1);
             for (;;) {
-                const uint32_t e = ht[slot];
+                const uint32_t e = ONE ? (uint32_t)ht16[slot] : ht[slot];
                 if (e == 0u) break;
                 if (khi[e - 1] == cy.hi && ((uint64_t)klo[e - 1] << KLS) == cy.lo) { j = (int32_t)(e - 1); break; }
                 slot = (slot + 1) & (HT - 1);
@@ -264,73 +281,88 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
         // The misses of the batch (~0.15 per k-mer) are gathered into a dense list and classified by FOUR lanes each,
         // which split the shared M-mers between them -- instead of every lane of the wave idling through the scan
         // of the few lanes that have a miss.
-        if (tid == 0) mcnt = 0;
+        // A round of the list takes the misses numbered [base, base + ML) of the batch (a lane's may lie in two rounds); what a round
+        // decides is gathered in resL, which is read behind the last one.  The bench has ~10 misses per batch: one round.
+        if constexpr (!ONE) { if (tid == 0) mcnt = 0; }
         resL[tid] = 0;
         __syncthreads();
-        uint32_t pos = snk_wave_alloc(&mcnt, (uint32_t)__popc(miss));
-        if (miss) {
-            for (uint32_t bit = 0; bit < 8; ++bit)
-                if (miss & (1u << bit)) mlist[pos++] = (uint16_t)((tid << 3) | bit);
-        }
-        __syncthreads();
-        const uint32_t nm = mcnt;
+        const uint32_t nmiss = (uint32_t)__popc(miss);
+        uint32_t pos, total = 0;
+        if constexpr (ONE) {
+            // (all 64 lanes are here: lanes beyond the chunk's end take part with no miss and leave the batch only further down)
+            const uint32_t incl = snk_wave_scan_incl(nmiss);
+            total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            pos = incl - nmiss;
+        } else pos = snk_wave_alloc(&mcnt, nmiss);
         constexpr int SH = K - MM;               // shared M-mers of a k-mer and its neighbour
         constexpr int PER = (SH + 3) / 4;
-        for (uint32_t it0 = 0; it0 < nm; it0 += T / 4) {
-            const uint32_t item = it0 + (tid >> 2), sub = tid & 3u;
-            const bool on = item < nm;
-            const uint32_t ent = on ? mlist[item] : 0u;
-            const uint32_t th = ent >> 3, bit = ent & 7u;
-            const uint32_t ni = i0 + th;
-            snk_kmer kk;
-            kk.hi = on ? khi[ni] : 0ull;
-            kk.lo = on ? ((uint64_t)klo[ni] << KLS) : 0ull;
-            uint64_t ktag = 0;
-            if (GR) { ktag = kk.lo & 0xFFFFFFFFull; kk.lo &= ~0xFFFFFFFFull; }
-            const int first = bit < 4 ? 1 : 0;   // successors share positions 1..K-M, predecessors 0..K-M-1
-            uint32_t mk = 0xFFFFFFFFu;
-            for (int t = 0; t < PER; ++t) {
-                const int sp = (int)sub * PER + t;
-                if (sp < SH) {
-                    const int pp = first + sp;
-                    uint64_t w;
-                    if (pp == 0) w = kk.hi;
-                    else if (pp < 32) w = (kk.hi << (2 * pp)) | (kk.lo >> (64 - 2 * pp));
-                    else if (pp == 32) w = kk.lo;
-                    else w = kk.lo << (2 * pp - 64);
-                    const uint32_t key = snk_mmer_key_top<MM>(w);
-                    mk = key < mk ? key : mk;
+        for (uint32_t base = 0;; base += ML) {
+            {
+                uint32_t e = pos - base;
+                for (uint32_t rem = miss; rem; rem &= rem - 1, ++e)
+                    if (e < (uint32_t)ML) mlist[e] = (uint16_t)((tid << 3) | (__ffs(rem) - 1));
+            }
+            __syncthreads();
+            if constexpr (!ONE) total = mcnt;
+            const uint32_t nm = total - base < (uint32_t)ML ? total - base : (uint32_t)ML;
+            for (uint32_t it0 = 0; it0 < nm; it0 += T / 4) {
+                const uint32_t item = it0 + (tid >> 2), sub = tid & 3u;
+                const bool on = item < nm;
+                const uint32_t ent = on ? mlist[item] : 0u;
+                const uint32_t th = ent >> 3, bit = ent & 7u;
+                const uint32_t ni = i0 + th;
+                snk_kmer kk;
+                kk.hi = on ? khi[ni] : 0ull;
+                kk.lo = on ? ((uint64_t)klo[ni] << KLS) : 0ull;
+                uint64_t ktag = 0;
+                if (GR) { ktag = kk.lo & 0xFFFFFFFFull; kk.lo &= ~0xFFFFFFFFull; }
+                const int first = bit < 4 ? 1 : 0;   // successors share positions 1..K-M, predecessors 0..K-M-1
+                uint32_t mk = 0xFFFFFFFFu;
+                for (int t = 0; t < PER; ++t) {
+                    const int sp = (int)sub * PER + t;
+                    if (sp < SH) {
+                        const int pp = first + sp;
+                        uint64_t w;
+                        if (pp == 0) w = kk.hi;
+                        else if (pp < 32) w = (kk.hi << (2 * pp)) | (kk.lo >> (64 - 2 * pp));
+                        else if (pp == 32) w = kk.lo;
+                        else w = kk.lo << (2 * pp - 64);
+                        const uint32_t key = snk_mmer_key_top<MM>(w);
+                        mk = key < mk ? key : mk;
+                    }
+                }
+                { const uint32_t o = __shfl_xor(mk, 1); mk = o < mk ? o : mk; }
+                { const uint32_t o = __shfl_xor(mk, 2); mk = o < mk ? o : mk; }
+                if (on && sub == 0) {
+                    const snk_kmer y = bit < 4 ? snk_kmer_succ<K>(kk, bit) : snk_kmer_pred<K>(kk, bit - 4);
+                    uint64_t wn;     // the one M-mer of the neighbour that k does not have (left-aligned)
+                    if (bit < 4) {
+                        constexpr int pl = K - MM;
+                        wn = pl < 32 ? ((y.hi << (2 * pl)) | (y.lo >> (64 - 2 * pl))) : (pl == 32 ? y.lo : (y.lo << (2 * pl - 64)));
+                    } else wn = y.hi;
+                    const uint32_t nkey = snk_mmer_key_top<MM>(wn);
+                    if (nkey < mk) mk = nkey;
+                    const uint32_t gb = snk_bucket_of_key(mk ^ (GR ? snk_group_mix((uint32_t)ktag) : 0u), NB);   // (global) bucket of the neighbour
+                    const uint32_t db = gb - (sh.bucket_base + ch.bucket);          // (wraps below the chunk's first bucket: then no multiple of G below span * G... checked)
+                    bool here = ch.span == 1 ? db == 0u : (gb >= sh.bucket_base + ch.bucket && db % sh.G == 0u && db / sh.G < ch.span);
+                    const bool remote = sh.NBl && gb / sh.NBl != sh.me;              // lives (if anywhere) on another rank
+                    if (here && ch.lg) {
+                        const snk_kmer r = snk_kmer_rc<K>(y);
+                        snk_kmer cn = snk_kmer_lt(r, y) ? r : y;
+                        if (GR) cn.lo |= ktag;
+                        uint32_t h1, h2;
+                        snk_kmer_hash_count<(K > 48) || GR>(cn, &h1, &h2);       // the count kernel's split function
+                        here = (h2 & split_mask) == ch.id;
+                    }
+                    // (do_prune & 2, option bl_noclassify, a measurement aid: a miss is never settled here, the index resolves them all -- same result.
+                    // The neighbour's bucket is still worked out: on a rank of an N-GPU job it says whether the k-mer is another rank's to answer;
+                    // without it such misses were looked up in this rank's index, not found, and their context bits dropped.)
+                    if (here && !(do_prune & 2u)) { if (!(do_prune & 1u)) atomicOr(&resL[th], 1u << bit); }
+                    else atomicOr(&resL[th], (1u << bit) | (0x100u << bit) | (remote ? (0x10000u << bit) : 0u));
                 }
             }
-            { const uint32_t o = __shfl_xor(mk, 1); mk = o < mk ? o : mk; }
-            { const uint32_t o = __shfl_xor(mk, 2); mk = o < mk ? o : mk; }
-            if (on && sub == 0) {
-                const snk_kmer y = bit < 4 ? snk_kmer_succ<K>(kk, bit) : snk_kmer_pred<K>(kk, bit - 4);
-                uint64_t wn;     // the one M-mer of the neighbour that k does not have (left-aligned)
-                if (bit < 4) {
-                    constexpr int pl = K - MM;
-                    wn = pl < 32 ? ((y.hi << (2 * pl)) | (y.lo >> (64 - 2 * pl))) : (pl == 32 ? y.lo : (y.lo << (2 * pl - 64)));
-                } else wn = y.hi;
-                const uint32_t nkey = snk_mmer_key_top<MM>(wn);
-                if (nkey < mk) mk = nkey;
-                const uint32_t gb = snk_bucket_of_key(mk ^ (GR ? snk_group_mix((uint32_t)ktag) : 0u), NB);   // (global) bucket of the neighbour
-                const uint32_t db = gb - (sh.bucket_base + ch.bucket);          // (wraps below the chunk's first bucket: then no multiple of G below span * G... checked)
-                bool here = ch.span == 1 ? db == 0u : (gb >= sh.bucket_base + ch.bucket && db % sh.G == 0u && db / sh.G < ch.span);
-                const bool remote = sh.NBl && gb / sh.NBl != sh.me;              // lives (if anywhere) on another rank
-                if (here && ch.lg) {
-                    const snk_kmer r = snk_kmer_rc<K>(y);
-                    snk_kmer cn = snk_kmer_lt(r, y) ? r : y;
-                    if (GR) cn.lo |= ktag;
-                    uint32_t h1, h2;
-                    snk_kmer_hash_count<(K > 48) || GR>(cn, &h1, &h2);       // the count kernel's split function
-                    here = (h2 & split_mask) == ch.id;
-                }
-                // (do_prune & 2, option bl_noclassify, a measurement aid: a miss is never settled here, the index resolves them all -- same result.
-                // The neighbour's bucket is still worked out: on a rank of an N-GPU job it says whether the k-mer is another rank's to answer;
-                // without it such misses were looked up in this rank's index, not found, and their context bits dropped.)
-                if (here && !(do_prune & 2u)) { if (!(do_prune & 1u)) atomicOr(&resL[th], 1u << bit); }
-                else atomicOr(&resL[th], (1u << bit) | (0x100u << bit) | (remote ? (0x10000u << bit) : 0u));
-            }
+            if (base + ML >= total) break;
+            __syncthreads();      // the round's entries are read: the next round writes over them
         }
         __syncthreads();
         const uint32_t res = resL[tid];
@@ -382,12 +414,23 @@ __device__ __forceinline__ void bl_prune_chunk(const uint32_t c, const uint4* __
             }
         }
     }
-    snk_wave_add(&bcnt, mybnd);
-    __syncthreads();
-    if (tid == 0) nbnd[c] = bcnt;
+    if constexpr (ONE) {
+        // (the scan needs all 64 lanes: they are back together here, behind the batch loop's `continue` and the uniform early returns)
+        const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)snk_wave_scan_incl(mybnd), 63);
+        if (tid == 0) nbnd[c] = b;
+    } else {
+        snk_wave_add(&bcnt, mybnd);
+        __syncthreads();
+        if (tid == 0) nbnd[c] = bcnt;
+    }
 }
+// Waves per SIMD the register allocator is held to (one-wave variant; each instantiation does it without scratch): 8 = 64 VGPRs at K=48 with
+// 16-base minimisers, where 5120 B of LDS let 32 workgroups onto a CU and left alone the allocator stops at 70 VGPRs = 28; 7 = 72 VGPRs with
+// 20-base minimisers; 6 = 80 VGPRs at K=60 and with groups, whose 6144 B of LDS place 26.
+template <int K, bool BIG, bool GR, int MM>
+constexpr int bl_prune_waves = BIG ? 1 : (K <= 48 && !GR) ? (MM <= 16 ? 8 : 7) : 6;
 template <int K, int CAP, int T, bool BIG, bool GR, int MM>
-__global__ void __launch_bounds__(T) bl_prune_kernel(const uint4* __restrict__ desc, uint32_t NB, bl_shard sh, bl_regions rg, const uint32_t* __restrict__ biglist_in,
+__global__ void __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(bl_prune_waves<K, BIG, GR, MM>, 8))) bl_prune_kernel(const uint4* __restrict__ desc, uint32_t NB, bl_shard sh, bl_regions rg, const uint32_t* __restrict__ biglist_in,
                                                      uint32_t nchunks, uint32_t cpw,
                                                      const snk_u128* __restrict__ keys, const uint64_t* __restrict__ vals,
                                                      uint32_t do_prune, uint8_t* __restrict__ ctx_out,
