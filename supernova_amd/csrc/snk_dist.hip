@@ -1,13 +1,20 @@
-// snk_dist.hip -- C ABI of the minimiser-sharded (multi-GPU) path: stage entry points between which the host
-// runs the exchanges (torch.distributed over RCCL/xGMI).  SURVEY.md 8(e); the reference's counterpart is the
-// shardio exchange + per-shard processing + global join of tada
+// snk_dist.hip -- the minimiser-sharded (multi-GPU) path: the session state of a step, its read intake, and the phases of the step that
+// do more than forward to the bucket-local stage (snk_local.hip) or the join (snk_graph.hip).  snk_shard_step.hip drives everything and
+// runs the exchanges (snk_comm.hip: RCCL over xGMI, or in-process ranks).  SURVEY.md 8(e); the reference's counterpart is the shardio
+// exchange + per-shard processing + global join of tada
 // (lib/tada/external/rust-shardio/src/shard.rs:184-211,488-493; cmd_shard_asm.rs:37-94; cmd_main_asm.rs:25-89)
 // and the thread swizzle of MapReduceEngine.h:362-385.
 //
-//   rank r:  snk_shard_hist  -> [all-to-all of bucket counts] -> snk_shard_scatter -> [all-to-all of records]
-//            -> snk_shard_count -> snk_shard_prune_plan/fill -> [all-to-all of queries] -> snk_shard_prune_answer
-//            -> [all-to-all of answers] -> snk_shard_prune_apply -> snk_shard_fragments -> [gather to rank 0]
-//   rank 0:  snk_shard_join
+// One process (or host thread) per GPU.  The k-mer space is cut into NB_total minimiser buckets; rank r owns buckets
+// [r*NB_total/world, (r+1)*NB_total/world).  Every rank runs, with [..] an exchange:
+//   snk_shard_begin (or the slabs' snk_shard_job_*)  trim + one-pass partition over all buckets
+//   -> [histograms] -> [records of the buckets other ranks own, in bucket ranges] -> snk_stage_count_table (own buckets in place)
+//   -> snk_shard_prune_plan / snk_bl_dist_fill -> [membership queries] -> snk_dist_answer -> [answers] -> snk_dist_apply
+//   -> snk_bl_dist_fragments -> snk_dist_links_query -> [link queries] -> snk_dist_links_answer -> [answers] -> snk_dist_links_apply_regions
+//   -> [links + k-mer counts of all fragments] -> snk_shard_prank_begin -> [splitters] -> snk_prank_walk / snk_prank_route -> [ranks]
+//   -> snk_shard_place_ranked  (or snk_shard_place: the ranking replicated, when a list is a circle)
+//   -> snk_shard_route_fill -> [fragments to the owners of their unitigs' heads] -> snk_shard_emit: this rank's unitigs.
+// There is no rank-0 funnel: every rank writes the unitigs whose head fragment it owns.
 #include <string.h>
 
 #include <vector>
@@ -19,45 +26,38 @@
 #include "snk_stages.h"
 #include "snk_shard.h"
 
-static snk_shard_state* state_of(snk_ctx* ctx) { return snk_shard_state_of(ctx); }
 void snk_shard_state_free(void* p) { delete static_cast<snk_shard_state*>(p); }
 void snk_shard_state_invalidate_job(void* p) { if (p) static_cast<snk_shard_state*>(p)->job_open = false; }
 
-int snk_shard_begin(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, uint32_t rank, uint32_t world, uint32_t NB_total,
-                    uint64_t* n_instances, hipStream_t st, char* err, size_t errcap) {
-    if (!ctx || !in || !p) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_hist: NULL argument");
-    if (p->K != 48 && p->K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", p->K);
-    if (p->min_bc > 8) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "min_bc=%u: the device barcode rule tells up to eight distinct barcodes apart (min_bc <= 8)", p->min_bc);
-    if (world == 0 || rank >= world || NB_total == 0 || NB_total % world) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_hist: NB_total must be a positive multiple of world");
-    if (world > 0x7FFF) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "world > 32767");
-    if (in->n_reads && (!in->rows || in->row_words * 16 < in->read_len || in->read_len > 256 || (!in->quals && !in->good_len)))
-        return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_hist: bad reads");
-    SNK_HIP_TRY(snk_enter(ctx));
+// a new step on this context: everything the last one held goes back
+static snk_shard_state* step_reset(snk_ctx* ctx, const snk_params* p, uint32_t rank, uint32_t world, uint32_t NB_total) {
     snk_ctx_release_scratch(ctx);
-    snk_shard_state* S = state_of(ctx);
-    S->reads = *in;
+    snk_shard_state* S = snk_shard_state_of(ctx);
     S->params = *p;
     S->rank = rank; S->world = world; S->NB_total = NB_total; S->NBl = NB_total / world;
     S->circ_all = nullptr; S->join_circles = 0;
     ctx->last_bl_attempts = ctx->last_bl_big_chunks = 0; ctx->last_bl_circles = 0;
-    const uint16_t* good_len = (const uint16_t*)in->good_len;
+    return S;
+}
+
+// (its refusals carry the name of the round-2 entry point this was the first half of: callers of snk_shard_step have seen it since,
+// and the texts stay as they are)
+static const char* const BEGIN_WHO = "snk_shard_hist";
+int snk_shard_begin(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, uint32_t rank, uint32_t world, uint32_t NB_total,
+                    uint64_t* n_instances, hipStream_t st, char* err, size_t errcap) {
+    if (!ctx || !in || !p) return snk_fail(SNK_E_ARG, err, errcap, "%s: NULL argument", BEGIN_WHO);
     int rc;
-    const bool fused = in->n_reads && snk_fused_trim_ok(ctx, in);      // the trim inside the partition kernel (snk_msp.hip)
+    if ((rc = snk_intake_check_params(p, err, errcap))) return rc;
+    if (world == 0 || rank >= world || NB_total == 0 || NB_total % world) return snk_fail(SNK_E_ARG, err, errcap, "%s: NB_total must be a positive multiple of world", BEGIN_WHO);
+    if (world > 0x7FFF) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "world > 32767");
+    if (snk_intake_reads_fault(in)) return snk_fail(SNK_E_ARG, err, errcap, "%s: bad reads", BEGIN_WHO);
+    SNK_HIP_TRY(snk_enter(ctx));
+    snk_shard_state* S = step_reset(ctx, p, rank, world, NB_total);
+    const uint16_t* good_len;
     snk_fused_trim ft;
-    if (!good_len) {
-        void* gl;
-        if ((rc = snk_ctx_alloc(ctx, in->n_reads * 2 + 2, &gl, err, errcap))) return rc;
-        if (fused) { ft.quals = in->quals; ft.qstride = in->qstride; ft.lens = in->lens; ft.min_qual = p->min_qual; ft.good_out = (uint16_t*)gl; }
-        else if (in->n_reads) {
-            rc = snk_dev_trim(ctx, in->quals, in->qstride, in->lens, in->read_len, in->n_reads, p->K, p->min_qual, gl, st);
-            if (rc) return snk_fail(rc, err, errcap, "%s", snk_last_error());
-        }
-        good_len = (const uint16_t*)gl;
-    }
-    S->good_len = good_len;
-    void* q;
-    if ((rc = snk_ctx_alloc(ctx, 64, &q, err, errcap))) return rc; S->status = (uint32_t*)q;
-    SNK_HIP_TRY(hipMemsetAsync(S->status, 0, 64, st));
+    bool fused;
+    if ((rc = snk_intake_trim(ctx, st, in, p, &good_len, &ft, &fused, err, errcap))) return rc;
+    if ((rc = snk_intake_status(ctx, st, &S->status, err, errcap))) return rc;
     // one partition pass into fixed-capacity bucket slots (as on one GPU); the histogram is its cursor array
     // the slots are sized from what the untrimmed reads could hold at most (a few per cent above what the trim leaves: the
     // capacity is 2.5 x the mean anyway); the exact instance count comes back with the partition's own read-back
@@ -76,23 +76,15 @@ int snk_shard_begin(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, 
 int snk_shard_job_open(snk_ctx* ctx, const snk_params* p, uint32_t rank, uint32_t world, uint32_t NB_total, uint32_t read_len, uint64_t reads_ub,
                        uint64_t total_reads, int has_bc, hipStream_t st, char* err, size_t errcap) {
     if (!ctx || !p) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_begin: NULL argument");
-    if (p->K != 48 && p->K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", p->K);
-    if (p->min_bc > 8) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "min_bc=%u: the device barcode rule tells up to eight distinct barcodes apart (min_bc <= 8)", p->min_bc);
+    int rc;
+    if ((rc = snk_intake_check_params(p, err, errcap))) return rc;
     if (world == 0 || rank >= world || NB_total == 0 || NB_total % world) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_begin: NB_total must be a positive multiple of world");
     if (read_len == 0 || read_len > 256 || reads_ub == 0) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_begin: read_len 1..256 and an upper bound of this rank's reads are needed");
     SNK_HIP_TRY(snk_enter(ctx));
-    snk_ctx_release_scratch(ctx);
-    snk_shard_state* S = state_of(ctx);
-    memset(&S->reads, 0, sizeof S->reads);
-    S->params = *p;
-    S->rank = rank; S->world = world; S->NB_total = NB_total; S->NBl = NB_total / world;
-    S->circ_all = nullptr; S->join_circles = 0;
-    ctx->last_bl_attempts = ctx->last_bl_big_chunks = 0; ctx->last_bl_circles = 0;
+    snk_shard_state* S = step_reset(ctx, p, rank, world, NB_total);
     S->job_open = false; S->job_read_len = read_len; S->job_has_bc = has_bc; S->job_reads_ub = reads_ub; S->job_total_reads = total_reads;
+    if ((rc = snk_intake_status(ctx, st, &S->status, err, errcap))) return rc;
     void* q;
-    int rc;
-    if ((rc = snk_ctx_alloc(ctx, 64, &q, err, errcap))) return rc; S->status = (uint32_t*)q;
-    SNK_HIP_TRY(hipMemsetAsync(S->status, 0, 64, st));
     if ((rc = snk_ctx_alloc(ctx, reads_ub * 2 + 64, &q, err, errcap))) return rc; S->job_good_len = (uint16_t*)q;
     const unsigned long long kpr = read_len >= p->K ? read_len - p->K + 1 : 0;
     if ((rc = snk_partition_open(ctx, st, p->K, NB_total, reads_ub * kpr, reads_ub, false, S->status, &S->job, err, errcap))) return rc;
@@ -101,40 +93,18 @@ int snk_shard_job_open(snk_ctx* ctx, const snk_params* p, uint32_t rank, uint32_
 }
 int snk_shard_job_add(snk_ctx* ctx, const snk_dev_reads* slab, hipStream_t st, char* err, size_t errcap) {
     if (!ctx || !ctx->shard || !slab) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_append: NULL argument / no open step");
-    snk_shard_state* S = state_of(ctx);
+    snk_shard_state* S = snk_shard_state_of(ctx);
     if (!S->job_open) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_append: no open step (snk_shard_stream_begin)");
     if (slab->n_reads == 0) return SNK_OK;
-    if (!slab->rows || slab->read_len != S->job_read_len || slab->row_words * 16 < slab->read_len) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_append: bad rows / read_len (the step's is %u)", S->job_read_len);
-    if (!slab->good_len && !slab->quals) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_append: need quals or good_len");
-    if ((slab->bc != nullptr) != (S->job_has_bc != 0)) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_append: every slab carries barcodes, or none does");
-    if (S->job.n_reads + slab->n_reads > S->job_reads_ub)
-        return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_append: more reads than the rank's upper bound (%llu + %llu > %llu)", (unsigned long long)S->job.n_reads,
-                        (unsigned long long)slab->n_reads, (unsigned long long)S->job_reads_ub);
+    int rc = snk_intake_check_slab(slab, S->job_read_len, S->job_has_bc != 0, S->job.n_reads, S->job_reads_ub, "snk_shard_stream_append", "step's", "rank's", err, errcap);
+    if (rc) return rc;
     SNK_HIP_TRY(snk_enter(ctx));
-    snk_dev_reads r = *slab;
-    uint16_t* gl = S->job_good_len + S->job.n_reads;
-    int rc;
-    if (slab->good_len) {
-        SNK_HIP_TRY(hipMemcpyAsync(gl, slab->good_len, slab->n_reads * 2, hipMemcpyDeviceToDevice, st));
-        rc = snk_partition_add(ctx, st, &S->job, &r, gl, nullptr, err, errcap);
-    } else if (snk_fused_trim_ok(ctx, &r)) {
-        snk_fused_trim ft;
-        ft.quals = r.quals; ft.qstride = r.qstride; ft.lens = r.lens; ft.min_qual = S->params.min_qual; ft.good_out = gl;
-        rc = snk_partition_add(ctx, st, &S->job, &r, gl, &ft, err, errcap);
-    } else {
-        rc = snk_dev_trim(ctx, r.quals, r.qstride, r.lens, r.read_len, r.n_reads, S->params.K, S->params.min_qual, gl, st);
-        if (rc) return snk_fail(rc, err, errcap, "%s", snk_last_error());
-        rc = snk_partition_add(ctx, st, &S->job, &r, gl, nullptr, err, errcap);
-    }
-    return rc;
+    return snk_intake_add_slab(ctx, st, &S->job, slab, S->params.min_qual, S->job_good_len + S->job.n_reads, err, errcap);
 }
 int snk_shard_job_adopt(snk_ctx* ctx, uint64_t* n_instances, hipStream_t st, char* err, size_t errcap) {
-    snk_shard_state* S = state_of(ctx);
+    snk_shard_state* S = snk_shard_state_of(ctx);
     if (!S->job_open) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_stream_finish: no open step");
     S->job_open = false;
-    S->good_len = S->job_good_len;
-    S->reads.n_reads = S->job.n_reads;
-    S->reads.read_len = S->job_read_len;
     unsigned long long h_plan[2] = {0, 0};
     int rc = snk_partition_close(ctx, st, &S->job, &S->part, h_plan, err, errcap);
     if (rc) return rc;
@@ -142,207 +112,24 @@ int snk_shard_job_adopt(snk_ctx* ctx, uint64_t* n_instances, hipStream_t st, cha
     return SNK_OK;
 }
 
-extern "C" int snk_shard_hist(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, uint32_t rank, uint32_t world,
-                              uint32_t NB_total, void* d_hist, uint64_t* n_instances, void* stream, char* err, size_t errcap) {
-    if (!ctx || !d_hist) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_hist: NULL argument");
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    int rc = snk_shard_begin(ctx, in, p, rank, world, NB_total, n_instances, st, err, errcap);
-    if (rc) return rc;
-    // the "scatter" stage compacts the slots into the caller's exact, destination-contiguous send buffer
-    SNK_HIP_TRY(hipMemcpyAsync(d_hist, state_of(ctx)->part.cursor, (size_t)NB_total * 4, hipMemcpyDeviceToDevice, st));
-    SNK_HIP_TRY(snk_sync(st));
-    return SNK_OK;
-}
-
-extern "C" int snk_shard_scatter(snk_ctx* ctx, const void* d_offsets, void* d_records, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_offsets || !d_records) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_scatter: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    return snk_stage_partition_compact(ctx, st, &S->part, (const uint32_t*)d_offsets, d_records, err, errcap);
-}
-
-extern "C" int snk_shard_count(snk_ctx* ctx, const void* d_records, const void* d_seg_off, uint64_t n_inst_hint, int has_bc,
-                               uint64_t* n_kmers, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_seg_off) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_count: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    int rc = snk_stage_count_table(ctx, st, S->params.K, d_records, (const uint64_t*)d_seg_off, (const uint64_t*)d_seg_off + 1, S->NBl + 1, S->world, S->NBl, S->params.min_freq,
-                                   has_bc ? S->params.min_bc : 0u, 0u, n_inst_hint, S->status, false, &S->tab, err, errcap);
-    if (rc) return rc;
-    if (n_kmers) *n_kmers = S->tab.n;
-    return SNK_OK;
-}
-
-extern "C" int snk_shard_count_ranged(snk_ctx* ctx, const void* d_records, const void* d_seg_off, uint64_t n_inst_hint, int has_bc,
-                                      uint32_t n_ranges, const uint32_t* bounds, int (*ready)(void*, uint32_t), void* user,
-                                      uint64_t* n_kmers, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_seg_off || (n_ranges && !bounds)) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_count_ranged: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    if (n_ranges && (bounds[0] != 0 || bounds[n_ranges] != S->NBl)) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_count_ranged: the ranges must cover the local buckets");
-    for (uint32_t r = 0; r < n_ranges; ++r) if (bounds[r] > bounds[r + 1]) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_count_ranged: descending range bounds");
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    snk_count_ranges rg{n_ranges, bounds, ready, user};
-    int rc = snk_stage_count_table(ctx, st, S->params.K, d_records, (const uint64_t*)d_seg_off, (const uint64_t*)d_seg_off + 1, S->NBl + 1, S->world, S->NBl, S->params.min_freq,
-                                   has_bc ? S->params.min_bc : 0u, 0u, n_inst_hint, S->status, false, &S->tab, err, errcap, n_ranges ? &rg : nullptr);
-    if (rc) return rc;
-    if (n_kmers) *n_kmers = S->tab.n;
-    return SNK_OK;
-}
-
-extern "C" int snk_shard_prune_plan(snk_ctx* ctx, uint64_t* h_qcount, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prune_plan: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
+int snk_shard_prune_plan(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, char* err, size_t errcap) {
     // bucket-local prune (snk_local.hip); only neighbours owned by another rank become queries
-    snk_bl_state& B = S->bl;
+    snk_bl_state& B = S.bl;
     memset(&B, 0, sizeof B);
-    B.tab = &S->tab;
-    B.K = S->params.K; B.rank = S->rank; B.world = S->world; B.NB_total = S->NB_total; B.NBl = S->NBl;
-    B.do_prune = S->params.min_freq > 1 ? 1u : 0u;
-    std::vector<unsigned long long> h(S->world);
-    int rc = snk_bl_dist_plan(ctx, st, &B, h_qcount ? h.data() : nullptr, err, errcap);      // NULL: the counts stay on the device (B.qcount)
+    B.tab = &S.tab;
+    B.K = S.params.K; B.rank = S.rank; B.world = S.world; B.NB_total = S.NB_total; B.NBl = S.NBl;
+    B.do_prune = S.params.min_freq > 1 ? 1u : 0u;
+    int rc = snk_bl_dist_plan(ctx, st, &B, err, errcap);      // (the counts stay on the device: B.qcount)
     if (rc) return rc;
-    if (h_qcount) for (uint32_t r = 0; r < S->world; ++r) h_qcount[r] = h[r];
     // the answering / applying kernels of the global sharded stage work on the same arrays
-    snk_dist_graph& g = S->g;
+    snk_dist_graph& g = S.g;
     memset(&g, 0, sizeof g);
     g.K = B.K; g.rank = B.rank; g.world = B.world; g.NB_total = B.NB_total; g.NBl = B.NBl; g.do_prune = B.do_prune;
-    g.n = S->tab.n; g.keys = S->tab.keys; g.vals = S->tab.vals;
+    g.n = S.tab.n; g.keys = S.tab.keys; g.vals = S.tab.vals;
     g.index = B.index; g.index_mask = B.index_mask;
     g.ctx = B.ctx; g.counts = B.counts; g.rq_idx = B.rq_idx; g.rq_meta = B.rq_meta;
     return SNK_OK;
 }
-extern "C" int snk_shard_prune_fill(snk_ctx* ctx, const void* d_qoff, void* d_qbuf, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_qoff) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prune_fill: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    return snk_bl_dist_fill(ctx, stream ? (hipStream_t)stream : ctx->stream, &S->bl, (const unsigned long long*)d_qoff, d_qbuf, err, errcap);
-}
-extern "C" int snk_shard_prune_answer(snk_ctx* ctx, const void* d_queries, uint64_t nq, void* d_ans, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prune_answer: no session");
-    snk_shard_state* S = state_of(ctx);
-    return snk_dist_answer(ctx, stream ? (hipStream_t)stream : ctx->stream, &S->g, d_queries, nq, d_ans, err, errcap);
-}
-extern "C" int snk_shard_prune_apply(snk_ctx* ctx, const void* d_qbuf, const void* d_ans, uint64_t nq, const void* d_qoff, void* stream,
-                                     char* err, size_t errcap) {
-    if (!ctx || !ctx->shard) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prune_apply: no session");
-    snk_shard_state* S = state_of(ctx);
-    return snk_dist_apply(ctx, stream ? (hipStream_t)stream : ctx->stream, &S->g, d_qbuf, d_ans, nq, (const unsigned long long*)d_qoff, err, errcap);
-}
-
-extern "C" int snk_shard_fragments(snk_ctx* ctx, const void* d_node_off, uint64_t my_node_off, snk_shard_frags* out, void* stream,
-                                   char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !out || !d_node_off) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_fragments: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    snk_frag_out fo;
-    int rc = snk_bl_dist_fragments(ctx, st, &S->bl, (const unsigned long long*)d_node_off, my_node_off, &fo, err, errcap);
-    if (rc) return rc;
-    S->frags = fo;
-    S->d_node_off = (const unsigned long long*)d_node_off;
-    S->my_node_off = my_node_off;
-    memset(out, 0, sizeof *out);
-    out->n_kmers = S->tab.n;
-    out->keys = S->tab.keys;
-    out->counts = S->bl.counts;
-    out->ctx = S->bl.ctx;
-    out->spectrum = fo.spectrum;
-    out->spectrum_bins = fo.spectrum_bins;
-    out->n_frags = fo.n_frags;
-    out->total_bases = fo.total_bases;
-    out->nk = fo.nk;
-    out->hl_self = fo.hl_self;
-    out->hl_nb = fo.hl_nb;
-    out->boff = fo.boff;
-    out->bases = fo.bases;
-    out->n_circles = fo.n_circles;
-    out->rank_rounds = fo.rank_rounds;
-    out->buckets_split = S->tab.buckets_split;
-    out->max_slots_used = S->tab.max_slots_used;
-    out->count_ms = S->tab.count_ms;
-    out->sort_ms = S->tab.sort_ms;
-    out->count_kernel_ms = S->tab.count_kernel_ms;
-    return SNK_OK;
-}
-
-// ---- fragment links decided on the owners (instead of a hash match over every end on rank 0)
-extern "C" int snk_shard_links_plan(snk_ctx* ctx, uint64_t my_frag_off, uint64_t* h_qcount, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !h_qcount) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_links_plan: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    S->my_end_base = 2ull * my_frag_off;
-    void* q;
-    int rc;
-    if ((rc = snk_ctx_alloc(ctx, (S->world + 1) * 8ull, &q, err, errcap))) return rc; S->lq_count = (unsigned long long*)q;
-    if ((rc = snk_ctx_alloc(ctx, (S->world + 1) * 8ull, &q, err, errcap))) return rc; S->lq_cursor = (unsigned long long*)q;
-    SNK_HIP_TRY(hipMemsetAsync(S->lq_count, 0, (S->world + 1) * 8ull, st));
-    if ((rc = snk_dist_links_query(ctx, st, false, &S->frags, S->d_node_off, S->world, S->my_end_base, S->lq_count, nullptr, err, errcap))) return rc;
-    std::vector<unsigned long long> h(S->world);
-    SNK_HIP_TRY(hipMemcpyAsync(h.data(), S->lq_count, S->world * 8ull, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    for (uint32_t r = 0; r < S->world; ++r) h_qcount[r] = h[r];
-    return SNK_OK;
-}
-extern "C" int snk_shard_links_fill(snk_ctx* ctx, const void* d_qoff, void* d_qbuf, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_qoff) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_links_fill: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    SNK_HIP_TRY(hipMemcpyAsync(S->lq_cursor, d_qoff, (S->world + 1) * 8ull, hipMemcpyDeviceToDevice, st));
-    return snk_dist_links_query(ctx, st, true, &S->frags, S->d_node_off, S->world, S->my_end_base, S->lq_cursor, d_qbuf, err, errcap);
-}
-extern "C" int snk_shard_links_answer(snk_ctx* ctx, const void* d_queries, uint64_t nq, void* d_ans, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_links_answer: no session");
-    snk_shard_state* S = state_of(ctx);
-    return snk_dist_links_answer(ctx, stream ? (hipStream_t)stream : ctx->stream, &S->frags, d_queries, nq, 2ull * S->my_node_off, 2ull * S->tab.n,
-                                 S->my_end_base, d_ans, err, errcap);
-}
-extern "C" int snk_shard_links_apply(snk_ctx* ctx, const void* d_qbuf, const void* d_ans, uint64_t nq, const void** d_flink, void* stream,
-                                     char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_flink) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_links_apply: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    uint32_t* fl = nullptr;
-    int rc = snk_dist_links_apply(ctx, stream ? (hipStream_t)stream : ctx->stream, &S->frags, d_qbuf, d_ans, nq, &fl, err, errcap);
-    if (rc) return rc;
-    *d_flink = fl;
-    return SNK_OK;
-}
-
-extern "C" int snk_shard_join(snk_ctx* ctx, uint32_t K, uint64_t n_frags, const void* d_nk, const void* d_hl_self, const void* d_hl_nb,
-                              const void* d_boff, const void* d_bases, uint64_t total_bases, snk_shard_unitigs* out, void* stream,
-                              char* err, size_t errcap) {
-    return snk_shard_join_linked(ctx, K, n_frags, d_nk, d_hl_self, d_hl_nb, nullptr, d_boff, d_bases, total_bases, out, stream, err, errcap);
-}
-
-extern "C" int snk_shard_join_linked(snk_ctx* ctx, uint32_t K, uint64_t n_frags, const void* d_nk, const void* d_hl_self, const void* d_hl_nb,
-                                     void* d_flink, const void* d_boff, const void* d_bases, uint64_t total_bases, snk_shard_unitigs* out,
-                                     void* stream, char* err, size_t errcap) {
-    if (!ctx || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_join: NULL argument");
-    if (!d_flink && (!d_hl_self || !d_hl_nb)) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_join: need half links or links");
-    if (K != 48 && K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", K);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    snk_join_out jo;
-    int rc = snk_dist_join(ctx, st, K, n_frags, (const uint32_t*)d_nk, (const unsigned long long*)d_hl_self,
-                           (const unsigned long long*)d_hl_nb, (const uint64_t*)d_boff, (const uint8_t*)d_bases, total_bases, &jo, err, errcap, nullptr, nullptr, 0,
-                           (uint32_t*)d_flink);
-    if (rc) return rc;
-    out->n_unitigs = jo.n_unitigs;
-    out->total_bases = jo.total_bases;
-    out->unitig_off = jo.unitig_off;
-    out->unitig_bases = jo.unitig_bases;
-    out->unitig_circular = jo.unitig_circular;
-    out->n_circles = jo.n_circles;
-    out->rank_rounds = jo.rank_rounds;
-    return SNK_OK;
-}
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Owner-side join (no rank-0 funnel).  tada's MAIN_ASM_SN is one process (lib/tada/src/cmd_main_asm.rs:25-89,184-193) and so
@@ -350,7 +137,7 @@ extern "C" int snk_shard_join_linked(snk_ctx* ctx, uint32_t K, uint64_t n_frags,
 // the size of the job.  Now the only thing every rank sees of the whole job is the LINK structure (8 + 4 bytes per fragment,
 // all-gathered): it ranks the fragment lists, places its own fragments (unitig = the smaller terminal state, offset,
 // strand) and sends each fragment's bases to the rank that owns the unitig's head fragment, which writes the unitig.
-//   snk_shard_place       links + k-mer counts of all ranks -> placement of my fragments, fragments / bases per owner
+//   snk_shard_place*      links + k-mer counts of all ranks -> placement of my fragments
 //   snk_shard_route_fill  32-byte headers + bases grouped by owner (the two send buffers of one all-to-all each)
 //   snk_shard_emit        headers + bases received -> this rank's unitigs (canonical, circles rotated, ordered)
 namespace {
@@ -360,7 +147,8 @@ __device__ __forceinline__ uint32_t owner_of_frag(const unsigned long long* __re
     while (r + 1 < world && g >= frag_off[r + 1]) ++r;
     return r;
 }
-// FILL = false: count fragments and base bytes per owner; true: write header and bases at reserved positions.
+// FILL = false: count fragments and base bytes per owner; true: write header and bases at reserved positions (the step routes in one
+// pass into per-owner regions and launches FILL = true only).
 // header (4 x u64): pid | gfid << 32;  nk | flags << 32;  koff (heads: N);  offset of the bases inside the owner's segment.
 // One fragment per thread for the bookkeeping: the workgroup adds up its fragments and bytes per owner in LDS and goes to
 // the `world` device counters once per owner (2 M fragments on the same few addresses, one device atomic each, took 100 ms);
@@ -462,146 +250,65 @@ __global__ void __launch_bounds__(256) unroute_kernel(const unsigned long long* 
 }
 }  // namespace
 
-// placement of this rank's fragments from a ranking (whole list: rk_f0 = 0; own states only: rk_f0 = my_frag_off) and the
-// fragments / base bytes owed to every owner
-static int place_and_count(snk_ctx* ctx, snk_shard_state* S, hipStream_t st, uint32_t K, const uint2* rk, uint64_t rk_f0, const uint8_t* circ,
-                           const uint32_t* nk_all, const void* d_frag_off, uint64_t* h_frags_to, uint64_t* h_bases_to, char* err, size_t errcap) {
-    const uint64_t Fl = S->frags.n_frags;
+// placement of this rank's fragments from a ranking (whole list: rk_f0 = 0; own states only: rk_f0 = my_frag_off), and the cursors of the
+// one-pass routing into per-owner regions (snk_shard_route_fill)
+static int place(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, const uint2* rk, uint64_t rk_f0, const uint8_t* circ, const uint32_t* nk_all, char* err,
+                 size_t errcap) {
     int rc;
-    if ((rc = snk_join_place(ctx, st, rk, nk_all, circ, S->my_frag_off, Fl, &S->pl, err, errcap, rk_f0))) return rc;
+    if ((rc = snk_join_place(ctx, st, rk, nk_all, circ, S.my_frag_off, S.frags.n_frags, &S.pl, err, errcap, rk_f0))) return rc;
     void* q;
-    if (!h_frags_to) {          // the caller routes in one pass into per-owner regions (snk_shard_step.hip): nothing to count
-        if ((rc = snk_ctx_alloc(ctx, 2ull * (S->world + 1) * 8, &q, err, errcap))) return rc; S->rt_cursor = (unsigned long long*)q;
-        return SNK_OK;
-    }
-    if ((rc = snk_ctx_alloc(ctx, 2ull * (S->world + 1) * 8, &q, err, errcap))) return rc; S->rt_count = (unsigned long long*)q;
-    if ((rc = snk_ctx_alloc(ctx, 2ull * (S->world + 1) * 8, &q, err, errcap))) return rc; S->rt_cursor = (unsigned long long*)q;
-    SNK_HIP_TRY(hipMemsetAsync(S->rt_count, 0, 2ull * (S->world + 1) * 8, st));
-    SNK_HIP_TRY(snk_launch(route_kernel<false>, snk_blocks(Fl, 256 * ROUTE_TILES), 256, 4ull * S->world * 8, st, Fl, (unsigned long long)S->my_frag_off, S->frags.nk, S->pl.pid, S->pl.koff,
-                           S->pl.N, S->pl.circ, (const unsigned long long*)d_frag_off, S->world, K, S->frags.boff, S->frags.bases, S->rt_count, nullptr, nullptr, nullptr));
-    std::vector<unsigned long long> h(2 * S->world);
-    SNK_HIP_TRY(hipMemcpyAsync(h.data(), S->rt_count, 2ull * S->world * 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    for (uint32_t r = 0; r < S->world; ++r) { h_frags_to[r] = h[r]; h_bases_to[r] = h[S->world + r]; }
+    if ((rc = snk_ctx_alloc(ctx, 2ull * (S.world + 1) * 8, &q, err, errcap))) return rc; S.rt_cursor = (unsigned long long*)q;
     return SNK_OK;
 }
 
-extern "C" int snk_shard_place(snk_ctx* ctx, uint32_t K, uint64_t n_frags_total, const void* d_nk_all, void* d_flink_all, const void* d_frag_off,
-                               uint64_t my_frag_off, uint64_t* h_frags_to /* [world] */, uint64_t* h_bases_to /* [world] */, void* stream, char* err,
-                               size_t errcap) {
-    if (!ctx || !ctx->shard || !d_frag_off || (!h_frags_to) != (!h_bases_to)) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_place: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
+int snk_shard_place(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint64_t n_frags_total, const uint32_t* nk_all, uint32_t* flink_all,
+                    uint64_t my_frag_off, char* err, size_t errcap) {
     if (2 * n_frags_total >= (1ull << 32)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments in the job");
-    S->my_frag_off = my_frag_off;
-    S->n_frags_total = n_frags_total;
+    S.my_frag_off = my_frag_off;
     const uint2* rk = nullptr;
     uint8_t* circ = nullptr;
     uint32_t nc = 0;
-    int rc = snk_join_rank(ctx, st, n_frags_total, (const uint32_t*)d_nk_all, (uint32_t*)d_flink_all, &rk, &circ, &nc, &S->join_rounds, err, errcap, S->circ_all);
+    int rc = snk_join_rank(ctx, st, n_frags_total, nk_all, flink_all, &rk, &circ, &nc, &S.join_rounds, err, errcap, S.circ_all);
     if (rc) return rc;
-    S->join_circles += nc;
-    return place_and_count(ctx, S, st, K, rk, 0, circ, (const uint32_t*)d_nk_all, d_frag_off, h_frags_to, h_bases_to, err, errcap);
+    S.join_circles += nc;
+    return place(ctx, S, st, rk, 0, circ, nk_all, err, errcap);
 }
 
-// ---- the ranking partitioned over the ranks (snk_graph.hip: snk_prank_*): begin -> [all-gather of 16 B per splitter] -> walk ->
-// [all-to-all of 16 B per state] -> snk_shard_place_ranked.  *circles = 1 after the walk: a list is a circle, use snk_shard_place.
-extern "C" int snk_shard_prank_begin(snk_ctx* ctx, uint64_t n_frags_total, const void* d_nk_all, void* d_flink_all, uint64_t my_frag_off,
-                                     uint64_t* n_splitters, const void** d_w1_share, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !n_splitters || !d_w1_share) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prank_begin: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
+// ---- the ranking partitioned over the ranks (snk_graph.hip: snk_prank_*)
+int snk_shard_prank_begin(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint64_t n_frags_total, const uint32_t* nk_all, uint32_t* flink_all,
+                          uint64_t my_frag_off, char* err, size_t errcap) {
     if (2 * n_frags_total >= (1ull << 32)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments in the job");
-    S->my_frag_off = my_frag_off;
-    S->n_frags_total = n_frags_total;
-    S->nk_all = (const uint32_t*)d_nk_all;
-    if (!S->circ_all) {          // first ranking attempt of this step (a second one follows a circle cut and keeps the marks)
+    S.my_frag_off = my_frag_off;
+    S.nk_all = nk_all;
+    if (!S.circ_all) {          // first ranking attempt of this step (a second one follows a circle cut and keeps the marks)
         void* q;
         int rc0 = snk_ctx_alloc(ctx, 2 * n_frags_total + 16, &q, err, errcap);
         if (rc0) return rc0;
-        S->circ_all = (uint8_t*)q;
-        SNK_HIP_TRY(hipMemsetAsync(S->circ_all, 0, 2 * n_frags_total + 16, st));
+        S.circ_all = (uint8_t*)q;
+        SNK_HIP_TRY(hipMemsetAsync(S.circ_all, 0, 2 * n_frags_total + 16, st));
     }
-    int rc = snk_prank_begin(ctx, st, n_frags_total, (const uint32_t*)d_nk_all, (uint32_t*)d_flink_all, S->rank, S->world, &S->pr, err, errcap);
-    if (rc) return rc;
-    *n_splitters = S->pr.m;       // (the share is consumed by a collective on the same stream: nothing to wait for here)
-    *d_w1_share = S->pr.w1_share;
-    return SNK_OK;
+    // (the share S.pr.w1_share is consumed by a collective on the same stream: nothing to wait for here)
+    return snk_prank_begin(ctx, st, n_frags_total, nk_all, flink_all, S.rank, S.world, &S.pr, err, errcap);
 }
-extern "C" int snk_shard_prank_walk(snk_ctx* ctx, const void* d_w1_all, const void* d_frag_off, uint64_t* h_recs_to /* [world] */, uint32_t* circles,
-                                    void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !circles) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prank_walk: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    uint32_t n_cut = 0;
-    int rc = snk_prank_walk(ctx, st, &S->pr, (const uint4*)d_w1_all, circles, &S->join_rounds, err, errcap, S->circ_all, &n_cut);
-    if (rc) return rc;
-    S->join_circles += n_cut;
-    if (h_recs_to) for (uint32_t r = 0; r < S->world; ++r) h_recs_to[r] = 0;
-    if (*circles) return SNK_OK;       // 2: circles were cut in the replicated links, call snk_shard_prank_begin again; 1: use snk_shard_place
-    if (!h_recs_to) return SNK_OK;       // one-pass routing into per-owner regions: S->pr.n_rec records, no count pass
-    void* q;
-    if ((rc = snk_ctx_alloc(ctx, (S->world + 1) * 8ull, &q, err, errcap))) return rc;
-    unsigned long long* cnt = (unsigned long long*)q;
-    SNK_HIP_TRY(hipMemsetAsync(cnt, 0, (S->world + 1) * 8ull, st));
-    if ((rc = snk_prank_route(ctx, st, &S->pr, false, (const unsigned long long*)d_frag_off, S->world, cnt, nullptr, err, errcap))) return rc;
-    std::vector<unsigned long long> h(S->world);
-    SNK_HIP_TRY(hipMemcpyAsync(h.data(), cnt, S->world * 8ull, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    for (uint32_t r = 0; r < S->world; ++r) h_recs_to[r] = h[r];
-    return SNK_OK;
-}
-extern "C" int snk_shard_prank_route(snk_ctx* ctx, const void* d_frag_off, const void* d_rec_off /* u64[world]: first record of every owner */, void* d_out,
-                                     void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_rec_off) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_prank_route: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    void* q;
-    int rc;
-    if ((rc = snk_ctx_alloc(ctx, (S->world + 1) * 8ull, &q, err, errcap))) return rc;
-    SNK_HIP_TRY(hipMemcpyAsync(q, d_rec_off, S->world * 8ull, hipMemcpyDeviceToDevice, st));
-    S->pr_cursor = (unsigned long long*)q;
-    return snk_prank_route(ctx, st, &S->pr, true, (const unsigned long long*)d_frag_off, S->world, (unsigned long long*)q, d_out, err, errcap);
-}
-extern "C" int snk_shard_place_ranked(snk_ctx* ctx, uint32_t K, const void* d_recs, uint64_t n_recs, const void* d_frag_off, uint64_t* h_frags_to,
-                                      uint64_t* h_bases_to, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_frag_off || (!h_frags_to) != (!h_bases_to)) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_place_ranked: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
+int snk_shard_place_ranked(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, const void* d_recs, uint64_t n_recs, char* err, size_t errcap) {
     const uint2* rk = nullptr;
-    int rc = snk_prank_apply(ctx, st, d_recs, n_recs, 2ull * S->my_frag_off, 2ull * S->frags.n_frags, &rk, err, errcap);
+    int rc = snk_prank_apply(ctx, st, d_recs, n_recs, 2ull * S.my_frag_off, 2ull * S.frags.n_frags, &rk, err, errcap);
     if (rc) return rc;
-    return place_and_count(ctx, S, st, K, rk, S->my_frag_off, S->join_circles ? S->circ_all : nullptr, S->nk_all, d_frag_off, h_frags_to, h_bases_to, err, errcap);
+    return place(ctx, S, st, rk, S.my_frag_off, S.join_circles ? S.circ_all : nullptr, S.nk_all, err, errcap);
 }
 
-extern "C" int snk_shard_route_fill(snk_ctx* ctx, uint32_t K, const void* d_frag_off, const void* d_hdr_off /* u64[world]: first header of every owner */,
-                                    const void* d_base_off /* u64[world]: first base byte of every owner */, void* d_hdr, void* d_bases, void* stream,
-                                    char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !d_frag_off || !d_hdr_off || !d_base_off) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_route_fill: NULL argument / no session");
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
-    const uint64_t Fl = S->frags.n_frags;
-    SNK_HIP_TRY(hipMemcpyAsync(S->rt_cursor, d_hdr_off, S->world * 8ull, hipMemcpyDeviceToDevice, st));
-    SNK_HIP_TRY(hipMemcpyAsync(S->rt_cursor + S->world, d_base_off, S->world * 8ull, hipMemcpyDeviceToDevice, st));
-    SNK_HIP_TRY(snk_launch(route_kernel<true>, snk_blocks(Fl, 256 * ROUTE_TILES), 256, 4ull * S->world * 8, st, Fl, (unsigned long long)S->my_frag_off, S->frags.nk, S->pl.pid, S->pl.koff,
-                           S->pl.N, S->pl.circ, (const unsigned long long*)d_frag_off, S->world, K, S->frags.boff, S->frags.bases, S->rt_cursor,
-                           (unsigned long long*)d_hdr, (uint8_t*)d_bases, (const unsigned long long*)d_base_off));
+int snk_shard_route_fill(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint32_t K, const unsigned long long* d_frag_off, const unsigned long long* d_hdr_off,
+                         const unsigned long long* d_base_off, void* d_hdr, void* d_bases, char* err, size_t errcap) {
+    const uint64_t Fl = S.frags.n_frags;
+    SNK_HIP_TRY(hipMemcpyAsync(S.rt_cursor, d_hdr_off, S.world * 8ull, hipMemcpyDeviceToDevice, st));
+    SNK_HIP_TRY(hipMemcpyAsync(S.rt_cursor + S.world, d_base_off, S.world * 8ull, hipMemcpyDeviceToDevice, st));
+    SNK_HIP_TRY(snk_launch(route_kernel<true>, snk_blocks(Fl, 256 * ROUTE_TILES), 256, 4ull * S.world * 8, st, Fl, (unsigned long long)S.my_frag_off, S.frags.nk, S.pl.pid, S.pl.koff,
+                           S.pl.N, S.pl.circ, d_frag_off, S.world, K, S.frags.boff, S.frags.bases, S.rt_cursor, (unsigned long long*)d_hdr, (uint8_t*)d_bases, d_base_off));
     return SNK_OK;
 }
 
-extern "C" int snk_shard_emit(snk_ctx* ctx, uint32_t K, uint64_t n_recv, const void* d_hdr, const void* d_hdr_seg /* u64[world+1] */,
-                              const void* d_base_seg /* u64[world+1] */, const void* d_bases, snk_shard_unitigs* out, void* stream, char* err, size_t errcap) {
-    if (!ctx || !ctx->shard || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_shard_emit: NULL argument / no session");
-    if (K != 48 && K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", K);
-    snk_shard_state* S = state_of(ctx);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    ctx->cur_stream = st;
+int snk_shard_emit(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint32_t K, uint64_t n_recv, const void* d_hdr, const unsigned long long* d_hdr_seg,
+                   const unsigned long long* d_base_seg, const uint8_t* d_bases, snk_join_out* out, char* err, size_t errcap) {
     uint32_t *nk, *gfid, *pid;
     unsigned long long *koff, *N;
     uint8_t* circ;
@@ -615,21 +322,10 @@ extern "C" int snk_shard_emit(snk_ctx* ctx, uint32_t K, uint64_t n_recv, const v
     if ((rc = snk_ctx_alloc(ctx, (n_recv + 1) * 8, &q, err, errcap))) return rc; N = (unsigned long long*)q;
     if ((rc = snk_ctx_alloc(ctx, (n_recv + 1), &q, err, errcap))) return rc; circ = (uint8_t*)q;
     if ((rc = snk_ctx_alloc(ctx, (n_recv + 2) * 8, &q, err, errcap))) return rc; boff = (uint64_t*)q;
-    SNK_HIP_TRY(snk_launch(unroute_kernel, snk_blocks(n_recv, 256), 256, 0, st, (const unsigned long long*)d_hdr, n_recv,
-                           (const unsigned long long*)d_hdr_seg, (const unsigned long long*)d_base_seg, S->world, nk, gfid, pid, koff, N, circ, boff));
-    snk_join_out jo;
+    SNK_HIP_TRY(snk_launch(unroute_kernel, snk_blocks(n_recv, 256), 256, 0, st, (const unsigned long long*)d_hdr, n_recv, d_hdr_seg, d_base_seg, S.world, nk, gfid, pid, koff, N,
+                           circ, boff));
     // every pid received here is a terminal state of one of this rank's own fragments
-    rc = snk_join_emit(ctx, st, K, n_recv, nk, gfid, pid, koff, N, circ, (uint32_t)(2 * S->my_frag_off), 2 * S->frags.n_frags, boff, (const uint8_t*)d_bases,
-                       nullptr, &jo, err, errcap);
-    if (rc) return rc;
-    out->n_unitigs = jo.n_unitigs;
-    out->total_bases = jo.total_bases;
-    out->unitig_off = jo.unitig_off;
-    out->unitig_bases = jo.unitig_bases;
-    out->unitig_circular = jo.unitig_circular;
-    out->n_circles = S->join_circles;
-    out->rank_rounds = S->join_rounds;
-    return SNK_OK;
+    return snk_join_emit(ctx, st, K, n_recv, nk, gfid, pid, koff, N, circ, (uint32_t)(2 * S.my_frag_off), 2 * S.frags.n_frags, boff, d_bases, nullptr, out, err, errcap);
 }
 
 // ---- fragment bases on the wire: 2 bits per base (the gather to rank 0 is the only place where bases cross xGMI)

@@ -83,8 +83,8 @@ int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk
                     size_t errcap);
 int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_all, uint32_t* circles, uint32_t* rounds, char* err, size_t errcap,
                    uint8_t* circ = nullptr /* [ns]: given = circles are cut here (*circles = 2: begin again) */, uint32_t* n_cut = nullptr);
-int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, bool fill, const unsigned long long* d_frag_off, uint32_t world,
-                    unsigned long long* d_cnt_or_cur, void* d_out, char* err, size_t errcap);
+int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, const unsigned long long* d_frag_off, uint32_t world,
+                    unsigned long long* d_cursor /* [world]: first record of every owner's region; the regions' ends afterwards */, void* d_out, char* err, size_t errcap);
 int snk_prank_apply(snk_ctx* ctx, hipStream_t st, const void* d_rec, uint64_t n, unsigned long long state_base, uint64_t n_local_states,
                     const uint2** rk_out, char* err, size_t errcap);
 int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const uint32_t* nk, const uint32_t* gfid, const uint32_t* pl_pid,
@@ -97,14 +97,14 @@ int snk_dist_apply(snk_ctx* ctx, hipStream_t st, snk_dist_graph* g, const void* 
 int snk_dist_join(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const uint32_t* nk, const unsigned long long* hl_self,
                   const unsigned long long* hl_nb, const uint64_t* boff, const uint8_t* fbases, uint64_t total_fbases,
                   snk_join_out* out, char* err, size_t errcap, const uint32_t* fgroup = nullptr, const uint32_t* sfrag = nullptr,
-                  uint64_t n_states = 0, uint32_t* flink_given = nullptr);
-int snk_dist_links_query(snk_ctx* ctx, hipStream_t st, bool fill, const snk_frag_out* fr, const unsigned long long* d_node_off, uint32_t world,
-                         unsigned long long my_end_base, unsigned long long* d_count_or_cursor, void* d_qbuf, char* err, size_t errcap);
+                  uint64_t n_states = 0);
+// sharded runs, fragment links decided on the owners: every fragment end whose half link names a state of rank q asks q (24 bytes, written
+// into q's region of d_qbuf at d_cursor[q]), q answers with the global id of the fragment end that sits on that state and points back, or
+// ~0 (4 bytes); applied, the answers are flink u32[2*n_frags]: global fragment-end id linked to each local end, or ~0
+int snk_dist_links_query(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const unsigned long long* d_node_off, uint32_t world,
+                         unsigned long long my_end_base, unsigned long long* d_cursor, void* d_qbuf, char* err, size_t errcap);
 int snk_dist_links_answer(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_queries, uint64_t nq, unsigned long long my_state_base,
                           uint64_t n_local_states, unsigned long long my_end_base, void* d_ans, char* err, size_t errcap);
-int snk_dist_links_apply(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_qbuf, const void* d_ans, uint64_t nq, uint32_t** flink_out,
-                         char* err, size_t errcap);
-
 int snk_dist_links_apply_regions(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_qbuf, const void* d_ans, uint32_t world, uint64_t cap,
                                  const unsigned long long* counts, uint32_t** flink_out, char* err, size_t errcap);
 
@@ -128,7 +128,7 @@ struct snk_bl_state {          // device arrays of the bucket-local stage (index
     unsigned long long* spec;
     uint32_t want_spec, spec_over;
 };
-int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, unsigned long long* h_qcount, char* err, size_t errcap);
+int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* err, size_t errcap);
 int snk_bl_dist_fill(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, const unsigned long long* d_qoff, void* d_qbuf, char* err, size_t errcap);
 int snk_bl_dist_fragments(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, const unsigned long long* d_node_off, unsigned long long my_node_off,
                           snk_frag_out* out, char* err, size_t errcap);

@@ -1484,19 +1484,17 @@ int snk_dist_apply(snk_ctx* ctx, hipStream_t st, snk_dist_graph* g, const void* 
     return SNK_OK;
 }
 
-// rank 0: fragments of every rank -> canonical unitigs
+// all fragments of a job on one device (the one-GPU bucket-local stage) -> canonical unitigs
 int snk_dist_join(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const uint32_t* nk, const unsigned long long* hl_self,
                   const unsigned long long* hl_nb, const uint64_t* boff, const uint8_t* fbases, uint64_t total_fbases,
-                  snk_join_out* out, char* err, size_t errcap, const uint32_t* fgroup, const uint32_t* sfrag, uint64_t n_states,
-                  uint32_t* flink_given) {
+                  snk_join_out* out, char* err, size_t errcap, const uint32_t* fgroup, const uint32_t* sfrag, uint64_t n_states) {
     memset(out, 0, sizeof *out);
     if (F == 0) return snk_join_emit(ctx, st, K, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, out, err, errcap);
     if (F >= (1ull << 31)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments at the join (%llu)", (unsigned long long)F);
     const uint64_t ne = 2 * F;
-    uint32_t* flink = flink_given;          // sharded runs: the links were decided on the owners (jlink_* kernels)
-    if (!flink) G_ALLOC(flink, uint32_t, ne);
-    if (flink_given) {
-    } else if (sfrag) {
+    uint32_t* flink;
+    G_ALLOC(flink, uint32_t, ne);
+    if (sfrag) {
         SNK_HIP_TRY(snk_launch(jmatch_direct_kernel, snk_blocks(ne, TB), TB, 0, st, hl_self, hl_nb, ne, sfrag, n_states, flink));
     } else {
         uint64_t tg = 1024;
@@ -1713,14 +1711,13 @@ int snk_spectrum(snk_ctx* ctx, hipStream_t st, const uint32_t* counts, uint64_t 
 }
 
 // ---- sharded runs: link matching on the owners
-int snk_dist_links_query(snk_ctx* ctx, hipStream_t st, bool fill, const snk_frag_out* fr, const unsigned long long* d_node_off, uint32_t world,
-                         unsigned long long my_end_base, unsigned long long* d_count_or_cursor, void* d_qbuf, char* err, size_t errcap) {
+int snk_dist_links_query(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const unsigned long long* d_node_off, uint32_t world,
+                         unsigned long long my_end_base, unsigned long long* d_cursor, void* d_qbuf, char* err, size_t errcap) {
     const uint64_t ne = 2 * fr->n_frags;
     if (ne == 0) return SNK_OK;
     if (ne >= (1ull << 32)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments on one rank");
     const size_t lds = (size_t)world * 12 + 16;
-    if (fill) SNK_HIP_TRY(snk_launch(jlink_query_kernel<true>, snk_blocks(snk_blocks(ne, RT_TILES), TB), TB, lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_count_or_cursor, (unsigned long long*)d_qbuf));
-    else SNK_HIP_TRY(snk_launch(jlink_query_kernel<false>, snk_blocks(snk_blocks(ne, RT_TILES), TB), TB, lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_count_or_cursor, (unsigned long long*)nullptr));
+    SNK_HIP_TRY(snk_launch(jlink_query_kernel<true>, snk_blocks(snk_blocks(ne, RT_TILES), TB), TB, lds, st, fr->hl_self, fr->hl_nb, ne, d_node_off, world, my_end_base, d_cursor, (unsigned long long*)d_qbuf));
     return SNK_OK;
 }
 int snk_dist_links_answer(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_queries, uint64_t nq, unsigned long long my_state_base,
@@ -1729,17 +1726,7 @@ int snk_dist_links_answer(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, 
                            2 * fr->n_frags, fr->sfrag, my_state_base, n_local_states, my_end_base, (uint32_t*)d_ans));
     return SNK_OK;
 }
-int snk_dist_links_apply(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_qbuf, const void* d_ans, uint64_t nq, uint32_t** flink_out,
-                         char* err, size_t errcap) {
-    const uint64_t ne = 2 * fr->n_frags;
-    uint32_t* flink;
-    G_ALLOC(flink, uint32_t, ne + 2);
-    SNK_HIP_TRY(hipMemsetAsync(flink, 0xFF, (ne + 2) * 4, st));
-    SNK_HIP_TRY(snk_launch(jlink_apply_kernel, snk_blocks(nq, TB), TB, 0, st, (const unsigned long long*)d_qbuf, (const uint32_t*)d_ans, nq, flink));
-    *flink_out = flink;
-    return SNK_OK;
-}
-// the same for queries / answers that sit in per-destination regions of `cap` items (one-pass routing, snk_shard_step.hip)
+// the answers applied: queries / answers sit in per-destination regions of `cap` items (one-pass routing, snk_shard_step.hip)
 int snk_dist_links_apply_regions(snk_ctx* ctx, hipStream_t st, const snk_frag_out* fr, const void* d_qbuf, const void* d_ans, uint32_t world, uint64_t cap,
                                  const unsigned long long* counts, uint32_t** flink_out, char* err, size_t errcap) {
     const uint64_t ne = 2 * fr->n_frags;
@@ -1865,12 +1852,11 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
     return SNK_OK;
 }
 
-int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, bool fill, const unsigned long long* d_frag_off, uint32_t world,
-                    unsigned long long* d_cnt_or_cur, void* d_out, char* err, size_t errcap) {
+int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, const unsigned long long* d_frag_off, uint32_t world,
+                    unsigned long long* d_cursor, void* d_out, char* err, size_t errcap) {
     if (!P->n_rec) return SNK_OK;
     const uint64_t nb = snk_blocks(P->n_rec, 256 * PR_TILES);
-    if (fill) SNK_HIP_TRY(snk_launch(prank_route_kernel<true>, nb, 256, world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cnt_or_cur, (uint4*)d_out));
-    else SNK_HIP_TRY(snk_launch(prank_route_kernel<false>, nb, 256, world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cnt_or_cur, (uint4*)nullptr));
+    SNK_HIP_TRY(snk_launch(prank_route_kernel<true>, nb, 256, world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cursor, (uint4*)d_out));
     return SNK_OK;
 }
 

@@ -1366,7 +1366,7 @@ int snk_local_graph(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_table* t
 }
 
 // ---- sharded stages (snk_dist.hip drives them; the host runs the exchanges in between)
-int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, unsigned long long* h_qcount, char* err, size_t errcap) {
+int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, char* err, size_t errcap) {
     B->force_dist = 1;
     const uint64_t n = B->tab->n;
     G_ALLOC(B->qcount, unsigned long long, B->world + 4);      // (+ the words the step appends to the exchange of these counts)
@@ -1375,7 +1375,6 @@ int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, unsigned lon
     G_ALLOC(B->rq_meta, uint16_t, 2 * n + 2);
     SNK_HIP_TRY(hipMemsetAsync(B->qcount, 0, (B->world + 1) * 8ull, st));
     SNK_HIP_TRY(hipMemsetAsync(B->rq_idx, 0xFF, (2 * n + 2) * 4, st));
-    if (h_qcount) for (uint32_t r = 0; r < B->world; ++r) h_qcount[r] = 0;
     if (n == 0) {
         G_ALLOC(B->ctx, uint8_t, 16);
         G_ALLOC(B->counts, uint32_t, 4);
@@ -1391,10 +1390,6 @@ int snk_bl_dist_plan(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, unsigned lon
     const uint64_t grid = snk_blocks(n, QSPAN);
     if (B->K == 48) SNK_HIP_TRY(snk_launch(bl_query_kernel<48, false>, grid, TB, lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcount, (unsigned long long*)nullptr));
     else SNK_HIP_TRY(snk_launch(bl_query_kernel<60, false>, grid, TB, lds, st, B->tab->keys, (const uint8_t*)B->premote, n, B->NB_total, B->NBl, B->world, ctx->mlen, B->qcount, (unsigned long long*)nullptr));
-    if (h_qcount) {
-        SNK_HIP_TRY(hipMemcpyAsync(h_qcount, B->qcount, B->world * 8ull, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(snk_sync(st));
-    }
     return SNK_OK;
 }
 int snk_bl_dist_fill(snk_ctx* ctx, hipStream_t st, snk_bl_state* B, const unsigned long long* d_qoff, void* d_qbuf, char* err, size_t errcap) {

@@ -122,15 +122,171 @@ static int graph_tail(snk_ctx* ctx, hipStream_t st, const snk_params* p, uint32_
     return SNK_OK;
 }
 
+namespace {
+
+// One snk_dev_count_graph call as its count attempts see it.  An attempt partitions and counts under one bucket plan; it returns SNK_OK
+// (part, tab, h_ninst are the call's), SNK_RETARGET (retarget_ratio: distinct k-mers per instance its first buckets showed -- plan
+// again), SNK_OVF_RETRY (ovf_want: the overflow list the same plan needs) or an error.
+struct count_call {
+    snk_ctx* ctx; hipStream_t st; const snk_dev_reads* in; const snk_params* p; snk_dev_result* out;
+    bool grouped, local_graph, fused;
+    const uint16_t* good_len;
+    snk_fused_trim ft;
+    uint32_t* status;
+    unsigned long long ub_inst, ub_live;      // instances, contributing reads (fused trim: their upper bounds)
+    phase_timer* tm;
+    char* err; size_t errcap;
+    // the attempt at hand
+    uint32_t NB;
+    bool first, want_pilot;                   // first: no attempt was given up before (its marks 2 and 3 are the call's)
+    uint64_t ovf_floor;                       // bucket-range passes: the overflow list a pass asked for (SNK_OVF_RETRY)
+    // what it leaves
+    snk_partition part; snk_table tab;
+    unsigned long long h_ninst;
+    double retarget_ratio;
+    uint64_t ovf_want;
+};
+
+// K5-K8 count + filter + gather (+ sort for the global graph stage) of one attempt's records
+snk_count_job count_job_of(const count_call& C, const void* records, const uint64_t* seg, uint32_t nseg, unsigned long long n_inst, snk_count_pilot* pilot) {
+    snk_count_job cj;
+    cj.K = C.p->K; cj.records = records; cj.seg_beg = seg; cj.seg_end = seg + C.NB; cj.seg_stride = 2 * C.NB; cj.nseg = nseg; cj.NB = C.NB;
+    cj.min_freq = C.p->min_freq; cj.bc_mode = (C.in->bc && !C.grouped) ? C.p->min_bc : 0u; cj.grouped = C.grouped ? 1u : 0u;
+    cj.n_inst_hint = n_inst; cj.status = C.status; cj.want_sort = !C.local_graph; cj.defer_compact = C.local_graph;
+    cj.pilot = C.want_pilot ? pilot : nullptr;
+    return cj;
+}
+
+#ifdef SNK_PROBES
+// measurement aid: SNK_OVERLAP_PROBE = 1: the partition kernel once more (into scratch) on a second stream NEXT TO the count
+// kernel; 2: the same launch alone (waited for before the count starts); +4: the second stream has high priority;
+// SNK_OVERLAP_PROBE_DBG = the relaunched kernel's dbg mode (1 no record stores, 2 no slot atomics, 3 scan only).
+// Streams and events are made per probed call and go with the object, whichever way the call ends.
+struct overlap_probe {
+    uint32_t mode = 0;
+    hipStream_t s2 = nullptr, s2hi = nullptr, sp2 = nullptr;
+    hipEvent_t pe[3] = {nullptr, nullptr, nullptr};
+    ~overlap_probe() {
+        for (auto& e : pe) if (e) (void)hipEventDestroy(e);
+        if (s2) (void)hipStreamDestroy(s2);
+        if (s2hi) (void)hipStreamDestroy(s2hi);
+    }
+    int start(snk_ctx* ctx, hipStream_t st, char* err, size_t errcap) {
+        mode = snk_opt_u32(ctx, SNK_OPT_overlap_probe);
+        if (!mode) return SNK_OK;
+        { SNK_HIP_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking)); int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); SNK_HIP_TRY(hipStreamCreateWithPriority(&s2hi, hipStreamNonBlocking, hi)); }
+        sp2 = (mode & 4u) ? s2hi : s2;
+        for (auto& e : pe) SNK_HIP_TRY(hipEventCreate(&e));
+        SNK_HIP_TRY(hipEventRecord(pe[0], st));
+        SNK_HIP_TRY(hipStreamWaitEvent(sp2, pe[0], 0));
+        SNK_HIP_TRY(hipEventRecord(pe[1], sp2));
+        int rc = snk_probe_relaunch_msp(ctx, sp2, snk_opt_u32(ctx, SNK_OPT_overlap_probe_dbg), err, errcap);
+        if (rc) return rc;
+        SNK_HIP_TRY(hipEventRecord(pe[2], sp2));
+        if ((mode & 3u) == 2u) SNK_HIP_TRY(hipStreamSynchronize(sp2));
+        return SNK_OK;
+    }
+    int report(const snk_partition& part, const snk_table& tab, char* err, size_t errcap) {
+        if (!mode) return SNK_OK;
+        SNK_HIP_TRY(hipStreamSynchronize(sp2));
+        float pm = 0.f;
+        (void)hipEventElapsedTime(&pm, pe[1], pe[2]);
+        fprintf(stderr, "[snk overlap probe] mode %u: partition kernel (first launch, alone) %.2f ms; relaunched %s %.2f ms; count kernel %.2f ms; count stage %.2f ms\n", mode,
+                part.kernel_ms, (mode & 3u) == 2u ? "alone" : "next to the count kernel", pm, tab.count_kernel_ms, tab.count_ms);
+        return SNK_OK;
+    }
+};
+#endif
+
+// ---- a job whose slots would not fit: bucket-range passes over one slot array (snk_stages.h); the count stage's range hook
+//      partitions range r right before range r is counted
+int count_in_passes(count_call& C, uint32_t n_passes) {
+    snk_ctx* ctx = C.ctx;
+    snk_dev_result* out = C.out;
+    const uint32_t NB = C.NB;
+    int rc;
+    snk_partition_passes PS;
+    if ((rc = snk_partition_passes_open(ctx, C.st, C.p->K, C.in, C.good_len, C.fused ? &C.ft : nullptr, NB, n_passes, C.ub_inst, C.ub_live, C.grouped, &PS, C.err, C.errcap, C.ovf_floor))) return rc;
+    if (C.first) C.tm->mark();  // 3 (the partition's time is inside the count stage's here)
+    std::vector<snk_hot> pass_hots;
+    PS.hots = &pass_hots;
+    snk_count_ranges rgs{n_passes, PS.bounds, snk_partition_passes_run, &PS, true, &pass_hots};
+    rgs.finished = [](void* u) {
+        snk_partition_passes* S = static_cast<snk_partition_passes*>(u);
+        snk_ctx_release_block(S->ctx, S->records); S->records = nullptr;
+        snk_ctx_release_block(S->ctx, S->ovf_bucket); S->ovf_bucket = nullptr;
+    };
+    // (the first range's first buckets are the pilot here too: data whose tables run full -- error-rich reads -- are partitioned again into
+    // smaller buckets and get the count kernel they want, as in the one-pass path below)
+    snk_count_pilot pilot{0.0, nullptr, nullptr};
+    snk_count_job cj = count_job_of(C, PS.records, PS.seg, 2u, C.ub_inst, &pilot);
+    cj.ranges = &rgs;
+    rc = snk_stage_count_table(ctx, C.st, cj, &C.tab, C.err, C.errcap);
+    if (rc == SNK_OVF_RETRY) C.ovf_want = PS.ovf_want;      // a pass's overflow list was too short for this data (snk_stages.h)
+    if (rc == SNK_RETARGET) {
+        const unsigned long long inst_now = PS.h_plan[0] ? PS.h_plan[0] : C.ub_inst;
+        C.retarget_ratio = inst_now ? pilot.per_bucket * (double)NB / (double)inst_now : 0.0;
+    }
+    if (rc) return rc;
+    C.h_ninst = PS.h_plan[0];
+    snk_partition& part = C.part;
+    memset(&part, 0, sizeof part);
+    part.NB = NB; part.cap = PS.cap; part.nseg = 2; part.n_overflow = (uint32_t)std::min<uint64_t>(PS.n_overflow, 0xFFFFFFFFull); part.n_supermers = PS.n_supermers;
+    part.records = PS.records; part.cursor = PS.cursor; part.seg = PS.seg; part.kernel_ms = PS.kernel_ms;
+    out->n_instances = C.h_ninst;
+    out->n_supermers = part.n_supermers;
+    out->n_overflow = part.n_overflow;
+    out->n_hot_buckets = PS.n_hot;
+    return SNK_OK;
+}
+
+// ---- K3/K4 minimiser partition in ONE pass: exact k-mer instance count -> expected supermers -> fixed bucket capacity
+// (fused trim: the count is not known yet; every base of every read is the bound, a few per cent above what the trim leaves)
+int count_in_one_pass(count_call& C) {
+    snk_ctx* ctx = C.ctx;
+    snk_dev_result* out = C.out;
+    snk_partition& part = C.part;
+    unsigned long long h_plan[2] = {C.ub_inst, C.ub_live};
+    int rc = snk_stage_partition(ctx, C.st, C.p->K, C.in, C.good_len, C.NB, h_plan[0], h_plan[1], C.grouped, C.status, &part, C.err, C.errcap, nullptr, C.fused ? h_plan : nullptr,
+                                 C.fused ? &C.ft : nullptr, true);
+    if (rc) return rc;
+    C.h_ninst = h_plan[0];               // (fused trim: now the exact count)
+    out->n_instances = C.h_ninst;
+    out->n_supermers = part.n_supermers;
+    out->n_overflow = part.n_overflow;
+    if (C.first) C.tm->mark();  // 3
+
+    // ---- hot minimiser buckets (repeat families, homopolymer runs): re-partitioned by k-mer hash (snk_hot.hip)
+    snk_hot hot;
+    if ((rc = snk_stage_hot(ctx, C.st, C.p->K, C.grouped, &part, &hot, C.err, C.errcap))) return rc;
+    out->n_hot_buckets = hot.n_hot;
+    snk_count_pilot pilot{0.0, nullptr, nullptr};
+    snk_count_job cj = count_job_of(C, part.records, part.seg, part.nseg, C.h_ninst, &pilot);
+    cj.gidx = part.gidx; cj.hot = &hot;
+#ifdef SNK_PROBES
+    overlap_probe probe;
+    if ((rc = probe.start(ctx, C.st, C.err, C.errcap))) return rc;
+#endif
+    rc = snk_stage_count_table(ctx, C.st, cj, &C.tab, C.err, C.errcap);
+#ifdef SNK_PROBES
+    { const int rp = probe.report(part, C.tab, C.err, C.errcap); if (rp) return rp; }
+#endif
+    if (rc == SNK_RETARGET) C.retarget_ratio = C.h_ninst ? pilot.per_bucket * (double)C.NB / (double)C.h_ninst : 0.0;
+    return rc;
+}
+
+}  // namespace
+
 extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const snk_params* p, snk_dev_result* out,
                                    void* stream, char* err, size_t errcap) {
     if (!ctx || !in || !p || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_count_graph: NULL argument");
-    if (p->K != 48 && p->K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", p->K);
-    if (p->min_bc > 8) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "min_bc=%u: the device barcode rule tells up to eight distinct barcodes apart (min_bc <= 8)", p->min_bc);
+    int rc;
+    if ((rc = snk_intake_check_params(p, err, errcap))) return rc;
     snk_set_mlen(ctx, p);
-    if (in->n_reads && (!in->rows || in->row_words * 16 < in->read_len || in->read_len > 256))
-        return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_count_graph: bad rows/read_len (read_len <= 256)");
-    if (in->n_reads && !in->good_len && !in->quals) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_count_graph: need quals or good_len");
+    switch (snk_intake_reads_fault(in)) {
+        case 1: return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_count_graph: bad rows/read_len (read_len <= 256)");
+        case 2: return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_count_graph: need quals or good_len");
+    }
     const bool grouped = (p->flags & SNK_F_GROUPED) != 0;
     if (grouped) {
         if (p->K != 48) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "SNK_F_GROUPED: the group id rides in the 32 key bits that are free at K=48 only");
@@ -150,45 +306,25 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     phase_timer tm(st);
     tm.mark();  // 0
 
-    // ---- K1 trim: inside the partition kernel when the quality rows allow it (its loads ride under the slot reservations),
-    // else its own streaming kernel
-    const uint16_t* good_len = (const uint16_t*)in->good_len;
-    const bool fused = n_reads && snk_fused_trim_ok(ctx, in);
-    snk_fused_trim ft;
-    if (!good_len && n_reads) {
-        void* gl = nullptr;
-        int rc = snk_ctx_alloc(ctx, n_reads * 2 + 2, &gl, err, errcap);
-        if (rc) return rc;
-        if (fused) { ft.quals = in->quals; ft.qstride = in->qstride; ft.lens = in->lens; ft.min_qual = p->min_qual; ft.good_out = (uint16_t*)gl; }
-        else {
-            rc = snk_dev_trim(ctx, in->quals, in->qstride, in->lens, in->read_len, n_reads, K, p->min_qual, gl, st);
-            if (rc) return snk_fail(rc, err, errcap, "%s", snk_last_error());
-        }
-        good_len = (const uint16_t*)gl;
-    }
-    out->good_len = good_len;
+    count_call C;
+    C.ctx = ctx; C.st = st; C.in = in; C.p = p; C.out = out; C.grouped = grouped; C.tm = &tm; C.err = err; C.errcap = errcap;
+    C.local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32(ctx, SNK_OPT_global_graph);
+    C.h_ninst = 0; C.retarget_ratio = 0.0; C.ovf_floor = C.ovf_want = 0;
+    // ---- K1 trim: inside the partition kernel when the quality rows allow it, else its own streaming kernel
+    if ((rc = snk_intake_trim(ctx, st, in, p, &C.good_len, &C.ft, &C.fused, err, errcap))) return rc;
+    out->good_len = (n_reads || in->good_len) ? C.good_len : nullptr;      // (no reads: no array of the context's is handed out)
     tm.mark();  // 1
 
-    // ---- K3/K4 minimiser partition in ONE pass: exact k-mer instance count -> expected supermers -> fixed bucket capacity
-    // (fused trim: the count is not known yet; every base of every read is the bound, a few per cent above what the trim leaves)
-    uint32_t* status = nullptr;
-    {
-        void* q;
-        int rc;
-        if ((rc = snk_ctx_alloc(ctx, 64, &q, err, errcap))) return rc; status = (uint32_t*)q;
-    }
-    SNK_HIP_TRY(hipMemsetAsync(status, 0, 64, st));
+    if ((rc = snk_intake_status(ctx, st, &C.status, err, errcap))) return rc;
     unsigned long long h_plan[2] = {0, 0};
-    int rc = SNK_OK;
-    if (fused) {
+    if (C.fused) {
         const unsigned long long kpr = in->read_len >= K ? in->read_len - K + 1 : 0;
         h_plan[0] = n_reads * kpr;
         h_plan[1] = n_reads;
-    } else
-        rc = snk_stage_partition_plan(ctx, st, K, good_len, n_reads, h_plan, err, errcap);
-    if (rc) return rc;
-    unsigned long long h_ninst = h_plan[0];
-    out->n_instances = h_ninst;
+    } else if ((rc = snk_stage_partition_plan(ctx, st, K, C.good_len, n_reads, h_plan, err, errcap)))
+        return rc;
+    C.ub_inst = h_plan[0]; C.ub_live = h_plan[1];
+    out->n_instances = h_plan[0];
     // ---- is this the data set the context's sizing history was made on?  (one 8-byte read-back: ~40 us)
     bool same_data = true;
     if (n_reads && p->n_buckets == 0 && snk_opt_u32(ctx, SNK_OPT_input_fp)) {
@@ -217,141 +353,36 @@ extern "C" int snk_dev_count_graph(snk_ctx* ctx, const snk_dev_reads* in, const 
     const bool adaptive = p->n_buckets == 0 && !target_forced && !grouped && snk_opt_u32(ctx, SNK_OPT_adaptive_buckets) != 0;      // (the per-barcode default is tuned at ratio ~1)
     snk_plan_in pin;
     pin.K = K; pin.grouped = grouped; pin.has_bc = in->bc != nullptr; pin.min_freq = p->min_freq; pin.min_bc = p->min_bc;
-    pin.n_buckets = p->n_buckets; pin.inst_ub = h_plan[0]; pin.may_adapt = adaptive; pin.opts = &ctx->opts;
+    pin.n_buckets = p->n_buckets; pin.inst_ub = C.ub_inst; pin.may_adapt = adaptive; pin.opts = &ctx->opts;
     pin.retain = (my_history && ctx->sizing.retain > 0.0) ? ctx->sizing.retain : 0.0;
     pin.slots = snk_count_slots(K); pin.plain_limit = snk_count_limit(K, 0u, 0u); pin.screen_limit = snk_count_screen_limit();
     pin.nb_max = 1ull << 25; pin.use_retain = true;
-    uint32_t NB = 0;
-    snk_partition part;
-    snk_table tab;
-    void* records = nullptr;
-    const bool local_graph = !(p->flags & SNK_F_GLOBAL_GRAPH) && !snk_opt_u32(ctx, SNK_OPT_global_graph);
     const uint64_t mark = ctx->alloc_serial;
-    const unsigned long long ub_inst = h_plan[0], ub_live = h_plan[1];
-    uint64_t ovf_floor = 0;          // bucket-range passes: the overflow list a pass asked for (SNK_OVF_RETRY)
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int pass = 0; pass < 2;) {      // (plans: the second one follows SNK_RETARGET)
         pin.ratio = ratio;
         const snk_plan_out plan = snk_bucket_plan(pin);
-        NB = plan.NB;
+        const uint32_t NB = plan.NB;
         ctx->count_tight = plan.tight;
         ctx->count_screen = plan.screen;
         if (plan.screen && ratio > 0.0) ctx->sizing.screen_ratio = ratio;      // (what the screened call reports is the table's view: the decision keeps the ratio it was made on)
         ctx->last_count_limit = plan.count_limit;
         out->n_buckets = NB;
-        if (pass == 0 && !ovf_floor) tm.mark();  // 2
-        h_plan[0] = ub_inst; h_plan[1] = ub_live;
-        // ---- a job whose slots would not fit: bucket-range passes over one slot array (snk_stages.h); the count stage's range hook
-        //      partitions range r right before range r is counted
-        const uint32_t n_passes = (NB >= 2 && !snk_opt_u32(ctx, SNK_OPT_msp_dense)) ? std::min<uint32_t>(snk_partition_passes_needed(ctx, K, NB, ub_inst, ub_live, grouped), NB) : 1u;
+        C.NB = NB;
+        C.first = pass == 0 && !C.ovf_floor;
+        C.want_pilot = adaptive && pass == 0 && !have_hint;
+        if (C.first) tm.mark();  // 2
+        const uint32_t n_passes = (NB >= 2 && !snk_opt_u32(ctx, SNK_OPT_msp_dense)) ? std::min<uint32_t>(snk_partition_passes_needed(ctx, K, NB, C.ub_inst, C.ub_live, grouped), NB) : 1u;
         ctx->last_partition_passes = n_passes;
-        if (n_passes > 1) {
-            snk_partition_passes PS;
-            if ((rc = snk_partition_passes_open(ctx, st, K, in, good_len, fused ? &ft : nullptr, NB, n_passes, ub_inst, ub_live, grouped, &PS, err, errcap, ovf_floor))) return rc;
-            if (pass == 0 && !ovf_floor) tm.mark();  // 3 (the partition's time is inside the count stage's here)
-            std::vector<snk_hot> pass_hots;
-            PS.hots = &pass_hots;
-            snk_count_ranges rgs{n_passes, PS.bounds, snk_partition_passes_run, &PS, true, &pass_hots};
-            rgs.finished = [](void* u) {
-                snk_partition_passes* S = static_cast<snk_partition_passes*>(u);
-                snk_ctx_release_block(S->ctx, S->records); S->records = nullptr;
-                snk_ctx_release_block(S->ctx, S->ovf_bucket); S->ovf_bucket = nullptr;
-            };
-            // (the first range's first buckets are the pilot here too: data whose tables run full -- error-rich reads -- are partitioned again into
-            // smaller buckets and get the count kernel they want, as in the one-pass path below)
-            snk_count_pilot pilot_p{0.0, nullptr, nullptr};
-            const bool want_pilot_p = adaptive && pass == 0 && !have_hint;
-            rc = snk_stage_count_table(ctx, st, K, PS.records, PS.seg, PS.seg + NB, 2 * NB, 2u, NB, p->min_freq, (in->bc && !grouped) ? p->min_bc : 0u, grouped ? 1u : 0u,
-                                       ub_inst, status, !local_graph, &tab, err, errcap, &rgs, want_pilot_p ? &pilot_p : nullptr, nullptr, local_graph, nullptr);
-            if (rc == SNK_OVF_RETRY) {
-                // a pass's overflow list was too short for this data (snk_stages.h): everything since the mark goes back, the passes once more
-                // with a list that holds what the pass asked for -- this plan again, so the loop's counter stays
-                ovf_floor = PS.ovf_want;
-                snk_ctx_release_since(ctx, mark, nullptr, 0);
-                SNK_HIP_TRY(hipMemsetAsync(status, 0, 64, st));
-                --pass;
-                continue;
-            }
-            if (rc == SNK_RETARGET) {
-                const unsigned long long inst_now = PS.h_plan[0] ? PS.h_plan[0] : ub_inst;
-                snk_ctx_release_since(ctx, mark, nullptr, 0);
-                SNK_HIP_TRY(hipMemsetAsync(status, 0, 64, st));
-                ratio = inst_now ? pilot_p.per_bucket * (double)NB / (double)inst_now : 0.0;
-                out->repartitioned = 1;
-                continue;
-            }
-            if (rc) return rc;
-            h_ninst = PS.h_plan[0];
-            memset(&part, 0, sizeof part);
-            part.NB = NB; part.cap = PS.cap; part.nseg = 2; part.n_overflow = (uint32_t)std::min<uint64_t>(PS.n_overflow, 0xFFFFFFFFull); part.n_supermers = PS.n_supermers;
-            part.records = PS.records; part.cursor = PS.cursor; part.seg = PS.seg; part.kernel_ms = PS.kernel_ms;
-            out->n_instances = h_ninst;
-            out->n_supermers = part.n_supermers;
-            out->n_overflow = part.n_overflow;
-            out->n_hot_buckets = PS.n_hot;
-            break;
-        }
-        rc = snk_stage_partition(ctx, st, K, in, good_len, NB, h_plan[0], h_plan[1], grouped, status, &part, err, errcap, nullptr, fused ? h_plan : nullptr,
-                                 fused ? &ft : nullptr, true);
-        if (rc) return rc;
-        h_ninst = h_plan[0];               // (fused trim: now the exact count)
-        out->n_instances = h_ninst;
-        records = part.records;
-        out->n_supermers = part.n_supermers;
-        out->n_overflow = part.n_overflow;
-        if (pass == 0) tm.mark();  // 3
-
-        // ---- hot minimiser buckets (repeat families, homopolymer runs): re-partitioned by k-mer hash (snk_hot.hip)
-        snk_hot hot;
-        if ((rc = snk_stage_hot(ctx, st, K, grouped, &part, &hot, err, errcap))) return rc;
-        out->n_hot_buckets = hot.n_hot;
-        // ---- K5-K8 count + filter + gather (+ sort for the global graph stage)
-        snk_count_pilot pilot{0.0, nullptr, nullptr};
-        const bool want_pilot = adaptive && pass == 0 && !have_hint;
-#ifdef SNK_PROBES
-        // measurement aid: SNK_OVERLAP_PROBE = 1: the partition kernel once more (into scratch) on a second stream NEXT TO the count
-        // kernel; 2: the same launch alone (waited for before the count starts); +4: the second stream has high priority;
-        // SNK_OVERLAP_PROBE_DBG = the relaunched kernel's dbg mode (1 no record stores, 2 no slot atomics, 3 scan only)
-        const uint32_t oprobe = snk_opt_u32(ctx, SNK_OPT_overlap_probe);
-        hipStream_t s2 = nullptr, s2hi = nullptr;      // (a measurement aid of tuning builds: created per probed call, destroyed below)
-        hipStream_t sp2 = nullptr;
-        hipEvent_t pe[3] = {nullptr, nullptr, nullptr};
-        if (oprobe) {
-            { SNK_HIP_TRY(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking)); int lo = 0, hi = 0; (void)hipDeviceGetStreamPriorityRange(&lo, &hi); SNK_HIP_TRY(hipStreamCreateWithPriority(&s2hi, hipStreamNonBlocking, hi)); }
-            sp2 = (oprobe & 4u) ? s2hi : s2;
-            for (auto& e : pe) SNK_HIP_TRY(hipEventCreate(&e));
-            SNK_HIP_TRY(hipEventRecord(pe[0], st));
-            SNK_HIP_TRY(hipStreamWaitEvent(sp2, pe[0], 0));
-            SNK_HIP_TRY(hipEventRecord(pe[1], sp2));
-            if ((rc = snk_probe_relaunch_msp(ctx, sp2, snk_opt_u32(ctx, SNK_OPT_overlap_probe_dbg), err, errcap))) return rc;
-            SNK_HIP_TRY(hipEventRecord(pe[2], sp2));
-            if ((oprobe & 3u) == 2u) SNK_HIP_TRY(hipStreamSynchronize(sp2));
-        }
-#endif
-        rc = snk_stage_count_table(ctx, st, K, records, part.seg, part.seg + NB, 2 * NB, part.nseg, NB, p->min_freq, (in->bc && !grouped) ? p->min_bc : 0u, grouped ? 1u : 0u,
-                                   h_ninst, status, !local_graph, &tab, err, errcap, nullptr, want_pilot ? &pilot : nullptr, part.gidx, local_graph, &hot);
-#ifdef SNK_PROBES
-        if (oprobe) {
-            SNK_HIP_TRY(hipStreamSynchronize(sp2));
-            float pm = 0.f;
-            (void)hipEventElapsedTime(&pm, pe[1], pe[2]);
-            fprintf(stderr, "[snk overlap probe] mode %u: partition kernel (first launch, alone) %.2f ms; relaunched %s %.2f ms; count kernel %.2f ms; count stage %.2f ms\n", oprobe,
-                    part.kernel_ms, (oprobe & 3u) == 2u ? "alone" : "next to the count kernel", pm, tab.count_kernel_ms, tab.count_ms);
-            for (auto& e : pe) (void)hipEventDestroy(e);
-            (void)hipStreamDestroy(s2); (void)hipStreamDestroy(s2hi);
-        }
-#endif
-        if (rc == SNK_RETARGET) {
-            // everything since the partition goes back to the arena; the good lengths and the status words stay
-            snk_ctx_release_since(ctx, mark, nullptr, 0);
-            SNK_HIP_TRY(hipMemsetAsync(status, 0, 64, st));
-            ratio = h_ninst ? pilot.per_bucket * (double)NB / (double)h_ninst : 0.0;
-            out->repartitioned = 1;
-            continue;
-        }
-        if (rc) return rc;
-        break;
+        rc = n_passes > 1 ? count_in_passes(C, n_passes) : count_in_one_pass(C);
+        if (rc == SNK_OK) break;
+        if (rc != SNK_RETARGET && rc != SNK_OVF_RETRY) return rc;
+        // the attempt is given up: everything since the mark goes back to the arena (the good lengths and the status words stay)
+        snk_ctx_release_since(ctx, mark, nullptr, 0);
+        SNK_HIP_TRY(snk_intake_status_clear(C.status, st));
+        if (rc == SNK_RETARGET) { ratio = C.retarget_ratio; out->repartitioned = 1; ++pass; }      // smaller buckets: a new plan
+        else C.ovf_floor = C.ovf_want;                                                           // this plan again, with a list that holds what the pass asked for
     }
-    return graph_tail(ctx, st, p, K, grouped, local_graph, n_reads, h_ninst, tab, part, out, tm, err, errcap);
+    return graph_tail(ctx, st, p, K, grouped, C.local_graph, n_reads, C.h_ninst, C.tab, C.part, out, tm, err, errcap);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -384,8 +415,8 @@ void stream_job_invalidate(void* q) {
 
 extern "C" int snk_dev_stream_begin(snk_ctx* ctx, const snk_params* p, uint32_t read_len, uint64_t total_reads_ub, int has_bc, void* stream, char* err, size_t errcap) {
     if (!ctx || !p) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_stream_begin: NULL argument");
-    if (p->K != 48 && p->K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", p->K);
-    if (p->min_bc > 8) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "min_bc=%u: the device barcode rule tells up to eight distinct barcodes apart (min_bc <= 8)", p->min_bc);
+    int rc;
+    if ((rc = snk_intake_check_params(p, err, errcap))) return rc;
     snk_set_mlen(ctx, p);
     ctx->count_tight = 0;          // (a streamed job cannot partition again: the default kernel and its bucket rule)
     ctx->count_screen = 0;
@@ -416,10 +447,8 @@ extern "C" int snk_dev_stream_begin(snk_ctx* ctx, const snk_params* p, uint32_t 
     pin.nb_max = 1ull << 23; pin.may_book = false; pin.fill_unclamped = true;
     const uint32_t NB = snk_bucket_plan(pin).NB;
     j->NB = NB;
+    if ((rc = snk_intake_status(ctx, st, &j->status, err, errcap))) return rc;
     void* q;
-    int rc;
-    if ((rc = snk_ctx_alloc(ctx, 64, &q, err, errcap))) return rc; j->status = (uint32_t*)q;
-    SNK_HIP_TRY(hipMemsetAsync(j->status, 0, 64, st));
     if ((rc = snk_ctx_alloc(ctx, total_reads_ub * 2 + 64, &q, err, errcap))) return rc; j->good_len = (uint16_t*)q;
     if ((rc = snk_partition_open(ctx, st, K, NB, ub_inst, total_reads_ub, false, j->status, &j->J, err, errcap))) return rc;
     j->open = true;
@@ -432,37 +461,19 @@ extern "C" int snk_dev_stream_append(snk_ctx* ctx, const snk_dev_reads* slab, vo
     if (!j || !j->open) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_stream_append: no open job (snk_dev_stream_begin)");
     snk_set_mlen(ctx, &j->p);
     if (slab->n_reads == 0) return SNK_OK;
-    if (!slab->rows || slab->read_len != j->read_len || slab->row_words * 16 < slab->read_len) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_stream_append: bad rows / read_len (the job's is %u)", j->read_len);
-    if (!slab->good_len && !slab->quals) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_stream_append: need quals or good_len");
-    if ((slab->bc != nullptr) != j->has_bc) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_stream_append: every slab carries barcodes, or none does");
-    if (j->J.n_reads + slab->n_reads > j->total_ub)
-        return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_stream_append: more reads than the job's upper bound (%llu + %llu > %llu)", (unsigned long long)j->J.n_reads,
-                        (unsigned long long)slab->n_reads, (unsigned long long)j->total_ub);
+    int rc = snk_intake_check_slab(slab, j->read_len, j->has_bc, j->J.n_reads, j->total_ub, "snk_dev_stream_append", "job's", "job's", err, errcap);
+    if (rc) return rc;
     SNK_HIP_TRY(snk_enter(ctx));
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     ctx->cur_stream = st;
     snk_dev_reads r = *slab;
     if (r.read_index_base == 0) r.read_index_base = j->J.n_reads;           // reads are numbered in arrival order unless the caller numbers them
-    uint16_t* gl = j->good_len + j->J.n_reads;
     hipEvent_t e0, e1;
     SNK_HIP_TRY(hipEventCreate(&e0));
     SNK_HIP_TRY(hipEventCreate(&e1));
     j->ev.emplace_back(e0, e1);
     SNK_HIP_TRY(hipEventRecord(e0, st));
-    int rc;
-    if (slab->good_len) {
-        SNK_HIP_TRY(hipMemcpyAsync(gl, slab->good_len, slab->n_reads * 2, hipMemcpyDeviceToDevice, st));
-        rc = snk_partition_add(ctx, st, &j->J, &r, gl, nullptr, err, errcap);
-    } else if (snk_fused_trim_ok(ctx, &r)) {
-        snk_fused_trim ft;
-        ft.quals = r.quals; ft.qstride = r.qstride; ft.lens = r.lens; ft.min_qual = j->p.min_qual; ft.good_out = gl;
-        rc = snk_partition_add(ctx, st, &j->J, &r, gl, &ft, err, errcap);
-    } else {
-        rc = snk_dev_trim(ctx, r.quals, r.qstride, r.lens, r.read_len, r.n_reads, j->K, j->p.min_qual, gl, st);
-        if (rc) return snk_fail(rc, err, errcap, "%s", snk_last_error());
-        rc = snk_partition_add(ctx, st, &j->J, &r, gl, nullptr, err, errcap);
-    }
-    if (rc) return rc;
+    if ((rc = snk_intake_add_slab(ctx, st, &j->J, &r, j->p.min_qual, j->good_len + j->J.n_reads, err, errcap))) return rc;
     SNK_HIP_TRY(hipEventRecord(e1, st));
     return SNK_OK;
 }
@@ -503,9 +514,11 @@ extern "C" int snk_dev_stream_finish(snk_ctx* ctx, snk_dev_result* out, void* st
     if ((rc = snk_stage_hot(ctx, st, K, false, &part, &hot, err, errcap))) return rc;
     out->n_hot_buckets = hot.n_hot;
     snk_table tab;
-    rc = snk_stage_count_table(ctx, st, K, part.records, part.seg, part.seg + j->NB, 2 * j->NB, part.nseg, j->NB, p->min_freq, j->has_bc ? p->min_bc : 0u, 0u, h_ninst, j->status,
-                               !local_graph, &tab, err, errcap, nullptr, nullptr, nullptr, local_graph, &hot);
-    if (rc) return rc;
+    snk_count_job cj;
+    cj.K = K; cj.records = part.records; cj.seg_beg = part.seg; cj.seg_end = part.seg + j->NB; cj.seg_stride = 2 * j->NB; cj.nseg = part.nseg; cj.NB = j->NB;
+    cj.min_freq = p->min_freq; cj.bc_mode = j->has_bc ? p->min_bc : 0u; cj.n_inst_hint = h_ninst; cj.status = j->status;
+    cj.want_sort = !local_graph; cj.defer_compact = local_graph; cj.hot = &hot;
+    if ((rc = snk_stage_count_table(ctx, st, cj, &tab, err, errcap))) return rc;
     // (the ratio is keyed by the job's read bound: the next job of the same size starts from it)
     rc = graph_tail(ctx, st, p, K, false, local_graph, j->total_ub, h_ninst, tab, part, out, tm, err, errcap);
     if (rc) return rc;

@@ -22,8 +22,6 @@
 #include "snk_common.h"
 #include "snk_shard.h"
 
-// the stage entry points of snk_dist.hip (declared in include/snk.h)
-
 namespace {
 
 typedef unsigned long long ull;
@@ -273,6 +271,8 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
         tm.mark();   // 1
         inst_hint = total_reads ? total_reads * kpr / W : (inst_ub ? inst_ub / W : n_inst);
         exch_records = 0;
+        snk_count_job cj;          // (segment tables, ranges, pilot and hot buckets: filled where they are made below)
+        cj.K = K; cj.min_freq = p->min_freq; cj.bc_mode = has_bc ? p->min_bc : 0u; cj.n_inst_hint = inst_hint; cj.status = S->status;
         if (W == 1) {
             // one rank owns every bucket: the slots are counted where they are (exactly the one-GPU path)
             tm.mark();   // 2
@@ -282,15 +282,16 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
                 uint64_t* T;
                 ALLOC(T, uint64_t, 2ull * fake * NB_total + 2);
                 SNK_HIP_TRY(snk_launch(fake_seg_kernel, snk_blocks(NB_total, 256), 256, 0, st, part.cursor, NB_total, part.cap, fake, T));
-                TRY(snk_stage_count_table(ctx, st, K, part.records, T, T + (uint64_t)fake * NB_total, NB_total, fake, NB_total, p->min_freq,
-                                          has_bc ? p->min_bc : 0u, 0u, inst_hint, S->status, false, &S->tab, err, errcap));
+                cj.records = part.records; cj.seg_beg = T; cj.seg_end = T + (uint64_t)fake * NB_total; cj.seg_stride = NB_total; cj.nseg = fake; cj.NB = NB_total;
+                TRY(snk_stage_count_table(ctx, st, cj, &S->tab, err, errcap));
             } else {
             // (hot minimiser buckets -- repeat families -- are re-partitioned by k-mer hash as on the one-GPU path)
             snk_hot hot;
             TRY(snk_stage_hot(ctx, st, K, false, &S->part, &hot, err, errcap));
             n_hot_buckets = hot.n_hot;
-            TRY(snk_stage_count_table(ctx, st, K, part.records, part.seg, part.seg + NB_total, 2 * NB_total, part.nseg, NB_total, p->min_freq,
-                                      has_bc ? p->min_bc : 0u, 0u, inst_hint, S->status, false, &S->tab, err, errcap, nullptr, with_pilot ? &pilot : nullptr, nullptr, true, &hot));
+            cj.records = part.records; cj.seg_beg = part.seg; cj.seg_end = part.seg + NB_total; cj.seg_stride = 2 * NB_total; cj.nseg = part.nseg; cj.NB = NB_total;
+            cj.pilot = with_pilot ? &pilot : nullptr; cj.defer_compact = true; cj.hot = &hot;
+            TRY(snk_stage_count_table(ctx, st, cj, &S->tab, err, errcap));
             }
             snk_ctx_release_block(ctx, part.records);
         } else {
@@ -371,8 +372,10 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             snk_hot hot;
             TRY(snk_stage_hot_plan(ctx, st, K, false, T, T + (uint64_t)nseg * NBl, NBl, nseg, NBl, part.cap, &hot, err, errcap));
             hot.before_expand = all_ranges_ready; hot.user = &rw; hot.src_records = recvb;
-            const int rcc = snk_stage_count_table(ctx, st, K, recvb, T, T + (uint64_t)nseg * NBl, NBl, nseg, NBl, p->min_freq, has_bc ? p->min_bc : 0u, 0u, inst_hint,
-                                                  S->status, false, &S->tab, err, errcap, &rg, with_pilot ? &pilot : nullptr, nullptr, true, &hot);      // (the region compaction rides in the prune, as on the one-GPU path)
+            cj.records = recvb; cj.seg_beg = T; cj.seg_end = T + (uint64_t)nseg * NBl; cj.seg_stride = NBl; cj.nseg = nseg; cj.NB = NBl;
+            cj.ranges = &rg; cj.pilot = with_pilot ? &pilot : nullptr; cj.hot = &hot;
+            cj.defer_compact = true;      // (the region compaction rides in the prune, as on the one-GPU path)
+            const int rcc = snk_stage_count_table(ctx, st, cj, &S->tab, err, errcap);
             snk_stage_hot_drop(&hot);
             if (rcc) return rcc;
             n_hot_buckets = hot.n_hot;
@@ -414,7 +417,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     const uint64_t n_kmers = S->tab.n;
 
     // ---- bucket-local prune with membership queries for neighbours owned by other ranks
-    TRY(snk_shard_prune_plan(ctx, nullptr, st, err, errcap));
+    TRY(snk_shard_prune_plan(ctx, *S, st, err, errcap));
     // one read-back: every rank's query counts (still on the device: bl.qcount) and retained k-mers
     ull* d_cnt = S->bl.qcount;
     // ... and, riding along, what the tables of my count kernel held (distinct k-mers) over how many instances: the job-wide ratio
@@ -449,11 +452,11 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     ALLOC(qin, uint8_t, nq_in * 24 + 32);
     ALLOC(ans, uint8_t, nq_in * 4 + 32);
     ALLOC(ans_back, uint8_t, nq * 4 + 32);
-    TRY(snk_shard_prune_fill(ctx, d_qoff, qbuf, st, err, errcap));
+    TRY(snk_bl_dist_fill(ctx, st, &S->bl, d_qoff, qbuf, err, errcap));
     TRY(a2a_items(X, qbuf, q_send, qin, q_recv, 24));
-    TRY(snk_shard_prune_answer(ctx, qin, nq_in, ans, st, err, errcap));
+    TRY(snk_dist_answer(ctx, st, &S->g, qin, nq_in, ans, err, errcap));
     TRY(a2a_items(X, ans, q_recv, ans_back, q_send, 4));
-    TRY(snk_shard_prune_apply(ctx, qbuf, ans_back, nq, d_qoff, st, err, errcap));
+    TRY(snk_dist_apply(ctx, st, &S->g, qbuf, ans_back, nq, d_qoff, err, errcap));
     tm.mark();   // 5
 
     // ---- fragments of my chunks (global node numbering = the ranks' tables behind each other)
@@ -461,8 +464,10 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     for (uint32_t q = 0; q < W; ++q) node_off[q + 1] = node_off[q] + all_n[q];
     ull* d_node_off;
     TRY(upload(X, node_off.data(), W + 1, &d_node_off));
-    snk_shard_frags fr;
-    TRY(snk_shard_fragments(ctx, d_node_off, node_off[me], &fr, st, err, errcap));
+    TRY(snk_bl_dist_fragments(ctx, st, &S->bl, d_node_off, node_off[me], &S->frags, err, errcap));
+    S->d_node_off = d_node_off;
+    S->my_node_off = node_off[me];
+    const snk_frag_out& fr = S->frags;
     const uint64_t F = fr.n_frags;
     tm.mark();   // 6
 
@@ -472,7 +477,6 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     jt.mark();   // j0
     // One pass: destination q's queries go to region q of the buffer (capacity = every end I have), the cursors come back
     // with the fragment count in ONE read-back, the answers return into the same regions.
-    ALLOC(S->lq_count, ull, W + 2);
     ALLOC(S->lq_cursor, ull, W + 2);
     const uint64_t lcap = 2 * F + 1;
     uint8_t *lqbuf, *lans_back;
@@ -484,7 +488,9 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
         init[W] = F;
         ull* d_init;
         TRY(upload(X, init.data(), W + 1, &d_init));
-        TRY(snk_shard_links_fill(ctx, d_init, lqbuf, st, err, errcap));      // copies W+1 words: the cursors and, behind them, F
+        SNK_HIP_TRY(hipMemcpyAsync(S->lq_cursor, d_init, (W + 1) * 8ull, hipMemcpyDeviceToDevice, st));      // the cursors and, behind them, F
+        // (my_end_base is only known behind the read-back below; the queries carry it in a half-word that neither the answer nor the apply reads)
+        TRY(snk_dist_links_query(ctx, st, &S->frags, S->d_node_off, W, S->my_end_base, S->lq_cursor, lqbuf, err, errcap));
     }
     std::vector<ull> lall;
     TRY(exchange_counts(X, S->lq_cursor, W + 1, lall));
@@ -508,7 +514,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
         uint64_t acc = 0;
         for (uint32_t q = 0; q < W; ++q) { sbeg[q] = (uint64_t)q * lcap * 24; scnt[q] = l_send[q] * 24; rbeg[q] = acc * 24; rcnt[q] = l_recv[q] * 24; acc += l_recv[q]; }
         TRY(comm->a2a(lqbuf, sbeg.data(), scnt.data(), lqin, rbeg.data(), rcnt.data(), st, err, errcap));
-        TRY(snk_shard_links_answer(ctx, lqin, nlq_in, lans, st, err, errcap));
+        TRY(snk_dist_links_answer(ctx, st, &S->frags, lqin, nlq_in, 2ull * S->my_node_off, 2ull * S->tab.n, S->my_end_base, lans, err, errcap));
         for (uint32_t q = 0; q < W; ++q) { std::swap(sbeg[q], rbeg[q]); std::swap(scnt[q], rcnt[q]); sbeg[q] /= 6; scnt[q] /= 6; rbeg[q] /= 6; rcnt[q] /= 6; }
         TRY(comm->a2a(lans, sbeg.data(), scnt.data(), lans_back, rbeg.data(), rcnt.data(), st, err, errcap));
     }
@@ -537,18 +543,18 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     const bool want_partitioned = snk_opt_u32(ctx, SNK_OPT_join_replicated) == 0;
     for (int attempt = 0; want_partitioned && !ranked && attempt < 3; ++attempt) {
         // (a second attempt follows a circle cut: the links changed, everything derived from them is made again)
-        uint64_t m_spl = 0;
-        const void* w1p = nullptr;
-        TRY(snk_shard_prank_begin(ctx, Ft, nk_all, fl_all, frag_off[me], &m_spl, &w1p, st, err, errcap));
+        TRY(snk_shard_prank_begin(ctx, *S, st, Ft, nk_all, fl_all, frag_off[me], err, errcap));
+        const uint64_t m_spl = S->pr.m;
         std::vector<uint64_t> shares(W);
         uint64_t tot16 = 0;
         for (uint32_t q = 0; q < W; ++q) { shares[q] = (m_spl * (q + 1) / W - m_spl * q / W) * 16; tot16 += shares[q]; }
         uint8_t* w1_all;
         ALLOC(w1_all, uint8_t, tot16 + 32);
-        TRY(comm->allgatherv(w1p, shares.data(), w1_all, st, err, errcap));
+        TRY(comm->allgatherv(S->pr.w1_share, shares.data(), w1_all, st, err, errcap));
         exch_spl = m_spl * 16;
-        uint32_t circ = 0;
-        TRY(snk_shard_prank_walk(ctx, w1_all, d_frag_off, nullptr, &circ, st, err, errcap));
+        uint32_t circ = 0, n_cut = 0;
+        TRY(snk_prank_walk(ctx, st, &S->pr, (const uint4*)w1_all, &circ, &S->join_rounds, err, errcap, S->circ_all, &n_cut));
+        S->join_circles += n_cut;
         if (circ == 1) break;            // something the partitioned ranking does not handle: every rank ranks the replicated way
         if (circ == 2) continue;         // circles were cut (the same cuts on every rank: the data is replicated): rank again
         {
@@ -560,8 +566,10 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             TRY(upload(X, init.data(), W, &d_init));
             uint8_t* rsend;
             ALLOC(rsend, uint8_t, (uint64_t)W * rcap * 16 + 32);
-            TRY(snk_shard_prank_route(ctx, d_frag_off, d_init, rsend, st, err, errcap));
-            ull* d_cur = S->pr_cursor;
+            ull* d_cur;          // the regions' cursors: their ends after the fill
+            ALLOC(d_cur, ull, W + 1);
+            SNK_HIP_TRY(hipMemcpyAsync(d_cur, d_init, W * 8ull, hipMemcpyDeviceToDevice, st));
+            TRY(snk_prank_route(ctx, st, &S->pr, d_frag_off, W, d_cur, rsend, err, errcap));
             ull* d_cur2;
             ALLOC(d_cur2, ull, W + 2);
             if (n_rec) SNK_HIP_TRY(hipMemcpyAsync(d_cur2, d_cur, W * 8ull, hipMemcpyDeviceToDevice, st));
@@ -585,14 +593,14 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
             uint8_t* rk_in;
             ALLOC(rk_in, uint8_t, n_in * 16 + 32);
             TRY(comm->a2a(rsend, sbeg.data(), scnt.data(), rk_in, rbeg.data(), rcnt.data(), st, err, errcap));
-            TRY(snk_shard_place_ranked(ctx, K, rk_in, n_in, d_frag_off, nullptr, nullptr, st, err, errcap));
+            TRY(snk_shard_place_ranked(ctx, *S, st, rk_in, n_in, err, errcap));
             snk_ctx_release_block(ctx, rsend);
             ranked = true;
             exch_rank = n_out * 16;
         }
     }
     if (!ranked)      // a list is a circle (same verdict on every rank: it comes from replicated data), or the replicated mode was asked for
-        TRY(snk_shard_place(ctx, K, Ft, nk_all, fl_all, d_frag_off, frag_off[me], nullptr, nullptr, st, err, errcap));
+        TRY(snk_shard_place(ctx, *S, st, Ft, nk_all, fl_all, frag_off[me], err, errcap));
     jt.mark();   // j3 rank + place
     // headers + bases to the owners of the unitigs, one pass into per-owner regions (capacity: all my fragments / all my bases;
     // every region of bases starts 16-byte aligned); the cursors come back in one read-back
@@ -606,7 +614,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
         ull *d_hoff, *d_boff;
         TRY(upload(X, hb.data(), W, &d_hoff));
         TRY(upload(X, bb.data(), W, &d_boff));
-        TRY(snk_shard_route_fill(ctx, K, d_frag_off, d_hoff, d_boff, hdr, sb, st, err, errcap));
+        TRY(snk_shard_route_fill(ctx, *S, st, K, d_frag_off, d_hoff, d_boff, hdr, sb, err, errcap));
     }
     std::vector<ull> fall;
     {
@@ -642,8 +650,8 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     ull *d_hseg, *d_bseg;
     TRY(upload(X, hseg.data(), W + 1, &d_hseg));
     TRY(upload(X, bseg.data(), W + 1, &d_bseg));
-    snk_shard_unitigs un;
-    TRY(snk_shard_emit(ctx, K, hseg[W], hdr_in, d_hseg, d_bseg, b_in, &un, st, err, errcap));
+    snk_join_out un;
+    TRY(snk_shard_emit(ctx, *S, st, K, hseg[W], hdr_in, d_hseg, d_bseg, b_in, &un, err, errcap));
     jt.mark();   // j5 emit
     tm.mark();   // 7
     SNK_HIP_TRY(snk_sync(st));
@@ -654,16 +662,16 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     out->n_supermers = part.n_supermers;
     out->n_buckets_total = NB_total;
     out->n_kmers = n_kmers;
-    out->keys = fr.keys; out->counts = fr.counts; out->ctx = fr.ctx;
+    out->keys = S->tab.keys; out->counts = S->bl.counts; out->ctx = S->bl.ctx;      // (the table in bucket order, not sorted)
     out->spectrum = fr.spectrum; out->spectrum_bins = fr.spectrum_bins;
     out->n_unitigs = un.n_unitigs; out->unitig_total_bases = un.total_bases;
     out->unitig_off = un.unitig_off; out->unitig_bases = un.unitig_bases; out->unitig_circular = un.unitig_circular;
-    out->n_circles = un.n_circles;
+    out->n_circles = S->join_circles;
     out->n_frags = F; out->n_frags_total = Ft; out->n_queries = nq; out->n_link_queries = nlq;
     out->ranking = ranked ? 1u : 0u;
     out->repartitioned = repartitioned;
     out->n_hot_buckets = n_hot_buckets;
-    out->buckets_split = fr.buckets_split; out->max_slots_used = fr.max_slots_used;
+    out->buckets_split = S->tab.buckets_split; out->max_slots_used = S->tab.max_slots_used;
     out->exchanged_bytes[0] = exch_records;
     out->exchanged_bytes[1] = 0; for (uint32_t q = 0; q < W; ++q) if (q != me) out->exchanged_bytes[1] += q_send[q] * 24 + q_recv[q] * 4;
     out->exchanged_bytes[2] = 0; for (uint32_t q = 0; q < W; ++q) if (q != me) out->exchanged_bytes[2] += l_send[q] * 24 + l_recv[q] * 4;
@@ -688,7 +696,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     for (int q = 0; q < 7; ++q) out->phase_ms[q] = tm.ms(q, q + 1);
     out->phase_ms[7] = tm.ms(0, 7);
     for (int q = 0; q < 5; ++q) out->join_ms[q] = jt.ms(q, q + 1);
-    out->count_kernel_ms = fr.count_kernel_ms;
+    out->count_kernel_ms = S->tab.count_kernel_ms;
     out->host_syncs = (uint32_t)(snk_sync_count() - syncs0);
     out->world = W; out->rank = me;
     (void)flags;
@@ -842,6 +850,7 @@ static int shard_step_run(snk_ctx* ctx, snk_comm* comm, const snk_dev_reads* in,
     step_ctx X;
     X.ctx = ctx; X.comm = comm; X.st = stream ? (hipStream_t)stream : ctx->stream; X.err = err; X.errcap = errcap;
     X.W = comm->world; X.me = comm->rank; X.streamed = streamed;
+    ctx->cur_stream = X.st;
     const size_t need = 64ull * (X.W + 2) + 4096;
     if (H.pin_cap < need) {
         if (H.pin) (void)hipHostFree(H.pin);

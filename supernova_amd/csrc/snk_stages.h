@@ -77,11 +77,23 @@ struct snk_count_pilot {
 };
 uint32_t snk_count_limit(uint32_t K, uint32_t grouped, uint32_t tight);
 uint32_t snk_count_screen_limit();      // distinct k-mers one pass over a bucket may hold
-int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, uint32_t K, const void* records, const uint64_t* seg_beg,
-                          const uint64_t* seg_end, uint32_t seg_stride, uint32_t nseg, uint32_t NB, uint32_t min_freq, uint32_t bc_mode, uint32_t grouped, uint64_t n_inst_hint,
-                          uint32_t* status, bool want_sort, snk_table* out, char* err, size_t errcap,
-                          const snk_count_ranges* ranges = nullptr, snk_count_pilot* pilot = nullptr, const uint32_t* gidx = nullptr,
-                          bool defer_compact = false, const snk_hot* hot = nullptr);
+// what snk_stage_count_table counts and how; the defaults are a job without hooks whose table is compacted by the stage itself
+struct snk_count_job {
+    uint32_t K = 0;
+    const void* records = nullptr;
+    const uint64_t* seg_beg = nullptr;      // [s * seg_stride + b]: first record of segment s of bucket b ...
+    const uint64_t* seg_end = nullptr;      // ... and the one behind its last
+    uint32_t seg_stride = 0, nseg = 0, NB = 0, min_freq = 0, bc_mode = 0, grouped = 0;
+    uint64_t n_inst_hint = 0;
+    uint32_t* status = nullptr;             // device u32[16] scratch words (snk_intake_status)
+    bool want_sort = false;                 // the table sorted by key (global graph stage)
+    bool defer_compact = false;             // chunk order only: the bucket-local prune writes the dense keys (snk_table::keys_r)
+    const snk_count_ranges* ranges = nullptr;
+    snk_count_pilot* pilot = nullptr;
+    const uint32_t* gidx = nullptr;         // dense partition: record positions sorted by bucket
+    const snk_hot* hot = nullptr;
+};
+int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, const snk_count_job& job, snk_table* out, char* err, size_t errcap);
 
 // ---- minimiser partition in one pass (fixed bucket capacity + overflow segment)
 struct snk_partition {
@@ -181,7 +193,28 @@ int snk_partition_open(snk_ctx* ctx, hipStream_t st, uint32_t K, uint32_t NB, un
 int snk_partition_add(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, const snk_dev_reads* in, const uint16_t* good_len, const snk_fused_trim* ft, char* err,
                       size_t errcap);
 int snk_partition_close(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, snk_partition* out, unsigned long long h_plan[2], char* err, size_t errcap);
-// sharded runs: the buckets' records copied to exact offsets (u32 record index per bucket) of a compact buffer
-int snk_stage_partition_compact(snk_ctx* ctx, hipStream_t st, const snk_partition* part, const uint32_t* d_offsets, void* d_out, char* err, size_t errcap);
+// sharded runs: the records of the buckets OUTSIDE [skip_lo, skip_hi) copied to exact offsets (u32 record index per bucket) of a compact buffer
 int snk_stage_partition_compact_remote(snk_ctx* ctx, hipStream_t st, const snk_partition* part, const uint32_t* d_offsets, void* d_out,
                                        uint32_t skip_lo, uint32_t skip_hi, char* err, size_t errcap);
+
+// ---- the read intake of the resident, streamed and sharded entry points (snk_dev_count_graph, snk_dev_stream_*, snk_shard_step,
+// snk_shard_stream_*): the refusals, the trim choice and the slab append are written once.  The callers' names ride in the messages.
+#pragma GCC visibility push(hidden)
+int snk_intake_check_params(const snk_params* p, char* err, size_t errcap);      // K, min_bc
+// resident reads: 0 = fine, 1 = rows / read_len / row_words do not fit, 2 = neither quals nor good_len (the callers word the refusal)
+int snk_intake_reads_fault(const snk_dev_reads* in);
+// the 64-byte status block of a job, cleared
+int snk_intake_status(snk_ctx* ctx, hipStream_t st, uint32_t** status, char* err, size_t errcap);
+inline hipError_t snk_intake_status_clear(uint32_t* status, hipStream_t st) { return hipMemsetAsync(status, 0, 64, st); }
+// resident trim: the caller's good lengths, or an array of the context's filled by the partition kernel (*fused: *ft says how) or by
+// snk_dev_trim right here
+int snk_intake_trim(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, const snk_params* p, const uint16_t** good_len, snk_fused_trim* ft, bool* fused,
+                    char* err, size_t errcap);
+// one slab of a streamed job: the refusals (`whose_len` / `whose_bound`: "job's", "step's", "rank's" -- the messages name the caller's
+// own unit), then the slab's good lengths into good_len[0 .. n_reads) (copied, trimmed inside the partition kernel, or by snk_dev_trim)
+// and its supermers into the job's slots
+int snk_intake_check_slab(const snk_dev_reads* slab, uint32_t read_len, bool has_bc, uint64_t n_have, uint64_t reads_ub, const char* who, const char* whose_len,
+                          const char* whose_bound, char* err, size_t errcap);
+int snk_intake_add_slab(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, const snk_dev_reads* slab, uint32_t min_qual, uint16_t* good_len, char* err,
+                        size_t errcap);
+#pragma GCC visibility pop

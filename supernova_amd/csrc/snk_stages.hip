@@ -18,10 +18,18 @@
 
 // K5-K8 + gather + sort: supermer records of NB buckets (nseg segments) -> dense retained table sorted by key.
 // status: device u32[16] scratch words.
-int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, uint32_t K, const void* records, const uint64_t* seg_beg,
-                          const uint64_t* seg_end, uint32_t seg_stride, uint32_t nseg, uint32_t NB, uint32_t min_freq, uint32_t bc_mode, uint32_t grouped, uint64_t n_inst_hint,
-                          uint32_t* status, bool want_sort, snk_table* out, char* err, size_t errcap, const snk_count_ranges* ranges, snk_count_pilot* pilot,
-                          const uint32_t* gidx, bool defer_compact, const snk_hot* hot) {
+int snk_stage_count_table(snk_ctx* ctx, hipStream_t st, const snk_count_job& job, snk_table* out, char* err, size_t errcap) {
+    const uint32_t K = job.K, seg_stride = job.seg_stride, nseg = job.nseg, NB = job.NB, min_freq = job.min_freq, bc_mode = job.bc_mode, grouped = job.grouped;
+    const void* records = job.records;
+    const uint64_t *seg_beg = job.seg_beg, *seg_end = job.seg_end;
+    const uint64_t n_inst_hint = job.n_inst_hint;
+    uint32_t* status = job.status;
+    const bool want_sort = job.want_sort;
+    bool defer_compact = job.defer_compact;
+    const snk_count_ranges* ranges = job.ranges;
+    snk_count_pilot* pilot = job.pilot;
+    const uint32_t* gidx = job.gidx;
+    const snk_hot* hot = job.hot;
     if (hot && hot->NBv == 0) hot = nullptr;
     defer_compact = defer_compact && !want_sort && snk_opt_u32(ctx, SNK_OPT_defer_compact) != 0;
     int rc;
@@ -1004,18 +1012,8 @@ int snk_partition_passes_run(void* user, uint32_t r) {
     return SNK_OK;
 }
 
-int snk_stage_partition_compact(snk_ctx* ctx, hipStream_t st, const snk_partition* part, const uint32_t* d_offsets, void* d_out, char* err,
-                                size_t errcap) {
-    if (part->NB == 0) return SNK_OK;
-    SNK_HIP_TRY(snk_launch(compact_buckets_kernel, snk_blocks(part->NB, 4), 256, 0, st, (const uint4*)part->records, part->seg, part->NB,
-                           d_offsets, (uint4*)d_out, 0u, 0u));
-    SNK_HIP_TRY(snk_sync(st));
-    snk_ctx_release_block(ctx, part->records);      // the slot layout is dead once the send buffer is filled
-    return SNK_OK;
-}
-
-// the same for the buckets OUTSIDE [skip_lo, skip_hi): the rank's own buckets stay where they are and are counted in place
-// (snk_shard_step.hip); nothing is waited for, the slot layout stays alive
+// sharded runs: the records of the buckets OUTSIDE [skip_lo, skip_hi) copied to exact offsets of the send buffer: the rank's own buckets
+// stay where they are and are counted in place (snk_shard_step.hip); nothing is waited for, the slot layout stays alive
 int snk_stage_partition_compact_remote(snk_ctx* ctx, hipStream_t st, const snk_partition* part, const uint32_t* d_offsets, void* d_out,
                                        uint32_t skip_lo, uint32_t skip_hi, char* err, size_t errcap) {
     if (part->NB == 0) return SNK_OK;
@@ -1130,4 +1128,77 @@ int snk_partition_close(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, snk_
     out->seg = J->seg;
     out->kernel_ms = 0.f;
     return SNK_OK;
+}
+
+
+// ===================================================================================================================
+// The read intake (snk_stages.h): what every entry point that takes reads refuses, and how the good lengths get made.
+int snk_intake_check_params(const snk_params* p, char* err, size_t errcap) {
+    if (p->K != 48 && p->K != 60) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "K=%u is not supported (48 or 60)", p->K);
+    if (p->min_bc > 8) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "min_bc=%u: the device barcode rule tells up to eight distinct barcodes apart (min_bc <= 8)", p->min_bc);
+    return SNK_OK;
+}
+
+int snk_intake_reads_fault(const snk_dev_reads* in) {
+    if (in->n_reads == 0) return 0;
+    if (!in->rows || in->row_words * 16 < in->read_len || in->read_len > 256) return 1;
+    return (!in->good_len && !in->quals) ? 2 : 0;
+}
+
+int snk_intake_status(snk_ctx* ctx, hipStream_t st, uint32_t** status, char* err, size_t errcap) {
+    void* q;
+    int rc = snk_ctx_alloc(ctx, 64, &q, err, errcap);
+    if (rc) return rc;
+    *status = (uint32_t*)q;
+    SNK_HIP_TRY(snk_intake_status_clear(*status, st));
+    return SNK_OK;
+}
+
+static snk_fused_trim fused_trim_of(const snk_dev_reads* in, uint32_t min_qual, uint16_t* good_out) {
+    snk_fused_trim ft;
+    ft.quals = in->quals; ft.qstride = in->qstride; ft.lens = in->lens; ft.min_qual = min_qual; ft.good_out = good_out;
+    return ft;
+}
+
+int snk_intake_trim(snk_ctx* ctx, hipStream_t st, const snk_dev_reads* in, const snk_params* p, const uint16_t** good_len, snk_fused_trim* ft, bool* fused,
+                    char* err, size_t errcap) {
+    *good_len = (const uint16_t*)in->good_len;
+    *fused = in->n_reads && snk_fused_trim_ok(ctx, in);      // the trim inside the partition kernel (snk_msp.hip): its loads ride under the slot reservations
+    if (*good_len) return SNK_OK;
+    void* gl;
+    int rc = snk_ctx_alloc(ctx, in->n_reads * 2 + 2, &gl, err, errcap);
+    if (rc) return rc;
+    if (*fused) *ft = fused_trim_of(in, p->min_qual, (uint16_t*)gl);
+    else if (in->n_reads) {
+        rc = snk_dev_trim(ctx, in->quals, in->qstride, in->lens, in->read_len, in->n_reads, p->K, p->min_qual, gl, st);
+        if (rc) return snk_fail(rc, err, errcap, "%s", snk_last_error());
+    }
+    *good_len = (const uint16_t*)gl;
+    return SNK_OK;
+}
+
+int snk_intake_check_slab(const snk_dev_reads* slab, uint32_t read_len, bool has_bc, uint64_t n_have, uint64_t reads_ub, const char* who, const char* whose_len,
+                          const char* whose_bound, char* err, size_t errcap) {
+    if (!slab->rows || slab->read_len != read_len || slab->row_words * 16 < slab->read_len) return snk_fail(SNK_E_ARG, err, errcap, "%s: bad rows / read_len (the %s is %u)", who, whose_len, read_len);
+    if (!slab->good_len && !slab->quals) return snk_fail(SNK_E_ARG, err, errcap, "%s: need quals or good_len", who);
+    if ((slab->bc != nullptr) != has_bc) return snk_fail(SNK_E_ARG, err, errcap, "%s: every slab carries barcodes, or none does", who);
+    if (n_have + slab->n_reads > reads_ub)
+        return snk_fail(SNK_E_ARG, err, errcap, "%s: more reads than the %s upper bound (%llu + %llu > %llu)", who, whose_bound, (unsigned long long)n_have,
+                        (unsigned long long)slab->n_reads, (unsigned long long)reads_ub);
+    return SNK_OK;
+}
+
+int snk_intake_add_slab(snk_ctx* ctx, hipStream_t st, snk_partition_job* J, const snk_dev_reads* slab, uint32_t min_qual, uint16_t* good_len, char* err,
+                        size_t errcap) {
+    if (slab->good_len) {
+        SNK_HIP_TRY(hipMemcpyAsync(good_len, slab->good_len, slab->n_reads * 2, hipMemcpyDeviceToDevice, st));
+        return snk_partition_add(ctx, st, J, slab, good_len, nullptr, err, errcap);
+    }
+    if (snk_fused_trim_ok(ctx, slab)) {
+        const snk_fused_trim ft = fused_trim_of(slab, min_qual, good_len);
+        return snk_partition_add(ctx, st, J, slab, good_len, &ft, err, errcap);
+    }
+    int rc = snk_dev_trim(ctx, slab->quals, slab->qstride, slab->lens, slab->read_len, slab->n_reads, J->K, min_qual, good_len, st);
+    if (rc) return snk_fail(rc, err, errcap, "%s", snk_last_error());
+    return snk_partition_add(ctx, st, J, slab, good_len, nullptr, err, errcap);
 }
