@@ -28,8 +28,7 @@ int snk_bads_check_args(const char* who, uint32_t K, uint64_t n_reads, uint32_t 
 // refuses or would not give back unchanged), the zeroed flags and counters.  H is declared in front of the frame.
 int snk_bads_begin(snk_call& c, path_host& H, const char* who, uint32_t K, uint64_t n_reads, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases,
                    const snk_hbv* h, const snk_dev_paths* paths, uint32_t flags, bads_job* job, char* err, size_t errcap);
-// Reads [first, first + n) of the call (both even), given as the device arrays of a slab: enqueues the kernel on st.
-hipError_t snk_bads_slab(const bads_job& job, uint64_t first, uint64_t n, const uint32_t* rows, uint32_t row_words, uint32_t read_len, const uint8_t* quals,
-                         uint32_t qstride, const uint16_t* lens, hipStream_t st);
+// Reads [first, first + R.n) of the call (both even), given as the device arrays of a slab: enqueues the kernel on st.
+hipError_t snk_bads_slab(const bads_job& job, uint64_t first, const snk_reads_view& R, hipStream_t st);
 // Waits for the stream, brings the counters down and fills *out (all but ms and n_slabs).  The caller keeps job.bad (c.end).
 int snk_bads_finish(snk_call& c, const bads_job& job, snk_dev_bads* out, char* err, size_t errcap);

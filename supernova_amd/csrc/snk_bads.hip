@@ -17,8 +17,8 @@
 //   b_edges_kernel   one lane per read, once the edge ids are known to lie inside the graph: an edge shorter than K; with SNK_BADS_X a
 //                    path of more than 255 edges and a step e -> e' with e' not in From(ToRight(e))
 //   b_bads_kernel    8 lanes per PAIR, 4 per mate.  Lane q of a mate takes the read's row words q, q + 4, ...: a word's 16 bases are
-//                    XORed, piece by piece, against 16 bases of the edge taken from the packed unitigs (a reverse-complement edge the way
-//                    snk_extend.hip reads it).  A zero XOR loads no quality byte; a mismatch is found with clz and fetches its own.  A lane's
+//                    XORed, piece by piece, against 16 bases of the edge taken from the packed unitigs (pg_edge16: a reverse-complement edge is
+//                    read backwards).  A zero XOR loads no quality byte; a mismatch is found with clz and fetches its own.  A lane's
 //                    words rise, so its place in the path only moves forward: a path is walked once per lane.  The mate's sum is two
 //                    shuffles, the pair's flag a third: no atomic decides a result, and the counters are summed per workgroup before
 //                    five atomics.
@@ -40,47 +40,17 @@ constexpr uint64_t B_GRID_CAP = 1u << 20;
 constexpr uint32_t F_TABLE = 1, F_LONG = 2, F_STEP = 4, F_SHORT = 8;
 enum { N_PLACED, N_MISMATCH, N_BAD_READS, N_BAD_PAIRS, N_WRAPPED, N_COUNTED, N_COUNTERS = 8 };
 
-struct b_reads {
-    const uint32_t* rows;
-    const uint8_t* quals;
-    const uint16_t* lens;
-    uint32_t row_words, read_len, qstride;
-    uint64_t n;
-};
 struct b_paths {                             // of the launch's reads: read r of the launch is entry r (edges: the whole array, start indexes it)
     const unsigned long long* start;
     const uint32_t* n_edges;
     const int32_t* offset;
     const uint32_t* edges;
 };
-struct b_edge { uint64_t o; uint32_t len; uint32_t rc; };
-
-__device__ __forceinline__ b_edge b_load(const path_graph& G, uint32_t e) {
-    const uint4 q = G.uinfo[2 * (uint64_t)(uint32_t)G.e_unitig[e]];
-    b_edge x;
-    x.o = ((uint64_t)q.y << 32) | q.x; x.len = q.z; x.rc = G.e_rc[e];
-    return x;
-}
-// 16 bases from base p of a packed array, first base in the top bits
-__device__ __forceinline__ uint32_t b_pack16(const uint32_t* P, uint64_t p) {
-    const uint64_t wi = p >> 4;
-    const uint32_t sh = 2u * ((uint32_t)p & 15u);
-    return (uint32_t)(((((uint64_t)P[wi] << 32) | P[wi + 1]) << sh) >> 32);
-}
-// bases i .. i + 15 of an edge, i < len (behind its end: whatever the packed array holds there; the caller masks)
-__device__ __forceinline__ uint32_t b_edge16(const path_graph& G, const b_edge& x, uint32_t i) {
-    if (!x.rc) return b_pack16(G.upack, UPAD + x.o + i);
-    uint32_t w = __brev(b_pack16(G.upack, UPAD + x.o + x.len - 16 - i));        // (UPAD bases of slack in front: never below the array)
-    w = ((w >> 1) & 0x55555555u) | ((w & 0x55555555u) << 1);
-    return ~w;
-}
 
 __global__ void __launch_bounds__(BB) b_table_kernel(uint64_t n, const unsigned long long* __restrict__ start, const uint32_t* __restrict__ n_edges, uint64_t n_entries,
                                                      uint32_t* __restrict__ flags) {
     for (uint64_t r = (uint64_t)blockIdx.x * BB + threadIdx.x; r < n; r += (uint64_t)gridDim.x * BB) {
-        const uint64_t s = start[r], m = n_edges[r];
-        // start[0] = 0, start[r + 1] = start[r] + n_edges[r], start[n_reads] = n_entries (no gaps, no overlaps)
-        if (s > n_entries || m > n_entries - s || start[r + 1] != s + m || (r == 0 && s != 0) || (r + 1 == n && s + m != n_entries)) atomicOr(flags, F_TABLE);
+        if (!snk_paths_row_ok(start, n_edges, r, n, n_entries)) atomicOr(flags, F_TABLE);
     }
 }
 
@@ -93,7 +63,7 @@ __global__ void __launch_bounds__(BB) b_edges_kernel(path_graph G, int K, uint32
         if (xmode && m > 255) { atomicOr(flags, F_LONG); continue; }
         uint32_t e = edges[s];
         for (uint64_t j = 0; j < m; ++j) {
-            if (b_load(G, e).len < (uint32_t)K) f |= F_SHORT;
+            if (pg_edge_len(G, e) < (uint32_t)K) f |= F_SHORT;
             if (j + 1 == m) break;
             const uint32_t e2 = edges[s + j + 1];
             if (xmode) {
@@ -108,7 +78,7 @@ __global__ void __launch_bounds__(BB) b_edges_kernel(path_graph G, int K, uint32
     }
 }
 
-__global__ void __launch_bounds__(BB) b_bads_kernel(path_graph G, b_reads R, b_paths P, int K, uint32_t xmode, uint8_t* __restrict__ bad,
+__global__ void __launch_bounds__(BB) b_bads_kernel(path_graph G, snk_reads_view R, b_paths P, int K, uint32_t xmode, uint8_t* __restrict__ bad,
                                                     unsigned long long* __restrict__ counters) {
     __shared__ uint32_t l_cnt[BB / 64][N_COUNTED];
     const uint32_t tid = threadIdx.x, q = tid & (LPM - 1), mate = (tid / LPM) & 1u;
@@ -123,7 +93,7 @@ __global__ void __launch_bounds__(BB) b_bads_kernel(path_graph G, b_reads R, b_p
         int badsum = 0, nmis = 0;
         bool wrapped = false;
         if (m) {
-            const int len = (int)(R.lens ? min((uint32_t)R.lens[r], R.read_len) : R.read_len);
+            const int len = (int)snk_read_len(R, r);
             const int off0 = P.offset[r];
             const int off = xmode ? (int)(int16_t)off0 : off0;          // (ReadPathParser.cc:184-198: the record holds static_cast<int16_t>)
             wrapped = (int)(int16_t)off0 != off0;
@@ -132,7 +102,7 @@ __global__ void __launch_bounds__(BB) b_bads_kernel(path_graph G, b_reads R, b_p
             const uint8_t* qual = R.quals + r * R.qstride;
             // the lane's place in the path: piece j = m[S, b), S = the k-mers in front of it
             uint32_t j = 0;
-            b_edge x = b_load(G, P.edges[s]);
+            pg_edge x = pg_edge_load(G, P.edges[s]);
             long long S = 0, b = m > 1 ? (long long)x.len - (K - 1) : (long long)x.len;
             for (int w = (int)q; 16 * w < len && j < m; w += (int)LPM) {
                 long long lo = (long long)off + 16 * w;
@@ -143,13 +113,13 @@ __global__ void __launch_bounds__(BB) b_bads_kernel(path_graph G, b_reads R, b_p
                 while (lo < hi) {
                     while (b <= lo && ++j < m) {
                         S = b;
-                        x = b_load(G, P.edges[s + j]);
+                        x = pg_edge_load(G, P.edges[s + j]);
                         b = S + (j + 1 < m ? (long long)x.len - (K - 1) : (long long)x.len);
                     }
                     if (j >= m) break;                                  // behind m: skipped
                     const long long top = hi < b ? hi : b;
                     const int rp = (int)(lo - off);
-                    uint32_t d = (word << (2 * (rp - 16 * w))) ^ b_edge16(G, x, (uint32_t)(lo - S));
+                    uint32_t d = (word << (2 * (rp - 16 * w))) ^ pg_edge16(G, x, (uint32_t)(lo - S));
                     d = (d | (d << 1)) & 0xAAAAAAAAu;
                     const uint32_t c = (uint32_t)(top - lo);
                     if (c < 16) d &= ~(0xFFFFFFFFu >> (2 * c));
@@ -262,12 +232,10 @@ int snk_bads_begin(snk_call& c, path_host& H, const char* who, uint32_t K, uint6
     return SNK_OK;
 }
 
-hipError_t snk_bads_slab(const bads_job& job, uint64_t first, uint64_t n, const uint32_t* rows, uint32_t row_words, uint32_t read_len, const uint8_t* quals,
-                         uint32_t qstride, const uint16_t* lens, hipStream_t st) {
+hipError_t snk_bads_slab(const bads_job& job, uint64_t first, const snk_reads_view& R, hipStream_t st) {
+    const uint64_t n = R.n;
     if (!n) return hipSuccess;
     if ((first & 1) || (n & 1) || first > job.n_reads || n > job.n_reads - first) return hipErrorInvalidValue;
-    b_reads R;
-    R.rows = rows; R.quals = quals; R.lens = lens; R.row_words = row_words; R.read_len = read_len; R.qstride = qstride; R.n = n;
     b_paths P;
     P.start = job.start + first; P.n_edges = job.n_edges + first; P.offset = job.offset + first; P.edges = job.edges;
     return snk_launch(b_bads_kernel, snk_blocks_capped(n / 2, PPB, B_GRID_CAP), BB, 0, st, job.G, R, P, job.K, job.x, job.bad + first / 2, job.counters);
@@ -305,7 +273,7 @@ extern "C" int snk_dev_mark_bads(snk_ctx* ctx, uint32_t K, const snk_dev_reads* 
         bads_job job;
         if ((rc2 = snk_bads_begin(c, H, who, K, n, n_unitigs, d_unitig_off, d_unitig_bases, h, paths, flags, &job, err, errcap))) return rc2;
         SNK_HIP_TRY(c.stamp());
-        SNK_HIP_TRY(snk_bads_slab(job, 0, n, (const uint32_t*)in->rows, in->row_words, in->read_len, (const uint8_t*)in->quals, in->qstride, (const uint16_t*)in->lens, c.st));
+        SNK_HIP_TRY(snk_bads_slab(job, 0, snk_reads_view_of(in, n), c.st));
         SNK_HIP_TRY(c.stamp());
         if ((rc2 = snk_bads_finish(c, job, out, err, errcap))) return rc2;
         out->ms = c.ms(0, 2);

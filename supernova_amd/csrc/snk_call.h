@@ -127,6 +127,14 @@ int snk_call_run(snk_ctx* ctx, void* stream, const char* who, Out* out, char* er
 // the caller; the result is their maximum).  Any 4-byte-aligned pointer.  Shared by the paths index and the compressed paths
 // (snk_pidx.hip), which refuse an id outside the graph before they index with it.
 hipError_t snk_max_edge_id(const uint32_t* edges, uint64_t n, uint32_t* range, hipStream_t st);
+// Row r of a path table of n reads adds up: start[0] = 0, start[r + 1] = start[r] + n_edges[r], start[n] = n_entries (no gaps, no
+// overlaps; start has n + 1 entries).  Every stage that indexes with start / n_edges asks this of every row first, in its own check
+// kernel, and refuses the table under its own flag and message.
+__device__ __forceinline__ bool snk_paths_row_ok(const unsigned long long* start, const uint32_t* n_edges, uint64_t r, uint64_t n, uint64_t n_entries) {
+    const uint64_t s = start[r], m = n_edges[r];
+    if (s > n_entries || m > n_entries - s || start[r + 1] != s + m || (r == 0 && s != 0) || (r + 1 == n && s + m != n_entries)) return false;
+    return true;
+}
 // The lists of the paths index inside a frame (snk_pidx.hip): off[E + 1], ids[n_edges_total] and, with_counts, room for counts[E] (the
 // caller fills it), all scratch of c.  Refuses, as `who`, a path table that does not add up and an edge id outside [0, E).  What
 // snk_dev_paths_index is made of, and what snk_dev_edge_pairs runs when it is given no index.

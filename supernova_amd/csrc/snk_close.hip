@@ -71,20 +71,8 @@ struct c_view {
     const int32_t *edges, *offset;
     const unsigned long long *ioff, *iids;
     const int32_t *inv, *km;
-    const uint32_t* rows;
-    const uint8_t* quals;
-    const uint16_t* lens;
-    uint32_t row_words, read_len, qstride;
+    snk_reads_view R;
 };
-__host__ __device__ inline int c_len(const c_view& V, uint64_t r) { return (int)(V.lens ? (V.lens[r] < V.read_len ? V.lens[r] : V.read_len) : V.read_len); }
-__host__ __device__ inline uint32_t c_row_base(const uint32_t* row, int j) { return (row[j >> 4] >> (30 - 2 * (j & 15))) & 3u; }
-__device__ __forceinline__ int c_edge_len(const path_graph& G, int e) { return (int)G.uinfo[2 * (uint64_t)(uint32_t)G.e_unitig[e]].z; }
-__device__ __forceinline__ uint32_t c_edge_base(const path_graph& G, int e, int i) {
-    const uint32_t u = (uint32_t)G.e_unitig[e];
-    const uint64_t o = G.uoff[u];
-    const int len = (int)(G.uoff[u + 1] - o);
-    return G.e_rc[e] ? 3u - G.ubases[o + (uint64_t)(len - 1 - i)] : G.ubases[o + (uint64_t)i];
-}
 __host__ __device__ inline uint32_t c_hash(unsigned long long k, uint32_t mask) { return (uint32_t)((k * 0x9E3779B97F4A7C15ull) >> 32) & mask; }
 
 __global__ void __launch_bounds__(CB) c_pairs_kernel(const int32_t* __restrict__ pairs, uint64_t n2, uint64_t E, uint32_t* __restrict__ flag) {
@@ -92,19 +80,7 @@ __global__ void __launch_bounds__(CB) c_pairs_kernel(const int32_t* __restrict__
         if (pairs[i] < 0 || (uint64_t)pairs[i] >= E) atomicOr(flag, 1u);
 }
 __global__ void __launch_bounds__(CB) c_km_kernel(path_graph G, int K, uint64_t E, int32_t* __restrict__ km) {
-    for (uint64_t e = (uint64_t)blockIdx.x * CB + threadIdx.x; e < E; e += (uint64_t)gridDim.x * CB) km[e] = c_edge_len(G, (int)e) - K + 1;
-}
-
-// a wave's lanes each have c items: -> the items of the lanes in front; *total = the wave's sum.  Reached by whole waves.
-__device__ __forceinline__ uint32_t c_wave_excl(uint32_t c, uint32_t* total) {
-    const unsigned lane = threadIdx.x & 63;
-    uint32_t incl = c;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= (unsigned)o) incl += up;
-    }
-    *total = (uint32_t)__shfl((int)incl, 63);
-    return incl - c;
+    for (uint64_t e = (uint64_t)blockIdx.x * CB + threadIdx.x; e < E; e += (uint64_t)gridDim.x * CB) km[e] = (int32_t)pg_edge_len(G, (int32_t)e) - K + 1;
 }
 
 // Closomatic.cc:381-392 and :505-531.  WRITE false: n_rows / n_fw / n_prec per (pair, side); true: the rows (id << 1 | forward, pos) at
@@ -136,8 +112,8 @@ __global__ void __launch_bounds__(CB) c_gather_kernel(c_view V, uint64_t n_pairs
                         if (p[j] == f) { ++cr; cp += (uint32_t)(pass ? j : m - 1 - j); }
                 }
                 if (!cg2) cp = 0;
-                uint32_t tr, tp;
-                const uint32_t er = c_wave_excl(cr, &tr), ep = c_wave_excl(cp, &tp);
+                uint32_t tr, tp;                              // (reached by whole waves: item, pass and n are the wave's)
+                const uint32_t er = snk_wave_scan_excl(cr, &tr), ep = snk_wave_scan_excl(cp, &tp);
                 if (WRITE && cr) {
                     unsigned long long ra = row_off[item] + rows_at + er, pa = prec_off[item] + prec_at + ep;
                     int pos = V.offset[r];
@@ -192,7 +168,7 @@ __global__ void __launch_bounds__(CB) c_bod_kernel(path_graph G, uint64_t n2, co
         uint32_t groups = 0;
         for (unsigned long long i = lo + lane; i < hi; i += 64)
             if (c_is_head(prec, lo, hi, i)) {
-                const int nk = c_edge_len(G, (int)(prec[i] >> 32)) - L32 + 1;
+                const int nk = (int)pg_edge_len(G, (int32_t)(prec[i] >> 32)) - L32 + 1;
                 sum += (unsigned long long)(nk > 0 ? nk : 0);
                 ++groups;
             }
@@ -237,10 +213,10 @@ __global__ void __launch_bounds__(CB) c_place_kernel(c_view V, path_graph G, uin
                     for (unsigned q = 0; q < CB; ++q) {
                         if (!s_head[q]) continue;
                         const unsigned long long key = prec[base + q];
-                        const int g = (int)(key >> 32), add = (int)(uint32_t)key, nk = c_edge_len(G, g) - L32 + 1;
+                        const int g = (int)(key >> 32), add = (int)(uint32_t)key, nk = (int)pg_edge_len(G, g) - L32 + 1;
                         for (int l = (int)tid; l < nk; l += (int)CB) {
                             unsigned long long x = 0;
-                            for (int b = 0; b < L32; ++b) x = x << 2 | c_edge_base(G, g, l + b);
+                            for (int b = 0; b < L32; ++b) x = x << 2 | pg_edge_base(G, g, (uint32_t)(l + b));
                             uint32_t slot = c_hash(x, mask);
                             while (atomicCAS(&h_pos[slot], C_EMPTY, add + l) != C_EMPTY) slot = (slot + 1) & mask;      // (at most slots / 2 entries: ends)
                             h_key[slot] = x;
@@ -261,11 +237,11 @@ __global__ void __launch_bounds__(CB) c_place_kernel(c_view V, path_graph G, uin
                 if (cand) {
                     ++tried;
                     if (!empty) {
-                        const uint32_t* row = V.rows + id2 * V.row_words;
-                        const int len = c_len(V, id2);
+                        const uint32_t* row = V.R.rows + id2 * V.R.row_words;
+                        const int len = (int)snk_read_len(V.R, id2);
                         for (int l = (int)lane; l + L32 <= len; l += 64) {
                             unsigned long long x = 0;
-                            for (int b = 0; b < L32; ++b) x = x << 2 | c_row_base(row, l + b);
+                            for (int b = 0; b < L32; ++b) x = x << 2 | snk_row_base(row, (uint32_t)(l + b));
                             for (uint32_t slot = c_hash(x, mask); h_pos[slot] != C_EMPTY; slot = (slot + 1) & mask) {
                                 if (h_key[slot] != x) continue;
                                 const int v = h_pos[slot] - l;
@@ -328,12 +304,12 @@ __device__ __forceinline__ bool c_cell(const c_view& V, const c_side& S, unsigne
     const uint64_t id = idfw >> 1;
     const bool fw = idfw & 1ull;
     const int j = fw ? u - pos : S.ne - 1 - u - pos;
-    if (j < 0 || j >= c_len(V, id)) return false;
-    int b = (int)c_row_base(V.rows + id * V.row_words, j);
+    if (j < 0 || j >= (int)snk_read_len(V.R, id)) return false;
+    int b = (int)snk_row_base(V.R.rows + id * V.R.row_words, (uint32_t)j);
     if (!fw) b = 3 - b;
     if (S.rev) b = 3 - b;
     *base = b;
-    *qual = (int)V.quals[id * V.qstride + j];
+    *qual = (int)V.R.quals[id * V.R.qstride + j];
     return true;
 }
 __device__ __forceinline__ double c_weight(int q) { return q == 0 ? 0.1 : q <= 2 ? 0.2 : (double)q; }          // Q0 counts 0.1, Q1 and Q2 0.2
@@ -362,7 +338,7 @@ __device__ inline void c_side_of(const c_view& V, const path_graph& G, const int
     const int e2 = pairs[2 * p + 1], e = s ? V.inv[e2] : pairs[2 * p];
     S->r0 = row_off[2 * p + s];
     S->n = n_rows_final[2 * p + s];
-    S->ne = c_edge_len(G, e);
+    S->ne = (int)pg_edge_len(G, e);
     S->M = M;
     S->T = M > max_width ? M - max_width : 0;
     S->cols = M - S->T;
@@ -394,7 +370,7 @@ __global__ void __launch_bounds__(CB) c_close_kernel(c_view V, path_graph G, uin
             int m = 0;
             for (uint32_t r = tid; r < S[s].n; r += CB) {
                 const unsigned long long idfw = row_idfw[S[s].r0 + r];
-                const int pos = row_pos[S[s].r0 + r], v = (idfw & 1ull) ? pos + c_len(V, idfw >> 1) : S[s].ne - pos;
+                const int pos = row_pos[S[s].r0 + r], v = (idfw & 1ull) ? pos + (int)snk_read_len(V.R, idfw >> 1) : S[s].ne - pos;
                 m = v > m ? v : m;
             }
             if (m) atomicMax(&s_M[s], m);
@@ -406,7 +382,7 @@ __global__ void __launch_bounds__(CB) c_close_kernel(c_view V, path_graph G, uin
             int kept = 0;
             for (uint32_t r = tid; r < S[s].n; r += CB) {
                 const unsigned long long idfw = row_idfw[S[s].r0 + r];
-                const int pos = row_pos[S[s].r0 + r], len = c_len(V, idfw >> 1);
+                const int pos = row_pos[S[s].r0 + r], len = (int)snk_read_len(V.R, idfw >> 1);
                 kept += S[s].T == 0 || (len > 0 && ((idfw & 1ull) ? pos + len : S[s].ne - pos) > S[s].T);
             }
             if (kept) atomicAdd(&s_kept, kept);
@@ -628,10 +604,10 @@ int c_table(snk_ctx* ctx, const double** d_tab, char* err, size_t errcap) {
 
 // reads ids[0 .. n): their packed rows one behind the other, and their lengths (what the host placement looks up)
 __global__ void __launch_bounds__(CB) c_fetch_kernel(c_view V, const unsigned long long* __restrict__ ids, uint64_t n, uint32_t* __restrict__ rows_out, uint16_t* __restrict__ lens_out) {
-    for (uint64_t i = (uint64_t)blockIdx.x * CB + threadIdx.x; i < n * V.row_words; i += (uint64_t)gridDim.x * CB) {
-        const uint64_t r = i / V.row_words, w = i - r * V.row_words;
-        rows_out[i] = V.rows[ids[r] * V.row_words + w];
-        if (w == 0) lens_out[r] = (uint16_t)c_len(V, ids[r]);
+    for (uint64_t i = (uint64_t)blockIdx.x * CB + threadIdx.x; i < n * V.R.row_words; i += (uint64_t)gridDim.x * CB) {
+        const uint64_t r = i / V.R.row_words, w = i - r * V.R.row_words;
+        rows_out[i] = V.R.rows[ids[r] * V.R.row_words + w];
+        if (w == 0) lens_out[r] = (uint16_t)snk_read_len(V.R, ids[r]);
     }
 }
 
@@ -676,7 +652,7 @@ int c_host_place(snk_call& c, const c_view& DV, const c_host_graph& HG, const st
             ids.push_back(id2);
         }
         if (bod.empty() || ids.empty()) continue;
-        const size_t m = ids.size(), rw = DV.row_words;
+        const size_t m = ids.size(), rw = DV.R.row_words;
         unsigned long long* d_ids;
         uint32_t* d_rows;
         uint16_t* d_lens;
@@ -696,7 +672,7 @@ int c_host_place(snk_call& c, const c_view& DV, const c_host_graph& HG, const st
             std::set<int> finds;
             for (int l = 0; l + L32 <= len; ++l) {
                 unsigned long long x = 0;
-                for (int b = 0; b < L32; ++b) x = x << 2 | c_row_base(row, l + b);
+                for (int b = 0; b < L32; ++b) x = x << 2 | snk_row_base(row, (uint32_t)(l + b));
                 const auto range = bod.equal_range(x);
                 for (auto it = range.first; it != range.second; ++it) finds.insert(it->second - l);
             }
@@ -756,10 +732,7 @@ extern "C" int snk_dev_close_gaps(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, 
         c_view V;
         memset(&V, 0, sizeof V);
         V.start = job.start; V.n_edges = job.n_edges; V.edges = (const int32_t*)job.edges; V.offset = job.offset;
-        if (in) {
-            V.rows = (const uint32_t*)in->rows; V.quals = (const uint8_t*)in->quals; V.lens = (const uint16_t*)in->lens;
-            V.row_words = in->row_words; V.read_len = in->read_len; V.qstride = in->qstride;
-        }
+        if (in) V.R = snk_reads_view_of(in, n);
         if (px) {
             V.ioff = (const unsigned long long*)px->index_off; V.iids = (const unsigned long long*)px->index_ids;
         } else {

@@ -8,8 +8,14 @@
 //                     For K=48 the top 96 bits equal KMer<48>'s three u32 words; word-lexicographic
 //                     order == lexicographic order on bases (KMer.h:305-311).
 //   context byte    : pred one-hot <<4 | succ one-hot  (KMerContext.h:27-28,36-37,55-56)
+//
+// Three families of accessors live here so that a stage includes them instead of writing its own: the wave scans (snk_wave_scan_incl /
+// _excl, snk_wave_alloc, snk_wave_add), the packed-row reads (snk_packed16, snk_row_base, snk_row16) and the reads of a launch
+// (snk_reads_view, snk_read_len, snk_reads_view_of).  The graph tables are read through snk_pathgraph.h.
 #pragma once
 #include <stdint.h>
+
+#include "../../include/snk.h"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -56,6 +62,23 @@ __device__ __forceinline__ uint32_t snk_wave_alloc(uint32_t* counter, uint32_t v
     if ((threadIdx.x & 63) == 63 && total) base = atomicAdd(counter, total);
     base = (uint32_t)__builtin_amdgcn_readlane((int)base, 63);
     return base + incl - v;
+}
+// exclusive form: what the lanes in front of this one hold together; *total = the wave's sum.  Reached by whole waves only (the DPP
+// adds of snk_wave_scan_incl take nothing from a lane that is switched off).
+__device__ __forceinline__ uint32_t snk_wave_scan_excl(uint32_t v, uint32_t* total) {
+    const uint32_t incl = snk_wave_scan_incl(v);
+    *total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    return incl - v;
+}
+// snk_wave_alloc behind a 64-bit counter in global memory: the place of the lane's first slot, one atomic per wave.  Reached by whole
+// waves only.
+__device__ __forceinline__ unsigned long long snk_wave_alloc(unsigned long long* counter, uint32_t v) {
+    uint32_t total;
+    const uint32_t excl = snk_wave_scan_excl(v, &total);
+    unsigned long long base = 0;
+    if ((threadIdx.x & 63) == 63 && total) base = atomicAdd(counter, (unsigned long long)total);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), 63);
+    return (((unsigned long long)hi << 32) | lo) + excl;
 }
 __device__ __forceinline__ void snk_wave_add(uint32_t* counter, uint32_t v) {
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)snk_wave_scan_incl(v), 63);
@@ -213,5 +236,43 @@ SNK_HD uint32_t snk_bucket_of_kmer(snk_kmer k, uint32_t NB) {
     return snk_bucket_of_key(best, NB);
 }
 
-// base i of a packed row
-SNK_HD uint32_t snk_row_base(const uint32_t* row, int i) { return (row[i >> 4] >> (30 - 2 * (i & 15))) & 3u; }
+// ---------------------------------------------------------------- packed rows and the reads of a launch
+// (the one set of accessors for the stages that read rows: the pather, the path extension, MarkBads, MarkDups, the gap closures)
+// 16 bases from base p of a packed array, first base in the top bits (two words, one funnel shift: P[(p >> 4) + 1] is read as well)
+SNK_HD uint32_t snk_packed16(const uint32_t* P, uint64_t p) {
+    const uint64_t wi = p >> 4;
+    const uint32_t sh = 2u * ((uint32_t)p & 15u);
+    const uint32_t w0 = P[wi], w1 = P[wi + 1];
+    return (uint32_t)(((((uint64_t)w0 << 32) | w1) << sh) >> 32);
+}
+// base p of a packed row
+SNK_HD uint32_t snk_row_base(const uint32_t* row, uint32_t p) { return (row[p >> 4] >> (30 - 2 * (p & 15))) & 3u; }
+// 16 bases from base p of a row of rw words, p < 16 rw (behind the row: zero, and no word behind it is read)
+SNK_HD uint32_t snk_row16(const uint32_t* row, uint32_t rw, uint32_t p) {
+    const uint32_t wi = p >> 4, sh = 2u * (p & 15u);
+    const uint32_t w0 = row[wi], w1 = wi + 1 < rw ? row[wi + 1] : 0u;
+    return (uint32_t)(((((uint64_t)w0 << 32) | w1) << sh) >> 32);
+}
+// the reads of a launch (device arrays): read r has its bases at rows + r * row_words and its raw qualities at quals + r * qstride
+struct snk_reads_view {
+    const uint32_t* rows;
+    const uint8_t* quals;
+    const uint16_t* lens;        // or NULL: every read is read_len long
+    uint32_t row_words, read_len, qstride;
+    uint64_t n;
+};
+// a read's length.  Never more than read_len, whatever lens says: this clamp decides which bases are compared and which quality bytes
+// are read, so there is one of it
+SNK_HD uint32_t snk_read_len(const uint16_t* lens, uint32_t read_len, uint64_t r) {
+    if (!lens) return read_len;
+    const uint32_t l = lens[r];
+    return l < read_len ? l : read_len;
+}
+SNK_HD uint32_t snk_read_len(const snk_reads_view& R, uint64_t r) { return snk_read_len(R.lens, R.read_len, r); }
+// reads [0, n) of the caller's arrays (host side: the casts live here)
+static inline snk_reads_view snk_reads_view_of(const snk_dev_reads* in, uint64_t n) {
+    snk_reads_view R;
+    R.rows = (const uint32_t*)in->rows; R.quals = (const uint8_t*)in->quals; R.lens = (const uint16_t*)in->lens;
+    R.row_words = in->row_words; R.read_len = in->read_len; R.qstride = in->qstride; R.n = n;
+    return R;
+}

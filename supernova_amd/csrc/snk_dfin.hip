@@ -838,7 +838,8 @@ extern "C" int snk_dev_mark_bads_df(snk_ctx* ctx, uint32_t K, snk_df_files* f, u
                            if (((sd.first - first) & 1) || (sd.n & 1))        // (a slab whose bytes do not fit its slot is decoded in pieces, cut where the bytes say)
                                return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "%s: the slab at read %llu had to be split inside a pair (its quality bytes do not fit a slot)", who,
                                                (unsigned long long)sd.first);
-                           SNK_HIP_TRY(snk_bads_slab(job, sd.first - first, sd.n, sd.rows, row_words, max_len, sd.quals, qstride, sd.lens, io->cs));
+                           const snk_reads_view R = {sd.rows, sd.quals, sd.lens, row_words, max_len, qstride, sd.n};
+                           SNK_HIP_TRY(snk_bads_slab(job, sd.first - first, R, io->cs));
                            return SNK_OK;
                        },
                        &st, err, errcap);

@@ -33,8 +33,6 @@ struct dup_in {
     uint64_t n;
 };
 
-__device__ __forceinline__ uint32_t read_len_of(const dup_in& a, uint64_t r) { return a.lens ? min((uint32_t)a.lens[r], a.read_len) : a.read_len; }
-
 // (e, offset, head of the mate): SecretOps.cc:430-441.  Reads without a path get the largest key and sort behind everything.
 __global__ void __launch_bounds__(256) dup_key_kernel(dup_in a, unsigned long long* __restrict__ key, uint32_t* __restrict__ head, uint32_t* __restrict__ id,
                                                       unsigned long long* __restrict__ n_placed, uint32_t* __restrict__ range /* [3][256] max edge, max / min biased offset */) {
@@ -129,15 +127,15 @@ __global__ void __launch_bounds__(256) dup_qsum_kernel(dup_in a, const uint32_t*
     for (int side = 0; side < 2; ++side) {
         const uint64_t x = side ? (r ^ 1ull) : r;
         const uint8_t* q = a.quals + x * a.qstride;
-        const uint32_t L = read_len_of(a, x);
+        const uint32_t L = snk_read_len(a.lens, a.read_len, x);
         for (uint32_t j = 0; j < L; ++j) s += q[j];
     }
     qsum[i] = s;
 }
 
 __device__ bool same_read(const dup_in& a, uint64_t x, uint64_t y) {
-    const uint32_t L = read_len_of(a, x);
-    if (L != read_len_of(a, y)) return false;
+    const uint32_t L = snk_read_len(a.lens, a.read_len, x);
+    if (L != snk_read_len(a.lens, a.read_len, y)) return false;
     const uint32_t full = L >> 4, rest = L & 15u;
     const uint32_t* rx = a.rows + x * a.row_words;
     const uint32_t* ry = a.rows + y * a.row_words;

@@ -21,7 +21,7 @@
 //                        Otherwise (or SNK_EBC_GENERAL_SORT): the 64-bit key edge << 31 | bc over key_bits + 31 bits
 //   ebc_heads_kernel     a key opens a run when (edge, bc) differs from the key before it: run heads per tile of 1024 keys
 //   exclusive scan       of the tile counts (rocPRIM: one value per 1024 keys)
-//   ebc_compact_kernel   rank of every run head = tile base + rank inside the tile (wave prefix by shuffles, wave sums through LDS);
+//   ebc_compact_kernel   rank of every run head = tile base + rank inside the tile (wave prefix by snk_wave_scan_excl, wave sums through LDS);
 //                        ebc[rank] = bc; the head that sees the EDGE change writes ebc_off of its edge and of the empty edges in the gap
 //                        before it, the last key those of the tail (as pidx_offsets_kernel does).  No atomic per key anywhere: a few
 //                        edges hold most keys
@@ -173,18 +173,17 @@ __global__ void __launch_bounds__(EB) ebc_compact_kernel(const uint32_t* __restr
                 prev = k[j];
             }
         }
-        uint32_t incl = c;                          // inclusive prefix inside the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-            if (lane >= (unsigned)o) incl += up;
-        }
-        if (lane == 63) wave_heads[wave] = incl;
+        // the heads in front of this lane inside the wave.  Every wave of the workgroup is here with all its lanes (the tile loop is
+        // uniform, which the barriers below need as well): what snk_wave_scan_excl asks for
+        uint32_t wave_total;
+        const uint32_t excl = snk_wave_scan_excl(c, &wave_total);
+        if (lane == 63) wave_heads[wave] = wave_total;
         __syncthreads();
         uint32_t base = 0;
         for (unsigned w = 0; w < wave; ++w) base += wave_heads[w];
         __syncthreads();                            // (wave_heads is written again in the next tile)
         if (i0 < n) {
-            uint64_t rank = tile_base[tile] + base + incl - c;
+            uint64_t rank = tile_base[tile] + base + excl;
             unsigned long long prev = before;
             for (unsigned j = 0; j < KPT && i0 + j < n; ++j) {
                 if (k[j] != prev) {

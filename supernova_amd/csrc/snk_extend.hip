@@ -60,42 +60,6 @@ constexpr uint8_t C_BACK = 1, C_MANY = 2, C_SLOW = 4;
 // counters
 enum { N_BACK, N_CUT, N_QUAL, N_AMBIG, N_TOO_MANY, N_EXACT, N_COUNTERS = 8 };
 
-struct x_reads {
-    const uint32_t* rows;
-    const uint8_t* quals;
-    const uint16_t* lens;
-    uint32_t row_words, read_len, qstride;
-    uint64_t n;
-};
-struct x_edge { uint64_t o; uint32_t len; uint32_t rc; };       // where the unitig starts, bases, read backwards and complemented
-
-__device__ __forceinline__ uint32_t x_len(const x_reads& R, uint64_t r) { return R.lens ? min((uint32_t)R.lens[r], R.read_len) : R.read_len; }
-__device__ __forceinline__ x_edge x_load(const path_graph& G, int32_t e) {
-    const uint4 q = G.uinfo[2 * (uint64_t)(uint32_t)G.e_unitig[e]];
-    x_edge x;
-    x.o = ((uint64_t)q.y << 32) | q.x; x.len = q.z; x.rc = G.e_rc[e];
-    return x;
-}
-// 16 bases from base p of a packed array, first base in the top bits
-__device__ __forceinline__ uint32_t x_pack16(const uint32_t* P, uint64_t p) {
-    const uint64_t wi = p >> 4;
-    const uint32_t sh = 2u * ((uint32_t)p & 15u);
-    return (uint32_t)(((((uint64_t)P[wi] << 32) | P[wi + 1]) << sh) >> 32);
-}
-// bases i .. i + 15 of an edge, i <= len (behind its end: whatever the packed array holds there; the callers mask)
-__device__ __forceinline__ uint32_t x_edge16(const path_graph& G, const x_edge& x, uint32_t i) {
-    if (!x.rc) return x_pack16(G.upack, UPAD + x.o + i);
-    uint32_t w = __brev(x_pack16(G.upack, UPAD + x.o + x.len - 16 - i));        // (UPAD bases of slack in front: never below the array)
-    w = ((w >> 1) & 0x55555555u) | ((w & 0x55555555u) << 1);
-    return ~w;
-}
-// 16 bases from base p < len of a read (behind the row: zero)
-__device__ __forceinline__ uint32_t x_read16(const uint32_t* row, uint32_t rw, uint32_t p) {
-    const uint32_t wi = p >> 4, sh = 2u * (p & 15u);
-    const uint32_t w0 = row[wi], w1 = wi + 1 < rw ? row[wi + 1] : 0u;
-    return (uint32_t)(((((uint64_t)w0 << 32) | w1) << sh) >> 32);
-}
-__device__ __forceinline__ uint32_t x_read_base(const uint32_t* row, uint32_t p) { return (row[p >> 4] >> (30 - 2 * (p & 15))) & 3u; }
 // the differing bases among the first c <= 16 of two words, as a mask of their top bits' groups
 __device__ __forceinline__ uint32_t x_diff(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t x = a ^ b;
@@ -103,9 +67,9 @@ __device__ __forceinline__ uint32_t x_diff(uint32_t a, uint32_t b, uint32_t c) {
     return c < 16 ? x & ~(0xFFFFFFFFu >> (2 * c)) : x;
 }
 // how many of the `run` bases from rpos of the read and from epos of the edge agree before the first that does not
-__device__ uint32_t x_match(const path_graph& G, const uint32_t* row, uint32_t rw, uint32_t rpos, const x_edge& x, uint32_t epos, uint32_t run) {
+__device__ uint32_t x_match(const path_graph& G, const uint32_t* row, uint32_t rw, uint32_t rpos, const pg_edge& x, uint32_t epos, uint32_t run) {
     for (uint32_t done = 0; done < run; done += 16) {
-        const uint32_t d = x_diff(x_read16(row, rw, rpos + done), x_edge16(G, x, epos + done), min(16u, run - done));
+        const uint32_t d = x_diff(snk_row16(row, rw, rpos + done), pg_edge16(G, x, epos + done), min(16u, run - done));
         if (d) return done + ((uint32_t)__clz((int)d) >> 1);
     }
     return run;
@@ -120,7 +84,7 @@ __device__ int x_leg1(const path_graph& G, int K, const uint32_t* row, uint32_t 
         bool ext = false;
         for (int j = t0; j < t1 && !ext; ++j) {
             const int32_t c = G.to_e[j];
-            const x_edge xc = x_load(G, c);
+            const pg_edge xc = pg_edge_load(G, c);
             const int km = (int)xc.len - (K - 1);
             if (km < 1) continue;
             const int l0 = max(0, off + km), run = (int)xc.len - l0, rp = l0 - off - km;
@@ -135,7 +99,7 @@ __device__ int x_leg1(const path_graph& G, int K, const uint32_t* row, uint32_t 
 // ExtendPath's early returns on the one-edge path [e] at off: 0, or how far the read reaches beyond the edge when it has to enumerate
 __device__ __forceinline__ int x_reach(const path_graph& G, int32_t e, int off, int len) {
     if (off < 0) return 0;
-    const int ext = len - ((int)x_load(G, e).len - off);
+    const int ext = len - ((int)pg_edge_len(G, e) - off);
     if (ext <= 0) return 0;
     const int32_t v = G.vright[e];
     return G.from_off[v + 1] == G.from_off[v] ? 0 : ext;
@@ -146,7 +110,7 @@ template <bool WRITE>
 __device__ int x_leg3(const path_graph& G, int K, const uint32_t* row, uint32_t rw, int len, int32_t e0, int off, const int32_t* chain, int nc, int32_t* out, int cap,
                       uint32_t* flag) {
     int32_t e = e0;
-    x_edge x = x_load(G, e);
+    pg_edge x = pg_edge_load(G, e);
     int rpos = off < 0 ? -off : 0, epos = off < 0 ? 0 : off, pp = 0;
     for (;;) {                                       // do the path's bases match the read's?
         const int run = min(len - rpos, (int)x.len - epos);
@@ -155,7 +119,7 @@ __device__ int x_leg3(const path_graph& G, int K, const uint32_t* row, uint32_t 
         if (rpos == len) return 0;
         if (++pp > nc) break;                        // off the path's last edge, inside the read
         e = chain[pp - 1];
-        x = x_load(G, e);
+        x = pg_edge_load(G, e);
         epos = K - 1;
     }
     int pushed = 0;
@@ -167,12 +131,12 @@ __device__ int x_leg3(const path_graph& G, int K, const uint32_t* row, uint32_t 
             if (m < run || rpos == len) break;
         } else {
             const int32_t v = G.vright[e];
-            const uint32_t b = x_read_base(row, (uint32_t)rpos);
+            const uint32_t b = snk_row_base(row, (uint32_t)rpos);
             int found = 0;
             for (int j = G.from_off[v]; j < G.from_off[v + 1]; ++j) {
                 const int32_t f = G.from_e[j];
-                const x_edge xf = x_load(G, f);
-                if ((int)xf.len >= K && (x_edge16(G, xf, (uint32_t)(K - 1)) >> 30) == b) {
+                const pg_edge xf = pg_edge_load(G, f);
+                if ((int)xf.len >= K && (pg_edge16(G, xf, (uint32_t)(K - 1)) >> 30) == b) {
                     e = f; x = xf; ++found;
                     if (WRITE && pushed < cap) out[pushed] = f;
                     ++pushed;
@@ -188,22 +152,21 @@ __device__ int x_leg3(const path_graph& G, int K, const uint32_t* row, uint32_t 
 }
 
 // the refusals.  range[256] = flags
-__global__ void __launch_bounds__(EB) x_check_kernel(path_graph G, x_reads R, int K, uint32_t back, uint64_t E, const unsigned long long* __restrict__ start,
+__global__ void __launch_bounds__(EB) x_check_kernel(path_graph G, snk_reads_view R, int K, uint32_t back, uint64_t E, const unsigned long long* __restrict__ start,
                                                      const uint32_t* __restrict__ n_edges, const int32_t* __restrict__ offset, const uint32_t* __restrict__ edges,
                                                      uint64_t n_entries, uint32_t* __restrict__ flags) {
     for (uint64_t r = (uint64_t)blockIdx.x * EB + threadIdx.x; r < R.n; r += (uint64_t)gridDim.x * EB) {
+        if (!snk_paths_row_ok(start, n_edges, r, R.n, n_entries)) { atomicOr(flags, F_TABLE); continue; }
         const uint64_t s = start[r], m = n_edges[r];
-        // the table must add up: start[0] = 0, start[r + 1] = start[r] + n_edges[r], start[n_reads] = n_entries (no gaps, no overlaps)
-        if (s > n_entries || m > n_entries - s || start[r + 1] != s + m || (r == 0 && s != 0) || (r + 1 == R.n && s + m != n_entries)) { atomicOr(flags, F_TABLE); continue; }
         if (!m) continue;
         if (m > (uint64_t)X_MAX_PATH) { atomicOr(flags, F_LONG_IN); continue; }
         const int32_t o = offset[r];
         const uint32_t e = edges[s];
-        const int len = (int)x_len(R, r);
+        const int len = (int)snk_read_len(R, r);
         if (e >= E) { atomicOr(flags, F_EDGE0); continue; }
         if (len == 0) { atomicOr(flags, F_LEN0); continue; }
         if (o < -32767 || o > 32767) { atomicOr(flags, F_OFF16); continue; }
-        if (o <= -len || o >= (int)x_load(G, (int32_t)e).len) { atomicOr(flags, F_OFF_RANGE); continue; }
+        if (o <= -len || o >= (int)pg_edge_len(G, (int32_t)e)) { atomicOr(flags, F_OFF_RANGE); continue; }
         if (back && o < 0) {
             const int32_t v = G.vleft[e];
             if (G.to_off[v + 1] != G.to_off[v] && len < -o + K - 1) atomicOr(flags, F_BACK_SHORT);
@@ -213,7 +176,7 @@ __global__ void __launch_bounds__(EB) x_check_kernel(path_graph G, x_reads R, in
 
 struct x_args {
     path_graph G;
-    x_reads R;
+    snk_reads_view R;
     int K;
     uint32_t back;
     const unsigned long long* in_start;
@@ -241,7 +204,7 @@ __global__ void __launch_bounds__(EB) x_classify_kernel(x_args a) {
         const uint32_t m = a.in_n[r];
         if (!m) { a.n_out[r] = 0; a.off[r] = 0; a.e0[r] = -1; a.cls[r] = 0; continue; }
         const uint32_t* row = a.R.rows + r * a.R.row_words;
-        const int len = (int)x_len(a.R, r);
+        const int len = (int)snk_read_len(a.R, r);
         int32_t e = (int32_t)a.in_edges[a.in_start[r]];
         int off = a.in_off[r];
         const int nb = a.back ? x_leg1(G, a.K, row, a.R.row_words, len, e, off) : 0;
@@ -288,7 +251,7 @@ __global__ void __launch_bounds__(EB) x_slow_kernel(x_args a) {
         const uint64_t r = on ? a.slow[base + w] : 0;
         const uint32_t* row = a.R.rows + r * a.R.row_words;
         const uint8_t* qual = a.R.quals + r * a.R.qstride;
-        const int len = on ? (int)x_len(a.R, r) : 0;
+        const int len = on ? (int)snk_read_len(a.R, r) : 0;
         const int32_t e0 = on ? a.e0[r] : 0;
         const int off = on ? a.off[r] : 0;
         const int ext = on ? x_reach(G, e0, off, len) : 0;        // > 0: that is why the read is here
@@ -303,7 +266,7 @@ __global__ void __launch_bounds__(EB) x_slow_kernel(x_args a) {
                 for (int l = G.from_off[y]; l < G.from_off[y + 1] && cnt < X_LIST; ++l) {
                     const int32_t f = G.from_e[l];
                     ed[cnt] = f;
-                    ln[cnt] = min(ln[j] + max((int)x_load(G, f).len - (K - 1), 1), 1 << 20);
+                    ln[cnt] = min(ln[j] + max((int)pg_edge_len(G, f) - (K - 1), 1), 1 << 20);
                     par[cnt] = (uint16_t)j;
                     ++cnt;
                 }
@@ -321,9 +284,9 @@ __global__ void __launch_bounds__(EB) x_slow_kernel(x_args a) {
                     q = 0;
                     for (int i = j; i != 0; i = par[i]) {
                         const int m0 = ln[par[i]], m1 = min(ln[i], ext);
-                        const x_edge x = x_load(G, ed[i]);
+                        const pg_edge x = pg_edge_load(G, ed[i]);
                         for (int m = m0; m < m1; m += 16) {
-                            uint32_t d = x_diff(x_read16(row, a.R.row_words, (uint32_t)(len - ext + m)), x_edge16(G, x, (uint32_t)(K - 1 + m - m0)), (uint32_t)min(16, m1 - m));
+                            uint32_t d = x_diff(snk_row16(row, a.R.row_words, (uint32_t)(len - ext + m)), pg_edge16(G, x, (uint32_t)(K - 1 + m - m0)), (uint32_t)min(16, m1 - m));
                             while (d) {
                                 const int g = __clz((int)d) >> 1;
                                 q += (int)qual[len - ext + m + g];
@@ -382,7 +345,7 @@ __global__ void __launch_bounds__(EB) x_write_kernel(x_args a) {
         if (!m || (a.cls[r] & C_SLOW)) continue;
         int32_t* out = a.edges + a.pos[r];
         out[0] = a.e0[r];
-        if (m > 1) x_leg3<true>(a.G, a.K, a.R.rows + r * a.R.row_words, a.R.row_words, (int)x_len(a.R, r), a.e0[r], a.off[r], nullptr, 0, out + 1, (int)m - 1, a.flags);
+        if (m > 1) x_leg3<true>(a.G, a.K, a.R.rows + r * a.R.row_words, a.R.row_words, (int)snk_read_len(a.R, r), a.e0[r], a.off[r], nullptr, 0, out + 1, (int)m - 1, a.flags);
     }
 }
 
@@ -434,8 +397,7 @@ extern "C" int snk_dev_extend_paths(snk_ctx* ctx, uint32_t K, const snk_dev_read
         for (int32_t v = 0; v < h->n_vertices; ++v)
             if (H.off_from[(size_t)v + 1] - H.off_from[v] > X_MAX_DEG)
                 return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "snk_dev_extend_paths: vertex %d has more than four out-edges (the list of continuations holds %d entries)", v, X_LIST);
-        a.R.rows = (const uint32_t*)in->rows; a.R.quals = (const uint8_t*)in->quals; a.R.lens = (const uint16_t*)in->lens;
-        a.R.row_words = in->row_words; a.R.read_len = in->read_len; a.R.qstride = in->qstride; a.R.n = n;
+        a.R = snk_reads_view_of(in, n);
         a.K = (int)K; a.back = flags & SNK_EXT_BACK;
         a.in_start = (const unsigned long long*)paths->start; a.in_n = (const uint32_t*)paths->n_edges; a.in_off = (const int32_t*)paths->offset;
         a.in_edges = (const uint32_t*)paths->edges;

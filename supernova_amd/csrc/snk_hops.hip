@@ -118,43 +118,25 @@ __host__ __device__ inline bool h_agrees(const int32_t* x, int n, const h_mem& y
     return true;
 }
 
-__device__ __forceinline__ int h_kmers(const path_graph& G, int K, int32_t e) { return (int)G.uinfo[2 * (uint64_t)(uint32_t)G.e_unitig[e]].z - K + 1; }
-
 __global__ void __launch_bounds__(HB) h_edge_kernel(path_graph G, int K, uint64_t E, int32_t* __restrict__ km, uint8_t* __restrict__ fl, unsigned long long* __restrict__ cnt) {
     uint32_t n_sink = 0;
     for (uint64_t e = (uint64_t)blockIdx.x * HB + threadIdx.x; e < E; e += (uint64_t)gridDim.x * HB) {
-        km[e] = h_kmers(G, K, (int32_t)e);
+        km[e] = (int32_t)pg_edge_len(G, (int32_t)e) - K + 1;
         bool sink = true, source = true;
         const int32_t v = G.vright[e], u = G.vleft[e];
         for (int l = G.from_off[v]; l < G.from_off[v + 1]; ++l) {      // Closomatic.cc:43-53
             const int32_t w = G.from_v[l];
-            if (G.from_off[w + 1] - G.from_off[w] > 0 || G.to_off[w + 1] - G.to_off[w] > 1 || h_kmers(G, K, G.from_e[l]) > MAX_DIST_TO_END) sink = false;
+            if (G.from_off[w + 1] - G.from_off[w] > 0 || G.to_off[w + 1] - G.to_off[w] > 1 || (int)pg_edge_len(G, G.from_e[l]) - K + 1 > MAX_DIST_TO_END) sink = false;
         }
         for (int l = G.to_off[u]; l < G.to_off[u + 1]; ++l) {          // :84-94
             const int32_t w = G.to_v[l];
-            if (G.to_off[w + 1] - G.to_off[w] > 0 || G.from_off[w + 1] - G.from_off[w] > 1 || h_kmers(G, K, G.to_e[l]) > MAX_DIST_TO_END) source = false;
+            if (G.to_off[w + 1] - G.to_off[w] > 0 || G.from_off[w + 1] - G.from_off[w] > 1 || (int)pg_edge_len(G, G.to_e[l]) - K + 1 > MAX_DIST_TO_END) source = false;
         }
         fl[e] = (uint8_t)((sink ? FL_SINK : 0) | (source ? FL_SOURCE : 0));
         n_sink += sink;
     }
     for (int o = 32; o > 0; o >>= 1) n_sink += (uint32_t)__shfl_xor((int)n_sink, o);
     if ((threadIdx.x & 63) == 0 && n_sink) atomicAdd(&cnt[C_SINK], (unsigned long long)n_sink);
-}
-
-// a wave's lanes each have c items for a list: the place of the lane's first one, the wave's sum taken from *cursor with one atomic.
-// Reached by whole waves.
-__device__ __forceinline__ unsigned long long h_wave_place(uint32_t c, unsigned long long* cursor) {
-    const unsigned lane = threadIdx.x & 63;
-    uint32_t incl = c;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = (uint32_t)__shfl_up((int)incl, o);
-        if (lane >= (unsigned)o) incl += up;
-    }
-    const uint32_t total = (uint32_t)__shfl((int)incl, 63);
-    unsigned long long base = 0;
-    if (lane == 63 && total) base = atomicAdd(cursor, (unsigned long long)total);
-    base = (unsigned long long)__shfl((long long)base, 63);
-    return base + incl - c;
 }
 
 // keys == NULL: count only.  cap: the keys the first run counted -- nothing is written behind them.
@@ -182,7 +164,7 @@ __global__ void __launch_bounds__(HB) h_keys_kernel(h_view V, const uint8_t* __r
                 }
             }
         }
-        unsigned long long at = h_wave_place(c, cursor);
+        unsigned long long at = snk_wave_alloc(cursor, c);          // (every lane of the wave is here: see the loop)
         if (!keys || !c) continue;
         const int32_t cls = V.bc[r];
         for (int j = 0; j < n; ++j) {

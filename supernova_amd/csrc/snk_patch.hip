@@ -243,12 +243,6 @@ struct w_args {
     int32_t* to3;
     uint32_t* flags;
 };
-__device__ __forceinline__ uint32_t w_new_len(const path_graph& G, int32_t e) { return G.uinfo[2 * (uint64_t)(uint32_t)G.e_unitig[e]].z; }
-__device__ __forceinline__ uint32_t w_new_base(const path_graph& G, int32_t e, uint32_t i) {
-    const uint32_t u = (uint32_t)G.e_unitig[e];
-    const uint64_t o = G.uoff[u], len = G.uoff[u + 1] - o;
-    return G.e_rc[e] ? 3u - (G.ubases[o + len - 1 - i] & 3u) : G.ubases[o + i] & 3u;
-}
 // Pather_sleek::operator() (kmers/BigKPather.cc:594-630) for old edge e; WRITE: the edges go to out[0 .. n3[e])
 template <int K, bool WRITE>
 __global__ void __launch_bounds__(PB) w_walk_kernel(w_args a) {
@@ -284,14 +278,14 @@ __global__ void __launch_bounds__(PB) w_walk_kernel(w_args a) {
         for (int32_t b = a.G.from_off[v]; b < a.G.from_off[v + 1] && next < 0; ++b) {
             const int32_t c2 = a.G.from_e[b];
             bool same = true;
-            for (uint32_t q = 0; q < (uint32_t)K && same; ++q) same = w_new_base(a.G, c2, q) == p_edge_base(a.old, (int32_t)e, ro + q);
+            for (uint32_t q = 0; q < (uint32_t)K && same; ++q) same = pg_edge_base(a.G, c2, q) == p_edge_base(a.old, (int32_t)e, ro + q);
             if (same) next = c2;
         }
         if (next < 0) { atomicOr(a.flags, F_WALK); break; }
         cur = next;
         if (WRITE) out[n] = cur;
         ++n;
-        edge_rem = w_new_len(a.G, cur);
+        edge_rem = pg_edge_len(a.G, cur);
     }
     if (!WRITE) { a.n3[e] = n; a.left3[e] = (int32_t)offset; }
 }
@@ -321,9 +315,7 @@ struct t_args {
 };
 __global__ void __launch_bounds__(PB) t_check_kernel(t_args a) {
     for (uint64_t r = (uint64_t)blockIdx.x * PB + threadIdx.x; r < a.n; r += (uint64_t)gridDim.x * PB) {
-        const uint64_t s = a.in_start[r], m = a.in_n[r];
-        // the table must add up: start[0] = 0, start[r + 1] = start[r] + n_edges[r], start[n_reads] = n_entries
-        if (s > a.n_entries || m > a.n_entries - s || a.in_start[r + 1] != s + m || (r == 0 && s != 0) || (r + 1 == a.n && s + m != a.n_entries)) atomicOr(a.flags, F_TABLE);
+        if (!snk_paths_row_ok(a.in_start, a.in_n, r, a.n, a.n_entries)) atomicOr(a.flags, F_TABLE);
     }
     for (uint64_t i = (uint64_t)blockIdx.x * PB + threadIdx.x; i < a.n_entries; i += (uint64_t)gridDim.x * PB)
         if (a.in_edges[i] >= a.E_old) atomicOr(a.flags, F_EDGE);
@@ -355,7 +347,7 @@ __global__ void __launch_bounds__(PB) t_first_kernel(t_args a) {
             const long long start = (long long)a.in_off[r] + a.left3[e];
             const uint64_t t0 = a.to3_off[e], t1 = a.to3_off[e + 1];
             if (t0 == t1) cnt.add(N_CLEARED);
-            else if (start < (long long)w_new_len(a.G, a.to3[t0])) {
+            else if (start < (long long)pg_edge_len(a.G, a.to3[t0])) {
                 e_out = a.to3[t0]; off_out = (int32_t)start; n_out = 1;
                 cnt.add(N_FIRST);
             } else {
@@ -398,8 +390,8 @@ __global__ void __launch_bounds__(PB) t_later_kernel(t_args a) {
             for (uint64_t t = best; t < nv; ++t) q[nq++] = v[t];
         }
         uint64_t trim = 0;
-        while (start >= (long long)w_new_len(a.G, q[trim])) {
-            start -= (long long)w_new_len(a.G, q[trim]) - (a.K - 1);
+        while (start >= (long long)pg_edge_len(a.G, q[trim])) {
+            start -= (long long)pg_edge_len(a.G, q[trim]) - (a.K - 1);
             if (++trim == nq) break;
         }
         if (trim == nq) { cnt.add(N_CLEARED); continue; }

@@ -122,13 +122,6 @@ __global__ void __launch_bounds__(256) ublk_kernel(const uint64_t* __restrict__ 
     while (hi - lo > 1) { const uint64_t mid = (lo + hi) >> 1; if (uoff[mid] <= p) lo = mid; else hi = mid; }
     ublk[b] = (uint32_t)lo;
 }
-// 16 bases starting at base p of a packed array (two words, one funnel shift)
-__device__ __forceinline__ uint32_t packed16(const uint32_t* P, uint64_t p) {
-    const uint64_t wi = p >> 4;
-    const uint32_t sh = 2u * ((uint32_t)p & 15u);
-    const uint32_t w0 = P[wi], w1 = P[wi + 1];
-    return (uint32_t)(((((uint64_t)w0 << 32) | w1) << sh) >> 32);
-}
 
 template <int K>
 __global__ void __launch_bounds__(256) dict_build_kernel(const uint64_t* __restrict__ uoff, const uint8_t* __restrict__ ubases, uint64_t U, uint64_t total,
@@ -252,7 +245,7 @@ __global__ void __launch_bounds__(256) mm_hist_kernel(const uint32_t* __restrict
 // the ordering keys of a read's 16-mers, by the lanes of its group (keys[i]: the 16-mer at base i)
 __device__ __forceinline__ void mm_read_keys(const uint32_t* row, uint32_t n, uint32_t cap, int sub, int gs, uint32_t* keys) {
     const uint32_t nk = n >= 16u ? (n - 15u < cap ? n - 15u : cap) : 0u;
-    for (uint32_t i = (uint32_t)sub; i < nk; i += (uint32_t)gs) { uint32_t o; keys[i] = mm_key(packed16(row, i), &o); }
+    for (uint32_t i = (uint32_t)sub; i < nk; i += (uint32_t)gs) { uint32_t o; keys[i] = mm_key(snk_packed16(row, i), &o); }
 }
 // dict_find through the minimiser index: the k-mer at base `pos` of the read (keys: mm_read_keys of that read).  Always exact.
 template <int K>
@@ -261,7 +254,7 @@ __device__ __forceinline__ bool mm_find(const path_graph& G, const uint32_t* row
     uint32_t best = keys[pos], bq = 0;
     for (uint32_t j = 1; j < W; ++j) { const uint32_t k = keys[pos + j]; if (k < best) { best = k; bq = j; } }
     if (G.idx_dbg == 1) return best == 0x12345u && bq == 99u;
-    const uint32_t x = packed16(row, pos + bq), rx = snk_rev2_32(~x);
+    const uint32_t x = snk_packed16(row, pos + bq), rx = snk_rev2_32(~x);
     const uint32_t orient_r = rx < x ? 1u : 0u;
     const uint32_t b = best >> (32u - G.mdir_bits);
     const uint32_t lo = G.mdir[b], hi = G.mdir[b + 1];
@@ -312,15 +305,6 @@ __device__ __forceinline__ uint32_t p_rc(const ppart& p) { return p.off_rc >> 31
 __device__ __forceinline__ bool p_same_edge(const ppart& a, const ppart& b) { return a.unitig == b.unitig && p_rc(a) == p_rc(b); }
 __device__ __forceinline__ ppart make_gap(uint32_t len) { ppart g; g.unitig = 0; g.off_rc = 0; g.len = len; g.elen = 0; return g; }
 
-__device__ __forceinline__ uint32_t u_len(const path_graph& G, uint32_t u) { return G.uinfo[2 * (uint64_t)u].z; }
-__device__ __forceinline__ uint32_t u_base(const path_graph& G, uint32_t u, uint32_t rc, uint32_t i) {
-    const uint4 q = G.uinfo[2 * (uint64_t)u];
-    const uint8_t* b = G.ubases + (((uint64_t)q.y << 32) | q.x);
-    return rc ? (uint32_t)(b[q.z - 1 - i] ^ 3u) & 3u : (uint32_t)b[i] & 3u;
-}
-__device__ __forceinline__ uint32_t e_len(const path_graph& G, int32_t e) { return u_len(G, (uint32_t)G.e_unitig[e]); }
-__device__ __forceinline__ int to_size(const path_graph& G, int32_t v) { return G.to_off[v + 1] - G.to_off[v]; }
-__device__ __forceinline__ int from_size(const path_graph& G, int32_t v) { return G.from_off[v + 1] - G.from_off[v]; }
 __device__ __forceinline__ int32_t part_edge(const path_graph& G, const ppart& p) { const uint4 q = G.uinfo[2 * (uint64_t)p.unitig + 1]; return (int32_t)(p_rc(p) ? q.y : q.x); }
 
 // PathPart::isConformingCapturedGap :659-666 (unsigned arithmetic as written)
@@ -335,24 +319,23 @@ __device__ bool conforming_gap(const ppart* p, uint32_t max_jitter) {
 template <int K>
 __device__ bool joinable(const path_graph& G, const ppart& a, const ppart& b) {
     if (a.unitig == b.unitig) return true;
-    const uint32_t la = u_len(G, a.unitig), lb = u_len(G, b.unitig);
+    const uint32_t la = pg_unitig_len(G, a.unitig), lb = pg_unitig_len(G, b.unitig);
     for (uint32_t q = 0; q + 1 < (uint32_t)K; ++q)
-        if (u_base(G, a.unitig, p_rc(a), la - (K - 1) + q) != u_base(G, b.unitig, p_rc(b), lb - (K - 1) + q)) return false;
+        if (pg_unitig_base(G, a.unitig, p_rc(a), la - (K - 1) + q) != pg_unitig_base(G, b.unitig, p_rc(b), lb - (K - 1) + q)) return false;
     return true;
 }
-__device__ __forceinline__ uint32_t read_base(const uint32_t* row, uint32_t p) { return (row[p >> 4] >> (30 - 2 * (p & 15))) & 3u; }
 // scoreLeftOverlap / scoreRightOverlap, ExtendReadPath.cc:15-106: decay 0.2, Q2 counted as Q20, 10 per read base left over
 template <int K>
 __device__ uint32_t score_overlap(const path_graph& G, const uint32_t* row, const uint8_t* __restrict__ quals /* the read's row in HBM */, uint32_t n, uint32_t start, int32_t e,
                                   bool left) {
-    const uint32_t esz = e_len(G, e), u = (uint32_t)G.e_unitig[e], erc = G.e_rc[e];
+    const uint32_t esz = pg_edge_len(G, e), u = (uint32_t)G.e_unitig[e], erc = G.e_rc[e];
     uint32_t qsum = 0, penalty = 0, steps = 0;
     for (;; ++steps) {
         if (steps >= start) break;
         uint32_t rp, ep;
         if (!left) { rp = n - start + steps; ep = K - 1 + steps; if (ep >= esz) break; }
         else { rp = start - 1 - steps; if (steps + K > esz) break; ep = esz - K - steps; }
-        if (read_base(row, rp) != u_base(G, u, erc, ep)) {
+        if (snk_row_base(row, rp) != pg_unitig_base(G, u, erc, ep)) {
             const uint32_t q = quals[rp] == 2 ? 20u : (uint32_t)quals[rp];
             penalty += q;
             qsum += penalty;
@@ -370,7 +353,7 @@ __device__ bool extend_once(const path_graph& G, int32_t* path, int* np, int pma
         last_gap = (uint64_t)(-(int64_t)*offset);
     } else {
         int32_t g = (int32_t)n + *offset;
-        for (int i = 0; i < *np; ++i) g -= (int32_t)(e_len(G, path[i]) - K + 1);
+        for (int i = 0; i < *np; ++i) g -= (int32_t)(pg_edge_len(G, path[i]) - K + 1);
         g -= K - 1;
         if (g < 10) return false;
         last_gap = (uint64_t)g;
@@ -385,19 +368,19 @@ __device__ bool extend_once(const path_graph& G, int32_t* path, int* np, int pma
     bool short_same = true;
     int32_t short_dest = -1;
     for (int i = 0; i < ne; ++i) {
-        const bool hanging = left ? (to_size(G, vd[i]) == 0 && from_size(G, vd[i]) == 1) : (from_size(G, vd[i]) == 0 && to_size(G, vd[i]) == 1);
-        const bool lng = (uint64_t)e_len(G, ee[i]) - (K - 1) >= last_gap;
+        const bool hanging = left ? (pg_to_size(G, vd[i]) == 0 && pg_from_size(G, vd[i]) == 1) : (pg_from_size(G, vd[i]) == 0 && pg_to_size(G, vd[i]) == 1);
+        const bool lng = (uint64_t)pg_edge_len(G, ee[i]) - (K - 1) >= last_gap;
         nlong += lng ? 1 : 0;
         if (!lng && !hanging) { if (nshort && vd[i] != short_dest) short_same = false; short_dest = vd[i]; ++nshort; }
     }
     if (ne != 1 && nshort > 0) {
         if (nlong > 0 || !short_same) return false;
-        if ((left ? to_size(G, short_dest) : from_size(G, short_dest)) != 1) return false;
+        if ((left ? pg_to_size(G, short_dest) : pg_from_size(G, short_dest)) != 1) return false;
     }
     int32_t least_edge = -1;
     uint32_t least = 0xFFFFFFFFu;
     for (int i = 0; i < ne; ++i) {
-        const bool hanging = left ? (to_size(G, vd[i]) == 0 && from_size(G, vd[i]) == 1) : (from_size(G, vd[i]) == 0 && to_size(G, vd[i]) == 1);
+        const bool hanging = left ? (pg_to_size(G, vd[i]) == 0 && pg_from_size(G, vd[i]) == 1) : (pg_from_size(G, vd[i]) == 0 && pg_to_size(G, vd[i]) == 1);
         if (!hanging || ne == 1) {
             const uint32_t sc = score_overlap<K>(G, row, quals, n, (uint32_t)last_gap, ee[i], left);
             if (sc < least) { least_edge = ee[i]; least = sc; }
@@ -408,7 +391,7 @@ __device__ bool extend_once(const path_graph& G, int32_t* path, int* np, int pma
     if (left) {
         for (int i = *np; i > 0; --i) path[i] = path[i - 1];
         path[0] = least_edge;
-        *offset += (int32_t)(e_len(G, least_edge) - K + 1);
+        *offset += (int32_t)(pg_edge_len(G, least_edge) - K + 1);
     } else path[*np] = least_edge;
     ++*np;
     return true;
@@ -671,7 +654,7 @@ __global__ void __launch_bounds__(256, MODE == 2 ? 1 : SNK_PATH_OCC) path_kernel
                         if (j >= Lmax) stop = true;
                         else {
                             const uint32_t vl = Lmax - j < 16u ? Lmax - j : 16u;
-                            const uint32_t xr = packed16(row, rs + j);
+                            const uint32_t xr = snk_packed16(row, rs + j);
                             uint32_t xu = (uint32_t)(((((uint64_t)w0[c] << 32) | w1[c]) << wsh[c]) >> 32);
                             if (rc) xu = snk_rev2_32(~xu);
                             const uint32_t d = xr ^ xu;

@@ -1,6 +1,8 @@
 // snk_pathgraph.h -- the per-edge and per-unitig device tables of a graph that the stages working on (reads, graph, paths) share:
 // the pather (snk_path.hip), which adds its k-mer dictionary or minimiser index to them, and the path extension (snk_extend.hip),
-// which needs nothing else.  One function fills them (snk_path.hip); the From / To lists are those of snk_hbv_lists_build.
+// which needs nothing else.  One function fills them (snk_path.hip); the From / To lists are those of snk_hbv_lists_build.  One set of
+// device accessors reads them (pg_*, below the struct): the pather, the extension, MarkBads, the patch insertion, FindEdgePairs and the
+// gap closures use these and keep no copy of their own.  (The verifier, snk_check.hip, shares nothing with what it verifies.)
 #pragma once
 #include <stdint.h>
 
@@ -43,6 +45,51 @@ struct path_graph {            // device arrays
     uint32_t mdir_bits;
     uint32_t idx_dbg;          // SNK_PATH_IDX_DBG (timing aid, results invalid): 1 = window minimum only, 2 = + directory and entries, 3 = + base comparison (no unitig-bounds check)
 };
+
+#if defined(__HIPCC__)
+// ---- how a kernel reads the tables.  An HBV edge is a unitig read forward or reverse-complemented: edge-keyed accessors go through
+// e_unitig / e_rc, unitig-keyed ones take the orientation as an argument.  Every stage reads the graph through these.
+struct pg_edge { uint64_t o; uint32_t len; uint32_t rc; };      // where the unitig starts in the concatenation, its bases, read backwards and complemented
+
+// (I: the edge id as the caller holds it -- int32_t from the graph's lists, uint32_t from a path table whose ids were checked as
+// unsigned.  It indexes as that type, so no caller pays for a conversion.)
+template <typename I>
+__device__ __forceinline__ pg_edge pg_edge_load(const path_graph& G, I e) {
+    const uint4 q = G.uinfo[2 * (uint64_t)(uint32_t)G.e_unitig[e]];
+    pg_edge x;
+    x.o = ((uint64_t)q.y << 32) | q.x; x.len = q.z; x.rc = G.e_rc[e];
+    return x;
+}
+__device__ __forceinline__ uint32_t pg_unitig_len(const path_graph& G, uint32_t u) { return G.uinfo[2 * (uint64_t)u].z; }
+template <typename I>
+__device__ __forceinline__ uint32_t pg_edge_len(const path_graph& G, I e) { return pg_unitig_len(G, (uint32_t)G.e_unitig[e]); }      // bases; k-mers: - K + 1
+// bases i .. i + 15 of an edge in its orientation, first base in the top bits, i <= len (behind its end: whatever the packed array
+// holds there; the callers mask).  The reverse-complement branch reads the 16 bases that END at base len - i of the unitig, so for
+// i > len - 16 it starts up to 16 bases IN FRONT of the unitig: of the first unitig that is in front of the array's first base, which
+// is why upack has UPAD bases of slack in front (and why the position is UPAD + ..., never below zero).  Reversed as 2-bit groups
+// (brev, then the bits of every pair swapped back) and complemented.
+__device__ __forceinline__ uint32_t pg_edge16(const path_graph& G, const pg_edge& x, uint32_t i) {
+    if (!x.rc) return snk_packed16(G.upack, UPAD + x.o + i);
+    uint32_t w = __brev(snk_packed16(G.upack, UPAD + x.o + x.len - 16 - i));
+    w = ((w >> 1) & 0x55555555u) | ((w & 0x55555555u) << 1);
+    return ~w;
+}
+// base i of an edge in its orientation, from the byte array through uoff
+__device__ __forceinline__ uint32_t pg_edge_base(const path_graph& G, int32_t e, uint32_t i) {
+    const uint32_t u = (uint32_t)G.e_unitig[e];
+    const uint64_t o = G.uoff[u], len = G.uoff[u + 1] - o;
+    return G.e_rc[e] ? 3u - (G.ubases[o + len - 1 - i] & 3u) : G.ubases[o + i] & 3u;
+}
+// base i of unitig u read forward (rc = 0) or reverse-complemented, through the uinfo record: what the pather's sequential part reads
+// (it holds (unitig, rc) in its path parts and has the record in cache)
+__device__ __forceinline__ uint32_t pg_unitig_base(const path_graph& G, uint32_t u, uint32_t rc, uint32_t i) {
+    const uint4 q = G.uinfo[2 * (uint64_t)u];
+    const uint8_t* b = G.ubases + (((uint64_t)q.y << 32) | q.x);
+    return rc ? (uint32_t)(b[q.z - 1 - i] ^ 3u) & 3u : (uint32_t)b[i] & 3u;
+}
+__device__ __forceinline__ int pg_to_size(const path_graph& G, int32_t v) { return G.to_off[v + 1] - G.to_off[v]; }            // in-edges of a vertex
+__device__ __forceinline__ int pg_from_size(const path_graph& G, int32_t v) { return G.from_off[v + 1] - G.from_off[v]; }      // out-edges
+#endif
 
 // the graph tables on the host: what the asynchronous uploads read.  The entry point declares them in front of the frame, which waits
 // for the stream before they are let go of, whichever way the call ends.

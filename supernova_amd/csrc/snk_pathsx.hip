@@ -65,10 +65,9 @@ __global__ void __launch_bounds__(XB) px_size_kernel(const unsigned long long* _
         const uint64_t r = base + threadIdx.x;
         bool empty = false, wrap = false;
         if (r < n_reads) {
-            const uint64_t s = start[r], m = n_edges[r];
+            const uint64_t m = n_edges[r];
             uint32_t n = (uint32_t)m;
-            // the table must add up: start[0] = 0, start[r + 1] = start[r] + n_edges[r], start[n_reads] = n_entries (no gaps, no overlaps)
-            if (s > n_entries || m > n_entries - s || start[r + 1] != s + m || (r == 0 && s != 0) || (r + 1 == n_reads && s + m != n_entries)) {
+            if (!snk_paths_row_ok(start, n_edges, r, n_reads, n_entries)) {
                 atomicOr(flags, F_TABLE);
                 n = 0;
             }
