@@ -461,7 +461,7 @@ uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components,
  * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
 uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps, snk_dev_delete_edges, snk_dev_hanging_ends and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -928,6 +928,86 @@ typedef struct snk_dev_patched {
 int snk_dev_patch_paths(snk_ctx* ctx, uint32_t K, uint64_t n_old_unitigs, const void* d_old_unitig_off, const void* d_old_unitig_bases, const snk_hbv* h_old,
                         uint64_t n_new_unitigs, const void* d_new_unitig_off, const void* d_new_unitig_bases, const snk_hbv* h_new, const snk_dev_paths* paths,
                         snk_dev_patched* out, void* stream, char* err, size_t errcap);
+
+/* ---- graph edits: DeleteEdges + Cleanup, and the hanging-end trim ------------------------------------------------------
+ * Every simplification step of the reference after DF picks edges, deletes them (hbv.DeleteEdgesParallel(dels)) and cleans up
+ * (Cleanup, lib/assembly/src/paths/long/large/GapToyTools.cc:1287-1302).  snk_dev_delete_edges is that pair; snk_dev_hanging_ends is
+ * the first selection the reference runs through it, the hanging-end rule of StageTrim (10X/runstages/RunStages.cc:91-146).
+ *
+ * snk_dev_delete_edges, in the reference's order:
+ *   1 the edges of dels (any order, duplicates allowed, closed under inv) leave the From / To lists;
+ *   2 every path is cut at its first deleted edge (GapToyTools.cc:1290-1297); a path cut to nothing keeps its offset;
+ *   3 RemoveUnneededVertices2 (GapToyTools3.cc:487-667): a vertex with one in-edge and one out-edge whose predecessor and successor
+ *     vertices differ (:520-527) is unneeded; from the highest such vertex down (:541-563) the maximal chain through it gives a run
+ *     eleft .. eright; a run is merged with its reverse complement when eleft < inv[eright] (:571) -- a run that is its own reverse
+ *     complement never is -- and a circle made only of unneeded vertices comes out as eleft == eright = the edge that leaves its highest
+ *     vertex, which is created again under a new id when it is smaller than its inverse.  The runs are taken from the back of the list
+ *     (:607-633): pair i gives the inverse run E_old + 2 i and the canonical run E_old + 2 i + 1; a new edge's bases are the TrimCat of
+ *     its run; offsets[e] = the k-mers of the run in front of e.  Paths (:653-664): offset += offsets[first edge], every edge renumbered,
+ *     consecutive equal ids collapse to one;
+ *   4 CleanupCore (GapToyTools.cc:1253-1285): the surviving edges are compacted in id order (new edges behind the old ones), inv and
+ *     the paths renumbered, vertices without an edge removed and the rest compacted in id order.
+ * The From / To lists of the result are those snk_hbv_lists_build derives (AddEdge inserts by upper_bound, deletions keep the order), so
+ * snk_write_hbv / snk_write_hbx on the result write the reference's files.
+ *
+ * Arguments: the graph as every stage after the graph takes it (d_unitig_off u64[n_unitigs + 1] and d_unitig_bases on the device, h on
+ * the host with bvcomp_order or NULL), inv i32[h->n_edges] on the host, the paths on the device, dels on the host.  flags must be 0.
+ * Result: device unitig arrays with ONE unitig per pair {e, inv[e]} of the new graph, numbered by the pair's smaller edge id and stored as
+ * that edge reads (a self-inverse edge once); out->h over them (bvcomp_order NULL), out->inv, out->edge_map / edge_koff per OLD edge (its
+ * new id or -1; its k-mer offset inside the new edge) on the host -- all four freed by snk_dev_edit_free --; the rewritten paths on the
+ * device.  The device arrays are context memory, valid until the context's next top-level call; the result goes into a second
+ * snk_dev_delete_edges, snk_dev_paths_zip, snk_dev_paths_index and snk_dev_extend_paths as it is.
+ * The path rewrite and the copy of the bases run on the device; the vertex classes, the runs and the id hand-out run on the host (one
+ * pass over the edges, the reference's own walk).
+ * SNK_E_ARG: an edge id in dels or in a path outside [0, E) (the reference cuts such a path; every stage here refuses the id), inv that
+ * is not an involution, dels not closed under inv, start / n_edges that do not add up, a path whose consecutive edges do not meet at
+ * a vertex (the reference's Validate asserts), flags other than 0.  The result rule of the stages after the graph applies. */
+typedef struct snk_dev_edit {
+    uint64_t n_unitigs, unitig_total_bases;
+    const void* unitig_off;       /* u64[n_unitigs + 1], device */
+    const void* unitig_bases;     /* u8 codes, device */
+    snk_hbv h;                    /* host */
+    int32_t* inv;                 /* host i32[h.n_edges] */
+    snk_dev_paths paths;          /* device; path_ms = the rewrite */
+    uint64_t n_old_edges;
+    int32_t* edge_map;            /* host i32[n_old_edges]: new id, -1 = deleted */
+    int32_t* edge_koff;           /* host i32[n_old_edges]: k-mers of the new edge in front of the old one */
+    uint64_t n_deleted;           /* distinct edges of dels */
+    uint64_t n_runs;              /* new edges made (a run and its inverse count as two) */
+    uint64_t n_absorbed;          /* old edges that went into them */
+    uint64_t max_run;             /* edges of the longest run */
+    uint64_t n_truncated;         /* paths cut at a deleted edge */
+    uint64_t n_emptied;           /* ... of which cut to nothing */
+    uint64_t n_collapsed;         /* path entries dropped because they repeat the new edge in front of them */
+    float ms, graph_ms;           /* HIP events: the whole call; wall clock of the host's part inside it */
+    uint64_t reserved[4];
+} snk_dev_edit;
+int snk_dev_delete_edges(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const int32_t* inv,
+                         const snk_dev_paths* paths, const int32_t* dels, uint64_t n_dels, uint32_t flags, snk_dev_edit* out, void* stream, char* err, size_t errcap);
+void snk_dev_edit_free(snk_dev_edit* r);      /* the host arrays; the device arrays are the context's */
+/* snk_dev_hanging_ends: rs[e] = over all path entries x, (x == e) + (inv[x] == e) (RunStages.cc:94-119: a self-inverse edge counts
+ * twice per entry, unlike a.countsb); an edge with rs[e] == 0 and at most max_kmers k-mers (the reference: 200) is deleted together
+ * with inv[e] when its left vertex has no in-edge and exactly one out-edge, or its right vertex has no out-edge and exactly one
+ * in-edge (:128-141).  The counts are made without atomics on global memory: up to SNK_HANG_LDS_MAX edges every workgroup counts its
+ * share of the entries in LDS and the per-workgroup tables are summed; above that the entries are sorted and every edge finds its run.
+ * The call chooses by size; flags may force either leg (tests).  support: i32[E] on the device (context memory); dels: ascending,
+ * distinct, on the host, freed by snk_host_free.  SNK_E_ARG as for snk_dev_delete_edges (the entries' ids, inv, the path table; the LDS
+ * leg forced above SNK_HANG_LDS_MAX edges). */
+#define SNK_HANG_LDS 1u
+#define SNK_HANG_SORT 2u
+#define SNK_HANG_LDS_MAX 16384u
+typedef struct snk_dev_hanging {
+    uint64_t n_hbv_edges, n_entries;
+    const void* support;          /* i32[n_hbv_edges], device */
+    uint64_t n_dels;
+    int32_t* dels;                /* host */
+    uint64_t n_unsupported;       /* edges with rs == 0 */
+    uint32_t leg;                 /* SNK_HANG_LDS or SNK_HANG_SORT: the one that ran */
+    float ms;
+    uint64_t reserved[4];
+} snk_dev_hanging;
+int snk_dev_hanging_ends(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const int32_t* inv,
+                         const snk_dev_paths* paths, uint32_t max_kmers, uint32_t flags, snk_dev_hanging* out, void* stream, char* err, size_t errcap);
 
 /* ---- the edge -> barcode lists: a.ebcx ------------------------------------------------------------------------------
  * computeEdgeToBarcodeX, lib/assembly/src/10X/PathsIndex.cc:297-358 (StageEBC, 10X/runstages/RunStages.cc:31-38): per HBV edge the

@@ -328,6 +328,50 @@ class PatchResult:
             _lib.call(self._e.lib.snk_write_hbx, str(path_hbx).encode(), *unitigs)
 
 
+class EditResult:
+    """What Engine.delete_edges leaves: the edited graph and the read paths on it, in tensors and arrays this object owns (they outlive the
+    engine's later calls).  h: a lib.SnkHbv over the new unitigs (one per pair {e, inv[e]}, numbered by the pair's smaller edge id; bvcomp_order
+    None), its arrays held by this object; unitig_off i64[U + 1], unitig_bases u8[], offset / n_edges / start / edges: tensors on the device;
+    inv, edge_map, edge_koff: numpy; stats: counters and times.  graph and paths are the tuples Engine.delete_edges, hanging_ends and
+    trim_hanging_ends take; h, the unitig tensors and the path tensors go into zip_paths, extend_paths and the paths index as they are."""
+
+    def __init__(self, engine: "Engine", K: int, raw: "_lib.SnkDevEdit", take):
+        self._e, self.K = engine, K
+        E, N, U, n, tot = int(raw.h.n_edges), int(raw.h.n_vertices), int(raw.n_unitigs), int(raw.paths.n_reads), int(raw.paths.n_edges_total)
+        host = lambda p, m, dt: (np.array(np.ctypeslib.as_array(p, shape=(m,)), dtype=dt, copy=True) if m else np.zeros(0, dt))
+        self._arrays = dict(v_left=host(raw.h.v_left, E, np.int32), v_right=host(raw.h.v_right, E, np.int32), src_unitig=host(raw.h.src_unitig, E, np.int32),
+                            is_rc=host(raw.h.is_rc, E, np.uint8), fwd_xlat=host(raw.h.fwd_xlat, U, np.int32), rev_xlat=host(raw.h.rev_xlat, U, np.int32))
+        self.h = _lib.SnkHbv()
+        self.h.n_vertices, self.h.n_edges = N, E
+        for k, a in self._arrays.items():
+            setattr(self.h, k, a.ctypes.data_as(C.POINTER(C.c_uint8 if k == "is_rc" else C.c_int32)))
+        self.inv = host(raw.inv, E, np.int32)
+        self.edge_map, self.edge_koff = host(raw.edge_map, int(raw.n_old_edges), np.int32), host(raw.edge_koff, int(raw.n_old_edges), np.int32)
+        self.unitig_off, self.unitig_bases = take(raw.unitig_off, U + 1, torch.int64), take(raw.unitig_bases, int(raw.unitig_total_bases), torch.uint8)
+        self.offset, self.n_edges, self.start, self.edges = take(raw.paths.offset, n, torch.int32), take(raw.paths.n_edges, n, torch.int32), \
+            take(raw.paths.start, n + 1, torch.int64), take(raw.paths.edges, tot, torch.int32)
+        self.stats = dict(n_deleted=int(raw.n_deleted), n_runs=int(raw.n_runs), n_absorbed=int(raw.n_absorbed), max_run=int(raw.max_run), n_truncated=int(raw.n_truncated),
+                          n_emptied=int(raw.n_emptied), n_collapsed=int(raw.n_collapsed), n_edges=E, n_vertices=N, n_unitigs=U, ms=float(raw.ms), graph_ms=float(raw.graph_ms),
+                          paths_ms=float(raw.paths.path_ms))
+
+    @property
+    def graph(self):
+        return (self.K, self.h, self.unitig_off, self.unitig_bases, self.inv)
+
+    @property
+    def paths(self):
+        return (self.offset, self.n_edges, self.edges, self.start)
+
+    def write(self, path_hbv, path_inv=None, path_hbx=None):
+        """a.hbv (+ a.inv, a.hbx) of the edited graph, as the reference writes them"""
+        off = self.unitig_off.cpu().numpy().view(np.uint64)
+        bases = np.ascontiguousarray(self.unitig_bases.cpu().numpy())
+        unitigs = (self.K, len(off) - 1, off.ctypes.data, bases.ctypes.data, C.byref(self.h))
+        _lib.call(self._e.lib.snk_write_hbv, str(path_hbv).encode(), str(path_inv).encode() if path_inv else None, *unitigs)
+        if path_hbx:
+            _lib.call(self._e.lib.snk_write_hbx, str(path_hbx).encode(), *unitigs)
+
+
 def _graph(h: "_lib.SnkHbv", unitig_off, unitig_bases):
     """(n_unitigs, unitig_off, unitig_bases, byref(h)): the graph arguments of the device stages, from tensors"""
     return int(unitig_off.shape[0]) - 1, unitig_off.data_ptr(), unitig_bases.data_ptr(), C.byref(h)
@@ -744,6 +788,69 @@ class Engine:
         except BaseException:
             self.lib.snk_hbv_free(C.byref(h_new))
             raise
+
+    # ---- graph edits: DeleteEdges + Cleanup, and the hanging-end trim of StageTrim
+    def _edit_input(self, graph, paths):
+        """(K, h, unitig_off, unitig_bases, inv) and (offset, n_edges, edges[, start]) -> the arguments of the two edit calls and what keeps
+        them alive; unitig_off / unitig_bases / the paths: tensors on the device or numpy"""
+        K, h, uoff, ub, inv = graph
+        dev = torch.device("cuda", self.device)
+        on = lambda a, dt: (a.detach().to(dev, dt) if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a)).to(dev, dt)).contiguous()
+        uoff = on(uoff.view(np.int64) if isinstance(uoff, np.ndarray) and uoff.dtype == np.uint64 else uoff, torch.int64)
+        ub = on(ub, torch.uint8)
+        inv = np.ascontiguousarray(inv, dtype=np.int32)
+        if len(inv) != int(h.n_edges):
+            raise ValueError("inv does not have one entry per edge")
+        p_off, p_n, p_edges = on(paths[0], torch.int32), on(paths[1].view(np.int32) if isinstance(paths[1], np.ndarray) else paths[1], torch.int32), on(paths[2], torch.int32)
+        ip, start = dev_paths(p_off, p_n, p_edges, on(paths[3], torch.int64) if len(paths) > 3 and paths[3] is not None else None)
+        return (int(K), int(uoff.shape[0]) - 1, uoff.data_ptr(), ub.data_ptr(), C.byref(h), inv.ctypes.data, C.byref(ip)), (uoff, ub, inv, p_off, p_n, p_edges, ip, start)
+
+    def delete_edges(self, graph, paths, dels) -> "EditResult":
+        """snk_dev_delete_edges -- hbv.DeleteEdgesParallel(dels) + Cleanup (paths/long/large/GapToyTools.cc:1287-1302) -- on this engine's device.
+          graph  (K, h, unitig_off, unitig_bases, inv): h a lib.SnkHbv (snk_dev_hbv, graphio.hbv_handle, an EditResult's), the unitigs in the
+                 order h names them, inv numpy i32[E]; an EditResult's .graph
+          paths  (offset i32[n], n_edges i32[n] read as u32, edges i32[sum], start i64[n + 1] or None); an EditResult's .paths
+          dels   edge ids, any order, duplicates allowed, closed under inv
+        The caller's arrays are only read.  -> EditResult: everything in tensors / arrays the result owns."""
+        args, hold = self._edit_input(graph, paths)
+        dels = np.ascontiguousarray(dels, dtype=np.int32).ravel()
+        raw = _lib.SnkDevEdit()
+        self._call(self.lib.snk_dev_delete_edges, *args, dels.ctypes.data, len(dels), 0, C.byref(raw))
+        try:
+            dev = torch.device("cuda", self.device)
+
+            def take(ptr, count, dt):
+                nbytes = count * torch.empty((), dtype=dt).element_size()
+                return torch.as_tensor(_DevBytes(ptr, nbytes), device=dev).clone().view(dt) if count else torch.empty((0,), dtype=dt, device=dev)
+            return EditResult(self, args[0], raw, take)
+        finally:
+            self.lib.snk_dev_edit_free(C.byref(raw))
+            del hold
+
+    def hanging_ends(self, graph, paths, max_kmers: int = 200, leg: str | None = None):
+        """snk_dev_hanging_ends -- the selection of StageTrim (10X/runstages/RunStages.cc:91-146): the read support of every edge and the
+        unsupported hanging ends of at most max_kmers k-mers, with their inverses.  graph / paths as for delete_edges.  leg: None (the call
+        chooses by size), "lds" or "sort" (tests).  -> (support i32[E], dels i32[] ascending, stats) on the host."""
+        args, hold = self._edit_input(graph, paths)
+        flags = {None: 0, "lds": _lib.HANG_LDS, "sort": _lib.HANG_SORT}[leg]
+        raw = _lib.SnkDevHanging()
+        self._call(self.lib.snk_dev_hanging_ends, *args, int(max_kmers), flags, C.byref(raw))
+        try:
+            support = self._fetch(raw.support, raw.n_hbv_edges, np.int32)
+            dels = np.array(np.ctypeslib.as_array(raw.dels, shape=(int(raw.n_dels),)), dtype=np.int32, copy=True) if raw.n_dels else np.zeros(0, np.int32)
+            return support, dels, dict(n_dels=int(raw.n_dels), n_unsupported=int(raw.n_unsupported), n_entries=int(raw.n_entries),
+                                       leg={_lib.HANG_LDS: "lds", _lib.HANG_SORT: "sort"}[int(raw.leg)], ms=float(raw.ms))
+        finally:
+            self.lib.snk_host_free(C.cast(raw.dels, C.c_void_p))
+            del hold
+
+    def trim_hanging_ends(self, graph, paths, max_kmers: int = 200) -> "EditResult":
+        """StageTrim from line 91 on: hanging_ends, then delete_edges with its selection.  stats gains the selection's."""
+        support, dels, hs = self.hanging_ends(graph, paths, max_kmers)
+        out = self.delete_edges(graph, paths, dels)
+        out.stats.update(hang_dels=len(dels), hang_unsupported=hs["n_unsupported"], hang_leg=hs["leg"], hang_ms=hs["ms"])
+        out.support, out.dels = support, dels
+        return out
 
     # ---- synthetic reads straight into HBM
     def synth(self, sp: _lib.SnkSynthParams, first: int = 0, n: int | None = None, qstride: int | None = None):

@@ -169,6 +169,22 @@ class SnkDevPatched(C.Structure):
                 ("map_ms", C.c_float), ("reserved", C.c_uint64 * 4)]
 
 
+class SnkDevEdit(C.Structure):
+    _fields_ = [("n_unitigs", C.c_uint64), ("unitig_total_bases", C.c_uint64), ("unitig_off", C.c_void_p), ("unitig_bases", C.c_void_p), ("h", SnkHbv),
+                ("inv", C.POINTER(C.c_int32)), ("paths", SnkDevPaths), ("n_old_edges", C.c_uint64), ("edge_map", C.POINTER(C.c_int32)),
+                ("edge_koff", C.POINTER(C.c_int32)), ("n_deleted", C.c_uint64), ("n_runs", C.c_uint64), ("n_absorbed", C.c_uint64), ("max_run", C.c_uint64),
+                ("n_truncated", C.c_uint64), ("n_emptied", C.c_uint64), ("n_collapsed", C.c_uint64), ("ms", C.c_float), ("graph_ms", C.c_float),
+                ("reserved", C.c_uint64 * 4)]
+
+
+class SnkDevHanging(C.Structure):
+    _fields_ = [("n_hbv_edges", C.c_uint64), ("n_entries", C.c_uint64), ("support", C.c_void_p), ("n_dels", C.c_uint64), ("dels", C.POINTER(C.c_int32)),
+                ("n_unsupported", C.c_uint64), ("leg", C.c_uint32), ("ms", C.c_float), ("reserved", C.c_uint64 * 4)]
+
+
+HANG_LDS, HANG_SORT, HANG_LDS_MAX = 1, 2, 16384      # SNK_HANG_LDS, SNK_HANG_SORT, SNK_HANG_LDS_MAX
+
+
 class SnkFasthBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("first_pair", C.c_uint64), ("file", C.c_uint32), ("max_len", C.c_uint32),
                 ("ascii", C.c_void_p), ("quals", C.c_void_p), ("lens", C.c_void_p), ("bc_fields", C.c_void_p),
@@ -345,6 +361,9 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_patch_pieces": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), u64, vp, vp, u64, vp, vp, u64, vp, P(SnkDevPieces), vp, cp, sz]),
         "snk_dev_patch_merge": (C.c_int, [vp, u32, P(SnkDevResult), vp, u64, P(SnkDevPatchUnitigs), vp, cp, sz]),
         "snk_dev_patch_paths": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), u64, vp, vp, P(SnkHbv), P(SnkDevPaths), P(SnkDevPatched), vp, cp, sz]),
+        "snk_dev_delete_edges": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevPaths), vp, u64, u32, P(SnkDevEdit), vp, cp, sz]),
+        "snk_dev_edit_free": (None, [P(SnkDevEdit)]),
+        "snk_dev_hanging_ends": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevPaths), u32, u32, P(SnkDevHanging), vp, cp, sz]),
         "snk_write_pathsx": (C.c_int, [cp, u64, vp, u64, vp, u64, cp, sz]),
         "snk_read_pathsx": (C.c_int, [cp, P(u64), P(u64), P(P(C.c_int64)), P(u64), P(P(C.c_uint8)), cp, sz]),
         "snk_write_hbx": (C.c_int, [cp, u32, u64, vp, vp, P(SnkHbv), cp, sz]),
