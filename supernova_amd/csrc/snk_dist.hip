@@ -1,5 +1,5 @@
 // snk_dist.hip -- the minimiser-sharded (multi-GPU) path: the session state of a step, its read intake, and the phases of the step that
-// do more than forward to the bucket-local stage (snk_local.hip) or the join (snk_graph.hip).  snk_shard_step.hip drives everything and
+// do more than forward to the bucket-local stage (snk_local.hip), the join (snk_graph.hip) or the list ranking (snk_rank.hip).  snk_shard_step.hip drives everything and
 // runs the exchanges (snk_comm.hip: RCCL over xGMI, or in-process ranks).  SURVEY.md 8(e); the reference's counterpart is the shardio
 // exchange + per-shard processing + global join of tada
 // (lib/tada/external/rust-shardio/src/shard.rs:184-211,488-493; cmd_shard_asm.rs:37-94; cmd_main_asm.rs:25-89)
@@ -11,7 +11,7 @@
 //   -> [histograms] -> [records of the buckets other ranks own, in bucket ranges] -> snk_stage_count_table (own buckets in place)
 //   -> snk_shard_prune_plan / snk_bl_dist_fill -> [membership queries] -> snk_dist_answer -> [answers] -> snk_dist_apply
 //   -> snk_bl_dist_fragments -> snk_dist_links_query -> [link queries] -> snk_dist_links_answer -> [answers] -> snk_dist_links_apply_regions
-//   -> [links + k-mer counts of all fragments] -> snk_shard_prank_begin -> [splitters] -> snk_prank_walk / snk_prank_route -> [ranks]
+//   -> [links + k-mer counts of all fragments] -> snk_shard_prank_begin -> [splitters] -> snk_prank_walk / snk_prank_route (snk_rank.hip) -> [ranks]
 //   -> snk_shard_place_ranked  (or snk_shard_place: the ranking replicated, when a list is a circle)
 //   -> snk_shard_route_fill -> [fragments to the owners of their unitigs' heads] -> snk_shard_emit: this rank's unitigs.
 // There is no rank-0 funnel: every rank writes the unitigs whose head fragment it owns.
@@ -274,7 +274,7 @@ int snk_shard_place(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint64_t n
     return place(ctx, S, st, rk, 0, circ, nk_all, err, errcap);
 }
 
-// ---- the ranking partitioned over the ranks (snk_graph.hip: snk_prank_*)
+// ---- the ranking partitioned over the ranks (snk_rank.hip: snk_prank_*)
 int snk_shard_prank_begin(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint64_t n_frags_total, const uint32_t* nk_all, uint32_t* flink_all,
                           uint64_t my_frag_off, char* err, size_t errcap) {
     if (2 * n_frags_total >= (1ull << 32)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments in the job");

@@ -7,7 +7,7 @@
 //       segment by segment, four output bases per lane and one dword store.  The part that grows with the edges only runs on the host
 //       in one pass over them, as snk_dev_hbv's small-graph flood does: vertex degrees, the unneeded vertices, the reference's own walk
 //       from the highest unneeded vertex down (its list of runs IS the id order), the compaction of edges and vertices.  A device form
-//       of that part (list ranking weighted by k-mers, as the join's rank_lists) is not built.
+//       of that part (list ranking weighted by k-mers, as the join's snk_rank_lists) is not built.
 //   snk_dev_hanging_ends   rs[e] = entries x with x == e or inv[x] == e.  Only (x == e) is counted; the inverse's count is added when the
 //       tables are summed, which halves the increments.  No atomic touches global memory: up to SNK_HANG_LDS_MAX edges a workgroup
 //       counts its share of the entries in LDS and writes its table out, and one lane per edge sums the tables; above that the entries

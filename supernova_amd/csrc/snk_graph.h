@@ -1,7 +1,31 @@
-// snk_graph.h -- internal interface of the graph stage (snk_graph.hip).
+// snk_graph.h -- internal interface of the graph stage (snk_graph.hip: global stage and fragment join; snk_local.hip: bucket-local
+// stage), and the two helpers its files and the ranking (snk_rank.hip) share.
 #pragma once
+#include <rocprim/rocprim.hpp>
+
 #include "snk_ctx.h"
 #include "snk_kernels.h"
+
+// scratch of the call, in a function that has ctx, err and errcap and returns a status
+#define G_ALLOC(ptr, type, count)                                                       \
+    do {                                                                                \
+        void* _p = nullptr;                                                             \
+        int _rc = snk_ctx_alloc(ctx, sizeof(type) * (size_t)(count), &_p, err, errcap); \
+        if (_rc) return _rc;                                                            \
+        ptr = (type*)_p;                                                                \
+    } while (0)
+
+// exclusive sum scan of `count` entries read through any iterator (an array: n+1 entries with a zero appended by the caller give the total)
+template <typename T, typename In>
+static int excl_scan(snk_ctx* ctx, hipStream_t st, In in, T* out, size_t count, char* err, size_t errcap) {
+    size_t tb = 0;
+    SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, in, out, (T)0, count, rocprim::plus<T>(), st));
+    void* tmp;
+    int rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap);
+    if (rc) return rc;
+    SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, in, out, (T)0, count, rocprim::plus<T>(), st));
+    return SNK_OK;
+}
 
 struct snk_graph_out {
     uint8_t* ctx;                 // [n] pruned context bytes (sorted k-mer order)
@@ -24,7 +48,7 @@ int snk_graph_sort(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t n, snk_u12
 int snk_graph_build(snk_ctx* ctx, hipStream_t st, uint32_t K, const snk_u128* keys, const uint64_t* vals, uint64_t n,
                     uint32_t do_prune, bool want_unitigs, snk_graph_out* out, char* err, size_t errcap);
 
-// ---- sharded graph stage (snk_graph.hip, second half)
+// ---- sharded graph stage and fragment join (snk_graph.hip)
 struct snk_dist_graph {
     uint32_t K, rank, world, NB_total, NBl, do_prune;
     uint64_t n;
@@ -69,24 +93,6 @@ int snk_join_rank(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, 
                   uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap, uint8_t* circ_given = nullptr);
 int snk_join_place(snk_ctx* ctx, hipStream_t st, const uint2* rk, const uint32_t* nk, const uint8_t* circ, uint64_t f0, uint64_t Fl,
                    snk_placement* pl, char* err, size_t errcap, uint64_t rk_f0 = 0);
-// partitioned ranking of the job's fragment lists (sharded runs): replicated streaming setup, walks for a 1/world share
-struct snk_prank {
-    uint64_t ns, m, k0, k1, n_rec;
-    const uint32_t* w;
-    uint32_t* link;
-    unsigned long long* wrec;
-    uint32_t* spl_state;
-    uint4* w1_share;           // [k1-k0] first walk of this rank's splitters: next splitter, distance, tail, states
-    uint4* rec;                // [n_rec] second walk: state, distance, terminal, 0
-};
-int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, uint32_t* link, uint32_t rank, uint32_t world, snk_prank* P, char* err,
-                    size_t errcap);
-int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_all, uint32_t* circles, uint32_t* rounds, char* err, size_t errcap,
-                   uint8_t* circ = nullptr /* [ns]: given = circles are cut here (*circles = 2: begin again) */, uint32_t* n_cut = nullptr);
-int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, const unsigned long long* d_frag_off, uint32_t world,
-                    unsigned long long* d_cursor /* [world]: first record of every owner's region; the regions' ends afterwards */, void* d_out, char* err, size_t errcap);
-int snk_prank_apply(snk_ctx* ctx, hipStream_t st, const void* d_rec, uint64_t n, unsigned long long state_base, uint64_t n_local_states,
-                    const uint2** rk_out, char* err, size_t errcap);
 int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const uint32_t* nk, const uint32_t* gfid, const uint32_t* pl_pid,
                   const unsigned long long* pl_koff, const unsigned long long* pl_N, const uint8_t* pl_circ, uint32_t pid_base, uint64_t n_pid,
                   const uint64_t* boff, const uint8_t* fbases, const uint32_t* fgroup, snk_join_out* out, char* err, size_t errcap);

@@ -18,11 +18,13 @@
 //      neighbour's position and relative strand;
 //   4. links: side s of node i is linked to the facing side of node j iff both sides have degree 1 and
 //      neither k-mer is a palindrome (BuildReadQGraph48.cc:408-428,445-456);
-//   5. pointer jumping (Wyllie) over the 2n directed states (node, exit side): distance to and identity
+//   5. list ranking (snk_rank.hip) over the 2n directed states (node, exit side): distance to and identity
 //      of both path ends for every node; states that never reach an end are on smooth circles: the
 //      circle is cut at the left side of its minimum k-mer (canonicalizeCircle :375-397) and re-ranked;
 //   6. orientation per path by the reference's rule (odd length: middle base & 2; even: lexicographic,
 //      dna/CanonicalForm.h:35-48), prefix sums for offsets, one base per node scattered into place.
+// Below the global stage: the sharded stage's answers and the fragment join (snk_dist_join, snk_join_*), which ranks fragment
+// ends with the same snk_rank_lists.
 #include <string.h>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -31,6 +33,7 @@
 #include "snk_common.h"
 #include "snk_kernels.h"
 #include "snk_graph.h"
+#include "snk_rank.h"
 #include "snk_stages.h"
 
 namespace {
@@ -142,64 +145,6 @@ __global__ void __launch_bounds__(TB) link_kernel(const snk_u128* __restrict__ k
         if (!pal && deg == 1) out = (j << 1) | fs;
     }
     link[s] = out;
-}
-
-// ------------------------------------------------------------------ list ranking over directed states
-__global__ void __launch_bounds__(TB) rank_init_kernel(const uint32_t* __restrict__ link, uint64_t ns,
-                                                       uint32_t* __restrict__ nxt, uint32_t* __restrict__ dist,
-                                                       uint32_t* __restrict__ tail) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    uint32_t l = link[s];
-    if (l == NONE) { nxt[s] = NONE; dist[s] = 0; tail[s] = (uint32_t)s; }
-    else { nxt[s] = l ^ 1u; dist[s] = 1; tail[s] = l ^ 1u; }
-}
-
-__global__ void __launch_bounds__(TB) rank_round_kernel(const uint32_t* __restrict__ nxt_in, const uint32_t* __restrict__ dist_in,
-                                                        const uint32_t* __restrict__ tail_in, uint64_t ns,
-                                                        uint32_t* __restrict__ nxt_out, uint32_t* __restrict__ dist_out,
-                                                        uint32_t* __restrict__ tail_out, uint32_t* __restrict__ changed) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    uint32_t n1 = nxt_in[s];
-    if (n1 == NONE) { nxt_out[s] = NONE; dist_out[s] = dist_in[s]; tail_out[s] = tail_in[s]; return; }
-    nxt_out[s] = nxt_in[n1];
-    dist_out[s] = dist_in[s] + dist_in[n1];
-    tail_out[s] = tail_in[n1];
-    *changed = 1u;
-}
-
-// smooth circles: states that still have a successor after ceil(log2(ns))+1 rounds
-__global__ void __launch_bounds__(TB) cyc_init_kernel(const uint32_t* __restrict__ nxt_final, const uint32_t* __restrict__ link,
-                                                      uint64_t ns, uint32_t* __restrict__ jump, uint32_t* __restrict__ mn) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    if (nxt_final[s] == NONE) { jump[s] = NONE; mn[s] = NONE; }
-    else { jump[s] = link[s] ^ 1u; mn[s] = (uint32_t)(s >> 1); }
-}
-__global__ void __launch_bounds__(TB) cyc_round_kernel(const uint32_t* __restrict__ jump_in, const uint32_t* __restrict__ mn_in,
-                                                       uint64_t ns, uint32_t* __restrict__ jump_out, uint32_t* __restrict__ mn_out) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    uint32_t j = jump_in[s];
-    if (j == NONE) { jump_out[s] = NONE; mn_out[s] = NONE; return; }
-    uint32_t a = mn_in[s], b = mn_in[j];
-    mn_out[s] = a < b ? a : b;
-    jump_out[s] = jump_in[j];
-}
-// cut every circle at the left side of its minimum k-mer
-__global__ void __launch_bounds__(TB) cyc_cut_kernel(const uint32_t* __restrict__ mn, uint64_t n, uint32_t* __restrict__ link,
-                                                     uint32_t* __restrict__ n_cut, uint8_t* __restrict__ circ_state) {
-    uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    uint64_t s = 2 * i + 1;
-    if (mn[s] == (uint32_t)i) {
-        uint32_t partner = link[s];
-        link[s] = NONE;
-        if (partner != NONE) link[partner] = NONE;
-        if (circ_state) { circ_state[s] = 1; if (partner != NONE) circ_state[partner] = 1; }   // both new terminals
-        atomicAdd(n_cut, 1u);
-    }
 }
 
 // ------------------------------------------------------------------ orientation, offsets, emission
@@ -318,14 +263,6 @@ __global__ void __launch_bounds__(TB) spectrum_kernel(const uint32_t* __restrict
 
 }  // namespace
 
-#define G_ALLOC(ptr, type, count)                                                       \
-    do {                                                                                \
-        void* _p = nullptr;                                                             \
-        int _rc = snk_ctx_alloc(ctx, sizeof(type) * (size_t)(count), &_p, err, errcap); \
-        if (_rc) return _rc;                                                            \
-        ptr = (type*)_p;                                                                \
-    } while (0)
-
 __global__ void __launch_bounds__(256) sorted_check_kernel(const snk_u128* __restrict__ keys, uint64_t n, uint32_t* __restrict__ bad) {
     uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i + 1 >= n) return;
@@ -365,536 +302,6 @@ int snk_graph_sort(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t n, snk_u12
     }
     return snk_fail(SNK_E_INTERNAL, err, errcap, "retained k-mer table is not strictly ascending after the sort");
 }
-
-// weighted start of the ranking (fragment join): the distance counts k-mers, not hops
-__global__ void __launch_bounds__(TB) rank_init_w_kernel(const uint32_t* __restrict__ link, const uint32_t* __restrict__ w,
-                                                         uint64_t ns, uint32_t* __restrict__ nxt, uint32_t* __restrict__ dist,
-                                                         uint32_t* __restrict__ tail) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    uint32_t l = link[s];
-    if (l == NONE) { nxt[s] = NONE; dist[s] = 0; tail[s] = (uint32_t)s; }
-    else { nxt[s] = l ^ 1u; dist[s] = w[l >> 1]; tail[s] = l ^ 1u; }
-}
-__global__ void __launch_bounds__(TB) rank_zip_kernel(const uint32_t* __restrict__ dist, const uint32_t* __restrict__ tail, uint64_t ns,
-                                                      uint2* __restrict__ rk) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s < ns) rk[s] = make_uint2(dist[s], tail[s]);
-}
-
-// List ranking over the 2n directed states (node, exit side) of a degree<=2 link graph: for every state the
-// number of steps (or summed weights) to the end of its path and the terminal state.  Smooth circles are cut
-// at the left side of their minimum node and ranked again.  link[] is modified by the cut.
-static int rank_lists_wyllie(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, const uint32_t* weights, uint8_t* circ /* per state, nullable */,
-                      const uint2** rk_out, uint32_t* n_circles, uint32_t* rounds,
-                      char* err, size_t errcap) {
-    const uint64_t ns = 2 * n;
-    uint32_t *nxt[2], *dst[2], *tl[2];
-    for (int b = 0; b < 2; ++b) { G_ALLOC(nxt[b], uint32_t, ns); G_ALLOC(dst[b], uint32_t, ns); G_ALLOC(tl[b], uint32_t, ns); }
-    uint32_t* flags;   // [0] changed, [1] circles cut
-    G_ALLOC(flags, uint32_t, 4);
-    SNK_HIP_TRY(hipMemsetAsync(flags, 0, 16, st));      // (flags[1] is read back as n_circles also when nothing was cut)
-    uint32_t* h_flags = nullptr;
-    SNK_HIP_TRY(hipHostMalloc((void**)&h_flags, 16, hipHostMallocDefault));
-    int max_rounds = 2;
-    while ((1ull << (max_rounds - 1)) < ns) ++max_rounds;
-    int cur = 0;
-    uint32_t rounds_total = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        cur = 0;
-        if (weights) SNK_HIP_TRY(snk_launch(rank_init_w_kernel, snk_blocks(ns, TB), TB, 0, st, link, weights, ns, nxt[0], dst[0], tl[0]));
-        else SNK_HIP_TRY(snk_launch(rank_init_kernel, snk_blocks(ns, TB), TB, 0, st, link, ns, nxt[0], dst[0], tl[0]));
-        bool converged = false;
-        for (int r = 0; r < max_rounds; ++r) {
-            SNK_HIP_TRY(hipMemsetAsync(flags, 0, 4, st));
-            SNK_HIP_TRY(snk_launch(rank_round_kernel, snk_blocks(ns, TB), TB, 0, st, nxt[cur], dst[cur], tl[cur], ns,
-                                   nxt[cur ^ 1], dst[cur ^ 1], tl[cur ^ 1], flags));
-            cur ^= 1;
-            ++rounds_total;
-            SNK_HIP_TRY(hipMemcpyAsync(h_flags, flags, 4, hipMemcpyDeviceToHost, st));
-            SNK_HIP_TRY(snk_sync(st));
-            if (h_flags[0] == 0) { converged = true; break; }
-        }
-        if (converged) break;
-        if (attempt == 1) { (void)hipHostFree(h_flags); return snk_fail(SNK_E_INTERNAL, err, errcap, "unitig ranking did not converge after the circle cut"); }
-        // smooth circles: find each circle's minimum k-mer (index order == key order), cut there, rank again
-        uint32_t *jump[2] = {dst[cur ^ 1], tl[cur ^ 1]};   // reuse the spare ranking buffers
-        uint32_t* mn[2];
-        G_ALLOC(mn[0], uint32_t, ns);
-        G_ALLOC(mn[1], uint32_t, ns);
-        SNK_HIP_TRY(snk_launch(cyc_init_kernel, snk_blocks(ns, TB), TB, 0, st, nxt[cur], link, ns, jump[0], mn[0]));
-        int c2 = 0;
-        for (int r = 0; r < max_rounds; ++r) {
-            SNK_HIP_TRY(snk_launch(cyc_round_kernel, snk_blocks(ns, TB), TB, 0, st, jump[c2], mn[c2], ns, jump[c2 ^ 1], mn[c2 ^ 1]));
-            c2 ^= 1;
-        }
-        SNK_HIP_TRY(hipMemsetAsync(flags + 1, 0, 4, st));
-        SNK_HIP_TRY(snk_launch(cyc_cut_kernel, snk_blocks(n, TB), TB, 0, st, mn[c2], n, link, flags + 1, circ));
-    }
-    SNK_HIP_TRY(hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    *n_circles = h_flags[1];
-    *rounds = rounds_total;
-    (void)hipHostFree(h_flags);
-    uint2* rkz;
-    G_ALLOC(rkz, uint2, ns);
-    SNK_HIP_TRY(snk_launch(rank_zip_kernel, snk_blocks(ns, TB), TB, 0, st, dst[cur], tl[cur], ns, rkz));
-    *rk_out = rkz;
-    return SNK_OK;
-}
-
-
-// ---- work-efficient ranking: sparse ruling set.  Wyllie's pointer jumping touches every state log2(len) times
-// (21-28 rounds of random 12-byte gathers on the benchmark, 60% of the whole step); here every state is touched
-// twice: list heads and a hashed 1/32 sample of the states are "splitters", each walks to the next splitter, the
-// short splitter list is ranked by pointer jumping, and a second walk hands the ranks to the states in between.
-__device__ __forceinline__ bool sampled_state(uint32_t s, uint32_t split_mask) { return ((snk_mix32(s >> 1) >> 7) & split_mask) == 0; }
-
-__global__ void __launch_bounds__(TB) spl_mark_kernel(const uint32_t* __restrict__ link, uint64_t ns, uint32_t split_mask,
-                                                      uint8_t* __restrict__ spl, uint32_t* __restrict__ flag32) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    bool head = link[s ^ 1] == NONE;                 // nobody walks into s: it starts a list
-    bool sp = head || sampled_state((uint32_t)s, split_mask);
-    spl[s] = sp ? 1 : 0;
-    flag32[s] = sp ? 1u : 0u;
-}
-__global__ void __launch_bounds__(TB) spl_collect_kernel(const uint8_t* __restrict__ spl, const uint32_t* __restrict__ sid, uint64_t ns,
-                                                         uint32_t* __restrict__ spl_state) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns || !spl[s]) return;
-    spl_state[sid[s]] = (uint32_t)s;
-}
-// one 8-byte record per state for the walks: link (32) | splitter id (31) | is-splitter (1) -- a walk step is then
-// ONE random HBM transaction instead of two (link[] and spl[]): the walks are transaction bound (PMC: ~128 B
-// fetched per step with separate arrays)
-__global__ void __launch_bounds__(TB) spl_pack_kernel(const uint32_t* __restrict__ link, const uint8_t* __restrict__ spl,
-                                                      const uint32_t* __restrict__ sid, uint64_t ns, unsigned long long* __restrict__ wrec) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    unsigned long long r = link[s];
-    if (spl[s]) r |= ((unsigned long long)sid[s] << 32) | (1ull << 63);
-    wrec[s] = r;
-}
-__global__ void __launch_bounds__(TB) spl_walk1_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
-                                                       const uint32_t* __restrict__ w, uint64_t m, uint32_t* __restrict__ rnxt,
-                                                       uint32_t* __restrict__ rdist, uint32_t* __restrict__ rtail) {
-    uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (k >= m) return;
-    uint32_t cur = spl_state[k];
-    unsigned long long rec = wrec[cur];
-    uint32_t d = 0, nx = NONE;
-    for (;;) {
-        uint32_t l = (uint32_t)rec;
-        if (l == NONE) { nx = NONE; break; }
-        cur = l ^ 1u;
-        rec = wrec[cur];
-        d += w ? w[cur >> 1] : 1u;
-        if (rec >> 63) { nx = (uint32_t)(rec >> 32) & 0x7FFFFFFFu; break; }
-    }
-    rnxt[k] = nx;
-    rdist[k] = d;
-    rtail[k] = cur;        // the terminal state when nx == NONE (overwritten by the jumping otherwise)
-}
-__global__ void __launch_bounds__(TB) unranked_check_kernel(const uint2* __restrict__ rk, uint64_t ns, uint32_t* __restrict__ flag) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s < ns && rk[s].y == NONE) *flag = 1u;
-}
-
-// ---- the one-GPU ranking's own set-up and second walk (rank_lists; the sharded ranking keeps the kernels above).
-// The splitter predicate is cheap to recompute from link[] and the hash, so no per-state mark array is kept: the scan reads
-// the predicate through an iterator, and one pass writes the compacted splitter list and the walk records.
-struct spl_flag_fn {
-    const uint32_t* link;
-    uint64_t ns;
-    uint32_t split_mask;
-    __device__ uint32_t operator()(uint64_t s) const {
-        if (s >= ns) return 0u;                       // the scan's closing element: sid[ns] = number of splitters
-        return (link[s ^ 1ull] == NONE || sampled_state((uint32_t)s, split_mask)) ? 1u : 0u;
-    }
-};
-__global__ void __launch_bounds__(TB) spl_setup_kernel(const uint32_t* __restrict__ link, const uint32_t* __restrict__ sid, uint64_t ns, uint32_t split_mask,
-                                                       uint32_t* __restrict__ spl_state, unsigned long long* __restrict__ wrec) {
-    uint64_t s = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s >= ns) return;
-    unsigned long long r = link[s];
-    if (link[s ^ 1ull] == NONE || sampled_state((uint32_t)s, split_mask)) {
-        const uint32_t id = sid[s];
-        r |= ((unsigned long long)id << 32) | (1ull << 63);
-        spl_state[id] = (uint32_t)s;
-    }
-    wrec[s] = r;
-}
-// The links are an involution: a list e_0 -> ... -> e_n also exists as its mirror e_n^1 -> ... -> e_0^1, and with
-// rk[e_i] = (d_i, e_n), d_i = sum of w_j over j > i, the mirror's rank is rk[e_i ^ 1] = (W - d_i - w_i, e_0 ^ 1) with
-// W = d_0 + w_0.  So only one list of each pair is walked a second time, and each visited state writes both ranks.
-// After the jumping has converged every head splitter knows its terminal t; t ^ 1 is the mirror's head, a splitter, and its
-// splitter id keys the pair (e_0, W): every entry that is read was written, so the table needs no clear.  (Before
-// convergence the entries read may be stale: that walk's result is thrown away.)
-__global__ void __launch_bounds__(TB) spl_head_info_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
-                                                           const uint32_t* __restrict__ w, const uint32_t* __restrict__ rdist,
-                                                           const uint32_t* __restrict__ rtail, uint64_t m, uint2* __restrict__ info) {
-    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (k >= m) return;
-    const uint32_t h = spl_state[k];
-    if ((uint32_t)wrec[h ^ 1u] != NONE) return;       // not a head
-    const uint32_t t = rtail[k];
-    const uint32_t id = (uint32_t)(wrec[t ^ 1u] >> 32) & 0x7FFFFFFFu;
-    info[id] = make_uint2(h, rdist[k] + (w ? w[h >> 1] : 1u));
-}
-// The list whose terminal is the smaller of (t, e_0 ^ 1) is the one walked.  t == e_0 ^ 1: the list is its own mirror (it
-// holds both states of every fragment on it), is walked as before and writes one rank per state.  *ranked counts the ranks
-// written: a state no walk reaches (a circle without a splitter) shows as *ranked != ns.
-__global__ void __launch_bounds__(TB) spl_walk2m_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
-                                                        const uint32_t* __restrict__ w, const uint32_t* __restrict__ rdist,
-                                                        const uint32_t* __restrict__ rtail, const uint2* __restrict__ info, uint64_t m,
-                                                        uint2* __restrict__ rk, uint32_t* __restrict__ ranked) {
-    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    uint32_t cnt = 0;
-    if (k < m) {
-        uint32_t cur = spl_state[k];
-        unsigned long long rec = wrec[cur];
-        uint32_t d = rdist[k];
-        const uint32_t t = rtail[k];
-        const uint2 hw = info[(uint32_t)(wrec[t ^ 1u] >> 32) & 0x7FFFFFFFu];
-        const uint32_t mt = hw.x ^ 1u;                // the mirror's terminal
-        if (t <= mt) {
-            const bool self = t == mt;
-            uint32_t wc = w ? w[cur >> 1] : 1u;
-            for (;;) {
-                if (self) {
-                    rk[cur] = make_uint2(d, t);
-                    cnt += 1;
-                } else {
-                    const uint32_t dm = hw.y - d - wc;
-                    // the two states of a fragment are neighbours in rk[]: one 16-byte store
-                    ((uint4*)rk)[cur >> 1] = (cur & 1u) ? make_uint4(dm, mt, d, t) : make_uint4(d, t, dm, mt);
-                    cnt += 2;
-                }
-                const uint32_t l = (uint32_t)rec;
-                if (l == NONE) break;
-                cur = l ^ 1u;
-                rec = wrec[cur];
-                if (rec >> 63) break;
-                wc = w ? w[cur >> 1] : 1u;
-                d -= wc;
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
-    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(ranked, cnt);
-}
-
-// ---- circles, cut without the general algorithm.  The ruling-set ranking sees a circle in one of two ways: its splitters form a
-// cycle in the splitter list (the jumping does not converge), or it holds no splitter at all and no walk reaches it.  Round 2
-// answered both with Wyllie's pointer jumping over ALL states (ceil(log2 ns) rounds of random gathers: ~50 ms at 35 M states,
-// a second at 280 M -- for ONE plasmid in the data set).  Here: the minimum sampled FRAGMENT of every splitter cycle by
-// pointer jumping on the splitter list only (1/32 of the states; both states of a fragment are sampled together, so the two
-// directed cycles of a circle agree on it), and the minimum fragment of a splitter-free circle (a few hundred states at most)
-// by walking it from every unreached odd state; the circle is cut at the odd state of that fragment -- one cut per circle --
-// and the caller ranks again.  Where a circle is cut does not matter in the join: jcircle_kernel rotates it to the
-// reference's cut (canonicalizeCircle, BuildReadQGraph48.cc:375-397).
-__global__ void __launch_bounds__(TB) spl_reach_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state, uint64_t m,
-                                                       uint8_t* __restrict__ reach) {
-    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (k >= m) return;
-    uint32_t cur = spl_state[k];
-    unsigned long long rec = wrec[cur];
-    for (;;) {
-        reach[cur] = 1;
-        const uint32_t l = (uint32_t)rec;
-        if (l == NONE) break;
-        cur = l ^ 1u;
-        rec = wrec[cur];
-        if (rec >> 63) break;
-    }
-}
-__global__ void __launch_bounds__(TB) scyc_init_kernel(const uint32_t* __restrict__ rn_final, const uint32_t* __restrict__ rn_orig,
-                                                       const uint32_t* __restrict__ spl_state, uint64_t m, uint32_t* __restrict__ jump, uint32_t* __restrict__ mn) {
-    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (k >= m) return;
-    const bool on = rn_final[k] != NONE;          // still has a successor after ceil(log2 m) + 1 doublings: on a cycle
-    jump[k] = on ? rn_orig[k] : NONE;
-    mn[k] = on ? spl_state[k] >> 1 : NONE;
-}
-__device__ __forceinline__ void cut_at(uint32_t* link, uint32_t s, uint8_t* circ, uint32_t* n_cut) {
-    const uint32_t partner = link[s];
-    link[s] = NONE;
-    if (partner != NONE) link[partner] = NONE;
-    circ[s] = 1;
-    if (partner != NONE) circ[partner] = 1;       // both new terminals
-    atomicAdd(n_cut, 1u);
-}
-__global__ void __launch_bounds__(TB) scyc_cut_kernel(const uint32_t* __restrict__ mn, const uint32_t* __restrict__ spl_state, uint64_t m,
-                                                      uint32_t* __restrict__ link, uint32_t* __restrict__ n_cut, uint8_t* __restrict__ circ) {
-    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (k >= m) return;
-    const uint32_t s = spl_state[k];
-    if (mn[k] != NONE && (s & 1u) && mn[k] == (s >> 1)) cut_at(link, s, circ, n_cut);
-}
-__global__ void __launch_bounds__(TB) free_circle_find_kernel(const uint8_t* __restrict__ reach, uint64_t ns, const uint32_t* __restrict__ link,
-                                                              uint32_t* __restrict__ list, uint32_t cap, uint32_t* __restrict__ n_list, uint32_t* __restrict__ bad) {
-    const uint64_t s0 = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (s0 >= ns || !(s0 & 1ull) || reach[s0]) return;
-    // an unreached state lies on a circle without a splitter; every odd state of that circle walks it, the one of the minimum
-    // fragment is where it will be cut.  Nothing is cut here: a cut also breaks the circle's OTHER direction, which other threads
-    // are walking at this moment -- the states are listed and cut by the next kernel.
-    const uint32_t s = (uint32_t)s0;
-    uint32_t cur = s, mn = s >> 1;
-    for (uint32_t steps = 0;; ++steps) {
-        const uint32_t l = link[cur];
-        if (l == NONE || steps > (1u << 22)) { atomicOr(bad, 1u); return; }      // not a circle / absurdly long: leave it to the general algorithm
-        cur = l ^ 1u;
-        if (cur == s) break;
-        const uint32_t f = cur >> 1;
-        mn = f < mn ? f : mn;
-    }
-    if (mn == (s >> 1)) { const uint32_t at = atomicAdd(n_list, 1u); if (at < cap) list[at] = s; else atomicOr(bad, 1u); }
-}
-__global__ void __launch_bounds__(TB) cut_list_kernel(const uint32_t* __restrict__ list, const uint32_t* __restrict__ n_list, uint32_t cap, uint32_t* __restrict__ link,
-                                                      uint32_t* __restrict__ n_cut, uint8_t* __restrict__ circ) {
-    const uint32_t i = blockIdx.x * TB + threadIdx.x;
-    const uint32_t n = *n_list < cap ? *n_list : cap;
-    if (i < n) cut_at(link, list[i], circ, n_cut);
-}
-
-// rn_orig: next splitter of every splitter after the first walk; rn_final: the same after the jumping (NONE unless on a cycle).
-// *n_cut = circles cut, *bad = 1: something the fast path does not understand (the caller uses the general algorithm).
-static int cut_circles_sparse(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t ns, uint64_t m, const uint32_t* spl_state,
-                              const unsigned long long* wrec, const uint32_t* rn_orig, const uint32_t* rn_final, bool jump_converged, uint8_t* circ,
-                              uint32_t* n_cut, uint32_t* bad, char* err, size_t errcap) {
-    uint32_t* d_flags;
-    G_ALLOC(d_flags, uint32_t, 4);
-    SNK_HIP_TRY(hipMemsetAsync(d_flags, 0, 16, st));
-    // (the reach marks come from the links as they are BEFORE any cut)
-    uint8_t* reach;
-    G_ALLOC(reach, uint8_t, ns + 1);
-    SNK_HIP_TRY(hipMemsetAsync(reach, 0, ns + 1, st));
-    SNK_HIP_TRY(snk_launch(spl_reach_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, m, reach));
-    if (!jump_converged && m) {
-        uint32_t *jump[2], *mn[2];
-        for (int b = 0; b < 2; ++b) { G_ALLOC(jump[b], uint32_t, m + 1); G_ALLOC(mn[b], uint32_t, m + 1); }
-        SNK_HIP_TRY(snk_launch(scyc_init_kernel, snk_blocks(m, TB), TB, 0, st, rn_final, rn_orig, spl_state, m, jump[0], mn[0]));
-        int max_rounds = 2;
-        while ((1ull << (max_rounds - 1)) < m + 1) ++max_rounds;
-        int c2 = 0;
-        for (int r = 0; r < max_rounds; ++r) {
-            SNK_HIP_TRY(snk_launch(cyc_round_kernel, snk_blocks(m, TB), TB, 0, st, jump[c2], mn[c2], m, jump[c2 ^ 1], mn[c2 ^ 1]));
-            c2 ^= 1;
-        }
-        SNK_HIP_TRY(snk_launch(scyc_cut_kernel, snk_blocks(m, TB), TB, 0, st, mn[c2], spl_state, m, link, d_flags, circ));
-    }
-    {
-        const uint32_t cap = 1u << 18;
-        uint32_t* list;
-        G_ALLOC(list, uint32_t, cap);
-        SNK_HIP_TRY(snk_launch(free_circle_find_kernel, snk_blocks(ns, TB), TB, 0, st, reach, ns, (const uint32_t*)link, list, cap, d_flags + 2, d_flags + 1));
-        SNK_HIP_TRY(snk_launch(cut_list_kernel, cap / TB, TB, 0, st, (const uint32_t*)list, (const uint32_t*)(d_flags + 2), cap, link, d_flags, circ));
-    }
-    uint32_t h[2] = {0, 0};
-    SNK_HIP_TRY(hipMemcpyAsync(h, d_flags, 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    *n_cut = h[0];
-    *bad = h[1];
-    return SNK_OK;
-}
-
-static int rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, const uint32_t* weights, uint8_t* circ /* per state, nullable */,
-                      const uint2** rk_out, uint32_t* n_circles, uint32_t* rounds,
-                      char* err, size_t errcap) {
-    const uint64_t ns = 2 * n;
-    if (ns < 4096 || snk_opt_u32(ctx, SNK_OPT_rank_wyllie))
-        return rank_lists_wyllie(ctx, st, link, n, weights, circ, rk_out, n_circles, rounds, err, errcap);
-    uint32_t cut_total = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    uint32_t* sid;
-    G_ALLOC(sid, uint32_t, ns + 1);
-    const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
-    {
-        auto flag_it = rocprim::make_transform_iterator(rocprim::counting_iterator<uint64_t>(0), spl_flag_fn{link, ns, split_mask});
-        size_t tb = 0;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, flag_it, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
-        void* tmp;
-        int rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap);
-        if (rc) return rc;
-        SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, flag_it, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
-    }
-    uint32_t m32 = 0;
-    SNK_HIP_TRY(hipMemcpyAsync(&m32, sid + ns, 4, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    const uint64_t m = m32;
-    uint32_t* spl_state;
-    G_ALLOC(spl_state, uint32_t, m + 1);
-    uint32_t *rn[2], *rd[2], *rt[2];
-    for (int b = 0; b < 2; ++b) { G_ALLOC(rn[b], uint32_t, m + 1); G_ALLOC(rd[b], uint32_t, m + 1); G_ALLOC(rt[b], uint32_t, m + 1); }
-    unsigned long long* wrec;
-    G_ALLOC(wrec, unsigned long long, ns);
-    SNK_HIP_TRY(snk_launch(spl_setup_kernel, snk_blocks(ns, TB), TB, 0, st, (const uint32_t*)link, (const uint32_t*)sid, ns, split_mask, spl_state, wrec));
-    SNK_HIP_TRY(snk_launch(spl_walk1_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, m, rn[0], rd[0], rt[0]));
-    uint2* info;                       // (head state, list weight) of every list, keyed by the splitter id of its mirror's head
-    G_ALLOC(info, uint2, m + 1);
-    // pointer jumping on the splitter list
-    uint32_t* flags;                   // [0] the batch's last round changed something, [1] ranks the second walk wrote
-    G_ALLOC(flags, uint32_t, 4);
-    int max_rounds = 2;
-    while ((1ull << (max_rounds - 1)) < m + 1) ++max_rounds;
-    int cur = 0;
-    uint32_t r_done = 0;
-    // Rounds are issued in batches without asking the device whether the last one still changed anything (a round over the
-    // ~n/32 splitters takes 10-15 us, a read-back 25-30 us of idle device): the first batch covers lists of 2^12 splitters
-    // (128 k fragments), and its verdict comes back together with the walk's "every state ranked" check.
-    uint2* rk = nullptr;
-    bool converged = false, unranked = false;
-    G_ALLOC(rk, uint2, ns);
-    const int batch0 = (int)snk_opt_u32(ctx, SNK_OPT_rank_round_batch0);
-    for (int r = 0; r < max_rounds && !converged;) {
-        const int upto = r == 0 ? (batch0 < max_rounds ? batch0 : max_rounds) : max_rounds;
-        SNK_HIP_TRY(hipMemsetAsync(flags, 0, 8, st));
-        for (; r < upto; ++r) {
-            SNK_HIP_TRY(snk_launch(rank_round_kernel, snk_blocks(m, TB), TB, 0, st, rn[cur], rd[cur], rt[cur], m, rn[cur ^ 1], rd[cur ^ 1], rt[cur ^ 1],
-                                   r + 1 == upto ? flags : flags + 2));      // only the batch's last round reports
-            cur ^= 1;
-            ++r_done;
-        }
-        // optimistic: rank the states from what the rounds left (harmless if they had not converged: it is redone)
-        // (flags[1] was cleared with flags[0] above: a redone walk counts from zero)
-        SNK_HIP_TRY(snk_launch(spl_head_info_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, rd[cur], rt[cur], m, info));
-        SNK_HIP_TRY(snk_launch(spl_walk2m_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, rd[cur], rt[cur], (const uint2*)info, m, rk, flags + 1));
-        uint32_t h2[2] = {0, 0};
-        SNK_HIP_TRY(hipMemcpyAsync(h2, flags, 8, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(snk_sync(st));
-        converged = h2[0] == 0;
-        unranked = h2[1] != ns;         // states no walk reached: a circle without a splitter
-    }
-    if (converged && !unranked) {
-        *rk_out = rk;
-        *n_circles = cut_total;
-        *rounds = r_done;
-        return SNK_OK;
-    }
-    // circles.  In the join (circ given) they are cut here and the lists ranked once more; the k-mer level ranking of the global
-    // graph stage needs the cut AT the minimum k-mer (it is the reference's cut there): the general algorithm does that.
-    if (!circ || attempt == 1) break;
-    // the cut wants every splitter's next splitter as the first walk left it; the jumping has overwritten that, and only this
-    // rare path needs it: walk again (wrec[] is unchanged) instead of keeping a copy on every call
-    uint32_t *rn_orig, *rd_spare, *rt_spare;
-    G_ALLOC(rn_orig, uint32_t, m + 1);
-    G_ALLOC(rd_spare, uint32_t, m + 1);
-    G_ALLOC(rt_spare, uint32_t, m + 1);
-    SNK_HIP_TRY(snk_launch(spl_walk1_kernel, snk_blocks(m, TB), TB, 0, st, wrec, spl_state, weights, m, rn_orig, rd_spare, rt_spare));
-    uint32_t n_cut = 0, bad = 0;
-    int rcc = cut_circles_sparse(ctx, st, link, ns, m, spl_state, wrec, rn_orig, rn[cur], converged, circ, &n_cut, &bad, err, errcap);
-    if (rcc) return rcc;
-    if (bad || n_cut == 0) break;
-    cut_total += n_cut;
-    }
-    {
-        uint32_t nc2 = 0;
-        int rcw = rank_lists_wyllie(ctx, st, link, n, weights, circ, rk_out, &nc2, rounds, err, errcap);
-        *n_circles = cut_total + nc2;
-        return rcw;
-    }
-}
-
-namespace {
-// ---- partitioned ranking (sharded runs, owner-side join).  Every rank holds the job's whole link structure (all-gathered),
-// but ranking it in full on every rank would cost each of them what the rank-0 funnel cost one.  The ruling-set scheme
-// splits naturally: marking and packing are streaming passes (replicated, ~30 B per state); the two walks -- the random
-// access part -- are done for a 1/world share of the splitters per rank; what leaves a rank is 16 B per splitter after
-// walk 1 (all-gather) and 16 B per visited state after walk 2 (to the state's owner).  The splitter list itself (1/32 of
-// the states) is jumped on every rank.  Lists that are circles are not handled here: the caller falls back to the
-// replicated ranking (snk_join_rank) when it is told so -- the decision is the same on every rank because it is taken
-// from replicated data.
-__global__ void __launch_bounds__(TB) spl_walk1p_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
-                                                        const uint32_t* __restrict__ w, uint64_t k0, uint64_t cnt, uint4* __restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= cnt) return;
-    uint32_t cur = spl_state[k0 + i];
-    unsigned long long rec = wrec[cur];
-    uint32_t d = 0, nx = NONE, steps = 1;
-    for (;;) {
-        const uint32_t l = (uint32_t)rec;
-        if (l == NONE) { nx = NONE; break; }
-        cur = l ^ 1u;
-        rec = wrec[cur];
-        d += w[cur >> 1];
-        if (rec >> 63) { nx = (uint32_t)(rec >> 32) & 0x7FFFFFFFu; break; }
-        ++steps;
-    }
-    out[i] = make_uint4(nx, d, cur, steps);      // cur = the terminal state when nx == NONE
-}
-__global__ void __launch_bounds__(TB) prank_unzip_kernel(const uint4* __restrict__ all, uint64_t m, uint32_t* __restrict__ rn, uint32_t* __restrict__ rd,
-                                                         uint32_t* __restrict__ rt, unsigned long long* __restrict__ total_steps) {
-    const uint64_t k = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    unsigned long long st = 0;
-    if (k < m) { const uint4 v = all[k]; rn[k] = v.x; rd[k] = v.y; rt[k] = v.z; st = v.w; }
-    for (int o = 32; o > 0; o >>= 1) st += __shfl_xor(st, o);
-    if ((threadIdx.x & 63) == 0 && st) atomicAdd(total_steps, st);
-}
-__global__ void __launch_bounds__(TB) prank_steps_kernel(const uint4* __restrict__ all, uint64_t k0, uint64_t cnt, uint64_t* __restrict__ steps) {
-    const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (i <= cnt) steps[i] = i < cnt ? all[k0 + i].w : 0ull;
-}
-// second walk of this rank's share: one 16-byte record (state, distance, terminal, 0) per visited state, at positions known
-// from the step counts of the first walk
-__global__ void __launch_bounds__(TB) spl_walk2p_kernel(const unsigned long long* __restrict__ wrec, const uint32_t* __restrict__ spl_state,
-                                                        const uint32_t* __restrict__ w, const uint32_t* __restrict__ rdist, const uint32_t* __restrict__ rtail,
-                                                        uint64_t k0, uint64_t cnt, const uint64_t* __restrict__ pos, uint4* __restrict__ rec_out) {
-    const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= cnt) return;
-    uint32_t cur = spl_state[k0 + i];
-    unsigned long long rec = wrec[cur];
-    uint32_t d = rdist[k0 + i];
-    const uint32_t t = rtail[k0 + i];
-    uint64_t p = pos[i];
-    for (;;) {
-        rec_out[p++] = make_uint4(cur, d, t, 0u);
-        const uint32_t l = (uint32_t)rec;
-        if (l == NONE) break;
-        cur = l ^ 1u;
-        rec = wrec[cur];
-        if (rec >> 63) break;
-        d -= w[cur >> 1];
-    }
-}
-// records to the owners of their states: count / fill with the per-owner sums taken in LDS first, one reservation per owner and PR_TILES tiles
-constexpr int PR_TILES = 16;
-template <bool FILL>
-__global__ void __launch_bounds__(256) prank_route_kernel(const uint4* __restrict__ rec, uint64_t n, const unsigned long long* __restrict__ frag_off, uint32_t world,
-                                                          unsigned long long* __restrict__ cnt_or_cur, uint4* __restrict__ out) {
-    extern __shared__ unsigned long long dynp[];          // [world] counts -> reserved bases, then [world] u32 local cursors
-    uint32_t* lcur = reinterpret_cast<uint32_t*>(dynp + world);
-    for (uint32_t r = threadIdx.x; r < world; r += 256) { dynp[r] = 0; lcur[r] = 0; }
-    __syncthreads();
-    const uint64_t i0 = (uint64_t)blockIdx.x * 256 * PR_TILES + threadIdx.x;
-    auto owner_of = [&](unsigned long long g) { uint32_t o = 0; while (o + 1 < world && g >= frag_off[o + 1]) ++o; return o; };
-    for (int t = 0; t < PR_TILES; ++t) {
-        const uint64_t i = i0 + (uint64_t)t * 256;
-        if (i < n) atomicAdd(&dynp[owner_of(rec[i].x >> 1)], 1ull);
-    }
-    __syncthreads();
-    for (uint32_t r = threadIdx.x; r < world; r += 256) { const unsigned long long c = dynp[r]; if (c) dynp[r] = atomicAdd(&cnt_or_cur[r], c); }
-    if (!FILL) return;
-    __syncthreads();
-    for (int t = 0; t < PR_TILES; ++t) {
-        const uint64_t i = i0 + (uint64_t)t * 256;
-        if (i < n) {
-            const uint4 v = rec[i];
-            const uint32_t owner = owner_of(v.x >> 1);
-            out[dynp[owner] + atomicAdd(&lcur[owner], 1u)] = v;
-        }
-    }
-}
-__global__ void __launch_bounds__(TB) prank_apply_kernel(const uint4* __restrict__ rec, uint64_t n, unsigned long long state_base, uint64_t n_local_states,
-                                                         uint2* __restrict__ rk, uint32_t* __restrict__ bad) {
-    const uint64_t i = (uint64_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    const uint4 v = rec[i];
-    const unsigned long long s = (unsigned long long)v.x - state_base;
-    if (s < n_local_states) rk[s] = make_uint2(v.y, v.z);
-    else *bad = 1u;
-}
-}  // namespace
 
 template <int K>
 static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const uint64_t* vals, uint64_t n,
@@ -943,7 +350,7 @@ static int graph_impl(snk_ctx* ctx, hipStream_t st, const snk_u128* keys, const 
 
     const uint2* rk = nullptr;
     {
-        int rc = rank_lists(ctx, st, link, n, nullptr, nullptr, &rk, &out->n_circles, &out->rank_rounds, err, errcap);
+        int rc = snk_rank_lists(ctx, st, link, n, nullptr, nullptr, &rk, &out->n_circles, &out->rank_rounds, err, errcap);
         if (rc) return rc;
     }
 
@@ -1427,17 +834,6 @@ __global__ void __launch_bounds__(256) jorder_copy_kernel(const uint32_t* __rest
 
 }  // namespace
 
-// exclusive scan helper (u32 and u64), n+1 entries with a zero sentinel appended by the caller
-template <typename T>
-static int excl_scan(snk_ctx* ctx, hipStream_t st, const T* in, T* out, size_t count, char* err, size_t errcap) {
-    size_t tb = 0;
-    SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, in, out, (T)0, count, rocprim::plus<T>(), st));
-    void* tmp;
-    int rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap);
-    if (rc) return rc;
-    SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, in, out, (T)0, count, rocprim::plus<T>(), st));
-    return SNK_OK;
-}
 // owner of every chunk from per-owner chunk counts: scatter the owner id at its first chunk, then max-scan
 // total_ub != 0: an upper bound of the chunk count the caller knows without asking the device (sum of ceil(len / JCH) <= sum(len) / JCH
 // + count): the tables are sized and the copy kernels launched for it -- no read-back; the owner of an item past the true total is the
@@ -1511,7 +907,7 @@ int snk_dist_join(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
     G_ALLOC(circ, uint8_t, ne + 1);
     SNK_HIP_TRY(hipMemsetAsync(circ, 0, ne + 1, st));
     const uint2* rk;
-    int rc = rank_lists(ctx, st, flink, F, nk, circ, &rk, &out->n_circles, &out->rank_rounds, err, errcap);
+    int rc = snk_rank_lists(ctx, st, flink, F, nk, circ, &rk, &out->n_circles, &out->rank_rounds, err, errcap);
     if (rc) return rc;
     snk_placement pl;
     if ((rc = snk_join_place(ctx, st, rk, nk, circ, 0, F, &pl, err, errcap))) return rc;
@@ -1535,7 +931,7 @@ int snk_join_rank(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, 
     *n_circles = 0;
     *rounds = 0;
     if (F == 0) { *rk_out = nullptr; return SNK_OK; }
-    return rank_lists(ctx, st, flink, F, nk, circ, rk_out, n_circles, rounds, err, errcap);
+    return snk_rank_lists(ctx, st, flink, F, nk, circ, rk_out, n_circles, rounds, err, errcap);
 }
 
 int snk_join_place(snk_ctx* ctx, hipStream_t st, const uint2* rk, const uint32_t* nk, const uint8_t* circ, uint64_t f0, uint64_t Fl,
@@ -1740,141 +1136,3 @@ int snk_dist_links_apply_regions(snk_ctx* ctx, hipStream_t st, const snk_frag_ou
     return SNK_OK;
 }
 
-int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, uint32_t* link, uint32_t rank, uint32_t world, snk_prank* P, char* err,
-                    size_t errcap) {
-    memset(P, 0, sizeof *P);
-    const uint64_t ns = 2 * F;
-    P->ns = ns; P->w = nk; P->link = link;
-    if (F >= (1ull << 31)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments at the join (%llu)", (unsigned long long)F);
-    uint8_t* spl;
-    uint32_t *flag32, *sid;
-    G_ALLOC(spl, uint8_t, ns + 1);
-    G_ALLOC(flag32, uint32_t, ns + 1);
-    G_ALLOC(sid, uint32_t, ns + 1);
-    SNK_HIP_TRY(hipMemsetAsync(flag32 + ns, 0, 4, st));
-    const uint32_t split_mask = (1u << snk_opt_u32(ctx, SNK_OPT_split_log2)) - 1u;
-    SNK_HIP_TRY(snk_launch(spl_mark_kernel, snk_blocks(ns, TB), TB, 0, st, link, ns, split_mask, spl, flag32));
-    {
-        size_t tb = 0;
-        SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, flag32, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
-        void* tmp;
-        int rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap);
-        if (rc) return rc;
-        SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, flag32, sid, 0u, (size_t)(ns + 1), rocprim::plus<uint32_t>(), st));
-    }
-    uint32_t m32 = 0;
-    SNK_HIP_TRY(hipMemcpyAsync(&m32, sid + ns, 4, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    const uint64_t m = m32;
-    P->m = m;
-    P->spl_state = flag32;             // flag32 is dead after the scan: reuse it for the compacted splitter list
-    if (m) SNK_HIP_TRY(snk_launch(spl_collect_kernel, snk_blocks(ns, TB), TB, 0, st, spl, sid, ns, P->spl_state));
-    G_ALLOC(P->wrec, unsigned long long, ns + 1);
-    SNK_HIP_TRY(snk_launch(spl_pack_kernel, snk_blocks(ns, TB), TB, 0, st, link, spl, sid, ns, P->wrec));
-    P->k0 = m * rank / world;
-    P->k1 = m * (rank + 1) / world;
-    const uint64_t cnt = P->k1 - P->k0;
-    G_ALLOC(P->w1_share, uint4, cnt + 1);
-    SNK_HIP_TRY(snk_launch(spl_walk1p_kernel, snk_blocks(cnt, TB), TB, 0, st, P->wrec, P->spl_state, nk, P->k0, cnt, P->w1_share));
-    return SNK_OK;
-}
-
-// w1_all: the first walk's results of all ranks in splitter order.  *circles = 1: some list is a circle (the caller ranks the
-// replicated way); else rec_out / n_rec = this rank's share of (state, distance, terminal) records.
-int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_all, uint32_t* circles, uint32_t* rounds, char* err, size_t errcap,
-                   uint8_t* circ, uint32_t* n_cut_out) {
-    const uint64_t m = P->m;
-    *circles = 0;
-    *rounds = 0;
-    P->n_rec = 0;
-    uint32_t *rn[2], *rd[2], *rt[2];
-    for (int b = 0; b < 2; ++b) { G_ALLOC(rn[b], uint32_t, m + 1); G_ALLOC(rd[b], uint32_t, m + 1); G_ALLOC(rt[b], uint32_t, m + 1); }
-    unsigned long long* tot;
-    uint32_t* flags;
-    G_ALLOC(tot, unsigned long long, 2);
-    G_ALLOC(flags, uint32_t, 4);
-    SNK_HIP_TRY(hipMemsetAsync(tot, 0, 8, st));
-    SNK_HIP_TRY(snk_launch(prank_unzip_kernel, snk_blocks(m, TB), TB, 0, st, w1_all, m, rn[0], rd[0], rt[0], tot));
-    uint32_t* rn_orig;
-    G_ALLOC(rn_orig, uint32_t, m + 1);
-    if (m) SNK_HIP_TRY(hipMemcpyAsync(rn_orig, rn[0], m * 4, hipMemcpyDeviceToDevice, st));
-    // pointer jumping over the splitter list in batches of rounds: one read-back per batch (flag of the batch's last round +,
-    // the first time, the total the first walk reached), not per round; rounds past convergence change nothing
-    unsigned long long h_tot = 0;
-    uint32_t h_flag = 0;
-    int max_rounds = 2;
-    while ((1ull << (max_rounds - 1)) < m + 1) ++max_rounds;
-    int cur = 0;
-    bool converged = false, first = true;
-    const int BATCH_R = (int)snk_opt_u32(ctx, SNK_OPT_rank_round_batch);
-    for (int r = 0; r < max_rounds && !converged;) {
-        int did = 0;
-        for (; did < BATCH_R && r < max_rounds && m; ++did, ++r) {
-            SNK_HIP_TRY(hipMemsetAsync(flags, 0, 4, st));
-            SNK_HIP_TRY(snk_launch(rank_round_kernel, snk_blocks(m, TB), TB, 0, st, rn[cur], rd[cur], rt[cur], m, rn[cur ^ 1], rd[cur ^ 1], rt[cur ^ 1], flags));
-            cur ^= 1;
-            ++*rounds;
-        }
-        if (first) SNK_HIP_TRY(hipMemcpyAsync(&h_tot, tot, 8, hipMemcpyDeviceToHost, st));
-        if (m) SNK_HIP_TRY(hipMemcpyAsync(&h_flag, flags, 4, hipMemcpyDeviceToHost, st));
-        SNK_HIP_TRY(snk_sync(st));
-        first = false;
-        if (m == 0 || h_flag == 0) converged = true;
-        if (m == 0) break;
-    }
-    if (!converged || h_tot != P->ns) {
-        // circles: splitters that form a cycle (the jumping did not converge) and / or states no walk reached (a circle without a
-        // splitter).  Everything needed to cut them is replicated -- links, splitter list, the first walk of ALL ranks -- so every
-        // rank makes the same cuts (cut_circles_sparse) and the caller starts the ranking again: *circles = 2.  1: fall back to the
-        // replicated general algorithm (no circ array, or something the fast path does not understand).
-        if (n_cut_out) *n_cut_out = 0;
-        if (!circ) { *circles = 1; return SNK_OK; }
-        uint32_t n_cut = 0, bad = 0;
-        int rcc = cut_circles_sparse(ctx, st, P->link, P->ns, m, P->spl_state, P->wrec, rn_orig, rn[cur], converged, circ, &n_cut, &bad, err, errcap);
-        if (rcc) return rcc;
-        if (n_cut_out) *n_cut_out = n_cut;
-        *circles = (bad || n_cut == 0) ? 1u : 2u;
-        return SNK_OK;
-    }
-    const uint64_t cnt = P->k1 - P->k0;
-    uint64_t *steps, *pos;
-    G_ALLOC(steps, uint64_t, cnt + 1);
-    G_ALLOC(pos, uint64_t, cnt + 1);
-    SNK_HIP_TRY(snk_launch(prank_steps_kernel, snk_blocks(cnt + 1, TB), TB, 0, st, w1_all, P->k0, cnt, steps));
-    int rc = excl_scan<uint64_t>(ctx, st, steps, pos, cnt + 1, err, errcap);
-    if (rc) return rc;
-    uint64_t n_rec = 0;
-    SNK_HIP_TRY(hipMemcpyAsync(&n_rec, pos + cnt, 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    G_ALLOC(P->rec, uint4, n_rec + 1);
-    SNK_HIP_TRY(snk_launch(spl_walk2p_kernel, snk_blocks(cnt, TB), TB, 0, st, P->wrec, P->spl_state, P->w, rd[cur], rt[cur], P->k0, cnt, pos, P->rec));
-    P->n_rec = n_rec;
-    return SNK_OK;
-}
-
-int snk_prank_route(snk_ctx* ctx, hipStream_t st, snk_prank* P, const unsigned long long* d_frag_off, uint32_t world,
-                    unsigned long long* d_cursor, void* d_out, char* err, size_t errcap) {
-    if (!P->n_rec) return SNK_OK;
-    const uint64_t nb = snk_blocks(P->n_rec, 256 * PR_TILES);
-    SNK_HIP_TRY(snk_launch(prank_route_kernel<true>, nb, 256, world * 12ull + 16, st, P->rec, P->n_rec, d_frag_off, world, d_cursor, (uint4*)d_out));
-    return SNK_OK;
-}
-
-// the records that arrived -> rk of this rank's own states [state_base, state_base + n_local_states)
-int snk_prank_apply(snk_ctx* ctx, hipStream_t st, const void* d_rec, uint64_t n, unsigned long long state_base, uint64_t n_local_states,
-                    const uint2** rk_out, char* err, size_t errcap) {
-    uint2* rk;
-    uint32_t* flag;
-    G_ALLOC(rk, uint2, n_local_states + 1);
-    G_ALLOC(flag, uint32_t, 4);
-    SNK_HIP_TRY(hipMemsetAsync(rk, 0xFF, (n_local_states + 1) * 8, st));
-    SNK_HIP_TRY(hipMemsetAsync(flag, 0, 8, st));
-    SNK_HIP_TRY(snk_launch(prank_apply_kernel, snk_blocks(n, TB), TB, 0, st, (const uint4*)d_rec, n, state_base, n_local_states, rk, flag));
-    SNK_HIP_TRY(snk_launch(unranked_check_kernel, snk_blocks(n_local_states, TB), TB, 0, st, (const uint2*)rk, n_local_states, flag + 1));
-    uint32_t h[2] = {0, 0};
-    SNK_HIP_TRY(hipMemcpyAsync(h, flag, 8, hipMemcpyDeviceToHost, st));
-    SNK_HIP_TRY(snk_sync(st));
-    if (h[0] || h[1]) return snk_fail(SNK_E_INTERNAL, err, errcap, "partitioned ranking: %s", h[0] ? "a record for a foreign state arrived" : "a local state was not ranked");
-    *rk_out = rk;
-    return SNK_OK;
-}

@@ -964,25 +964,6 @@ __global__ void __launch_bounds__(TB) bl_unpack_vals_kernel(const uint64_t* __re
 
 }  // namespace
 
-#define G_ALLOC(ptr, type, count)                                                       \
-    do {                                                                                \
-        void* _p = nullptr;                                                             \
-        int _rc = snk_ctx_alloc(ctx, sizeof(type) * (size_t)(count), &_p, err, errcap); \
-        if (_rc) return _rc;                                                            \
-        ptr = (type*)_p;                                                                \
-    } while (0)
-
-template <typename T>
-static int excl_scan(snk_ctx* ctx, hipStream_t st, const T* in, T* out, size_t count, char* err, size_t errcap) {
-    size_t tb = 0;
-    SNK_HIP_TRY(rocprim::exclusive_scan((void*)nullptr, tb, in, out, (T)0, count, rocprim::plus<T>(), st));
-    void* tmp;
-    int rc = snk_ctx_alloc(ctx, tb, &tmp, err, errcap);
-    if (rc) return rc;
-    SNK_HIP_TRY(rocprim::exclusive_scan(tmp, tb, in, out, (T)0, count, rocprim::plus<T>(), st));
-    return SNK_OK;
-}
-
 constexpr int SCAP = 256, ST = 64;      // small chunks: one wave per chunk
 constexpr int BCAP = SNK_GRAPH_CHUNK_MAX, BT = 256;    // big chunks (a count sub-pass that retains more is counted again in halves: snk_count.hip)
 

@@ -68,7 +68,7 @@
     X(bl_index_fused, 1, SNK_SW, "boundary index built by the prune (1)") \
     X(bl_noclassify, 0, SNK_SW, "1: every miss of the prune is pending (no neighbour classification)") \
     X(bl_pool, 4096, SNK_R(0, 1048576), "slots of the in-chunk circle pool (4096; 0 forces the exact re-run)") \
-    /* (sampled_state makes a state a splitter when the low split_log2 bits of a 25-bit hash are zero, and a splitter's walk to the  \
+    /* (snk_rank.hip: sampled_state makes a state a splitter when the low split_log2 bits of a 25-bit hash are zero, and a splitter's walk to the  \
        next one is one thread's serial work: 2^12 dependent loads on average at 12; a circle that drew no splitter is walked in full  \
        by each of its odd states, quadratic in the spacing.  At 0 every state is a splitter: pointer jumping over all states with three \
        times its memory, which rank_wyllie does better.  From 32 on the mask's shift is undefined.) */ \

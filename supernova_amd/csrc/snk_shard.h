@@ -1,9 +1,10 @@
 // snk_shard.h -- the minimiser-sharded step's per-context session state and the phases snk_shard_step.hip runs between its exchanges
-// (snk_dist.hip implements those that do more than forward to snk_local.hip / snk_graph.hip).  Library-internal: the multi-GPU surface
+// (snk_dist.hip implements those that do more than forward to snk_local.hip / snk_graph.hip / snk_rank.hip).  Library-internal: the multi-GPU surface
 // of include/snk.h is snk_shard_step / snk_shard_stream_* / snk_shard_gather_unitigs.
 #pragma once
 #include "snk_ctx.h"
 #include "snk_graph.h"
+#include "snk_rank.h"
 #include "snk_kernels.h"
 #include "snk_stages.h"
 
@@ -62,8 +63,8 @@ int snk_shard_prune_plan(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, char*
 // snk_shard_place: the ranking replicated on every rank (a list is a circle, or the option asks for it).
 int snk_shard_place(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint64_t n_frags_total, const uint32_t* nk_all, uint32_t* flink_all,
                     uint64_t my_frag_off, char* err, size_t errcap);
-// The ranking partitioned over the ranks (a rank walks 1/world of the splitters of the ruling-set scheme; only the streaming set-up and
-// the short splitter list are replicated): snk_shard_prank_begin -> all-gather of S.pr.w1_share (16 B per splitter, shares
+// The ranking partitioned over the ranks (snk_rank.hip; a rank walks 1/world of the splitters of the ruling-set scheme; only the streaming
+// set-up, which is the one-GPU ranking's, and the short splitter list are replicated): snk_shard_prank_begin -> all-gather of S.pr.w1_share (16 B per splitter, shares
 // [m*r/world, m*(r+1)/world)) -> snk_prank_walk (circles = 1: some list is a circle, rank the replicated way; 2: circles were cut in the
 // replicated links, begin again) -> snk_prank_route -> all-to-all (16 B per state) -> snk_shard_place_ranked.
 int snk_shard_prank_begin(snk_ctx* ctx, snk_shard_state& S, hipStream_t st, uint64_t n_frags_total, const uint32_t* nk_all, uint32_t* flink_all,

@@ -544,7 +544,7 @@ int step_impl(step_ctx& X, shard_host& H, const snk_dev_reads* in, const snk_par
     for (int attempt = 0; want_partitioned && !ranked && attempt < 3; ++attempt) {
         // (a second attempt follows a circle cut: the links changed, everything derived from them is made again)
         TRY(snk_shard_prank_begin(ctx, *S, st, Ft, nk_all, fl_all, frag_off[me], err, errcap));
-        const uint64_t m_spl = S->pr.m;
+        const uint64_t m_spl = S->pr.set.m;
         std::vector<uint64_t> shares(W);
         uint64_t tot16 = 0;
         for (uint32_t q = 0; q < W; ++q) { shares[q] = (m_spl * (q + 1) / W - m_spl * q / W) * 16; tot16 += shares[q]; }

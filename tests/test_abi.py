@@ -296,7 +296,7 @@ def test_every_option_has_a_range_and_refuses_what_lies_outside(snk):
 
 # values that reach a shift, a divisor, a loop bound or a packed field at the call site (file:line as of the commit that added the ranges)
 HARMFUL = {
-    "split_log2": (0, 32, 40, 64),                   # (1u << v) - 1u, snk_graph.hip rank_lists / snk_prank_mark: undefined from 32 on
+    "split_log2": (0, 32, 40, 64),                   # (1u << v) - 1u, snk_rank.hip rank_setup: undefined from 32 on
     "rank_round_batch0": (0,),                       # no round runs, the flag stays zero, "converged": unconverged ranks go out
     "rank_round_batch": (0,),                        # the same in snk_prank_walk
     "tight_tries": (0, 65536, 1 << 20),              # << 16 into the high half of a 32-bit word (snk_pipeline.hip tight_for)

@@ -167,10 +167,8 @@ def test_five_thousand_circles_and_nothing_else(engine, graph_stage, K):
         assert (attempts, circles, res.n_circles) == (2, 5000, 0)
 
 
-@pytest.mark.parametrize("W", [2, 3])
-@pytest.mark.parametrize("K", hr.KS)
-@pytest.mark.parametrize("name", THREE)
-def test_sharded_ranks_write_the_references_unitigs_between_them(snk, name, K, W):
+def _sharded_held(name, K, W):
+    """W in-process ranks on the noisy reads of a case, their union held to the reference -> the ranking every rank reports"""
     import sharded_cases
     r, exp = hr.load(name, K, True)
     out = sharded_cases.run_ranks(W, hr.rows(r), r.read_len, r.quals, bc=r.bc if K == 48 else None, lens=r.lens, K=K)
@@ -184,4 +182,28 @@ def test_sharded_ranks_write_the_references_unitigs_between_them(snk, name, K, W
     assert hr.differs(exp, got, hr.FIELDS[1:]) is None, hr.differs(exp, got, hr.FIELDS[1:])
     if name == "tiny_circles":
         assert sum(o["n_circles"] for o in out) > 0
-    print(f"{name} K={K} W={W}: ranking {sorted({o['ranking'] for o in out})}")
+    print(f"{name} K={K} W={W}: ranking {[o['ranking'] for o in out]}")
+    return [o["ranking"] for o in out]
+
+
+@pytest.mark.parametrize("W", [2, 3])
+@pytest.mark.parametrize("K", hr.KS)
+@pytest.mark.parametrize("name", THREE)
+def test_sharded_ranks_write_the_references_unitigs_between_them(snk, name, K, W):
+    _sharded_held(name, K, W)
+
+
+# The partitioned ranking where its set-up and its share arithmetic are thin.  split_log2 = 12: no sampled splitter is left in sets this
+# small, so chain_1025 has a handful of head splitters for 8 ranks (ranks with an empty share, k0 == k1) and the circles of tiny_circles
+# (31/32/33 and 255/256/257 k-mers) hold no splitter at all; split_log2 = 1: every second fragment is a splitter and the circles show as
+# splitter cycles.  The ranking each leg takes was recorded on the commit before the one-GPU and the partitioned ranking were given one
+# set-up: all sixteen legs, every rank, "partitioned" -- the circles are cut by the fast path on replicated data and the partitioned
+# ranking begins again; none falls back to the replicated ranking.  (No other test runs one of these legs: the test above runs W = 2
+# and 3 at the default spacing only.)
+@pytest.mark.parametrize("split_log2", [1, 12])
+@pytest.mark.parametrize("W", [2, 8])
+@pytest.mark.parametrize("K", hr.KS)
+@pytest.mark.parametrize("name", ["tiny_circles", "chain_1025"])
+def test_sharded_ranks_with_thin_and_dense_splitter_sets(snk, tune, name, K, W, split_log2):
+    tune("split_log2", split_log2)
+    assert _sharded_held(name, K, W) == ["partitioned"] * W

@@ -1,4 +1,4 @@
-"""The join's list ranking after the mirror walk (snk_graph.hip, rank_lists): one list of each mirror pair is walked a second time and
+"""The join's list ranking after the mirror walk (snk_rank.hip, snk_rank_lists): one list of each mirror pair is walked a second time and
 writes the ranks of both, the "every state ranked" check is a count, and the set-up passes are folded.  rk[] must come out as before,
 so every result must: the hand-made read sets of tests/handreads.py against the reference's goldens, under the default ranking, under
 plain pointer jumping (rank_wyllie=1) and under splitter spacings of 2, 32 and 4096 states (split_log2 = 1, 5, 12) -- byte-equal with
