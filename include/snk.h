@@ -1316,6 +1316,35 @@ typedef struct snk_check_report {
 int snk_dev_check_graph(snk_ctx* ctx, const snk_check_input* in, const snk_dev_reads* reads, snk_check_report* out, void* stream,
                         char* err, size_t errcap);
 
+/* ---- the list ranking on its own (an entry for the tests, like snk_comm_selftest and the snk_ctx_last_* witnesses).
+ * The join's ranking (csrc/snk_rank.hip) over a link structure the caller made: n nodes, 2n directed states (node, exit side).
+ *   d_link[2n]    u32: link[s] = the state that s is joined to, or 0xFFFFFFFF (none); an involution (link[link[s]] == s; link[s] == s is
+ *                 a turn).  Circles are cut in place: both states of ONE pair of every circle become 0xFFFFFFFF.
+ *   d_weights[n]  u32 or NULL (every node weighs 1)
+ *   d_circ[2n]    u8, zeroed by the caller, or NULL: 1 on the states whose link a cut removed
+ *   d_rk[2n]      two u32 per state: (summed weight of the nodes stepped onto after the state up to the end of its list, terminal state)
+ * world == 0: the one-GPU ranking exactly as the join calls it (frag_off is ignored).  world >= 1: the partitioned ranking of the
+ * sharded step with every rank emulated in this context -- its attempt loop without a communicator, owner q holding the nodes
+ * [frag_off[q], frag_off[q + 1]) --; it needs d_weights and d_circ.
+ * SNK_E_ARG, before anything is launched and with *out zeroed: links that are no involution or point outside [0, 2n), 2n >= 2^32, a
+ * frag_off[world + 1] that does not ascend from 0 to n, world >= 1 without weights or circ.  n == 0: SNK_OK, nothing written. */
+#define SNK_RANK_WYLLIE 1               /* plain pointer jumping over all states */
+#define SNK_RANK_RULING 2               /* the sparse ruling set */
+#define SNK_RANK_RULING_THEN_WYLLIE 3   /* the ruling set met circles it left to pointer jumping, which ranked */
+typedef struct snk_rank_evidence {
+    uint32_t n_circles, rounds;    /* as snk_dev_result reports them */
+    uint32_t source;               /* SNK_RANK_*: what produced rk */
+    uint32_t ruling_attempts;      /* ruling-set attempts of the one-GPU ranking (also where it ran as the partitioned form's fallback) */
+    uint64_t splitters;            /* splitters of the first ruling-set attempt (partitioned: of the first partitioned attempt) */
+    uint32_t sparse_cut;           /* circles cut by the sparse cut */
+    uint32_t bad;                  /* the sparse cut gave up on something */
+    uint32_t part_attempts;        /* world >= 1: partitioned attempts made */
+    uint32_t partitioned;          /* world >= 1: 1 = rk is the partitioned ranking's, 0 = the replicated fallback's */
+    uint64_t reserved[4];
+} snk_rank_evidence;
+int snk_dev_rank_lists(snk_ctx* ctx, uint64_t n, void* d_link, const void* d_weights, void* d_circ, uint32_t world, const uint64_t* frag_off,
+                       void* d_rk, snk_rank_evidence* out, void* stream, char* err, size_t errcap);
+
 #ifdef __cplusplus
 }
 #endif

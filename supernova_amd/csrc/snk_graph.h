@@ -89,8 +89,10 @@ struct snk_placement {
     unsigned long long* N;       // k-mers of the whole unitig
     uint8_t* circ;               // the unitig is a circle that was cut at an arbitrary fragment
 };
+struct snk_rank_trace;
 int snk_join_rank(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, uint32_t* flink, const uint2** rk_out, uint8_t** circ_out,
-                  uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap, uint8_t* circ_given = nullptr);
+                  uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap, uint8_t* circ_given = nullptr,
+                  snk_rank_trace* trace = nullptr /* snk_rank.h */);
 int snk_join_place(snk_ctx* ctx, hipStream_t st, const uint2* rk, const uint32_t* nk, const uint8_t* circ, uint64_t f0, uint64_t Fl,
                    snk_placement* pl, char* err, size_t errcap, uint64_t rk_f0 = 0);
 int snk_join_emit(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const uint32_t* nk, const uint32_t* gfid, const uint32_t* pl_pid,

@@ -920,7 +920,7 @@ int snk_dist_join(snk_ctx* ctx, hipStream_t st, uint32_t K, uint64_t F, const ui
 
 // ranking of a whole fragment list (sharded runs: every rank holds the job's links and k-mer counts) -- rk[2F], circ[2F]
 int snk_join_rank(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, uint32_t* flink, const uint2** rk_out, uint8_t** circ_out,
-                  uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap, uint8_t* circ_given) {
+                  uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap, uint8_t* circ_given, snk_rank_trace* trace) {
     if (F >= (1ull << 31)) return snk_fail(SNK_E_UNSUPPORTED, err, errcap, "more than 2^31 fragments at the join (%llu)", (unsigned long long)F);
     uint8_t* circ = circ_given;          // given: the marks of circles an earlier (partitioned) attempt already cut in these links
     if (!circ) {
@@ -931,7 +931,7 @@ int snk_join_rank(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk, 
     *n_circles = 0;
     *rounds = 0;
     if (F == 0) { *rk_out = nullptr; return SNK_OK; }
-    return snk_rank_lists(ctx, st, flink, F, nk, circ, rk_out, n_circles, rounds, err, errcap);
+    return snk_rank_lists(ctx, st, flink, F, nk, circ, rk_out, n_circles, rounds, err, errcap, trace);
 }
 
 int snk_join_place(snk_ctx* ctx, hipStream_t st, const uint2* rk, const uint32_t* nk, const uint8_t* circ, uint64_t f0, uint64_t Fl,

@@ -11,7 +11,10 @@
 #include <string.h>
 #include <rocprim/rocprim.hpp>
 
+#include <vector>
+
 #include "snk_ctx.h"
+#include "snk_call.h"
 #include "snk_common.h"
 #include "snk_graph.h"
 #include "snk_rank.h"
@@ -564,17 +567,24 @@ __global__ void __launch_bounds__(TB) prank_apply_kernel(const uint4* __restrict
 }  // namespace
 
 int snk_rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, const uint32_t* weights, uint8_t* circ, const uint2** rk_out,
-                   uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap) {
+                   uint32_t* n_circles, uint32_t* rounds, char* err, size_t errcap, snk_rank_trace* trace) {
+    snk_rank_trace unused;
+    snk_rank_trace& tr = trace ? *trace : unused;
+    tr = snk_rank_trace{};
     const uint64_t ns = 2 * n;
-    if (ns < 4096 || snk_opt_u32(ctx, SNK_OPT_rank_wyllie))
+    if (ns < 4096 || snk_opt_u32(ctx, SNK_OPT_rank_wyllie)) {
+        tr.source = SNK_RANK_WYLLIE;
         return rank_lists_wyllie(ctx, st, link, n, weights, circ, rk_out, n_circles, rounds, err, errcap);
+    }
     uint32_t cut_total = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         ruling_attempt T;
         bool ranked = false;
         int rc = rank_ruling_set(ctx, st, link, ns, weights, &T, rk_out, rounds, &ranked, err, errcap);
         if (rc) return rc;
-        if (ranked) { *n_circles = cut_total; return SNK_OK; }
+        tr.ruling_attempts = (uint32_t)attempt + 1;
+        if (attempt == 0) tr.m_first = T.S.m;
+        if (ranked) { *n_circles = cut_total; tr.source = SNK_RANK_RULING; return SNK_OK; }
         // circles.  In the join (circ given) they are cut here and the lists ranked once more; the k-mer level ranking of the global
         // graph stage needs the cut AT the minimum k-mer (it is the reference's cut there): the general algorithm does that.
         if (!circ || attempt == 1) break;
@@ -584,12 +594,16 @@ int snk_rank_lists(snk_ctx* ctx, hipStream_t st, uint32_t* link, uint64_t n, con
         SNK_HIP_TRY(snk_launch(spl_walk1_kernel, snk_blocks(T.S.m, TB), TB, 0, st, T.S.wrec, T.S.spl_state, weights, T.S.m, J.nxt[spare], J.dst[spare], J.tl[spare]));
         uint32_t n_cut = 0, bad = 0;
         if ((rc = cut_circles_sparse(ctx, st, link, T.S, J, T.jump_converged, circ, &n_cut, &bad, err, errcap))) return rc;
-        if (bad || n_cut == 0) break;
+        // (the cuts are in link[] and circ[] whatever the verdict: a cut that gave up at its list's capacity has still made that many)
         cut_total += n_cut;
+        tr.sparse_cut += n_cut;
+        tr.bad |= bad;
+        if (bad || n_cut == 0) break;
     }
     uint32_t nc2 = 0;
     int rcw = rank_lists_wyllie(ctx, st, link, n, weights, circ, rk_out, &nc2, rounds, err, errcap);
     *n_circles = cut_total + nc2;
+    tr.source = SNK_RANK_RULING_THEN_WYLLIE;
     return rcw;
 }
 
@@ -612,7 +626,7 @@ int snk_prank_begin(snk_ctx* ctx, hipStream_t st, uint64_t F, const uint32_t* nk
 // w1_all: the first walk's results of all ranks in splitter order.  *circles = 1: some list is a circle (the caller ranks the
 // replicated way); else rec_out / n_rec = this rank's share of (state, distance, terminal) records.
 int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_all, uint32_t* circles, uint32_t* rounds, char* err, size_t errcap,
-                   uint8_t* circ, uint32_t* n_cut_out) {
+                   uint8_t* circ, uint32_t* n_cut_out, snk_rank_trace* trace) {
     const snk_rank_setup& S = P->set;
     const uint64_t m = S.m;
     *circles = 0;
@@ -658,6 +672,7 @@ int snk_prank_walk(snk_ctx* ctx, hipStream_t st, snk_prank* P, const uint4* w1_a
         uint32_t n_cut = 0, bad = 0;
         if ((rc = cut_circles_sparse(ctx, st, P->link, S, J, converged, circ, &n_cut, &bad, err, errcap))) return rc;
         if (n_cut_out) *n_cut_out = n_cut;
+        if (trace) { trace->sparse_cut += n_cut; trace->bad |= bad; }
         *circles = (bad || n_cut == 0) ? 1u : 2u;
         return SNK_OK;
     }
@@ -701,4 +716,161 @@ int snk_prank_apply(snk_ctx* ctx, hipStream_t st, const void* d_rec, uint64_t n,
     if (h[0] || h[1]) return snk_fail(SNK_E_INTERNAL, err, errcap, "partitioned ranking: %s", h[0] ? "a record for a foreign state arrived" : "a local state was not ranked");
     *rk_out = rk;
     return SNK_OK;
+}
+
+// ---- the ranking on its own (include/snk.h: snk_dev_rank_lists): an entry for the tests.  Host code only: the input is judged on the
+// host, the one-GPU form is snk_rank_lists as the join calls it, and the partitioned form is the attempt loop of the sharded step
+// (snk_shard_step.hip) with the collectives replaced by copies inside this context.
+namespace {
+// Every rank of the sharded step holds its own replica of links and marks and cuts it; rank 0 works on the caller's arrays here, the
+// others on copies taken at the start of the attempt.
+int prank_emulated(snk_call& c, uint64_t n, uint32_t* link, const uint32_t* w, uint8_t* circ, uint32_t world, const uint64_t* frag_off, uint2* rk_out,
+                   snk_rank_evidence* ev, char* err, size_t errcap) {
+    snk_ctx* ctx = c.ctx;
+    const hipStream_t st = c.st;
+    const uint64_t ns = 2 * n;
+    int rc;
+    std::vector<unsigned long long> h_off(frag_off, frag_off + world + 1);
+    unsigned long long* d_frag_off;
+    G_ALLOC(d_frag_off, unsigned long long, world + 1);
+    SNK_HIP_TRY(hipMemcpyAsync(d_frag_off, h_off.data(), (world + 1) * 8ull, hipMemcpyHostToDevice, st));
+    SNK_HIP_TRY(snk_sync(st));         // (h_off does not outlive an early return)
+    std::vector<uint32_t*> r_link(world, link);
+    std::vector<uint8_t*> r_circ(world, circ);
+    for (uint32_t r = 1; r < world; ++r) { G_ALLOC(r_link[r], uint32_t, ns + 4); G_ALLOC(r_circ[r], uint8_t, ns + 16); }
+    uint32_t join_circles = 0;
+    snk_rank_trace tr;
+    bool ranked = false;
+    std::vector<snk_prank> P(world);
+    for (int attempt = 0; !ranked && attempt < 3; ++attempt) {
+        ev->part_attempts = (uint32_t)attempt + 1;
+        for (uint32_t r = 1; r < world; ++r) {
+            SNK_HIP_TRY(hipMemcpyAsync(r_link[r], link, ns * 4, hipMemcpyDeviceToDevice, st));
+            SNK_HIP_TRY(hipMemcpyAsync(r_circ[r], circ, ns, hipMemcpyDeviceToDevice, st));
+        }
+        for (uint32_t r = 0; r < world; ++r)
+            if ((rc = snk_prank_begin(ctx, st, n, w, r_link[r], r, world, &P[r], err, errcap))) return rc;
+        const uint64_t m = P[0].set.m;
+        if (attempt == 0) ev->splitters = m;
+        uint4* w1_all;                 // (the step's all-gather of the shares, in rank order)
+        G_ALLOC(w1_all, uint4, m + 2);
+        for (uint32_t r = 0; r < world; ++r) {
+            if (P[r].set.m != m || P[r].k0 != m * r / world || P[r].k1 != m * (r + 1) / world)
+                return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_rank_lists: the ranks' splitter shares do not tile the splitter list");
+            if (P[r].k1 > P[r].k0) SNK_HIP_TRY(hipMemcpyAsync(w1_all + P[r].k0, P[r].w1_share, (P[r].k1 - P[r].k0) * 16, hipMemcpyDeviceToDevice, st));
+        }
+        uint32_t verdict = 0, n_cut = 0;
+        for (uint32_t r = 0; r < world; ++r) {
+            uint32_t v = 0, nc = 0, rounds = 0;
+            if ((rc = snk_prank_walk(ctx, st, &P[r], w1_all, &v, &rounds, err, errcap, r_circ[r], &nc, r == 0 ? &tr : nullptr))) return rc;
+            if (r == 0) { verdict = v; n_cut = nc; ev->rounds = rounds; }
+            else if (v != verdict || nc != n_cut)
+                return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_rank_lists: rank %u says circles = %u (%u cut), rank 0 says %u (%u cut)", r, v, nc, verdict, n_cut);
+        }
+        join_circles += n_cut;
+        if (verdict == 1) break;
+        if (verdict == 2) continue;
+        // the records of every rank's walks into per-owner regions, then every owner's regions into its slice of rk
+        std::vector<uint4*> rsend(world);
+        std::vector<std::vector<unsigned long long>> ends(world, std::vector<unsigned long long>(world));
+        for (uint32_t r = 0; r < world; ++r) {
+            const uint64_t rcap = P[r].n_rec + 1;
+            for (uint32_t q = 0; q < world; ++q) ends[r][q] = (unsigned long long)q * rcap;
+            if (!P[r].n_rec) continue;          // (no records: the fill is not launched)
+            unsigned long long* d_cur;
+            G_ALLOC(rsend[r], uint4, (uint64_t)world * rcap + 2);
+            G_ALLOC(d_cur, unsigned long long, world + 1);
+            SNK_HIP_TRY(hipMemcpyAsync(d_cur, ends[r].data(), world * 8ull, hipMemcpyHostToDevice, st));
+            SNK_HIP_TRY(snk_sync(st));          // (ends[r] is written next)
+            if ((rc = snk_prank_route(ctx, st, &P[r], d_frag_off, world, d_cur, rsend[r], err, errcap))) return rc;
+            SNK_HIP_TRY(hipMemcpyAsync(ends[r].data(), d_cur, world * 8ull, hipMemcpyDeviceToHost, st));
+            SNK_HIP_TRY(snk_sync(st));
+        }
+        for (uint32_t q = 0; q < world; ++q) {
+            uint64_t n_in = 0;
+            for (uint32_t r = 0; r < world; ++r) {
+                const unsigned long long base = (unsigned long long)q * (P[r].n_rec + 1);
+                if (ends[r][q] < base || ends[r][q] - base > P[r].n_rec) return snk_fail(SNK_E_INTERNAL, err, errcap, "snk_dev_rank_lists: a record region overran");
+                n_in += ends[r][q] - base;
+            }
+            uint4* rk_in;
+            G_ALLOC(rk_in, uint4, n_in + 2);
+            uint64_t at = 0;
+            for (uint32_t r = 0; r < world; ++r) {
+                const unsigned long long base = (unsigned long long)q * (P[r].n_rec + 1), cnt = ends[r][q] - base;
+                if (cnt) SNK_HIP_TRY(hipMemcpyAsync(rk_in + at, rsend[r] + base, cnt * 16, hipMemcpyDeviceToDevice, st));
+                at += cnt;
+            }
+            const uint64_t s0 = 2 * frag_off[q], nl = 2 * (frag_off[q + 1] - frag_off[q]);
+            const uint2* rk_q = nullptr;
+            if ((rc = snk_prank_apply(ctx, st, rk_in, n_in, s0, nl, &rk_q, err, errcap))) return rc;
+            if (nl) SNK_HIP_TRY(hipMemcpyAsync(rk_out + s0, rk_q, nl * 8, hipMemcpyDeviceToDevice, st));
+        }
+        ranked = true;
+    }
+    ev->sparse_cut = tr.sparse_cut;
+    ev->bad = tr.bad;
+    ev->n_circles = join_circles;
+    ev->partitioned = ranked ? 1u : 0u;
+    ev->source = SNK_RANK_RULING;
+    if (!ranked) {
+        // a circle the fast cut refuses, or no attempt left: the replicated ranking on the links as the cuts left them, marks kept
+        const uint2* rk = nullptr;
+        uint8_t* circ_out = nullptr;
+        uint32_t nc = 0;
+        snk_rank_trace tf;
+        if ((rc = snk_join_rank(ctx, st, n, w, link, &rk, &circ_out, &nc, &ev->rounds, err, errcap, circ, &tf))) return rc;
+        SNK_HIP_TRY(hipMemcpyAsync(rk_out, rk, ns * 8, hipMemcpyDeviceToDevice, st));
+        ev->n_circles += nc;
+        ev->source = tf.source;
+        ev->ruling_attempts = tf.ruling_attempts;
+        ev->sparse_cut += tf.sparse_cut;
+        ev->bad |= tf.bad;
+    }
+    return SNK_OK;
+}
+}  // namespace
+
+extern "C" int snk_dev_rank_lists(snk_ctx* ctx, uint64_t n, void* d_link, const void* d_weights, void* d_circ, uint32_t world, const uint64_t* frag_off,
+                                  void* d_rk, snk_rank_evidence* out, void* stream, char* err, size_t errcap) {
+    if (!ctx || !out) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: NULL argument");
+    memset(out, 0, sizeof *out);
+    if (n == 0) return SNK_OK;
+    if (!d_link || !d_rk) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: NULL device array");
+    if (n >= (1ull << 31)) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: %llu nodes (2n must stay below 2^32)", (unsigned long long)n);
+    if (world) {
+        if (!d_weights || !d_circ) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: the partitioned ranking needs weights and circ");
+        if (!frag_off || frag_off[0] != 0 || frag_off[world] != n) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: frag_off does not run from 0 to n");
+        for (uint32_t q = 0; q < world; ++q)
+            if (frag_off[q] > frag_off[q + 1]) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: frag_off descends at owner %u", q);
+    }
+    const uint64_t ns = 2 * n;
+    return snk_call_run(ctx, stream, "snk_dev_rank_lists", out, err, errcap, [&](snk_call& c) -> int {
+        const hipStream_t st = c.st;
+        // the links are an involution, or no walk over them need end: judged on the host before anything is launched
+        std::vector<uint32_t> h_link(ns);
+        SNK_HIP_TRY(hipMemcpyAsync(h_link.data(), d_link, ns * 4, hipMemcpyDeviceToHost, st));
+        SNK_HIP_TRY(snk_sync(st));
+        for (uint64_t s = 0; s < ns; ++s) {
+            const uint32_t l = h_link[s];
+            if (l == NONE) continue;
+            if (l >= ns) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: link[%llu] = %u lies outside the %llu states", (unsigned long long)s, l, (unsigned long long)ns);
+            if (h_link[l] != s) return snk_fail(SNK_E_ARG, err, errcap, "snk_dev_rank_lists: link[link[%llu]] != %llu: not an involution", (unsigned long long)s, (unsigned long long)s);
+        }
+        uint32_t* link = (uint32_t*)d_link;
+        const uint32_t* w = (const uint32_t*)d_weights;
+        uint8_t* circ = (uint8_t*)d_circ;
+        if (world) return prank_emulated(c, n, link, w, circ, world, frag_off, (uint2*)d_rk, out, err, errcap);
+        const uint2* rk = nullptr;
+        snk_rank_trace tr;
+        int rc2 = snk_rank_lists(ctx, st, link, n, w, circ, &rk, &out->n_circles, &out->rounds, err, errcap, &tr);
+        if (rc2) return rc2;
+        SNK_HIP_TRY(hipMemcpyAsync(d_rk, rk, ns * 8, hipMemcpyDeviceToDevice, st));
+        out->source = tr.source;
+        out->ruling_attempts = tr.ruling_attempts;
+        out->splitters = tr.m_first;
+        out->sparse_cut = tr.sparse_cut;
+        out->bad = tr.bad;
+        return SNK_OK;
+    });
 }

@@ -255,6 +255,18 @@ class SnkCheckReport(C.Structure):
         d["graph_ms"], d["reads_ms"] = float(self.graph_ms), float(self.reads_ms)
         return d
 
+
+RANK_WYLLIE, RANK_RULING, RANK_RULING_THEN_WYLLIE = 1, 2, 3      # SNK_RANK_*
+
+
+class SnkRankEvidence(C.Structure):
+    _fields_ = [("n_circles", C.c_uint32), ("rounds", C.c_uint32), ("source", C.c_uint32), ("ruling_attempts", C.c_uint32), ("splitters", C.c_uint64),
+                ("sparse_cut", C.c_uint32), ("bad", C.c_uint32), ("part_attempts", C.c_uint32), ("partitioned", C.c_uint32), ("reserved", C.c_uint64 * 4)]
+
+    def to_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
+
+
 COMM_A2A = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64),
                        C.POINTER(C.c_uint64), C.c_uint32)
 COMM_GATHER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.c_uint32)
@@ -425,6 +437,7 @@ def _declare(lib: C.CDLL) -> None:
         "snk_shard_stream_finish": (C.c_int, [vp, vp, u32, P(SnkShardResult), vp, cp, sz]),
         "snk_shard_gather_unitigs": (C.c_int, [vp, vp, P(SnkShardResult), u32, u32, u32, P(SnkResult), vp, cp, sz]),
         "snk_dev_check_graph": (C.c_int, [vp, P(SnkCheckInput), P(SnkDevReads), P(SnkCheckReport), vp, cp, sz]),
+        "snk_dev_rank_lists": (C.c_int, [vp, u64, vp, vp, vp, u32, P(u64), vp, P(SnkRankEvidence), vp, cp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
