@@ -20,6 +20,7 @@ MAX_WIDTH = 400                                        # RunStages.cc: DF's max_
 MIN_EDGE_COUNT, L32 = 5, 32                            # Closomatic.cc:494-495
 MIN_STRETCH, W, MIN_BITS, MIN_BITS_SAVE, WX, MAX_EWX, MAX_OVERLAP = 8, 20, 25.0, 40.0, 40, 20, 1000        # ReadStack.cc:1205-1213
 FLANK, MIN_SLOPE, MIN_ADD = 10, 2.0, 10.0              # :1434, :1489-1490
+Q0_WEIGHT, Q12_WEIGHT = 0.1, 0.2                       # what a quality of 0, and of 1 or 2, counts in a column sum
 COUNTERS = ("n_pairs_0", "n_pairs_1", "n_pairs_2", "n_pairs_many", "n_rows", "n_partners_tried", "n_partners_placed", "n_followers", "n_cons_too_long")
 FILTERS = ("seeds", "below_bits", "invalidated", "big_near_small", "survive")
 
@@ -60,7 +61,7 @@ def _col_sums(base, qual):
         if not d.any():
             continue
         q = qual[r][d].astype(np.float64)
-        q = np.where(q == 0, 0.1, np.where(q <= 2, 0.2, q))
+        q = np.where(q == 0, Q0_WEIGHT, np.where(q <= 2, Q12_WEIGHT, q))
         s[base[r][d], ci[d]] += q
     return s
 
@@ -373,6 +374,7 @@ GENERATED = ("gapped",) + tuple(TANDEM) + tuple(HAND)
 ALL = GOLDEN + GENERATED
 FLAGS = ("cg2", "cg1")
 BOD_BUDGET = 1 << 18                                   # the library's default bod_budget (include/snk.h)
+FUZZ = (10, 16, 34, 36, 66, 108, 9, 31, 93, 117, 119, 121)                                              # the pinned seeds of tests/closegen.py: fixtures fuzz_<seed>.npz, six per K
 WIDE, WIDE_CASES = 1200, ("tandem", "hand_k48", "hand_k60")                  # a second max_width, for the cases with a stack that wide: keys <key>_wide
 _cases: dict = {}
 
@@ -584,6 +586,13 @@ def load(name: str):
     c.ref_summary_closures = bytes(z["ref_summary"]).decode()
     _cases[name] = c
     return c
+
+
+def load_fuzz(seed: int) -> dict:
+    """the fixture of a pinned seed of tests/closegen.py: what the reference's own CloseGap2 / CloseGap wrote for the input that
+    closegen.make_case(seed) makes again -> {fastb_<flag>[_wide]: bytes, pair_first_<flag>[_wide]: u64[], input_digest, ref_summary: str}"""
+    z = np.load(CLOSURES / f"fuzz_{seed}.npz")
+    return {k: bytes(z[k]).decode() if k in ("input_digest", "ref_summary") else bytes(z[k]) if k.startswith("fastb_") else z[k].astype(np.uint64) for k in z.files}
 
 
 def full_reads(c, read_len: int | None = None):

@@ -16,6 +16,10 @@ own instead of a hops fixture; `tandem` also runs with max_width = 1 200 (<key>_
 more and gives nothing; hand_k48 / hand_k60 (tests/handclose.py): every item's stated closures -- CloseGap2, CloseGap, max_width 1 200 -- are asserted against
 the reference by name, its filters against the restatement, and that only the long follower passes the default bod_budget.  Over all cases every counter and every filter of GetOffsets1 must move.
 
+`fuzz` (or fuzz_<seed>) makes the fuzz_<seed> family: the pinned seeds closeref.FUZZ of the seeded generator tests/closegen.py, every one
+at max_width 400 and 1 200.  Such a fixture holds results only -- fastb_<f>[_wide], pair_first_<f>[_wide], input_digest, ref_summary --:
+the input is made again from the seed, and the digest says when the generator has drifted.
+
 A fixture holds per flag (cg2, cg1) fastb_<f> (the file bytes: the closures are parsed from them), pair_first_<f>, counts_<f>
 (closeref.COUNTERS, from the restatement) and filters_<f> (closeref.FILTERS); ref_summary (with the reference's wall time); input_digest (over
 the hops fixture's input, the pairs, and the reads that the pairs' edges index with their mates).  No read is stored: those of the golden
@@ -25,11 +29,14 @@ usage: python tests/golden/make_closures_golden.py [--work DIR] [case ...]
 """
 from __future__ import annotations
 
+import io
 import os
+import re
 import shutil
 import subprocess
 import sys
 import tempfile
+import zipfile
 from pathlib import Path
 from types import SimpleNamespace
 
@@ -142,6 +149,37 @@ def check_and_save(name, c, ref, line, reads, extra, wide=None):
     return infos
 
 
+def save_fuzz(exe: Path, work: Path, seed: int) -> None:
+    """fuzz_<seed>.npz: the reference on closegen.make_case(seed) at both widths, the restatement asserted against it"""
+    import closegen
+    c = closegen.make_case(seed)
+    assert c is not None, f"seed {seed} is skipped: its unitigs are no valid set"
+    r = c.reads
+    save, lines = {}, []
+    with tempfile.TemporaryDirectory(dir=work) as td:
+        for sfx, width in (("", closeref.MAX_WIDTH), ("_wide", closeref.WIDE)):
+            ref, line = run_reference(exe, Path(td), c, r.codes, r.quals, r.lens, width)
+            lines.append(line)
+            for flag in closeref.FLAGS:
+                fastb, first = ref[flag]
+                off, bases, pf, _, _ = closeref.close_gaps(c.I, c.pairs, flag == "cg2", width)
+                assert np.array_equal(pf, first), f"fuzz_{seed} {flag} {width}: the restatement gives other closures per pair: {pf.tolist()} against {first.tolist()}"
+                assert closeref.fastb_bytes(off, bases) == fastb, f"fuzz_{seed} {flag} {width}: the restatement does not reproduce the reference's closures"
+                save.update({f"fastb_{flag}{sfx}": np.frombuffer(fastb, np.uint8), f"pair_first_{flag}{sfx}": first})
+    # the same bytes from every run: no wall time in the summary, no time of day in the archive
+    line = re.sub(r" seconds \S+", "", " | ".join(lines))
+    u8 = lambda b: np.frombuffer(b, dtype=np.uint8)
+    out = GOLD / "closures" / f"fuzz_{seed}.npz"
+    save.update(ref_summary=u8(line.encode()), input_digest=u8(closeref.digest(c, r).encode()))
+    with zipfile.ZipFile(out, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k in sorted(save):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(save[k]), allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), zipfile.ZIP_DEFLATED)
+    assert out.stat().st_size <= 64 << 10, f"{out.name}: {out.stat().st_size} B"
+    print(f"fuzz_{seed}: {line} -> {out.name} ({out.stat().st_size / 1024:.1f} KiB)")
+
+
 def main(argv: list[str]) -> None:
     work, names = None, []
     it = iter(argv)
@@ -158,7 +196,11 @@ def main(argv: list[str]) -> None:
         (GOLD / "closures").mkdir(exist_ok=True)
         full = not names
         all_infos = []
-        for name in names or list(closeref.ALL):
+        fuzz = [int(a[5:]) for a in names if a.startswith("fuzz_")] + (list(closeref.FUZZ) if "fuzz" in names or full else [])
+        names = [a for a in names if not a.startswith("fuzz")]
+        for seed in fuzz:
+            save_fuzz(exe, work, seed)
+        for name in (names if names or fuzz and not full else list(closeref.ALL)):
             extra = {}
             if name in closeref.TANDEM or name in closeref.HAND:
                 a_hbv, a_inv = closeref.made_graph(name)
