@@ -461,7 +461,7 @@ uint32_t snk_ctx_last_hbv_flood(const snk_ctx* ctx, uint64_t* device_components,
  * the large-chunk kernels (either may be NULL).  A NULL context answers 0 everywhere.  Read-only; for tests and diagnostics. */
 uint32_t snk_ctx_last_local_graph(const snk_ctx* ctx, uint64_t* in_chunk_circles, uint32_t* big_chunks);
 /* The device stages that run after snk_dev_count_graph -- snk_dev_hbv, snk_dev_path_reads2, snk_dev_mark_dups, snk_dev_paths_index,
- * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps, snk_dev_delete_edges, snk_dev_hanging_ends and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
+ * snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps, snk_dev_delete_edges, snk_dev_hanging_ends, snk_dev_mow_lawn and snk_dev_check_graph -- share one result rule: after ANY non-zero return *out is all
  * zero (nothing to free, no device pointer to use; a snk_check_report keeps its struct_size), the call's work on the stream has
  * ended and its scratch is back in the context. */
 /* device_ms (optional): time of the device part, HIP events */
@@ -1008,6 +1008,57 @@ typedef struct snk_dev_hanging {
 } snk_dev_hanging;
 int snk_dev_hanging_ends(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const int32_t* inv,
                          const snk_dev_paths* paths, uint32_t max_kmers, uint32_t flags, snk_dev_hanging* out, void* stream, char* err, size_t errcap);
+/* snk_dev_mow_lawn: MowLawn (10X/Lawnmower.cc:301-554, the ReadPathVecX overload StageTrim calls at 10X/runstages/RunStages.cc:84), the
+ * weak-branch rule that picks StageTrim's first batch of deletions.  Kmers(e) = bases - K + 1.
+ *   candidate   (v, e1, e2): To(v) = {e1, e2} (both orders are tried), From(v) has one edge, Kmers(e2) <= Kmers(e1), and the left vertex of
+ *               e2 has no in-edge and exactly one out-edge;
+ *   read limit  npe = the path entries equal to e2 plus those equal to inv[e2] (a self-inverse e2 counts twice per entry), over reads
+ *               whose pair is not dup; a candidate with npe > 2 is dropped;
+ *   windows     n = Kmers(e2), del = Kmers(e1) - n; x1 = bases [del, del + n) of e1, x2 = bases [0, n) of e2;
+ *   records     for e = e1 (pass 1), then e = e2 (pass 2): every entry of e at a path position l that is not the last (fw) and every
+ *               entry of inv[e] at a position l >= 1 (not fw), of a read whose pair is not dup and that has fewer than 5 mismatches of
+ *               quality >= 30 against hb.Cat(path) at the path's offset (positions off the sequence are skipped; the offset is the
+ *               ReadPathVecX's, static_cast<int16_t>).  offset_l = the offset minus the k-mers of the edges in front of l.  A fw read has
+ *               base m at epos = offset_l + m; a read that is not fw is reverse-complemented, its qualities reversed, and starts at
+ *               epos = Bases(e) - offset_l - len.  In pass 1 epos is lowered by del.  Over 0 <= epos < n, q1 sums the qualities where
+ *               the read differs from x1 and q2 where it differs from x2; (fw, offset_l, q1 - q2) is a record when q1 != q2;
+ *   decision    the records are grouped by (fw, offset_l); a group whose smallest and largest difference have the same sign is worth
+ *               min(largest magnitude, 50), to z2 when positive, to z1 when negative; qss1 / qss2 = the sum of z1 / z2 without its
+ *               largest value; e2 and inv[e2] are deleted when qss1 >= 300 and qss2 <= 30.
+ * An entry whose read does not reach the window makes no record, and a group keeps only its extremes, so every path entry is
+ * visited once and the window test -- arithmetic on offset, length, del and n -- runs before a base or a quality is loaded.
+ *
+ * Arguments: the graph as for snk_dev_delete_edges; the reads as for snk_dev_mark_bads (rows, quality rows, lens); d_dup the u8 per PAIR
+ * that snk_dev_mark_dups returns; the paths of these reads, which must be what snk_dev_paths_zip accepts and gives back unchanged (the
+ * refusals of SNK_BADS_X).  flags must be 0.
+ * Result: dels on the host, ascending and distinct, freed by snk_host_free; scored, i32[4 * n_scored] on the device (context memory):
+ * (e1, e2, qss1, qss2) ascending by (e2, e1), one row per candidate that passed the read limit -- what the reference prints when it is
+ * given a `tests` list.  The candidates and the two thresholds are edge-sized work and run on the host; the read limit, the work items,
+ * the scoring, the sort and the group reductions run on the device.  No atomic decides anything but an integer sum: the result is the
+ * same bytes from call to call.
+ * SNK_E_ARG: as for snk_dev_hanging_ends and snk_dev_mark_bads with SNK_BADS_X, an odd read count, NULL d_dup with reads, flags != 0. */
+typedef struct snk_dev_mow {
+    uint64_t n_dels;
+    int32_t* dels;                /* host */
+    uint64_t n_scored;
+    const void* scored;           /* i32[4 * n_scored], device */
+    uint64_t n_candidates;        /* (v, e1, e2) that pass the graph's part of the rule */
+    uint64_t n_too_many_reads;    /* ... dropped by the read limit */
+    uint64_t n_entries_on_candidates; /* (path entry, role) of a non-dup read on e1, e2 or an inverse of a candidate that passed the read
+                                         limit, at a position the rule takes */
+    uint64_t n_entries_in_window; /* ... whose read reaches the window: the work items */
+    uint64_t n_reads_hq_excluded; /* work items whose read has 5 or more mismatches of quality >= 30 */
+    uint64_t n_records;           /* work items with q1 != q2 that pass the filter */
+    uint64_t n_groups;            /* distinct (candidate, fw, offset_l) among them */
+    uint64_t n_groups_mixed_sign; /* groups that count for nothing */
+    uint64_t n_deleted_candidates;
+    float ms, tables_ms;          /* HIP events: the whole call; the graph tables and the checks of the paths */
+    float phase_ms[6];            /* candidates (host, wall clock), read limit, work items, scoring, sort, decision */
+    uint64_t reserved[4];
+} snk_dev_mow;
+int snk_dev_mow_lawn(snk_ctx* ctx, uint32_t K, uint64_t n_unitigs, const void* d_unitig_off, const void* d_unitig_bases, const snk_hbv* h, const int32_t* inv /* host */,
+                     const snk_dev_reads* in, const snk_dev_paths* paths, const void* d_dup /* u8 per pair */, uint32_t flags, snk_dev_mow* out, void* stream, char* err,
+                     size_t errcap);
 
 /* ---- the edge -> barcode lists: a.ebcx ------------------------------------------------------------------------------
  * computeEdgeToBarcodeX, lib/assembly/src/10X/PathsIndex.cc:297-358 (StageEBC, 10X/runstages/RunStages.cc:31-38): per HBV edge the

@@ -1,5 +1,5 @@
 // snk_call.h -- the call frame of the device stages that run after the graph (snk_dev_hbv, snk_dev_check_graph, snk_dev_path_reads2,
-// snk_dev_mark_dups, snk_dev_paths_index, snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps, snk_dev_delete_edges, snk_dev_hanging_ends).
+// snk_dev_mark_dups, snk_dev_paths_index, snk_dev_edge_barcodes, snk_dev_paths_zip, snk_dev_paths_unzip, snk_dev_extend_paths, snk_dev_patch_pieces, snk_dev_patch_merge, snk_dev_patch_paths, snk_dev_mark_bads, snk_dev_mark_bads_df, snk_dev_edge_pairs, snk_dev_close_gaps, snk_dev_delete_edges, snk_dev_hanging_ends, snk_dev_mow_lawn).
 //
 // One protocol, one owner.  Such an entry point checks the arguments that need no device, zeroes *out and hands its body to
 // snk_call_run.  The frame makes the context's device current, picks the stream, remembers where the call's scratch begins, and on
@@ -37,7 +37,7 @@ struct snk_call {
     size_t errcap;
     uint64_t mark;              // the call's scratch = the blocks handed out after this serial
     size_t bytes = 0;           // ... and their sum (the verifier reports it)
-    hipEvent_t ev[5];
+    hipEvent_t ev[8];
     int n_ev = 0;
     hipError_t entered;
     bool done = false;

@@ -852,6 +852,54 @@ class Engine:
         out.support, out.dels = support, dels
         return out
 
+    # ---- MowLawn, and StageTrim as one call
+    def mow_lawn(self, graph, rows: torch.Tensor, read_len: int, quals: torch.Tensor, lens: torch.Tensor | None, paths, dup, download: bool = True):
+        """snk_dev_mow_lawn -- MowLawn (10X/Lawnmower.cc:301-554, the ReadPathVecX overload StageTrim calls): the weak-branch rule that picks
+        StageTrim's first batch of deletions.  graph / paths as for delete_edges (an EditResult's .graph and .paths are taken as they are);
+        the reads as for mark_bads (packed rows i32[n, words], quals u8[n, stride], lens i16[n] or None), reads 2q and 2q + 1 mates; dup
+        u8[n / 2], a tensor on the device or numpy: what MarkDups gave (path_reads(mark_dups=True), or the "dup" of stage_trim's stats).
+        -> (dels i32[] ascending, scored i32[n, 4] = (e1, e2, qss1, qss2) ascending by (e2, e1), stats); download=False leaves scored out
+        (None)."""
+        args, hold = self._edit_input(graph, paths)
+        dev = torch.device("cuda", self.device)
+        d_dup = (dup.detach().to(dev, torch.uint8) if isinstance(dup, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(dup, dtype=np.uint8)).to(dev)).contiguous()
+        if int(d_dup.shape[0]) != int(rows.shape[0]) // 2:
+            raise ValueError("dup does not have one entry per pair")
+        r = dev_reads(rows, read_len, quals, lens)
+        raw = _lib.SnkDevMow()
+        self._call(self.lib.snk_dev_mow_lawn, *args[:-1], C.byref(r), args[-1], d_dup.data_ptr() if int(d_dup.shape[0]) else None, 0, C.byref(raw))
+        try:
+            dels = np.array(np.ctypeslib.as_array(raw.dels, shape=(int(raw.n_dels),)), dtype=np.int32, copy=True) if raw.n_dels else np.zeros(0, np.int32)
+            scored = self._fetch(raw.scored, 4 * raw.n_scored, np.int32).reshape(-1, 4) if download else None
+            stats = {k: int(getattr(raw, k)) for k in _lib.MOW_COUNTERS}
+            stats.update(n_dels=int(raw.n_dels), n_scored=int(raw.n_scored), ms=float(raw.ms), tables_ms=float(raw.tables_ms),
+                         phase_ms={k: float(raw.phase_ms[i]) for i, k in enumerate(_lib.MOW_PHASES)})
+            return dels, scored, stats
+        finally:
+            self.lib.snk_host_free(C.cast(raw.dels, C.c_void_p))
+            del hold, d_dup
+
+    def stage_trim(self, graph, rows: torch.Tensor, read_len: int, quals: torch.Tensor, lens: torch.Tensor | None, bc: torch.Tensor, paths, max_kmers: int = 200) -> "EditResult":
+        """StageTrim (10X/runstages/RunStages.cc:56-156) as one call: MarkDups, mow_lawn, delete_edges with its selection, hanging_ends on
+        that result, delete_edges again.  graph / paths as for delete_edges, the reads as for mow_lawn, bc i32[n] the raw barcode ids.
+        -> the EditResult of the second edit.  Its stats carry both selections -- mow_dels, mow (the counters and times of mow_lawn),
+        first (the first edit's stats), hang_dels, hang_unsupported, hang_leg, hang_ms -- and dups; the result also has .dup (u8 per pair),
+        .scored, .mow_dels, .support and .dels (the second round's) as arrays.  The stage's a.pathsX is zip_paths(result.h, *result.paths).
+        MarkDups here is the one the library has (the ReadPath form, 10X/SecretOps.cc:413-593); the reference's StageTrim calls version 2
+        (:599), which reads the offsets through the ReadPathVecX -- the two agree on every fixture under tests/golden/mow/."""
+        args, hold = self._edit_input(graph, paths)
+        ip = hold[6]
+        dd = self._dups(dev_reads(rows, read_len, quals, lens, bc=bc), ip)
+        dup = self._fetch(dd.dup, dd.n_pairs, np.uint8)
+        dups = self._dups_info(dd, False)["dups"]
+        del hold
+        mow_dels, scored, ms = self.mow_lawn(graph, rows, read_len, quals, lens, paths, dup)
+        first = self.delete_edges(graph, paths, mow_dels)
+        out = self.trim_hanging_ends(first.graph, first.paths, max_kmers)
+        out.stats.update(mow_dels=len(mow_dels), mow=ms, first=first.stats, dups=dups)
+        out.dup, out.scored, out.mow_dels = dup, scored, mow_dels
+        return out
+
     # ---- synthetic reads straight into HBM
     def synth(self, sp: _lib.SnkSynthParams, first: int = 0, n: int | None = None, qstride: int | None = None):
         n = sp.n_reads - first if n is None else n

@@ -185,6 +185,16 @@ class SnkDevHanging(C.Structure):
 HANG_LDS, HANG_SORT, HANG_LDS_MAX = 1, 2, 16384      # SNK_HANG_LDS, SNK_HANG_SORT, SNK_HANG_LDS_MAX
 
 
+MOW_COUNTERS = ("n_candidates", "n_too_many_reads", "n_entries_on_candidates", "n_entries_in_window", "n_reads_hq_excluded", "n_records", "n_groups",
+                "n_groups_mixed_sign", "n_deleted_candidates")
+MOW_PHASES = ("candidates", "read_limit", "work_items", "scoring", "sort", "decision")      # snk_dev_mow.phase_ms
+
+
+class SnkDevMow(C.Structure):
+    _fields_ = [("n_dels", C.c_uint64), ("dels", C.POINTER(C.c_int32)), ("n_scored", C.c_uint64), ("scored", C.c_void_p)] + \
+               [(k, C.c_uint64) for k in MOW_COUNTERS] + [("ms", C.c_float), ("tables_ms", C.c_float), ("phase_ms", C.c_float * 6), ("reserved", C.c_uint64 * 4)]
+
+
 class SnkFasthBatch(C.Structure):
     _fields_ = [("n_pairs", C.c_uint64), ("first_pair", C.c_uint64), ("file", C.c_uint32), ("max_len", C.c_uint32),
                 ("ascii", C.c_void_p), ("quals", C.c_void_p), ("lens", C.c_void_p), ("bc_fields", C.c_void_p),
@@ -376,6 +386,7 @@ def _declare(lib: C.CDLL) -> None:
         "snk_dev_delete_edges": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevPaths), vp, u64, u32, P(SnkDevEdit), vp, cp, sz]),
         "snk_dev_edit_free": (None, [P(SnkDevEdit)]),
         "snk_dev_hanging_ends": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevPaths), u32, u32, P(SnkDevHanging), vp, cp, sz]),
+        "snk_dev_mow_lawn": (C.c_int, [vp, u32, u64, vp, vp, P(SnkHbv), vp, P(SnkDevReads), P(SnkDevPaths), vp, u32, P(SnkDevMow), vp, cp, sz]),
         "snk_write_pathsx": (C.c_int, [cp, u64, vp, u64, vp, u64, cp, sz]),
         "snk_read_pathsx": (C.c_int, [cp, P(u64), P(u64), P(P(C.c_int64)), P(u64), P(P(C.c_uint8)), cp, sz]),
         "snk_write_hbx": (C.c_int, [cp, u32, u64, vp, vp, P(SnkHbv), cp, sz]),
