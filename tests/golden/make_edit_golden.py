@@ -13,6 +13,11 @@ A fixture holds what identifies the input it was made from (the generator makes 
 reference's a.hbv / a.inv bytes, the paths and the a.pathsX bytes, the driver's summary line -- and, from the restatement alone (the rule
 is inline in StageTrim and cannot be called), the read support and the hanging-end selection on the case's input.
 
+`fuzz` (or fuzz_<seed>) makes the fuzz_<seed> family: the edit step of the pinned seeds patchgen.PINNED of tests/patchgen.py, on the graph
+that gap-patch insertion left (tests/golden/patch/fuzz_<seed>.npz holds that graph as the reference made it).  Such a fixture holds
+results only -- no dels: in_digest covers them -- and is never made unpinned; it is written without a time of day, so a second run gives
+the same bytes.
+
 usage: python tests/golden/make_edit_golden.py [--work DIR] [case ...]
 """
 from __future__ import annotations
@@ -37,6 +42,7 @@ import editref  # noqa: E402
 import make_a48_golden  # noqa: E402
 import make_ext_golden  # noqa: E402
 import make_hops_golden  # noqa: E402
+from make_patch_golden import fuzz_limit, save_fixed  # noqa: E402
 
 GOLD = Path(__file__).resolve().parent
 EXTRA = ("paths/long/large/GapToyTools",)
@@ -118,6 +124,14 @@ def make(exe, work: Path, key: str):
     if c.hang_want is not None:
         assert np.array_equal(hang, c.hang_want), f"{key}: the hanging-end rule does not pick the edges the case names"
     out = GOLD / "edit" / f"{key}.npz"
+    if key.startswith("fuzz_"):
+        assert exe is not None, f"{key}: a fuzz fixture is made by the reference or not at all"
+        limit = fuzz_limit(GOLD / "edit")
+        save_fixed(out, dict(in_digest=u8(editref.digest(c)), n_steps=np.int64(len(mine)), pinned=np.bool_(True), support=support, hang_dels=hang, ref_summary=u8(line.encode()),
+                             **keep))
+        assert out.stat().st_size <= limit, f"{out.name}: {out.stat().st_size} B, the largest hand-made fixture has {limit}"
+        print(f"{key}: {line} | restatement {[m.counters for m in mine]} -> {out.name} ({out.stat().st_size / 1024:.0f} KiB)")
+        return
     np.savez_compressed(out, in_digest=u8(editref.digest(c)), dels=c.dels, n_steps=np.int64(len(mine)), pinned=np.bool_(exe is not None), support=support, hang_dels=hang,
                         ref_summary=u8(line.encode()), **keep)
     assert out.stat().st_size < (1 << 20), f"{out.name} is larger than a committed file may be"
@@ -140,7 +154,10 @@ def main(argv: list[str]) -> None:
     try:
         exe = None if unpinned else build_driver(work)
         (GOLD / "edit").mkdir(exist_ok=True)
-        for key in names or editref.ALL:
+        import patchgen
+        fuzz = [patchgen.key_of(s) for s in patchgen.PINNED]
+        names = [k for a in names for k in (fuzz if a == "fuzz" else [a])]
+        for key in names or editref.ALL + tuple(fuzz):
             make(exe, work, key)
     finally:
         if not keep:

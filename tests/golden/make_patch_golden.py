@@ -16,16 +16,23 @@ driver's summary line, and what identifies the input it was made from (the gener
 synth_2k_err_ext.npz is the chain case: the a.pathsX bytes the reference's ExtendPathsNew (make_ext_golden's ext_driver, BACK_EXTEND 0)
 leaves on that fixture's patched graph and translated paths.
 
+`fuzz` (or fuzz_<seed>) makes the fuzz_<seed> family: the pinned seeds patchgen.PINNED of the seeded generator tests/patchgen.py.  Such a
+fixture holds results only -- the same arrays without the closures, and in_digest (patchref.digest) over the whole input --: the input
+is made again from the seed, and the digest says when the generator has drifted.  It is written without a time of day, so a second run
+gives the same bytes.
+
 usage: python tests/golden/make_patch_golden.py [--work DIR] [case ...]
 """
 from __future__ import annotations
 
+import io
 import os
 import shutil
 import struct
 import subprocess
 import sys
 import tempfile
+import zipfile
 import zlib
 from pathlib import Path
 
@@ -88,6 +95,21 @@ def run_reference(exe: Path, td: Path, c):
     return got[1], line
 
 
+def save_fixed(out: Path, arrays: dict) -> None:
+    """an .npz that a second run writes again byte for byte: sorted names, no time of day in the archive"""
+    with zipfile.ZipFile(out, "w", zipfile.ZIP_DEFLATED) as zf:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            a = np.asarray(arrays[k])
+            np.lib.format.write_array(buf, np.ascontiguousarray(a) if a.ndim else a, allow_pickle=False)
+            zf.writestr(zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), zipfile.ZIP_DEFLATED)
+
+
+def fuzz_limit(folder: Path) -> int:
+    """a fuzz_<seed> fixture stays below the largest hand-made one beside it"""
+    return max(p.stat().st_size for p in folder.glob("*.npz") if not p.name.startswith("fuzz_"))
+
+
 def make(exe: Path, work: Path, key: str):
     c = patchref.case(key)
     with tempfile.TemporaryDirectory(dir=work) as td:
@@ -106,6 +128,12 @@ def make(exe: Path, work: Path, key: str):
     off, cb = patchref.closures_arrays(c.closures)
     u8 = lambda b: np.frombuffer(b, np.uint8)
     out = GOLD / "patch" / f"{key}.npz"
+    if key.startswith("fuzz_"):
+        save_fixed(out, dict(a_hbv=u8(ref["a.hbv"]), a_inv=u8(ref["a.inv"]), to3_off=to3_off, to3=to3, left3=left3, edge=reads[:, 0].copy(), offset=reads[:, 1].copy(),
+                             pathsx=u8(ref["a.pathsX"]), ref_summary=u8(line.encode()), in_digest=u8(patchref.digest(c))))
+        assert out.stat().st_size <= fuzz_limit(GOLD / "edit"), f"{out.name}: {out.stat().st_size} B"
+        print(f"{key}: {line} | restatement {m.counters} -> {out.name} ({out.stat().st_size / 1024:.0f} KiB)")
+        return
     np.savez_compressed(out, a_hbv=u8(ref["a.hbv"]), a_inv=u8(ref["a.inv"]), to3_off=to3_off, to3=to3, left3=left3, edge=reads[:, 0].copy(), offset=reads[:, 1].copy(),
                         pathsx=u8(ref["a.pathsX"]), ref_summary=u8(line.encode()), in_hbv_crc=u8(str(zlib.crc32(c.a_hbv)).encode()), closure_off=off,
                         closure_codes2=hu.pack2(cb), in_paths_crc=u8(str(zlib.crc32(c.offset.tobytes() + c.n_edges.tobytes() + c.edges.tobytes())).encode()))
@@ -151,7 +179,10 @@ def main(argv: list[str]) -> None:
     try:
         exe = build_driver(work)
         (GOLD / "patch").mkdir(exist_ok=True)
-        for key in names or patchref.ALL:
+        import patchgen
+        fuzz = [patchgen.key_of(s) for s in patchgen.PINNED]
+        names = [k for a in names for k in (fuzz if a == "fuzz" else [a])]
+        for key in names or patchref.ALL + tuple(fuzz):
             make(exe, work, key)
         if not names or patchref.SYNTH in names:
             make_chain(work)

@@ -386,6 +386,11 @@ def case(key: str):
     """-> namespace(key, K, a_hbv, a_inv (the old graph's files), old_unitigs (BVComp order), closures: strings, offset, n_edges, edges)"""
     if key in _made:
         return _made[key]
+    if key.startswith("fuzz_"):                  # a seed of tests/patchgen.py (a namespace with the same fields, and a few more)
+        import patchgen
+        c = patchgen.make_case(int(key[5:]))
+        assert c is not None, f"{key}: the seed is skipped"
+        return c
     if key == SYNTH:
         import a48ref
         import goldens
@@ -426,6 +431,12 @@ def closures_arrays(closures):
     return off, np.ascontiguousarray(codes("".join(closures)))
 
 
+def digest(c) -> bytes:
+    """what identifies the input of a case whose fixture holds results only (the seeds of tests/patchgen.py)"""
+    off, cb = closures_arrays(c.closures)
+    return str(zlib.crc32(c.a_hbv + c.a_inv + off.tobytes() + cb.tobytes() + c.offset.tobytes() + c.n_edges.tobytes() + c.edges.tobytes())).encode()
+
+
 _gold: dict = {}
 
 
@@ -436,7 +447,8 @@ def golden(key: str):
         z = np.load(PATCH / f"{key}.npz")
         c = case(key)
         off, cb = closures_arrays(c.closures)
-        assert bytes(z["in_hbv_crc"]) == str(zlib.crc32(c.a_hbv)).encode() and np.array_equal(z["closure_off"], off) and np.array_equal(z["closure_codes2"], hu.pack2(cb)) \
+        assert (bytes(z["in_digest"]) == digest(c)) if "in_digest" in z else \
+            bytes(z["in_hbv_crc"]) == str(zlib.crc32(c.a_hbv)).encode() and np.array_equal(z["closure_off"], off) and np.array_equal(z["closure_codes2"], hu.pack2(cb)) \
             and bytes(z["in_paths_crc"]) == str(zlib.crc32(c.offset.tobytes() + c.n_edges.tobytes() + c.edges.tobytes())).encode(), \
             f"{key}: the generator no longer makes the input of the fixture"
         _gold[key] = SimpleNamespace(a_hbv=bytes(z["a_hbv"]), a_inv=bytes(z["a_inv"]), to3_off=z["to3_off"], to3=z["to3"], left3=z["left3"], edge=z["edge"],
